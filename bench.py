@@ -80,7 +80,50 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="CPU-only check of the self-launch path: the ranks rendezvous over gloo, shard a small cloud "
                          "exactly as the timed run would, and rank 0 prints what every rank got")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the map the last timed step built (what TwoDmap.export() returns) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB: one GPU, one process")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.gpus > 1 or a.mode in ("global", "owner")):
+        ap.error("--dump-outputs needs --gpus 1 without --mode global / owner (one process holding the whole map)")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64_000_000      # --dump-outputs: all files together, .npy headers included
+DUMP_SEED = 0x5EED0D0           # the row sample of a map too large for the limit
+
+
+def dump_outputs(cells, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the arrays of `cells` (TwoDmap.export()) as out_dir/<name>.npy.  Float fields stay float32; an integer field is
+    written as float32 when all its values are below 2^24 in magnitude (exact there), otherwise as float64.  If the rows do not fit
+    `limit`, a fixed, seeded sample of rows is written in row order, with the row numbers in row_index.npy; the same map gives the
+    same sample.  -> (rows written, rows in the map, bytes written)."""
+    n = int(cells["num_nodes"])
+    rows = {}
+    for k, v in cells.items():
+        if isinstance(v, np.ndarray):
+            exact32 = v.dtype.kind == "f" or v.size == 0 or int(np.abs(v.astype(np.int64)).max()) < (1 << 24)
+            rows[k] = v.astype(np.float32 if exact32 else np.float64)
+    counts = {k: np.float64(cells[k]) for k in ("num_nodes", "num_columns", "num_slopes")}
+    row_bytes = sum(v.itemsize * (v.size // n) for v in rows.values()) if n else 0
+    room = limit - 256 * (len(rows) + len(counts) + 1)        # (an .npy header is 128 bytes; twice that is margin)
+    if n * row_bytes > room:
+        keep = room // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        rows = {k: v[idx] for k, v in rows.items()}
+        rows["row_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k, v in {**rows, **counts}.items():
+        fn = os.path.join(out_dir, k + ".npy")
+        np.save(fn, v)
+        total += os.path.getsize(fn)
+    assert total <= limit, (total, limit)
+    written = rows["row_index"].size if "row_index" in rows else n
+    print(f"bench.py: --dump-outputs wrote {written} of {n} rows ({total} bytes) to {out_dir}", file=sys.stderr)
+    return written, n, total
 
 
 # what the N > 1 line carries beside the N = 1 keys (tests/test_bench_launcher.py; VERDICT r02 item 3)
@@ -580,6 +623,8 @@ def run_stream(a):
 
     dt, _, (nodes, cols, slopes), m = run(False)
     strat = m.STRATEGY_NAMES.get(m.last_strategy(), "?")
+    if a.dump_outputs:
+        dump_outputs(m.export(), a.dump_outputs)
     del m
     _, lat, _, _ = run(True)
     lat = np.sort(np.array(lat))
@@ -760,6 +805,8 @@ def main():
     if retries_timed and rank == 0:
         print(f"bench.py: ERROR {retries_timed} build re-run(s) inside the timed region: the step time is not that of complete builds "
               "(the line is printed with \"valid\": false and the exit code is 3)", file=sys.stderr)
+    if a.dump_outputs:                    # before any further build on this handle
+        dump_outputs(m.export(), a.dump_outputs)
     if global_mode:                       # stage times from a few extra, untimed steps (their events make the call wait)
         exch.clear()
         for _ in range(3):

@@ -78,3 +78,36 @@ def test_single_gpu_line_carries_every_config_and_the_host_path():
     for k in ("drivable_site_400k", "bridge_ground_360k_own_parameters", "terrain_2M"):
         assert cf[k]["h_bit_exact"] and cf[k]["state_exact"] and cf[k]["layers"] > 10 and cf[k]["gpu_ms"] > 0, (k, cf[k])
     assert cf["bridge_ground_360k_own_parameters"]["ring_depth"] == 2 and cf["drivable_site_400k"]["ring_depth"] == 0
+
+
+def test_dump_outputs_is_the_map_of_the_last_timed_step(tmp_path):
+    """--dump-outputs: after the timed steps, the map the last one built as float32 / float64 .npy files within 64 MB — the map a fresh
+    handle builds from the same seeded cloud: keys, counts, first-seen indices, order and labels exactly, the fp32 fields within one
+    output rounding, as between any two builds of one cloud (tests/test_gpu_reproducible.py)."""
+    import numpy as np
+    import torch
+    import bench
+    import grid_ndt_amd as g
+    from tests.test_gpu_reproducible import TOL_OUT, _compare_runs
+    out_dir = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--points", "300000", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+                        "--no-extras", "--no-configs", "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 4 and d["ms_per_step"] > 0
+    files = sorted(out_dir.iterdir())
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_LIMIT_BYTES
+    got = {f.stem: np.load(f) for f in files}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert "row_index" not in got and int(got["num_nodes"]) == d["config"]["nodes"]
+    W = bench.WORKLOADS["S2"]
+    origin, pts, _, _ = bench.make_cloud("S2", 300_000, 0, 1, False)
+    m = g.TwoDmap(W["grid_len"], W["z_len"], max_nodes_hint=W["hint"])
+    m.setInterval(0.08)
+    m.setCloudFirst(origin)
+    m.create2DMap("slope", torch.from_numpy(pts).cuda())
+    want = m.export()
+    del m
+    assert set(got) == set(want)
+    _, worst = _compare_runs(want, got)
+    assert worst <= TOL_OUT, worst

@@ -1,18 +1,19 @@
 #!/bin/bash
 # Regenerates tests/golden/morton_known_answers.csv from the REFERENCE's own key helpers, compiled where they lie:
-#   countMorton(a, b)           /root/reference/include/Stopwatch.h:116-147  (with decToBinStr2 :39-47, binToDec :102-110, intToString :59-64)
-#   mortonToXY(a, b, morton)    /root/reference/include/Stopwatch.h:171-189  (with strToInt :20-25)
+#   countMorton(a, b)           include/Stopwatch.h:116-147  (with decToBinStr2 :39-47, binToDec :102-110, intToString :59-64)
+#   mortonToXY(a, b, morton)    include/Stopwatch.h:171-189  (with strToInt :20-25)
 #
-#   tools/make_morton_golden.sh [out.csv]      (default: tests/golden/morton_known_answers.csv)
+#   GNDT_REFERENCE=<reference tree> tools/make_morton_golden.sh [out.csv]      (default: tests/golden/morton_known_answers.csv)
 #
 # This is the one piece of the path the reference pins by itself and that compiles in this image: the header needs
 # nothing but the standard library for these functions.  Its line 9 includes <boost/format.hpp> without using it in them; Boost
 # is not installed here, so the include is satisfied by an EMPTY file in a temporary directory that is deleted again (nothing of
 # Boost is restated; VERDICT r5 item 7 asks for exactly this recipe).  The caller below is this repo's; nothing of the reference
 # is copied, and only the CSV (data: inputs and the reference's answers) is committed and travels to the GPU box.
-# tests/test_oracle_golden.py::test_golden_file_regenerates re-runs this script when /root/reference exists and diffs.
+# tests/test_oracle_golden.py::test_golden_file_regenerates re-runs this script when GNDT_REFERENCE is set and diffs; without it,
+# the test restates this script's rows and answers them with the oracle.
 set -euo pipefail
-ref=${GNDT_REFERENCE:-/root/reference}
+ref=${GNDT_REFERENCE:?set GNDT_REFERENCE to the reference tree}
 root=$(cd "$(dirname "$0")/.." && pwd)
 out=${1:-$root/tests/golden/morton_known_answers.csv}
 [ -f "$ref/include/Stopwatch.h" ] || { echo "no reference at $ref: the committed CSV stays as it is" >&2; exit 3; }
