@@ -6,6 +6,7 @@
 //   gndt_api_build.hip  strategy PARTITION: launch, pending-build resolution, gndt_build*
 //   gndt_api_dist.hip   one global map from a sharded cloud (shard statistics, exchange, finalize from statistics)
 //   gndt_api_cost.hip   cost-map flood over the finished grid
+//   gndt_api_query.hip  batched point queries against the finished grid
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
@@ -191,6 +192,16 @@ struct gndt_handle {
         float tables_robot[4] = {0, 0, 0, 0};   // ... and the robot they were worked out for: the next goal on the same map reuses them
         int ring_n = 0, ring_store = 0;
     } cost;
+    // point queries (gndt_query.hpp): their own (sx, sy) -> first row index, apart from the flood's (whose reuse logic, tables_kept,
+    // then keeps serving one caller), and the device copies of a host query's input and answers
+    struct Query {
+        uint32_t ctab_cap = 0;     uint64_t* ctab_key = nullptr; uint32_t* ctab_val = nullptr;
+        uint32_t ctab_mask = 0;
+        uint64_t serial = 0;            // result_serial the index was built for (0 = none)
+        CostCounters* d_cc = nullptr;   // k_cost_columns' counters: scratch (its column range bound belongs to the flood)
+        uint64_t in_cap = 0, out_cap = 0;   // bytes
+        void* in = nullptr;  uint32_t *rows = nullptr, *h_bits = nullptr, *state = nullptr;
+    } query;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -341,6 +352,7 @@ struct Tuning {
     bool stamps = false;         // gndt_debug_enable_stamps: in-kernel phase stamps of the bucket kernel
     bool verbose = false;        // GNDT_DEBUG_VERBOSE      stderr line per resolved two-level build
     bool cost_one_workgroup = true;   // GNDT_DEBUG_COST_ONE_WORKGROUP   0: every layer of the flood its own launch
+    int query_ilp = 1;           // GNDT_DEBUG_QUERY_ILP           queries a thread of k_query works on at once (1, 2 or 4)
 };
 const Tuning& tuning();
 void tuning_force_stamps(bool on);   // bench.py --stamps flips this after the timed run
@@ -486,5 +498,7 @@ int partition_begin(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride
 int partition_resolve(gndt_handle* h);
 // ---- gndt_api_cost.hip ----
 void free_cost(gndt_handle* h);
+// ---- gndt_api_query.hip ----
+void free_query(gndt_handle* h);
 
 }  // namespace gndt_host

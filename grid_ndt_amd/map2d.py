@@ -491,7 +491,7 @@ class TwoDmap:
         self._ensure(demand)
         self._check(self._L.gndt_set_deferred_emit(self._h, int(bool(on))))
 
-    DEBUG_VERBOSE, DEBUG_TILE_RATIO, DEBUG_COST_ONE_WORKGROUP = 1, 2, 3
+    DEBUG_VERBOSE, DEBUG_TILE_RATIO, DEBUG_COST_ONE_WORKGROUP, DEBUG_QUERY_ILP = 1, 2, 3, 4
 
     @staticmethod
     def set_debug_option(option, value):
@@ -548,6 +548,36 @@ class TwoDmap:
         out = self._cost_stats(st)
         out.update(h=h, state=state.astype(np.uint8))
         return out
+
+    # ---- point queries (the lookup of computeCost's goal, map2D.h:1291-1306, and findRoute's start / goal, GlobalPlan.h:56-61) ----
+    QUERY_MODES = {"node": 0, "nearest_slope": 1}
+    NO_ROW = -1        # GNDT_NO_ROW as the int32 the rows come back in
+
+    def query(self, points, mode="node", cost=False, stream=None):
+        """Rows of the finished map (export order) at `points` ([N,3] or [N,4] float32), -1 where the map has no answer.
+        mode "node": the node whose key is the point's (any node: map_xy's view); "nearest_slope": the slope of the point's column
+        whose mean z is nearest the point's z.  A torch CUDA tensor is answered on the device (torch int32 rows, enqueued on `stream`,
+        default torch's current stream); a host array through gndt_query (numpy).  cost=True also returns the cost map's h (float32,
+        FLT_MAX where there is no row) and state (int32) of every row: (rows, h, state)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        m = self.QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+        ptr, n, stride, on_dev, keep = self._as_input(points)
+        if on_dev:
+            import torch
+            rows = torch.empty(n, dtype=torch.int32, device=keep.device)
+            h = torch.empty(n, dtype=torch.float32, device=keep.device) if cost else None
+            state = torch.empty(n, dtype=torch.int32, device=keep.device) if cost else None
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and n else 0)
+            self._check(self._L.gndt_query_device(self._h, C.c_void_p(ptr if n else 0), n, stride, m, p(rows), p(h), p(state),
+                                                  _stream_ptr(stream)))
+        else:
+            rows = np.empty(n, np.int32)
+            h = np.empty(n, np.float32) if cost else None
+            state = np.empty(n, np.int32) if cost else None
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and n else 0)
+            self._check(self._L.gndt_query(self._h, C.c_void_p(ptr if n else 0), n, stride, m, p(rows), p(h), p(state)))
+        return (rows, h, state) if cost else rows
 
     # ---- results ----
     def sync(self):

@@ -392,6 +392,41 @@ int gndt_cost_export_device(gndt_handle* h, const float** h_dev, const uint32_t*
 /* Copies into caller-allocated host arrays of num_nodes elements (NULL arrays skipped). */
 int gndt_cost_export(gndt_handle* h, float* h_out, uint32_t* state_out, gndt_cost_stats* stats);
 
+/* ---- point queries against the finished grid --------------------------------------------------------
+ * The lookup the reference writes out wherever a consumer needs the slope at a position:
+ *     transMortonXYZ(p) -> map_cell.find(morton_xy) -> map_slope.find(morton_z)
+ * (the goal of computeCost, map2D.h:1291-1306; start and goal of AstarPlanar::findRoute, GlobalPlan.h:56-61), for n points at once,
+ * on the device, against the rows gndt_export* hands out.  Per point the answer is a row number (gndt_cells order) or GNDT_NO_ROW.
+ *   GNDT_QUERY_NODE           the row whose (sx, sy, sz) is point_key(p): the key the build gives the point (transMortonXYZ,
+ *                             map2D.h:950-976, from the handle's origin, grid_len and z_len).  ANY node counts — also one below
+ *                             min_points or without a slope: map_xy's view.  The reference's goal / start lookup (map2D.h:1293-1306,
+ *                             GlobalPlan.h:56-61: map_cell.find, then map_slope.find(morton_z)) is "a NODE row whose flags have
+ *                             GNDT_FLAG_SLOPE": a row without that flag is the reference's "Goal position wrong".
+ *   GNDT_QUERY_NEAREST_SLOPE  only the column (sx, sy) is keyed (z only has to be finite): among its rows with GNDT_FLAG_SLOPE the
+ *                             one with the least fabsf(mean_z - p.z) in fp32, a tie going to the smaller sz; GNDT_NO_ROW if the column
+ *                             has no slope.  The slope under a robot whose pose z need not fall into the slope's level (the reference
+ *                             needs it to: findRoute finds no start otherwise, hence receiver.cpp:257-266's hand-tuned pos / goal).
+ * A point with no answer is a normal question, not an error: GNDT_NO_ROW for a non-finite coordinate (tested before keying), a key
+ * outside the codec's range (|nx|, |ny| > 65535; in NODE mode also |nz| >= 2^21) and a column or node the map does not hold.
+ * h_out / state_out may be NULL; when given they receive the cost map's h / state of the row (FLT_MAX / 0 for GNDT_NO_ROW) and need
+ * a cost map of the current grid (the condition of gndt_cost_export).
+ * GNDT_ERR_INVALID: null handle, null xyz or row_out with n > 0, unknown mode, stride other than 12 / 16, no finished build, h_out /
+ * state_out without a current cost map, a stream under hipGraph capture (queries are not recorded).  There is no CPU path: without a
+ * device the call fails like every compute entry point.  n == 0 returns GNDT_OK and launches nothing.
+ * Order: the call first finishes what gndt_compute_cost finishes (a pending build, a deferred emit, a re-run: gndt_sync), then builds
+ * or reuses its column index — rebuilt after every build / update / remove, and on every call on a handle that has recorded a
+ * hipGraph (a replay rewrites the map unseen) — and enqueues one kernel.  Row numbers stay valid until the next build, update, remove
+ * or reset.  A sharded map answers from the rows this rank holds. */
+enum { GNDT_QUERY_NODE = 0, GNDT_QUERY_NEAREST_SLOPE = 1 };
+#define GNDT_NO_ROW 0xFFFFFFFFu
+/* Device memory in and out (stride 12 or 16, like gndt_build_device); enqueued on `hip_stream` (NULL = the handle's stream, the rules
+ * of gndt_build_device) and not awaited: the outputs are valid once that stream reaches them. */
+int gndt_query_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, int32_t mode,
+                      uint32_t* row_out, float* h_out, uint32_t* state_out, void* hip_stream);
+/* Host memory in and out; synchronous. */
+int gndt_query(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, int32_t mode,
+               uint32_t* row_out, float* h_out, uint32_t* state_out);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
@@ -474,10 +509,12 @@ int gndt_debug_enable_stamps(int on);
  *   GNDT_DEBUG_TILE_RATIO         points per partial from which strategy AUTO takes TILE (tools/calibrate_tile.py sweeps it);
  *                                 value >= 1                                                                        default 48
  *   GNDT_DEBUG_COST_ONE_WORKGROUP value == 0: gndt_compute_cost launches every layer on its own, the one-workgroup kernel that walks
- *                                 the narrow layers is not used (tests run the flood both ways)                     default 1 */
+ *                                 the narrow layers is not used (tests run the flood both ways)                     default 1
+ *   GNDT_DEBUG_QUERY_ILP          independent queries one thread of gndt_query* works on at once: 1, 2 or 4       default 1 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
+#define GNDT_DEBUG_QUERY_ILP 4
 int gndt_debug_set_option(int option, double value);
 /* The bucket kernel finds a node through a 21-bit fingerprint of its key and confirms it with the key itself; a bucket in
  * which a fingerprint named the wrong node (~1 in 10^4) is accumulated a second time with every probe confirmed.  Tests narrow
