@@ -6,7 +6,7 @@
 // arbitrary set of columns.  If a bucket is instead a spatial BLOCK of 2^shx x 2^shy columns x 2^shz levels = 512 nodes
 // (GridParams::blk), a node's slot is a function of its key,
 //        slot = (cz - z0) << (shx + shy) | (cy - y0 & mask_y) << shx | (cx - x0 & mask_x),
-// the accumulate loop is key -> slot -> eleven atomics, and a node's column is the 2^shz slots that differ in the level bits: the
+// the accumulate phase is a counting sort by slot with no search (see BlockedLds), and a node's column is the 2^shz slots that differ in the level bits: the
 // column phases are eight independent LDS reads.  What it needs: every column of a block in ONE bucket and blocks of similar fill —
 // i.e. a box of bounded height, evenly filled (the bench scene; a levelled site; not a LiDAR sweep, whose hottest hashed bucket is
 // already 20 x the mean).  The host takes this kernel when the map of the previous build on the handle says so (partition_launch); a
@@ -22,45 +22,29 @@
 
 namespace gndt {
 
-struct BlockedLds {            // 47 KB: three workgroups per CU
-#if GNDT_BLOCKED_FIXED
-    unsigned long long sum[9][512];    // FIXED-POINT sums (two's complement): see the accumulate loop
-#else
-    double sum[9][512];
-#endif
-    uint32_t cnt[512];
-    uint32_t first[512];
+// The accumulate phase sorts a bucket's records by slot, kBlkChunk records at a time, and thread s adds slot s's run into registers:
+// per record ONE returning LDS atomic (its rank inside its slot), one 16-byte LDS write and one 16-byte LDS read.  It replaced eleven
+// LDS atomics per record (count, nine fp64 sums, first-seen) whose issue and bank-conflict queue made two thirds of the kernel
+// (profiles/r07_ablation.txt).  A contribution is computed by the same fp64 expressions as before; only the order in which a node's
+// contributions are summed differs (it was the atomics' arrival order, and now is the order of the records in the image).
+constexpr uint32_t kBlkChunk = 2048;                     // records per chunk: 32 KB of image
+constexpr int kBlkPer = (int)kBlkChunk / 512;             // records per thread and chunk
+constexpr uint32_t kBlkNone = 0xFFFFFFFFu;                // (slot_rank of a record that is not added)
+struct BlockedLds {            // 43 KB: three workgroups per CU
+    float4 image[kBlkChunk];   // a chunk's raw records, sorted by slot
+    uint32_t hist[2][512];     // per chunk parity: a slot's records in the chunk (its ranks), then the slot's first entry inside its wave's part
+    uint32_t wpre[2][8];       // per chunk parity: records of the chunk in the waves before wave w
     uint2 fz[512];             // {first-seen index (0xFFFFFFFF: no node in this slot), fp32 mean z of a node that has statistics, else 0}: what a
                                //   node's look at its column reads of the others, one 8-byte load per level
     uint32_t cpre[512];        // per COLUMN (the first 2^(shx+shy) entries): first row of the column inside the bucket
     uint32_t wave_tot[8];
-    uint32_t n_nodes, n_cols, n_slopes, stage_base, err_range, miss, miss2;      // (miss2: raised after the accumulate phase — a word of its own, the first is being read then)
+    uint32_t n_nodes, n_cols, n_slopes, stage_base, err_range, miss;
 };
-
-// Fixed-point contributions (-DGNDT_BLOCKED_FIXED=1; built, parity-green, measured, NOT the default).  In this kernel the LDS array, not
-// the vector port, is the busy one (63 % against 34 %: profiles/r06_ablation.txt 8) and `ds_add_u64` takes half the time of `ds_add_f64` in
-// isolation (10.2 against 19.9 clocks per wave-instruction at random slots, profiles/r03_lds_atomic_rates.txt) — so the nine sums were
-// kept as 64-bit integers: a contribution x becomes round(x * 2^k) by ONE fused multiply-add against 1.5 * 2^52 (its low mantissa bits
-// ARE the integer for |x * 2^k| < 2^51), the sums are order-independent (bit-identical statistics run to run).  Scales: offsets from the
-// cell centre are below half a cell < 2^e, first moments take 2^(38 - e), second moments 2^(38 - 2 e); a node may hold 2^23 points
-// before a sum could pass 2^61 (beyond: the bucket is a miss).  Measured in one call, twice: bucket kernel 124.0 | 124.0 us against
-// 121.6 | 120.2 with fp64 sums, the accumulate stamps equal (33.6-34.2 k cycles) — the atomic unit's instruction rate is not what the
-// 63 % are made of (bank conflicts and the queue behind them are) — and k_emit_rows 45-46 us against 34.5 (the quantised sums send more
-// nodes through the eigen-solver's slow start).  Fp64 sums stay.
-#ifndef GNDT_BLOCKED_FIXED
-#define GNDT_BLOCKED_FIXED 0      // 1: fixed-point sums (A/B)
-#endif
-constexpr double kFixMagic = 6755399441055744.0;      // 1.5 * 2^52
-constexpr uint32_t kFixMaxCount = 1u << 23;
-__device__ __forceinline__ unsigned long long fix_round(double x, double scale) {
-    const double t = fma(x, scale, kFixMagic);
-    return (unsigned long long)__double_as_longlong(t) - (unsigned long long)__double_as_longlong(kFixMagic);
-}
 
 // One workgroup per bucket (the hardware's dynamic scheduling), three resident per CU.  The staging rows of a bucket are reserved with one
 // memory-side atomic whose answer takes ~3 us; to have it in time the bucket's node count is known the moment the accumulate phase
-// ends — a thread counts the slots it was the FIRST to add to (the count's atomic returns the old value, looked at one iteration
-// later) — and the answer travels while the columns are worked out.  (Built and measured on the way, profiles/r06_ablation.txt 8: the count
+// ends — every slot's count is in its thread's registers then: a ballot per wave — and the answer travels while the columns are
+// worked out.  (Built and measured on the way, profiles/r06_ablation.txt 8: the count
 // after the accumulate phase: ~5 k of 58 k cycles per bucket waiting; the rows of a bucket written behind the NEXT bucket's
 // accumulate phase from registers: slower — the held row spills, and every vector-memory wait that follows stores waits for them.)
 template <int T>
@@ -75,12 +59,7 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
     const BlockMap K = P.blk;
     const int sh_xy = K.shx + K.shy;
     const uint32_t col_mask = (1u << sh_xy) - 1u, n_levels = 1u << K.shz;
-    const double hx = 0.5 * (double)P.grid_len, hz = 0.5 * (double)P.z_len;
-    const double ox = (double)P.ox, oy = (double)P.oy, oz = (double)P.oz;
     if (blockIdx.x == 0 && tid == 0) { const uint32_t e = pc->l1_err; if (e) atomicAdd(&cnt->err_key_range, e); }   // (FoldClear, gndt_partition.hpp)
-    const int fix_e = ilogb(fmax(hx, hz)) + 1;                  // half a cell < 2^fix_e on every axis
-    const double scale1 = ldexp(1.0, 38 - fix_e), scale2 = ldexp(1.0, 38 - 2 * fix_e);
-    const double inv1 = ldexp(1.0, fix_e - 38), inv2 = ldexp(1.0, 2 * fix_e - 38);
     for (uint32_t bucket = blockIdx.x; bucket < num_buckets; bucket += gridDim.x) {
 #define GNDT_STAMPB(k) do { if (dbg && tid == 0) dbg[(size_t)bucket * 16 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
         uint32_t lo, hi;
@@ -88,73 +67,118 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         GNDT_STAMPB(0);
         // this bucket's block: contiguous indices bx0 .. bx0 + 2^shx - 1 (x), by0 .. (y), z0 .. z0 + 2^shz - 1 (levels)
         const int bx0 = K.x0 + (int)((bucket / (uint32_t)K.ny) << K.shx), by0 = K.y0 + (int)((bucket % (uint32_t)K.ny) << K.shy);
-        {
-            const int s = tid;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) L.sum[j][s] = 0;
-            L.cnt[s] = 0u; L.first[s] = 0xFFFFFFFFu;
-            if (tid == 0) { L.n_nodes = 0; L.n_cols = 0; L.n_slopes = 0; L.stage_base = 0; L.err_range = 0; L.miss = 0; L.miss2 = 0; }
-        }
+        // (s: thread s owns slot s.  It and the grid's parameters are opaque to the compiler, so that what it derives from them — the
+        //  slot's centre, the fp64 constants, a zero — is recomputed per bucket: hoisted out of the bucket loop, those values spilled)
+        uint32_t s = (uint32_t)tid;
+        asm volatile("" : "+v"(s));
+        const uint32_t zero = s - (uint32_t)tid;
+        float f_len = P.grid_len, f_zlen = P.z_len, f_ox = P.ox, f_oy = P.oy, f_oz = P.oz;
+        asm volatile("" : "+s"(f_len), "+s"(f_zlen), "+s"(f_ox), "+s"(f_oy), "+s"(f_oz));
+        const double hx = 0.5 * (double)f_len, hz = 0.5 * (double)f_zlen;
+        const double ox = (double)f_ox, oy = (double)f_oy, oz = (double)f_oz;
+        L.hist[0][s] = zero; L.hist[1][s] = zero;
+        if (s < 16) L.wpre[s >> 3][s & 7] = zero;
+        if (s == 0) { L.n_nodes = zero; L.n_cols = zero; L.n_slopes = zero; L.stage_base = zero; L.err_range = zero; L.miss = zero; }
         lds_barrier();
         GNDT_STAMPB(1);
-        // ---- accumulate: one record per thread and iteration, the next one's load in flight ----
-        const uint32_t n_rec = hi - lo, iters = (n_rec + (uint32_t)T - 1u) / (uint32_t)T;
-        float4 nxt = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lo < hi) nxt = recs[min(lo + (uint32_t)tid, hi - 1u)];
-        uint32_t my_new = 0, old_cnt = 1u;          // slots this thread was the first to add to (old_cnt: the last atomic's answer, looked at an iteration later)
-        for (uint32_t it = 0; it < iters; ++it) {
-            const uint32_t mine = lo + it * (uint32_t)T + (uint32_t)tid;
-            const float4 rec = nxt;
-            bool use = mine < hi;
-            if (it + 1u < iters) nxt = recs[min(mine + (uint32_t)T, hi - 1u)];
-            bool und = false;
-            float fx = axis_ceil_try(rec.x, P.ox, P.inv_grid, und);
-            float fy = axis_ceil_try(rec.y, P.oy, P.inv_grid, und);
-            float fz = axis_ceil_try(rec.z, P.oz, P.inv_z, und);
-            if (und) {                                 // (rare: within ~2 ulp of a cell border the reference's own divide decides)
-                fx = ceilf(fabsf(rec.x - P.ox) / P.grid_len);
-                fy = ceilf(fabsf(rec.y - P.oy) / P.grid_len);
-                fz = ceilf(fabsf(rec.z - P.oz) / P.z_len);
+        // ---- accumulate, a chunk of kBlkChunk records at a time: rank inside the slot (ONE returning LDS atomic per record), prefix over
+        //      the slots, the raw records sorted into the image by slot, then thread s walks slot s's run and adds into registers ----
+        const uint32_t col = s & col_mask, lz = s >> sh_xy;
+        // signed indices of this slot's node, and its centre on each axis (axis_index_offset's fma: a record of this slot has c = |n|)
+        const int cxi = bx0 + (int)(col & ((1u << K.shx) - 1u)), cyi = by0 + (int)(col >> K.shx), czi = K.z0 + (int)lz;
+        const int nsx = cxi >= 0 ? cxi + 1 : cxi, nsy = cyi >= 0 ? cyi + 1 : cyi, nsz = czi >= 0 ? czi + 1 : czi;
+        const double ctx = fma((double)(float)(nsx > 0 ? 2 * nsx - 1 : 2 * nsx + 1), hx, ox),
+                     cty = fma((double)(float)(nsy > 0 ? 2 * nsy - 1 : 2 * nsy + 1), hx, oy),
+                     ctz = fma((double)(float)(nsz > 0 ? 2 * nsz - 1 : 2 * nsz + 1), hz, oz);
+        const uint32_t n_rec = hi - lo, n_chunks = (n_rec + kBlkChunk - 1u) / kBlkChunk;
+        uint32_t my_n = 0, my_first = 0xFFFFFFFFu;
+        double sums[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) sums[j] = 0.0;
+        float4 rec[kBlkPer];
+#pragma unroll
+        for (int j = 0; j < kBlkPer; ++j) rec[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lo < hi) {
+#pragma unroll
+            for (int j = 0; j < kBlkPer; ++j) rec[j] = recs[min(lo + (uint32_t)(j * T + tid), hi - 1u)];
+        }
+        for (uint32_t ch = 0; ch < n_chunks; ++ch) {
+            const uint32_t par = ch & 1u, c0 = lo + ch * kBlkChunk;
+            uint32_t slot_rank[kBlkPer];        // slot << 16 | rank inside the slot; kBlkNone: the record is not added
+#pragma unroll
+            for (int j = 0; j < kBlkPer; ++j) {
+                bool use = c0 + (uint32_t)(j * T + tid) < hi;
+                bool und = false;
+                float fx = axis_ceil_try(rec[j].x, P.ox, P.inv_grid, und);
+                float fy = axis_ceil_try(rec[j].y, P.oy, P.inv_grid, und);
+                float fz = axis_ceil_try(rec[j].z, P.oz, P.inv_z, und);
+                if (und) {                                 // (rare: within ~2 ulp of a cell border the reference's own divide decides)
+                    fx = ceilf(fabsf(rec[j].x - P.ox) / P.grid_len);
+                    fy = ceilf(fabsf(rec[j].y - P.oy) / P.grid_len);
+                    fz = ceilf(fabsf(rec[j].z - P.oz) / P.z_len);
+                }
+                bool ok = true;
+                int sx, sy, sz;
+                double v0, v1, v2;
+                axis_index_offset(rec[j].x, P.ox, fx, (float)kMaxXY, hx, ox, ok, sx, v0);
+                axis_index_offset(rec[j].y, P.oy, fy, (float)kMaxXY, hx, oy, ok, sy, v1);
+                axis_index_offset(rec[j].z, P.oz, fz, (float)kMaxZ, hz, oz, ok, sz, v2);
+                (void)v0; (void)v1; (void)v2;               // (recomputed by the slot's thread from the slot's centre: the same fma)
+                if (use && !ok) { atomicAdd(&L.err_range, 1u); use = false; }      // |nz| beyond the key range (x, y: the partition)
+                const uint32_t lx = (uint32_t)(contiguous_index(sx) - bx0), ly = (uint32_t)(contiguous_index(sy) - by0),
+                               lz2 = (uint32_t)(contiguous_index(sz) - K.z0);
+                if (use && ((lx >> K.shx) | (ly >> K.shy) | (lz2 >> K.shz)) != 0u) { L.miss = 1u; use = false; }      // not this block's: the build is re-run hashed
+                const uint32_t rs = (lz2 << sh_xy) | (ly << K.shx) | lx;
+                slot_rank[j] = use ? (rs << 16) | atomicAdd(&L.hist[par][rs], 1u) : kBlkNone;
             }
-            bool ok = true;
-            int sx, sy, sz;
-            double v0, v1, v2;
-            axis_index_offset(rec.x, P.ox, fx, (float)kMaxXY, hx, ox, ok, sx, v0);
-            axis_index_offset(rec.y, P.oy, fy, (float)kMaxXY, hx, oy, ok, sy, v1);
-            axis_index_offset(rec.z, P.oz, fz, (float)kMaxZ, hz, oz, ok, sz, v2);
-            if (use && !ok) { atomicAdd(&L.err_range, 1u); use = false; }      // |nz| beyond the key range (x, y: the partition)
-            const uint32_t lx = (uint32_t)(contiguous_index(sx) - bx0), ly = (uint32_t)(contiguous_index(sy) - by0),
-                           lz = (uint32_t)(contiguous_index(sz) - K.z0);
-            if (use && ((lx >> K.shx) | (ly >> K.shy) | (lz >> K.shz)) != 0u) { L.miss = 1u; use = false; }      // not this block's: the build is re-run hashed
-            const uint32_t s = (lz << sh_xy) | (ly << K.shx) | lx;
-            const uint32_t iw = __float_as_uint(rec.w);
-            uint32_t cn = 1u, cf = iw;
-            double w0 = v0, w1 = v1, w2 = v2;
-            if (__any((iw & kWeight64Flag) != 0u)) {              // (wave-uniform) weighted records: 64 or 512 identical points in one
-                cn = record_weight(iw); cf = record_index(iw);
-                const double wf = (double)cn;
-                w0 = wf * v0; w1 = wf * v1; w2 = wf * v2;
-            }
-            my_new += old_cnt == 0u ? 1u : 0u;          // (the answer of the iteration before)
-            old_cnt = 1u;
-            if (use) {
-                old_cnt = atomicAdd(&L.cnt[s], cn);
-#if GNDT_BLOCKED_FIXED
-                atomicAdd(&L.sum[0][s], fix_round(w0, scale1)); atomicAdd(&L.sum[1][s], fix_round(w1, scale1)); atomicAdd(&L.sum[2][s], fix_round(w2, scale1));
-                atomicAdd(&L.sum[3][s], fix_round(w0 * v0, scale2)); atomicAdd(&L.sum[4][s], fix_round(w0 * v1, scale2)); atomicAdd(&L.sum[5][s], fix_round(w0 * v2, scale2));
-                atomicAdd(&L.sum[6][s], fix_round(w1 * v1, scale2)); atomicAdd(&L.sum[7][s], fix_round(w1 * v2, scale2)); atomicAdd(&L.sum[8][s], fix_round(w2 * v2, scale2));
-#else
-                atomicAdd(&L.sum[0][s], w0); atomicAdd(&L.sum[1][s], w1); atomicAdd(&L.sum[2][s], w2);
-                atomicAdd(&L.sum[3][s], w0 * v0); atomicAdd(&L.sum[4][s], w0 * v1); atomicAdd(&L.sum[5][s], w0 * v2);
-                atomicAdd(&L.sum[6][s], w1 * v1); atomicAdd(&L.sum[7][s], w1 * v2); atomicAdd(&L.sum[8][s], w2 * v2);
-#endif
-                atomicMin(&L.first[s], cf);
+            lds_barrier();
+            {   // exclusive prefix of the slots' counts: by shuffles inside a wave, the wave totals added into the later waves' entries
+                const uint32_t c = L.hist[par][s];
+                uint32_t incl = c;
+                const int lane = tid & 63, wv = tid >> 6;
+                for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += t; }
+                const uint32_t wtot = (uint32_t)__shfl((int)incl, 63, 64);
+                L.hist[par][s] = incl - c;
+                if (lane > wv && lane < T / 64 && wtot) atomicAdd(&L.wpre[par][lane], wtot);
+                // (the other parity's arrays were last read before the previous chunk's walk: cleared here for the next chunk)
+                L.hist[par ^ 1u][s] = 0u;
+                if (tid < T / 64) L.wpre[par ^ 1u][tid] = 0u;
+                lds_barrier();
+#pragma unroll
+                for (int j = 0; j < kBlkPer; ++j) {
+                    const uint32_t sr = slot_rank[j];
+                    if (sr != kBlkNone) L.image[L.hist[par][sr >> 16] + L.wpre[par][sr >> 22] + (sr & 0xFFFFu)] = rec[j];
+                }
+                const uint32_t b0 = incl - c + L.wpre[par][wv];
+                // the next chunk's records: in flight during the walk
+                if (ch + 1u < n_chunks) {
+#pragma unroll
+                    for (int j = 0; j < kBlkPer; ++j) rec[j] = recs[min(c0 + kBlkChunk + (uint32_t)(j * T + tid), hi - 1u)];
+                }
+                lds_barrier();
+                // slot s's run: today's contributions (weighted records included), added in the image's order
+#pragma unroll 1
+                for (uint32_t i = b0; i < b0 + c; ++i) {
+                    const float4 r = L.image[i];
+                    const double v0 = (double)r.x - ctx, v1 = (double)r.y - cty, v2 = (double)r.z - ctz;
+                    const uint32_t iw = __float_as_uint(r.w);
+                    uint32_t cn = 1u, cf = iw;
+                    double w0 = v0, w1 = v1, w2 = v2;
+                    if (__any((iw & kWeight64Flag) != 0u)) {              // weighted records: 64 or 512 identical points in one
+                        cn = record_weight(iw); cf = record_index(iw);
+                        const double wf = (double)cn;
+                        w0 = wf * v0; w1 = wf * v1; w2 = wf * v2;
+                    }
+                    my_n += cn; my_first = min(my_first, cf);
+                    sums[0] += w0; sums[1] += w1; sums[2] += w2;
+                    sums[3] += w0 * v0; sums[4] += w0 * v1; sums[5] += w0 * v2;
+                    sums[6] += w1 * v1; sums[7] += w1 * v2; sums[8] += w2 * v2;
+                }
             }
         }
-        my_new += old_cnt == 0u ? 1u : 0u;
-        {   // the bucket's node count: per wave, one LDS atomic each
-            uint32_t w = my_new;
-            for (int off = 32; off > 0; off >>= 1) w += (uint32_t)__shfl_down((int)w, off, 64);
+        const bool live = my_n != 0u;
+        {   // the bucket's node count: per wave, one ballot and one LDS atomic
+            const uint32_t w = (uint32_t)__popcll(__ballot(live));
             if ((tid & 63) == 0 && w) atomicAdd(&L.n_nodes, w);
         }
         lds_barrier();
@@ -169,32 +193,10 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         uint32_t stage_base_reg = 0;
         if (tid == T - 1 && M) stage_base_reg = atomicAdd(&cnt->num_nodes, M);
         if (tid == 0 && L.err_range) atomicAdd(&cnt->err_key_range, L.err_range);
-        // ---- the bucket's nodes: slot s in thread s; its statistics go to registers, {first-seen, mean z} to LDS ----
-        const uint32_t s = (uint32_t)tid;
-        const uint32_t my_n = L.cnt[s], my_first = L.first[s];
-        double sums[9];
-#pragma unroll
-#if GNDT_BLOCKED_FIXED
-        for (int j = 0; j < 9; ++j) sums[j] = (double)(long long)L.sum[j][s] * (j < 3 ? inv1 : inv2);
-#else
-        for (int j = 0; j < 9; ++j) sums[j] = L.sum[j][s];
-#endif
-        const bool live = my_n != 0u;
-#if GNDT_BLOCKED_FIXED
-        if (my_n > kFixMaxCount) L.miss2 = 1u;                  // (a node of more points than the fixed-point sums are sized for: hashed buckets)
-#endif
-        const uint32_t col = s & col_mask, lz = s >> sh_xy;
-        // signed indices of this slot's node
-        const int cxi = bx0 + (int)(col & ((1u << K.shx) - 1u)), cyi = by0 + (int)(col >> K.shx), czi = K.z0 + (int)lz;
-        const int nsx = cxi >= 0 ? cxi + 1 : cxi, nsy = cyi >= 0 ? cyi + 1 : cyi, nsz = czi >= 0 ? czi + 1 : czi;
+        // ---- the bucket's nodes: slot s in thread s; its statistics are in registers, {first-seen, mean z} go to LDS ----
         const float cz = (live && my_n >= (uint32_t)P.min_points) ? node_mean_z(my_n, sums[2], axis_centre(nsz, P.oz, P.z_len)) : 0.f;
         L.fz[s] = make_uint2(my_first, __float_as_uint(cz));
         lds_barrier();
-        if (L.miss2) {                                 // (uniform; nothing of this bucket has left the workgroup but its reservation: the build is re-run)
-            if (tid == 0) atomicAdd(&pc->blk_miss, 1u);
-            lds_barrier();
-            continue;
-        }
         // ---- the column of every node: the slots that differ in the level bits — independent 8-byte reads, no search.  The thread of a
         //      column's level-0 slot walks the column whether that slot holds a node or not: its node count is what the prefix over the
         //      columns (first row of every column inside the bucket) is made of ----
