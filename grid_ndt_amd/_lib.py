@@ -110,6 +110,14 @@ def source_hash():
     return h.hexdigest()
 
 
+# hipcc flags of every translation unit of libgndt (and of the test tier's device shim of the same headers, tests/host_emulation.py)
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c",
+               "-Wno-unused-command-line-argument", "-Wno-unused-function", "-Wno-pass-failed", "-fno-slp-vectorize",
+               # the code objects drop their local symbols (rocPRIM's ~500 instantiations in gndt_api_dist carried 1 MB of them).
+               # NOT --strip-all: the HIP runtime segfaults on a code object without .symtab (measured on the MI355X box)
+               "-Xoffload-linker", "--discard-all"]
+
+
 def build_native(force=False, verbose=False):
     """Compile the HIP sources into grid_ndt_amd/csrc/libgndt.so for gfx950 (cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
@@ -120,12 +128,8 @@ def build_native(force=False, verbose=False):
     objs, procs = [], []
     for src in srcs:                       # one hipcc per translation unit, side by side (8 small jobs)
         obj = os.path.splitext(src)[0] + ".o"
-        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c",
-               "-Wno-unused-command-line-argument", "-Wno-unused-function", "-Wno-pass-failed", "-fno-slp-vectorize",
-               # the code objects drop their local symbols (rocPRIM's ~500 instantiations in gndt_api_dist carried 1 MB of them).
-               # NOT --strip-all: the HIP runtime segfaults on a code object without .symtab (measured on the MI355X box)
-               "-Xoffload-linker", "--discard-all",
-               "-I", os.path.join(_ROOT, "include"), "-I", _CSRC, "-o", obj, src] + os.environ.get("GNDT_EXTRA_CXXFLAGS", "").split()
+        cmd = ([hipcc] + HIPCC_FLAGS + ["-I", os.path.join(_ROOT, "include"), "-I", _CSRC, "-o", obj, src]
+               + os.environ.get("GNDT_EXTRA_CXXFLAGS", "").split())
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd)))

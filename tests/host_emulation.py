@@ -28,6 +28,66 @@ def shim():
     return _lib
 
 
+_DSO = os.path.join(_HERE, "_device_math_shim.so")
+_dlib = None
+DSHIM_ENTRIES = ("point_keys", "point_keys_fast", "key_offset", "centres", "finalize", "mean_z_n", "min_eigen", "jacobi",
+                 "rough_normal", "cost_angle", "cost_travel", "ints")
+
+
+def build_device_shim(so_path=_DSO, force=False):
+    """Compile tests/device_math_shim.hip with libgndt's own hipcc flags (_lib.HIPCC_FLAGS) and link it like libgndt, against the
+    HIP runtime the process shares with torch.  Cross-compiles without a GPU.  Returns the compile command."""
+    from grid_ndt_amd import _lib
+    src = os.path.join(_HERE, "device_math_shim.hip")
+    obj = os.path.splitext(so_path)[0] + ".o"
+    cmd = ([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + _lib.HIPCC_FLAGS
+           + ["-I", os.path.join(_ROOT, "include"), "-I", _lib._CSRC, "-o", obj, src] + os.environ.get("GNDT_EXTRA_CXXFLAGS", "").split())
+    deps = [src, os.path.abspath(__file__), os.path.abspath(_lib.__file__)] + \
+        [h if os.path.isabs(h) else os.path.join(_lib._CSRC, h) for h in _lib.HEADERS]
+    if force or not os.path.exists(so_path) or os.path.getmtime(so_path) < max(os.path.getmtime(d) for d in deps):
+        subprocess.check_call(cmd)
+        libdir = _lib._hip_runtime_dir()
+        tmp = so_path + ".tmp.so"
+        subprocess.check_call(["g++", "-shared", "-o", tmp, obj, "-L", libdir, "-l:libamdhip64.so", "-Wl,-rpath," + libdir,
+                               "-Wl,--no-undefined", "-Wl,--strip-all", "-lpthread", "-ldl"])
+        os.replace(tmp, so_path)
+    return cmd
+
+
+def device_shim():
+    """The device twin of shim(): dshim_<name>(host shim's arguments with device pointers, stream) -> hipError_t."""
+    global _dlib
+    if _dlib is None:
+        from grid_ndt_amd import _lib
+        _lib.lib()                   # torch's HIP runtime first: the shim must bind to the one libgndt and torch use
+        build_device_shim()
+        _dlib = C.CDLL(_DSO)
+        for name in DSHIM_ENTRIES:
+            getattr(_dlib, "dshim_" + name).restype = C.c_int
+    return _dlib
+
+
+def call(backend, name, *args):
+    """shim_<name>(*args) on the host, or dshim_<name> on the current torch stream: numpy arguments are copied to the device and,
+    after a synchronise, back into the same arrays (outputs are filled in place either way).  Other arguments go as they are."""
+    if backend == "host":
+        return getattr(shim(), "shim_" + name)(*[C.c_void_p(a.ctypes.data) if isinstance(a, np.ndarray) else a for a in args])
+    import torch
+    L = device_shim()
+    dev = {}
+    for i, a in enumerate(args):
+        if isinstance(a, np.ndarray):
+            assert a.flags.c_contiguous
+            dev[i] = torch.from_numpy(a.reshape(-1).view(np.uint8)).cuda()
+    stream = torch.cuda.current_stream()
+    rc = getattr(L, "dshim_" + name)(*[C.c_void_p(dev[i].data_ptr()) if i in dev else a for i, a in enumerate(args)],
+                                     C.c_void_p(stream.cuda_stream))
+    assert rc == 0, f"dshim_{name}: hipError {rc}"
+    stream.synchronize()
+    for i, t in dev.items():
+        args[i].reshape(-1).view(np.uint8)[:] = t.cpu().numpy()
+
+
 def unpack(keys):
     k = keys.astype(np.uint64)
     sx = ((k >> np.uint64(43)) & np.uint64(0x1FFFFF)).astype(np.int64) - (1 << 20)

@@ -50,6 +50,12 @@ int shim_level_below(int z) { return gndt::level_below(z); }
 extern "C" void shim_min_eigen(const double* S, uint64_t n, double* lam, double* vec) {
     for (uint64_t i = 0; i < n; ++i) gndt::min_eigenpair_sym3(S + 6 * i, lam[i], vec + 3 * i);
 }
+extern "C" void shim_rough_normal(const double* S, uint64_t n, float* rough, float* normal) {
+    for (uint64_t i = 0; i < n; ++i) gndt::node_rough_normal(S + 6 * i, rough[i], normal + 3 * i);
+}
+extern "C" void shim_mean_z_n(const uint32_t* cnt, const double* sum_vz, const double* cz, uint64_t n, float* out) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = gndt::node_mean_z(cnt[i], sum_vz[i], cz[i]);
+}
 extern "C" void shim_jacobi(const double* S, uint64_t n, double* evals, double* evecs) {
     for (uint64_t i = 0; i < n; ++i) {
         double ev[3], vv[3][3];
@@ -132,6 +138,12 @@ extern "C" int shim_cost(uint64_t n, const int32_t* sx, const int32_t* sy, const
     return goal_status;
 }
 
+extern "C" void shim_cost_angle(const float* n1, const float* n2, uint64_t n, float* out) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = gndt::cost_angle(n1 + 3 * i, n2 + 3 * i);
+}
+extern "C" void shim_cost_travel(const float* cur, const float* des, uint64_t n, float* out) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = gndt::cost_travel(cur + 3 * i, des + 3 * i);
+}
 
 // CollisionCheck for EVERY slope of a grid, twice: the walk over the ring (cost_collide, the restatement of map2D.h:351-474) and the
 // rounds over the whole map the device runs instead (gndt_cost.hpp, "CollisionCheck without walking rings").  walk / rounds: 1 collide,

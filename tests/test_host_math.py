@@ -1,12 +1,16 @@
 """CPU tier: the arithmetic header the HIP kernels use (gndt_math.hpp), driven through a host shim and
 numpy data movement, must reproduce the oracle: keys, counts, order, labels exact; statistics within
 the stated tolerances.  This is the order-free restatement of isSlope the kernels rely on."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
 from tests import host_emulation as he
 from grid_ndt_amd import scenes
 from tests import parity
+
+BACKENDS = ["host", pytest.param("device", marks=pytest.mark.gpu)]
 
 CASES = {
     "bridge_ground": (lambda: scenes.bridge_ground(), scenes.BRIDGE_PARAMS),
@@ -47,7 +51,18 @@ def test_shard_additivity_and_first_idx_min():
     assert np.allclose(sums, whole[3], rtol=1e-12, atol=1e-12)
 
 
-def test_keys_on_and_around_cell_boundaries_match_the_reference_arithmetic():
+def _keys(backend, name, pts, o, gl, zl):
+    """shim_<name> / dshim_<name> over fp32 points (n, 3): packed keys and ok flags."""
+    pts = np.ascontiguousarray(pts, np.float32)
+    keys = np.zeros(pts.shape[0], np.uint64)
+    ok = np.zeros(pts.shape[0], np.uint8)
+    he.call(backend, name, pts, C.c_uint64(pts.shape[0]), C.c_int(3), (C.c_float * 3)(*[float(v) for v in o]), C.c_float(gl),
+            C.c_float(zl), keys, ok)
+    return keys, ok
+
+
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_keys_on_and_around_cell_boundaries_match_the_reference_arithmetic(backend):
     """point_key must give the
     reference's (int)ceilf(fabsf(p - o) / len) (map2D.h:965-970) for points ON cell boundaries, a few ulps either
     side of them, and everywhere else — for awkward cell sizes too."""
@@ -72,16 +87,9 @@ def test_keys_on_and_around_cell_boundaries_match_the_reference_arithmetic():
         q[q == 0] = 1
         want = np.where(pts > o, q, -q)
         ok_ref = (q[:, 0] <= 65535) & (q[:, 1] <= 65535) & (q[:, 2] <= (1 << 21) - 1)
-        keys = np.zeros(pts.shape[0], np.uint64)
-        ok = np.zeros(pts.shape[0], np.uint8)
-        oc = (he.C.c_float * 3)(*[float(v) for v in o])
-        he.shim().shim_point_keys(pts.ctypes.data_as(he.C.c_void_p), he.C.c_uint64(pts.shape[0]), 3, oc, he.C.c_float(gl),
-                                  he.C.c_float(zl), keys.ctypes.data_as(he.C.c_void_p), ok.ctypes.data_as(he.C.c_void_p))
+        keys, ok = _keys(backend, "point_keys", pts, o, gl, zl)
         # the divide-free form the hot kernels run (axis_index_fast) is the same function, bit for bit
-        keys_f = np.zeros(pts.shape[0], np.uint64)
-        ok_f = np.zeros(pts.shape[0], np.uint8)
-        he.shim().shim_point_keys_fast(pts.ctypes.data_as(he.C.c_void_p), he.C.c_uint64(pts.shape[0]), 3, oc, he.C.c_float(gl),
-                                       he.C.c_float(zl), keys_f.ctypes.data_as(he.C.c_void_p), ok_f.ctypes.data_as(he.C.c_void_p))
+        keys_f, ok_f = _keys(backend, "point_keys_fast", pts, o, gl, zl)
         assert np.array_equal(ok_f, ok) and np.array_equal(keys_f[ok != 0], keys[ok != 0])
         sx, sy, sz = he.unpack(keys)
         good = ok_ref & (ok != 0)
@@ -96,7 +104,8 @@ def test_keys_on_and_around_cell_boundaries_match_the_reference_arithmetic():
             assert (abs(int(want[i, 0])), abs(int(want[i, 1])), int(want[i, 2])) == (nx, ny, z)
 
 
-def test_divide_free_key_agrees_with_the_ieee_form_on_extreme_inputs():
+@pytest.mark.parametrize("backend", BACKENDS)
+def test_divide_free_key_agrees_with_the_ieee_form_on_extreme_inputs(backend):
     """axis_index_fast vs axis_index where no numpy restatement is needed: zeros, denormals, huge values, Inf, NaN,
     points exactly on the origin planes, indices around the key-range limits."""
     rng = np.random.default_rng(11)
@@ -107,14 +116,7 @@ def test_divide_free_key_agrees_with_the_ieee_form_on_extreme_inputs():
     near = np.concatenate([near, np.nextafter(near, np.float32(np.inf)), np.nextafter(near, np.float32(-np.inf))], 0)
     pts = np.ascontiguousarray(np.concatenate([grid, near], 0), np.float32)
     for o in ((0.0, 0.0, 0.0), (0.25, -0.5, 0.05), (1e-3, 7.0, -2.0)):
-        oc = (he.C.c_float * 3)(*o)
-        out = []
-        for fn in (he.shim().shim_point_keys, he.shim().shim_point_keys_fast):
-            keys = np.zeros(pts.shape[0], np.uint64)
-            ok = np.zeros(pts.shape[0], np.uint8)
-            fn(pts.ctypes.data_as(he.C.c_void_p), he.C.c_uint64(pts.shape[0]), 3, oc, he.C.c_float(0.5), he.C.c_float(0.1),
-               keys.ctypes.data_as(he.C.c_void_p), ok.ctypes.data_as(he.C.c_void_p))
-            out.append((keys, ok))
+        out = [_keys(backend, name, pts, o, 0.5, 0.1) for name in ("point_keys", "point_keys_fast")]
         assert np.array_equal(out[0][1], out[1][1])
         good = out[0][1] != 0
         assert np.array_equal(out[0][0][good], out[1][0][good])
