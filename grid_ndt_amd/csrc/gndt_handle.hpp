@@ -7,6 +7,7 @@
 //   gndt_api_dist.hip   one global map from a sharded cloud (shard statistics, exchange, finalize from statistics)
 //   gndt_api_cost.hip   cost-map flood over the finished grid
 //   gndt_api_query.hip  batched point queries against the finished grid
+//   gndt_api_crop.hip   region crop: the columns outside (or inside) a box leave the map
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
@@ -202,6 +203,12 @@ struct gndt_handle {
         uint64_t in_cap = 0, out_cap = 0;   // bytes
         void* in = nullptr;  uint32_t *rows = nullptr, *h_bits = nullptr, *state = nullptr;
     } query;
+    // region crop (gndt_crop.hpp): the second set of result arrays the kept rows are compacted into (then swapped with out / row_ncol:
+    // same capacities), and the per-tile counts of the scan
+    struct Crop {
+        OutView spare{};  uint32_t* spare_ncol = nullptr;  uint64_t spare_cap = 0, spare_ncol_cap = 0;
+        uint32_t* tiles = nullptr;  uint64_t tiles_cap = 0;
+    } crop;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -500,5 +507,7 @@ int partition_resolve(gndt_handle* h);
 void free_cost(gndt_handle* h);
 // ---- gndt_api_query.hip ----
 void free_query(gndt_handle* h);
+// ---- gndt_api_crop.hip ----
+void free_crop(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cells, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, Robot, Stats
+from ._lib import Cells, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, Robot, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -579,6 +579,27 @@ class TwoDmap:
             self._check(self._L.gndt_query(self._h, C.c_void_p(ptr if n else 0), n, stride, m, p(rows), p(h), p(state)))
         return (rows, h, state) if cost else rows
 
+    # ---- region crop (gndt_crop*: whole columns leave the map, without their points) ----
+    CROP_MODES = {"keep_inside": 0, "drop_inside": 1}
+
+    def crop(self, lo_xy, hi_xy, keep="inside", stream=None):
+        """Drop every node of the columns outside (keep="inside": the rolling window) or inside (keep="outside") the world rectangle
+        [lo_xy, hi_xy] — the columns that hold a point of it, as the codec keys them (crop_box_from_world).  Returns the index box."""
+        if keep not in ("inside", "outside"):
+            raise ValueError('keep must be "inside" or "outside"')
+        box = crop_box_from_world(self.cloudFirst, self.gridLen, lo_xy, hi_xy)
+        self.crop_box(box, "keep_inside" if keep == "inside" else "drop_inside", stream=stream)
+        return box
+
+    def crop_box(self, box, mode="keep_inside", stream=None):
+        """The same for an inclusive box of signed column indices (sx_min, sx_max, sy_min, sy_max); mode "keep_inside" / "drop_inside"
+        (or GNDT_CROP_*).  Enqueued on `stream` (default torch's current stream); the counts are read by the next sync / export."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        m = self.CROP_MODES[mode] if isinstance(mode, str) else int(mode)
+        b = CropBox(*[int(v) for v in box])
+        self._check(self._L.gndt_crop_device(self._h, C.byref(b), m, _stream_ptr(stream)))
+
     # ---- results ----
     def sync(self):
         n, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -643,6 +664,18 @@ def trans_morton_xyz(origin, grid_len, z_len, p):
     nx, ny, sz = C.c_int32(), C.c_int32(), C.c_int32()
     rc = _lib.lib().gndt_trans_morton_xyz(o, float(grid_len), float(z_len), q, quad, C.byref(nx), C.byref(ny), C.byref(sz), key)
     return rc, key.value.decode(), nx.value, ny.value, sz.value
+
+
+def crop_box_from_world(origin, grid_len, lo_xy, hi_xy):
+    """gndt_crop_box_from_world: (sx_min, sx_max, sy_min, sy_max) of the columns holding a point of [lo_xy, hi_xy] (host, no GPU)."""
+    o = (C.c_float * 3)(*[float(v) for v in origin[:3]])
+    lo = (C.c_float * 2)(*[float(v) for v in lo_xy[:2]])
+    hi = (C.c_float * 2)(*[float(v) for v in hi_xy[:2]])
+    b = CropBox()
+    rc = _lib.lib().gndt_crop_box_from_world(o, float(grid_len), lo, hi, C.byref(b))
+    if rc:
+        raise GndtError(rc, "crop_box_from_world: lo > hi, a non-finite value or grid_len <= 0")
+    return int(b.sx_min), int(b.sx_max), int(b.sy_min), int(b.sy_max)
 
 
 def device_info(device=0):

@@ -207,7 +207,7 @@ int gndt_finalize_device(gndt_handle* h, void* hip_stream);
 /* ---- results --------------------------------------------------------------------------------- */
 /* Waits for the handle's pending work, reports counts and any deferred device-side error. */
 int gndt_sync(gndt_handle* h, uint64_t* num_nodes, uint64_t* num_columns, uint64_t* num_slopes);
-/* Device-resident SoA of the last build/finalize; valid until the next build/update/destroy. */
+/* Device-resident SoA of the last build/finalize; valid until the next build/update/remove/crop/destroy. */
 int gndt_export_device(gndt_handle* h, gndt_cells* out);
 /* Copies into caller-allocated host arrays sized from gndt_sync's num_nodes (NULL arrays skipped). */
 int gndt_export(gndt_handle* h, gndt_cells* out_host);
@@ -387,7 +387,7 @@ typedef struct gndt_cost_stats {
 } gndt_cost_stats;
 
 int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot* robot, void* hip_stream);
-/* Device-resident h (fp32) and state (u32) per result row; valid until the next build/update/compute_cost. */
+/* Device-resident h (fp32) and state (u32) per result row; valid until the next build/update/crop/compute_cost. */
 int gndt_cost_export_device(gndt_handle* h, const float** h_dev, const uint32_t** state_dev, gndt_cost_stats* stats);
 /* Copies into caller-allocated host arrays of num_nodes elements (NULL arrays skipped). */
 int gndt_cost_export(gndt_handle* h, float* h_out, uint32_t* state_out, gndt_cost_stats* stats);
@@ -415,8 +415,8 @@ int gndt_cost_export(gndt_handle* h, float* h_out, uint32_t* state_out, gndt_cos
  * device the call fails like every compute entry point.  n == 0 returns GNDT_OK and launches nothing.
  * Order: the call first finishes what gndt_compute_cost finishes (a pending build, a deferred emit, a re-run: gndt_sync), then builds
  * or reuses its column index — rebuilt after every build / update / remove, and on every call on a handle that has recorded a
- * hipGraph (a replay rewrites the map unseen) — and enqueues one kernel.  Row numbers stay valid until the next build, update, remove
- * or reset.  A sharded map answers from the rows this rank holds. */
+ * hipGraph (a replay rewrites the map unseen) — and enqueues one kernel.  Row numbers stay valid until the next build, update, remove,
+ * crop or reset.  A sharded map answers from the rows this rank holds. */
 enum { GNDT_QUERY_NODE = 0, GNDT_QUERY_NEAREST_SLOPE = 1 };
 #define GNDT_NO_ROW 0xFFFFFFFFu
 /* Device memory in and out (stride 12 or 16, like gndt_build_device); enqueued on `hip_stream` (NULL = the handle's stream, the rules
@@ -426,6 +426,42 @@ int gndt_query_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stri
 /* Host memory in and out; synchronous. */
 int gndt_query(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, int32_t mode,
                uint32_t* row_out, float* h_out, uint32_t* state_out);
+
+/* ---- region crop: whole columns leave the map, without their points -------------------------------------------------------
+ * A rolling window around a robot (keep the columns inside a box) or an area cleared for re-mapping (drop the columns inside it).
+ * The region is an inclusive box of SIGNED column indices (gndt_cells.sx / sy).  Signed indices skip 0 and point_key's axis index is
+ * monotone in the coordinate, so an index range is a contiguous strip of the world.  min > max on either axis is GNDT_ERR_INVALID.
+ *   GNDT_CROP_KEEP_INSIDE   every node whose (sx, sy) lies OUTSIDE the box leaves the map (the rolling window)
+ *   GNDT_CROP_DROP_INSIDE   every node whose (sx, sy) lies INSIDE the box leaves the map
+ * A node leaves with everything it has (count, statistics, slope, labels), whether or not it reached min_points or holds a slope.
+ * Labels only look at nodes of their own column (isSlope, map2D.h:66-108), so every surviving row is BIT-IDENTICAL in all eleven
+ * gndt_cells fields and keeps its place relative to the other survivors: the export after the crop is the export before it, filtered
+ * by (sx, sy); num_nodes, num_columns and num_slopes are recounted.  No row is finalised again.
+ * The stream position is kept: the next gndt_update* numbers its points after everything ever added, and a dropped column that
+ * receives points again is a new column (first_idx = that of its new first point).  Hence, by definition,
+ *     crop(R)  ==  gndt_remove of every point added so far that lies in a column R drops.
+ * Any map the handle holds rows for can be cropped, whatever built it.  A map held in the node table (strategies ATOMIC / TILE, maps
+ * built by gndt_update*) leaves the table as well, so updates and removes go on afterwards; the next update then re-finalises every
+ * column (as after gndt_remove).  A PARTITION-built map is cropped as rows only.  A sharded map crops the rows this rank holds.
+ * Order and lifetime:
+ *   - the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a re-run);
+ *   - the map is new: the cost map is invalid until the next gndt_compute_cost (gndt_cost_export* refuse it, as after an update), the
+ *     query index is rebuilt, and device pointers from gndt_export_device and row numbers from gndt_query* are invalid;
+ *   - a stream under hipGraph capture is refused (GNDT_ERR_INVALID: a crop is not recorded);
+ *   - a graph recorded before a crop and replayed after it is reported stale by gndt_sync (GNDT_ERR_CAPACITY, as after a buffer
+ *     reallocation): the crop moves the result arrays.  Capture again after the crop.
+ * gndt_crop_device enqueues its kernels on `hip_stream` (NULL = the handle's stream, the rules of gndt_build_device) and returns; the
+ * counts are read by the next gndt_sync.  It waits for the device only to finish pending work (the gndt_sync above).  gndt_crop is
+ * the same followed by gndt_sync. */
+enum { GNDT_CROP_KEEP_INSIDE = 0, GNDT_CROP_DROP_INSIDE = 1 };
+typedef struct { int32_t sx_min, sx_max, sy_min, sy_max; } gndt_crop_box;
+int gndt_crop_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, void* hip_stream);
+int gndt_crop(gndt_handle* h, const gndt_crop_box* box, int32_t mode);
+/* Host helper, no handle, no GPU: the box of the columns that hold at least one point of the world rectangle [lo, hi] (inclusive), as the
+ * codec keys them — the IEEE fp32 axis index (gndt_trans_morton_xyz's arithmetic) of lo and of hi on each axis; exact at lattice
+ * multiples (a point on a cell border belongs to the cell the codec gives it).  Ends beyond the codec's range (|index| > 65535) clamp
+ * to it.  GNDT_ERR_INVALID: a null pointer, grid_len not > 0, a non-finite value, lo > hi on an axis. */
+int gndt_crop_box_from_world(const float origin[3], float grid_len, const float lo_xy[2], const float hi_xy[2], gndt_crop_box* out);
 
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a

@@ -1,0 +1,306 @@
+"""GPU tier: region crop (gndt_crop_device / gndt_crop, TwoDmap.crop / crop_box).  On every path that writes rows the export after a crop
+is the export before it filtered by (sx, sy), bit for bit; on a table-backed map the crop equals gndt_remove of the dropped columns'
+points, before and after the next update; a rolling window over a LiDAR stream equals the oracle's map of the stream without the evicted
+points; the cost flood and the point queries work on the cropped map; captures, inverted boxes and stale graphs are handled."""
+import numpy as np
+import pytest
+
+from grid_ndt_amd import scenes
+from tests import parity
+from tests import query_ref as qr
+
+pytestmark = pytest.mark.gpu
+
+ATOMIC, PARTITION, EXACT, TWO_LEVEL, TILE, AUTO = 1, 2, 3, 4, 5, 0
+TERRAIN = scenes.TERRAIN_PARAMS
+FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
+
+
+def _handle(P, strategy=AUTO, **kw):
+    import grid_ndt_amd as g
+    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
+    m.setInterval(P["slope_interval"])
+    return m
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+
+
+def _inside(cells, box):
+    return (cells["sx"] >= box[0]) & (cells["sx"] <= box[1]) & (cells["sy"] >= box[2]) & (cells["sy"] <= box[3])
+
+
+def _filtered(cells, box, mode):
+    keep = _inside(cells, box) if mode == "keep_inside" else ~_inside(cells, box)
+    out = {k: cells[k][keep] for k in FIELDS}
+    first_rows = qr.row_ncol(cells) != 0
+    out.update(num_nodes=int(keep.sum()), num_columns=int((first_rows & keep).sum()), num_slopes=int(((cells["flags"] & 2) != 0)[keep].sum()))
+    return out
+
+
+def _assert_same(got, want):
+    for k in ("num_nodes", "num_columns", "num_slopes"):
+        assert got[k] == want[k], (k, got[k], want[k])
+    for k in FIELDS:
+        a, b = np.ascontiguousarray(got[k]), np.ascontiguousarray(want[k])
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), k     # bit for bit
+
+
+def _boxes(cells):
+    """empty result, everything kept, a single column, an edge in each quadrant (and a strip through the origin's column)"""
+    x0, x1, y0, y1 = int(cells["sx"].min()), int(cells["sx"].max()), int(cells["sy"].min()), int(cells["sy"].max())
+    r = len(cells["sx"]) // 3
+    one = (int(cells["sx"][r]), int(cells["sx"][r]), int(cells["sy"][r]), int(cells["sy"][r]))
+    mx, my = (x0 + x1) // 2 or 1, (y0 + y1) // 2 or 1
+    return [("keep_inside", (x1 + 10, x1 + 20, y0, y1)),            # nothing left
+            ("drop_inside", (x0, x1, y0, y1)),                       # nothing left
+            ("keep_inside", (x0, x1, y0, y1)),                       # everything kept
+            ("drop_inside", (x1 + 10, x1 + 20, y0, y1)),             # everything kept
+            ("keep_inside", one), ("drop_inside", one),              # a single column
+            ("keep_inside", (mx, x1, my, y1)), ("drop_inside", (x0, mx, my, y1)),
+            ("keep_inside", (x0, mx, y0, my)), ("drop_inside", (mx, x1, y0, my)),
+            ("keep_inside", (-1, 1, y0, y1)), ("drop_inside", (x0, x1, -1, 1))]
+
+
+def _path(name):
+    """-> a function that builds the map of path `name` on a fresh handle and returns it"""
+    if name in ("atomic", "partition", "exact", "two_level"):
+        cloud = scenes.terrain_cloud(300_000)
+        strategy = {"atomic": ATOMIC, "partition": PARTITION, "exact": EXACT, "two_level": TWO_LEVEL}[name]
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(TERRAIN, strategy)
+            m.setCloudFirst(cloud[0])
+            m.create2DMap("slope", t)
+            return m
+        return make
+    if name == "tile":
+        cloud, P = scenes.depth_frame(), scenes.DEPTH_PARAMS
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(P, TILE)
+            m.setCloudFirst(cloud[0])
+            m.create2DMap("slope", t)
+            assert m.STRATEGY_NAMES[m.last_strategy()] == "tile"
+            return m
+        return make
+    if name == "blocked":
+        P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
+        cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(P)
+            m.setCloudFirst(cloud[0])
+            for _ in range(2):
+                m.create2DMap("slope", t)
+                m.sync()
+            assert m.STRATEGY_NAMES[m.last_strategy()] == "partition_blocked"
+            return m
+        return make
+    cloud = scenes.terrain_cloud(240_000)
+    cuts = [1, 90_000, 170_000, cloud.shape[0]]
+
+    def make():
+        m = _handle(TERRAIN, ATOMIC)
+        m.setCloudFirst(cloud[0])
+        if name == "deferred":
+            m.set_deferred_emit(True)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            m.change2DMap("slope", _dev(cloud[a:b]))
+        if name == "removed":
+            m.del2DMap("slope", _dev(cloud[170_000:]))
+        return m
+    return make
+
+
+@pytest.mark.parametrize("name", ["atomic", "partition", "exact", "two_level", "blocked", "tile", "updates", "deferred", "removed"])
+def test_crop_is_the_filtered_export(name):
+    make = _path(name)
+    m = make()
+    before = m.export()
+    assert before["num_nodes"] > 100
+    boxes = _boxes(before)
+    for mode, box in boxes:
+        m = make()
+        mine = m.export()          # (fp64 atomics add in any order: the rows of another build may differ in the last bits)
+        m.crop_box(box, mode)
+        _assert_same(m.export(), _filtered(mine, box, mode))
+    # two crops in a row on one handle: the second filters the first
+    m = make()
+    mine = m.export()
+    b1, b2 = boxes[6][1], boxes[9][1]
+    m.crop_box(b1, "keep_inside")
+    m.crop_box(b2, "drop_inside")
+    _assert_same(m.export(), _filtered(_filtered(mine, b1, "keep_inside"), b2, "drop_inside"))
+
+
+def test_crop_equals_remove_of_the_dropped_columns_points():
+    """handle A crops, handle B removes every point of the dropped columns: the same map; then both take the next frame, which falls
+    partly into the dropped columns (new columns, first_idx of their new first points): the same map again"""
+    P = TERRAIN
+    frames = scenes.terrain_frames(4, points_per_frame=32_768)
+    origin = frames[0]
+    body = frames[1:96_000]
+    nxt = frames[96_000:]
+    sx, sy, _, _, ok = qr.keys(body, origin, P["grid_len"], P["z_len"])
+    assert ok.all()
+    for mode in ("keep_inside", "drop_inside"):
+        box = (int(np.percentile(sx, 30)) or 1, int(np.percentile(sx, 80)) or 1, int(np.percentile(sy, 20)) or 1, int(np.percentile(sy, 70)) or 1)
+        inb = (sx >= box[0]) & (sx <= box[1]) & (sy >= box[2]) & (sy <= box[3])
+        dropped = ~inb if mode == "keep_inside" else inb
+        assert 0 < dropped.sum() < len(body)
+        # twins with the same fp64 sums (fp64 atomics add in any order: two builds may differ in the last bits): the statistics of one
+        # build merged into two tables, the stream position raised to the body's length
+        x = _handle(P, ATOMIC)
+        x.setCloudFirst(origin)
+        x.change2DMap("slope", _dev(body))
+        st = {k: v.clone() for k, v in x.stats_export().items()}
+        a, b = _handle(P, ATOMIC), _handle(P, ATOMIC)
+        for m in (a, b):
+            m.setCloudFirst(origin)
+            m.reset("slope")
+            m.stats_merge(st["key"], st["sums"], st["count"], st["first_idx"])
+            m.accumulate("slope", _dev(np.zeros((0, 3), np.float32)), first_idx_base=len(body))
+            m.finalize()
+        _assert_same(a.export(), b.export())
+        a.crop_box(box, mode)
+        b.del2DMap("slope", _dev(body[dropped]))
+        ea, eb = a.export(), b.export()
+        _assert_same(ea, eb)
+        assert 0 < ea["num_nodes"] < x.export()["num_nodes"]
+        for m in (a, b):
+            m.change2DMap("slope", _dev(nxt))
+        ea, eb = a.export(), b.export()
+        for k in ("num_nodes", "num_columns", "num_slopes"):
+            assert ea[k] == eb[k]
+        for k in ("sx", "sy", "sz", "count", "first_idx", "flags"):
+            assert np.array_equal(ea[k], eb[k]), k
+        # ... which is the oracle's map of the stream without the dropped points (first_idx through the original positions)
+        alive = np.concatenate([~dropped, np.ones(len(nxt), bool)])
+        ref = parity.ref_from_cloud(np.concatenate([origin[None], body[~dropped], nxt]), P)
+        ref["first_idx"] = np.flatnonzero(alive)[ref["first_idx"].astype(np.int64)].astype(ref["first_idx"].dtype)
+        parity.assert_parity(a.export(), ref)
+
+
+def test_rolling_window_over_a_lidar_stream():
+    """update every frame, crop to a box around the current pose every third frame: the final map is the oracle's map of the stream
+    with the evicted points taken out; the map stays inside the window and its node count bounded"""
+    import grid_ndt_amd as g
+    P = TERRAIN
+    n_frames, ppf, k, r = 15, 16_384, 3, 18.0
+    stream = scenes.terrain_frames(n_frames + 1, points_per_frame=ppf)
+    origin = stream[0]
+    pts = stream[1:1 + n_frames * ppf]
+    sx, sy, _, _, ok = qr.keys(pts, origin, P["grid_len"], P["z_len"])
+    assert ok.all()
+    alive = np.ones(len(pts), bool)
+    m = _handle(P, ATOMIC)
+    m.setCloudFirst(origin)
+    nodes_after_crop = []
+    for f in range(n_frames):
+        m.change2DMap("slope", _dev(pts[f * ppf:(f + 1) * ppf]))
+        if (f + 1) % k == 0:
+            px, py = scenes._pose_xy(np.int64(f), 200.0, 14.0)
+            box = m.crop((px - r, py - r), (px + r, py + r), keep="inside")
+            assert box == g.crop_box_from_world(origin, P["grid_len"], (px - r, py - r), (px + r, py + r))
+            seen = slice(0, (f + 1) * ppf)
+            inb = (sx[seen] >= box[0]) & (sx[seen] <= box[1]) & (sy[seen] >= box[2]) & (sy[seen] <= box[3])
+            alive[seen] &= inb
+            cells = m.export()
+            assert _inside(cells, box).all()
+            nodes_after_crop.append(cells["num_nodes"])
+    assert not alive.all() and alive.any()
+    ref = parity.ref_from_cloud(np.concatenate([origin[None], pts[alive]]), P)
+    ref["first_idx"] = np.flatnonzero(alive)[ref["first_idx"].astype(np.int64)].astype(ref["first_idx"].dtype)
+    parity.assert_parity(m.export(), ref)
+    whole = parity.ref_from_cloud(stream[:1 + n_frames * ppf], P)["num_nodes"]
+    assert max(nodes_after_crop) < 0.6 * whole, (nodes_after_crop, whole)
+
+
+def test_consumers_after_a_crop():
+    """cost flood = the oracle's on the cropped export (h and state bit for bit); NODE queries of points in dropped columns return no row,
+    the others still name their node; the cost map of the map before the crop is refused"""
+    from oracle import oracle
+    import grid_ndt_amd as g
+    cloud, P = scenes.campus_frame(200_000), scenes.CAMPUS_PARAMS
+    m = _handle(P, ATOMIC)
+    m.setCloudFirst(cloud[0])
+    m.create2DMap(P["demand"], _dev(cloud[1:]))
+    cells = m.export()
+    slopes = np.flatnonzero(cells["flags"] & 2)
+    goal = tuple(float(v) for v in cells["mean"][slopes[len(slopes) // 2]])
+    m.computeCost(goal, robot={"radius": 0.25})
+    box = g.crop_box_from_world(cloud[0], P["grid_len"], (goal[0] - 25.0, goal[1] - 20.0), (goal[0] + 15.0, goal[1] + 30.0))
+    m.crop_box(box, "keep_inside")
+    with pytest.raises(g.GndtError) as e:
+        m.cost_export()
+    assert e.value.code == 1
+    n_before = cells["num_nodes"]
+    cells = m.export()
+    assert 0 < cells["num_nodes"] < n_before
+    st = m.computeCost(goal, robot={"radius": 0.25})
+    got = m.cost_export()
+    want = oracle.compute_cost(cells, cloud[0], P["grid_len"], P["z_len"], P["slope_interval"], goal, demand=P["demand"], robot={"radius": 0.25})
+    assert st["rc"] == want["rc"] == 0
+    assert np.array_equal(got["h"].view(np.uint32), np.asarray(want["h"], np.float32).view(np.uint32)) and (got["state"] == want["state"]).all()
+    pts = cloud[1:]
+    sx, sy, _, _, _ = qr.keys(pts, cloud[0], P["grid_len"], P["z_len"])
+    inb = (sx >= box[0]) & (sx <= box[1]) & (sy >= box[2]) & (sy <= box[3])
+    assert 0 < inb.sum() < len(pts)
+    rows = m.query(_dev(pts)).cpu().numpy().astype(np.int64)
+    assert (rows[~inb] == qr.NO_ROW).all()
+    assert (rows[inb] == qr.node_rows(cells, pts[inb], cloud[0], P["grid_len"], P["z_len"])).all() and (rows[inb] >= 0).all()
+    assert (np.bincount(rows[inb], minlength=cells["num_nodes"]) == cells["count"]).all()
+
+
+def test_lifetime_capture_stale_graph_and_inverted_box():
+    """a crop on a capturing stream is refused; an update graph recorded before a crop and replayed after it is reported stale, never
+    a silently wrong map; an inverted box leaves the map untouched"""
+    import torch
+    import grid_ndt_amd as g
+    P = TERRAIN
+    frames = scenes.terrain_frames(3, points_per_frame=32_768)
+    origin, f0, f1 = frames[0], frames[1:32_769], frames[32_769:65_537]
+    m = _handle(P, ATOMIC, max_points_hint=200_000, max_nodes_hint=200_000)
+    m.setCloudFirst(origin)
+    m.change2DMap("slope", _dev(f0))
+    before = m.export()
+    box = (int(before["sx"].min()), int(before["sx"].max()) // 2 or 1, int(before["sy"].min()), int(before["sy"].max()))
+    # inverted boxes: refused, nothing changes
+    for bad in ((5, 4, box[2], box[3]), (box[0], box[1], 3, -3)):
+        with pytest.raises(g.GndtError) as e:
+            m.crop_box(bad, "keep_inside")
+        assert e.value.code == 1
+    with pytest.raises(g.GndtError) as e:
+        m.crop_box(box, 7)
+    assert e.value.code == 1
+    _assert_same(m.export(), before)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        buf = _dev(f1)
+        s.wait_stream(torch.cuda.default_stream())
+        graph = torch.cuda.CUDAGraph()
+        with g.graph_capture(graph, s):
+            m.change2DMap("slope", buf, s)
+        # a crop is not recorded
+        gr2 = torch.cuda.CUDAGraph()
+        with pytest.raises(g.GndtError) as e:
+            with g.graph_capture(gr2, s):
+                m.crop_box(box, "keep_inside", stream=s)
+        assert e.value.code == 1
+        del gr2
+        s.synchronize()
+        m.crop_box(box, "keep_inside", stream=s)
+        cropped = m.export()
+        _assert_same(cropped, _filtered(before, box, "keep_inside"))
+        graph.replay()
+        s.synchronize()
+        with pytest.raises(g.GndtError) as e:
+            m.sync()
+        assert e.value.code == 5 and "replay" in str(e.value)
+    del graph
