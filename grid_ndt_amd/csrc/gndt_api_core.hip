@@ -323,6 +323,7 @@ void gndt_destroy(gndt_handle* h) {
     free_part(h);
     free_cost(h);
     free_query(h);
+    free_raster(h);
     free_crop(h);
     void* ptrs[] = {h->out.sx, h->out.sy, h->out.sz, h->out.count, h->out.first_idx, h->out.mean, h->out.cov,
                     h->out.rough, h->out.normal, h->out.flags, h->st_key, h->st_sums, h->st_count, h->st_first,

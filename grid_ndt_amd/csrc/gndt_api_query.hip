@@ -16,28 +16,13 @@ void free_query(gndt_handle* h) {
     q = gndt_handle::Query{};
 }
 
-namespace {
-
-// A query buffer of `bytes` (the query's own: never recorded into a graph, so plainly freed — not retired)
-template <typename T>
-int query_alloc(gndt_handle* h, T*& p, uint64_t bytes) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    HIP_TRY(h, hipMalloc(&p, bytes));
-    return GNDT_OK;
-}
-
-// Arguments, the finished map, the cost map when asked for (n == 0 stops there), the stream; then the column index for the current map.
-int query_prepare(gndt_handle* h, const void* xyz, size_t n, size_t stride_bytes, int32_t mode, const uint32_t* row_out, bool gather,
-                  hipStream_t s) {
-    if (n && !xyz) { h->err = "gndt_query: null points"; return GNDT_ERR_INVALID; }
-    if (n && !row_out) { h->err = "gndt_query: null row_out"; return GNDT_ERR_INVALID; }
-    if (mode != GNDT_QUERY_NODE && mode != GNDT_QUERY_NEAREST_SLOPE) { h->err = "gndt_query: unknown mode"; return GNDT_ERR_INVALID; }
-    if (stride_bytes != 12 && stride_bytes != 16) { h->err = "gndt_query: stride_bytes must be 12 or 16"; return GNDT_ERR_INVALID; }
+// What a query or a raster does before its kernel (the rules of include/gndt.h "point queries", stated once for both): no capture,
+// a finished map (gndt_sync first finishes a pending build, a deferred emit, a re-run), a cost map of the current grid when gathered.
+int query_sync(gndt_handle* h, bool gather, hipStream_t s, const char* capture_err) {
     {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &cap);
-        if (cap != hipStreamCaptureStatusNone) { h->err = "gndt_query: a query is not recorded into a hipGraph"; return GNDT_ERR_INVALID; }
+        if (cap != hipStreamCaptureStatusNone) { h->err = capture_err; return GNDT_ERR_INVALID; }
     }
     { const int prc = partition_resolve(h); if (prc) return prc; }
     if (!h->results_valid) { h->err = "no finished build to query (the lookups run on the map create2DMap made, receiver.cpp:160, 171)"; return GNDT_ERR_INVALID; }
@@ -47,8 +32,12 @@ int query_prepare(gndt_handle* h, const void* xyz, size_t n, size_t stride_bytes
         h->err = "no cost map for the current grid (call gndt_compute_cost after the build)";
         return GNDT_ERR_INVALID;
     }
-    if (n == 0) return GNDT_OK;
-    rc = use_stream(h, s);
+    return GNDT_OK;
+}
+
+// The stream, then the column index for the current map (h->query: ctab_key / ctab_val / ctab_mask)
+int query_index(gndt_handle* h, hipStream_t s) {
+    int rc = use_stream(h, s);
     if (rc) return rc;
     // The column index: kept while the map is the one it was built for.  Not on a handle that has recorded a hipGraph: a replay rewrites
     // the map without the host's serial moving (gndt_compute_cost keeps its tables under the same rule).
@@ -77,6 +66,42 @@ int query_prepare(gndt_handle* h, const void* xyz, size_t n, size_t stride_bytes
     return GNDT_OK;
 }
 
+// The rows, the column index and the cost map as the query kernels read them
+QueryView query_view(gndt_handle* h) {
+    QueryView Q{};
+    Q.V.sx = h->out.sx; Q.V.sy = h->out.sy; Q.V.sz = h->out.sz;
+    Q.V.mean = h->out.mean; Q.V.flags = h->out.flags; Q.V.rough = h->out.rough;
+    Q.V.row_ncol = h->part.row_ncol;
+    Q.V.ctab_key = h->query.ctab_key; Q.V.ctab_val = h->query.ctab_val; Q.V.ctab_mask = h->query.ctab_mask;
+    Q.h_bits = h->cost.h_bits; Q.state = h->cost.state;
+    Q.ox = h->origin[0]; Q.oy = h->origin[1]; Q.oz = h->origin[2];
+    Q.grid_len = h->P.grid_len; Q.z_len = h->P.z_len;
+    return Q;
+}
+
+namespace {
+
+// A query buffer of `bytes` (the query's own: never recorded into a graph, so plainly freed — not retired)
+template <typename T>
+int query_alloc(gndt_handle* h, T*& p, uint64_t bytes) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    HIP_TRY(h, hipMalloc(&p, bytes));
+    return GNDT_OK;
+}
+
+// Arguments, the finished map, the cost map when asked for (n == 0 stops there), the stream; then the column index for the current map.
+int query_prepare(gndt_handle* h, const void* xyz, size_t n, size_t stride_bytes, int32_t mode, const uint32_t* row_out, bool gather,
+                  hipStream_t s) {
+    if (n && !xyz) { h->err = "gndt_query: null points"; return GNDT_ERR_INVALID; }
+    if (n && !row_out) { h->err = "gndt_query: null row_out"; return GNDT_ERR_INVALID; }
+    if (mode != GNDT_QUERY_NODE && mode != GNDT_QUERY_NEAREST_SLOPE) { h->err = "gndt_query: unknown mode"; return GNDT_ERR_INVALID; }
+    if (stride_bytes != 12 && stride_bytes != 16) { h->err = "gndt_query: stride_bytes must be 12 or 16"; return GNDT_ERR_INVALID; }
+    const int rc = query_sync(h, gather, s, "gndt_query: a query is not recorded into a hipGraph");
+    if (rc || n == 0) return rc;
+    return query_index(h, s);
+}
+
 template <int ILP, int MODE, bool GATHER>
 void query_launch(const QueryView& Q, const float* xyz, uint32_t sf, uint64_t n, uint32_t* row_out, float* h_out, uint32_t* state_out,
                   hipStream_t s) {
@@ -95,14 +120,7 @@ void query_launch_ilp(int ilp, const QueryView& Q, const float* xyz, uint32_t sf
 
 int query_run(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, int32_t mode, uint32_t* row_out, float* h_out,
               uint32_t* state_out, hipStream_t s) {
-    QueryView Q{};
-    Q.V.sx = h->out.sx; Q.V.sy = h->out.sy; Q.V.sz = h->out.sz;
-    Q.V.mean = h->out.mean; Q.V.flags = h->out.flags;
-    Q.V.row_ncol = h->part.row_ncol;
-    Q.V.ctab_key = h->query.ctab_key; Q.V.ctab_val = h->query.ctab_val; Q.V.ctab_mask = h->query.ctab_mask;
-    Q.h_bits = h->cost.h_bits; Q.state = h->cost.state;
-    Q.ox = h->origin[0]; Q.oy = h->origin[1]; Q.oz = h->origin[2];
-    Q.grid_len = h->P.grid_len; Q.z_len = h->P.z_len;
+    const QueryView Q = query_view(h);
     const float* xyz = static_cast<const float*>(xyz_dev);
     const uint32_t sf = (uint32_t)(stride_bytes / 4);
     const int ilp = tuning().query_ilp;

@@ -24,6 +24,8 @@
 
 #include "gndt.h"
 
+namespace gndt { struct QueryView; }   // gndt_query.hpp
+
 // Debug build (-DGNDT_POISON): every device allocation is filled with 0xA5 before it is handed out.  A fresh process gets zeroed
 // pages from hipMalloc, which hides reads of memory the library never initialised; a process that has freed and reallocated for a
 // while does not (tools/fuzz_graph.py found two such reads only after ~100 handles).  The tests run under this build as well.
@@ -203,6 +205,10 @@ struct gndt_handle {
         uint64_t in_cap = 0, out_cap = 0;   // bytes
         void* in = nullptr;  uint32_t *rows = nullptr, *h_bits = nullptr, *state = nullptr;
     } query;
+    // raster export (gndt_api_raster.hip): the device scratch gndt_raster fills and copies from (the layers side by side), grown on demand
+    struct Raster {
+        void* scratch = nullptr;  uint64_t cap = 0;     // bytes
+    } raster;
     // region crop (gndt_crop.hpp): the second set of result arrays the kept rows are compacted into (then swapped with out / row_ncol:
     // same capacities), and the per-tile counts of the scan
     struct Crop {
@@ -507,6 +513,13 @@ int partition_resolve(gndt_handle* h);
 void free_cost(gndt_handle* h);
 // ---- gndt_api_query.hip ----
 void free_query(gndt_handle* h);
+// the steps before a query's or a raster's kernel: capture, finished map, cost map when gathered (gndt_sync on the way); then the stream
+// and the column index of the current map (h->query); and the view of rows, index and cost map the kernels read
+int query_sync(gndt_handle* h, bool gather, hipStream_t s, const char* capture_err);
+int query_index(gndt_handle* h, hipStream_t s);
+gndt::QueryView query_view(gndt_handle* h);
+// ---- gndt_api_raster.hip ----
+void free_raster(gndt_handle* h);
 // ---- gndt_api_crop.hip ----
 void free_crop(gndt_handle* h);
 

@@ -24,6 +24,7 @@ namespace gndt {
 
 constexpr uint32_t kNoRow = 0xFFFFFFFFu;                 // GNDT_NO_ROW
 constexpr int kQueryNode = 0, kQueryNearestSlope = 1;    // GNDT_QUERY_NODE, GNDT_QUERY_NEAREST_SLOPE
+constexpr int kWalkLowest = 2, kWalkHighest = 3;         // the raster's other selections (GNDT_RASTER_LOWEST / _HIGHEST)
 constexpr uint32_t kQueryChunk = 4;                      // rows of a column read together (S2: 4 levels per column)
 
 struct QueryView {
@@ -77,14 +78,19 @@ struct QueryBest {
 };
 
 // One row of the query's column.  NODE: the row whose level is the point's (map_xy's view: any node, with or without statistics or a
-// slope).  NEAREST_SLOPE: among the rows with a slope, the least fabsf(mean_z - z) in fp32, a tie going to the smaller sz.
+// slope).  NEAREST_SLOPE: among the rows with a slope, the least fabsf(mean_z - z) in fp32, a tie going to the smaller sz.  The raster's
+// other selections walk the same rows (k_raster): LOWEST / HIGHEST, the slope with the least / greatest sz (a column's levels differ).
 template <int MODE>
 GNDT_HD void query_eval(uint32_t t, int sz_t, uint32_t flags_t, float mz_t, const QueryKey& k, float pz, QueryBest& b) {
     if (MODE == kQueryNode) {
         if (b.row == kNoRow && sz_t == k.sz) b.row = t;
     } else if (flags_t & 2u) {
-        const float d = fabsf(mz_t - pz);
-        if (b.row == kNoRow || d < b.d || (d == b.d && sz_t < b.sz)) { b.row = t; b.d = d; b.sz = sz_t; }
+        if (MODE == kQueryNearestSlope) {
+            const float d = fabsf(mz_t - pz);
+            if (b.row == kNoRow || d < b.d || (d == b.d && sz_t < b.sz)) { b.row = t; b.d = d; b.sz = sz_t; }
+        } else if (b.row == kNoRow || (MODE == kWalkLowest ? sz_t < b.sz : sz_t > b.sz)) {
+            b.row = t; b.sz = sz_t;
+        }
     }
 }
 
@@ -100,12 +106,20 @@ GNDT_HD void query_chunk(const QueryView& Q, uint32_t c, uint32_t ncol, uint32_t
         if (from + u < ncol) {
             const uint32_t t = c + from + u;
             szv[u] = Q.V.sz[t];
-            if (MODE == kQueryNearestSlope) { fl[u] = Q.V.flags[t]; mz[u] = Q.V.mean[3 * (size_t)t + 2]; }
+            if (MODE != kQueryNode) fl[u] = Q.V.flags[t];
+            if (MODE == kQueryNearestSlope) mz[u] = Q.V.mean[3 * (size_t)t + 2];
         }
     }
 #pragma unroll
     for (uint32_t u = 0; u < kQueryChunk; ++u)
         if (from + u < ncol) query_eval<MODE>(c + from + u, szv[u], fl[u], mz[u], k, pz, b);
+}
+
+// The column's rows after the first chunk (a NODE walk stops at its node)
+template <int MODE>
+GNDT_HD void query_rest(const QueryView& Q, uint32_t c, uint32_t ncol, const QueryKey& k, float pz, QueryBest& b) {
+    for (uint32_t from = kQueryChunk; from < ncol && !(MODE == kQueryNode && b.row != kNoRow); from += kQueryChunk)
+        query_chunk<MODE>(Q, c, ncol, from, k, pz, b);
 }
 
 // Queries i0, i0 + step, ..., i0 + (ILP - 1) step (those below n): row_out[i] = the row or kNoRow; with GATHER also the cost map's h
@@ -144,9 +158,7 @@ GNDT_HD void query_points(const QueryView& Q, const float* xyz, uint32_t sf, uin
         query_chunk<MODE>(Q, c[j], ncol[j], 0u, k[j], pz[j], b[j]);
     }
 #pragma unroll
-    for (int j = 0; j < ILP; ++j)
-        for (uint32_t from = kQueryChunk; from < ncol[j] && !(MODE == kQueryNode && b[j].row != kNoRow); from += kQueryChunk)
-            query_chunk<MODE>(Q, c[j], ncol[j], from, k[j], pz[j], b[j]);
+    for (int j = 0; j < ILP; ++j) query_rest<MODE>(Q, c[j], ncol[j], k[j], pz[j], b[j]);
     uint32_t hb[ILP], st[ILP];
 #pragma unroll
     for (int j = 0; j < ILP; ++j) {                 // 5. the answers (and what the cost map holds for them)
@@ -166,6 +178,65 @@ GNDT_HD void query_points(const QueryView& Q, const float* xyz, uint32_t sf, uin
     }
 }
 
+// ---- raster export (include/gndt.h "raster export"): one pixel per column of an inclusive box of signed column indices ----------------
+// Pixel (i, j) sits at j * width + i; i runs over the box's non-zero sx ascending, j over its non-zero sy ascending.  Per pixel: the
+// column from (i, j) (integer arithmetic, no keying of a coordinate), one probe of the query's column index, the column's node count,
+// the column's rows through the query's walk (query_chunk / query_rest), then the gathers of the selected row.
+constexpr int kRasterLowest = 0, kRasterHighest = 1, kRasterNearestZ = 2;   // GNDT_RASTER_LOWEST / _HIGHEST / _NEAREST_Z
+constexpr uint32_t kRasterSlope = 1u, kRasterCost = 2u;                       // gathers compiled in: mean z / rough; cost map h / state
+
+// The i-th non-zero index >= lo on an axis (signed indices skip 0: pixels stay one grid_len apart, across the origin too)
+GNDT_HD int raster_index(int lo, uint32_t i) {
+    const int s = lo + (int)i;
+    return lo <= 0 && s >= 0 ? s + 1 : s;
+}
+
+// Pixels of the axis [lo, hi]: its non-zero integers (0 when lo > hi)
+GNDT_HD uint32_t raster_count(int lo, int hi) {
+    if (lo > hi) return 0u;
+    return (uint32_t)(hi - lo + 1) - (lo <= 0 && hi >= 0 ? 1u : 0u);
+}
+
+struct RasterOut {           // one pointer per layer, null = not written
+    uint32_t* row;
+    float *z, *rough;
+    uint32_t* nodes;
+    float* h;
+    uint32_t* state;
+};
+
+// Pixel p (< width * height) of the box whose smallest indices are (sx_lo, sy_lo).  Q.V.rough is read with kRasterSlope, Q.h_bits and
+// Q.state with kRasterCost.
+template <int MODE, uint32_t GATHER>
+GNDT_HD void raster_pixel(const QueryView& Q, int sx_lo, int sy_lo, uint32_t width, float z_ref, uint32_t p, const RasterOut& o) {
+    constexpr int W = MODE == kRasterLowest ? kWalkLowest : MODE == kRasterHighest ? kWalkHighest : kQueryNearestSlope;
+    const uint32_t j = p / width, i = p - j * width;
+    QueryKey k;
+    k.sx = raster_index(sx_lo, i); k.sy = raster_index(sy_lo, j); k.sz = 0; k.ok = true;
+    const uint32_t slot = query_slot(Q, k);
+    const uint64_t skey = Q.V.ctab_key[slot];
+    const uint32_t sval = Q.V.ctab_val[slot];
+    const uint32_t c = query_column(Q, k, skey, sval);
+    const uint32_t ncol = c != kNoColumn ? Q.V.row_ncol[c] : 0u;
+    QueryBest b;
+    b.row = kNoRow; b.d = 0.f; b.sz = 0;
+    query_chunk<W>(Q, c, ncol, 0u, k, z_ref, b);
+    query_rest<W>(Q, c, ncol, k, z_ref, b);
+    uint32_t zb = 0x7FC00000u, rb = 0x7FC00000u, hb = 0x7F7FFFFFu, st = 0u;     // quiet NaN, quiet NaN, FLT_MAX, untouched
+    if (b.row != kNoRow) {
+        if ((GATHER & kRasterSlope) && o.z) zb = float_bits(Q.V.mean[3 * (size_t)b.row + 2]);
+        if ((GATHER & kRasterSlope) && o.rough) rb = float_bits(Q.V.rough[b.row]);
+        if ((GATHER & kRasterCost) && o.h) hb = Q.h_bits[b.row];
+        if ((GATHER & kRasterCost) && o.state) st = Q.state[b.row];
+    }
+    if (o.row) o.row[p] = b.row;
+    if (o.nodes) o.nodes[p] = ncol;
+    if ((GATHER & kRasterSlope) && o.z) o.z[p] = bits_float(zb);
+    if ((GATHER & kRasterSlope) && o.rough) o.rough[p] = bits_float(rb);
+    if ((GATHER & kRasterCost) && o.h) o.h[p] = bits_float(hb);
+    if ((GATHER & kRasterCost) && o.state) o.state[p] = st;
+}
+
 #if defined(__HIPCC__)
 // One thread: ILP queries per pass of a grid-stride loop (any n; the grid is sized to what the chip holds at once)
 template <int ILP, int MODE, bool GATHER>
@@ -174,6 +245,13 @@ static __global__ void __launch_bounds__(256) k_query(QueryView Q, const float* 
     const uint64_t gsz = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += gsz * ILP)
         query_points<ILP, MODE, GATHER>(Q, xyz, sf, i0, gsz, n, row_out, h_out, state_out);
+}
+
+// One thread per pixel, grid-stride beyond what the chip holds at once: a wave stores 64 consecutive pixels of every layer
+template <int MODE, uint32_t GATHER>
+static __global__ void __launch_bounds__(256) k_raster(QueryView Q, int sx_lo, int sy_lo, uint32_t width, uint32_t n, float z_ref, RasterOut o) {
+    const uint32_t gsz = gridDim.x * blockDim.x;     // (n <= 2^31 and gsz <= 2^19: p + gsz does not wrap)
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gsz) raster_pixel<MODE, GATHER>(Q, sx_lo, sy_lo, width, z_ref, p, o);
 }
 #endif
 

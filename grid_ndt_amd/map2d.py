@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cells, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, Robot, Stats
+from ._lib import Cells, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -600,6 +600,51 @@ class TwoDmap:
         b = CropBox(*[int(v) for v in box])
         self._check(self._L.gndt_crop_device(self._h, C.byref(b), m, _stream_ptr(stream)))
 
+    # ---- raster export (gndt_raster*: one pixel per column of a box, the reference's showBottom / showSlopeList, map2D.h:980-1284) ----
+    RASTER_MODES = {"lowest": 0, "highest": 1, "nearest_z": 2}
+    RASTER_LAYERS = {"row": np.int32, "z": np.float32, "rough": np.float32, "nodes": np.int32, "h": np.float32, "state": np.int32}
+
+    def raster(self, box, mode="lowest", z_ref=None, layers=("row", "z"), stream=None, host=False):
+        """The map over the inclusive box of signed column indices (sx_min, sx_max, sy_min, sy_max) — crop_box_from_world turns a world
+        rectangle into one — as a (height, width) image per layer, row-major from the smallest (sx, sy) (index 0 skipped: raster_shape).
+        Per pixel the slope of its column with the least sz (mode "lowest"), the greatest ("highest") or the mean z nearest z_ref
+        ("nearest_z", query's "nearest_slope" rule).  Layers: "row" (int32, -1 where the column has no slope: query's rows), "z" and
+        "rough" (float32, NaN there), "nodes" (int32, the column's node count, 0 = not observed), "h" (float32, FLT_MAX there) and
+        "state" (int32, 0 there) of the cost map.  Torch tensors on the handle's device enqueued on `stream` (default torch's current
+        stream), or numpy arrays through gndt_raster with host=True.  Also returns x0, y0 (the world centre of pixel (0, 0)) and res."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        m = self.RASTER_MODES[mode] if isinstance(mode, str) else int(mode)
+        if z_ref is None:
+            z_ref = float("nan") if m == self.RASTER_MODES["nearest_z"] else 0.0
+        layers = tuple(layers)
+        for name in layers:
+            if name not in self.RASTER_LAYERS:
+                raise ValueError(f"unknown raster layer {name!r} (one of {', '.join(self.RASTER_LAYERS)})")
+        b = CropBox(*[int(v) for v in box])
+        w, ht = raster_shape(box)
+        out = {}
+        if host:
+            for name in layers:
+                out[name] = np.empty((ht, w), self.RASTER_LAYERS[name])
+            ptr = lambda name: C.c_void_p(out[name].ctypes.data if name in out else 0)
+        else:
+            import torch
+            tdt = {np.int32: torch.int32, np.float32: torch.float32}
+            for name in layers:
+                out[name] = torch.empty((ht, w), dtype=tdt[self.RASTER_LAYERS[name]], device=f"cuda:{self.device}")
+            ptr = lambda name: C.c_void_p(out[name].data_ptr() if name in out else 0)
+        L = RasterLayers(*[ptr(name) for name in ("row", "z", "rough", "nodes", "h", "state")])
+        if host:
+            self._check(self._L.gndt_raster(self._h, C.byref(b), m, float(z_ref), C.byref(L)))
+        else:
+            self._check(self._L.gndt_raster_device(self._h, C.byref(b), m, float(z_ref), C.byref(L), _stream_ptr(stream)))
+        sx0 = _first_nonzero(b.sx_min)
+        sy0 = _first_nonzero(b.sy_min)
+        out.update(x0=_column_centre(self.cloudFirst[0], self.gridLen, sx0), y0=_column_centre(self.cloudFirst[1], self.gridLen, sy0),
+                   res=self.gridLen)
+        return out
+
     # ---- results ----
     def sync(self):
         n, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -676,6 +721,26 @@ def crop_box_from_world(origin, grid_len, lo_xy, hi_xy):
     if rc:
         raise GndtError(rc, "crop_box_from_world: lo > hi, a non-finite value or grid_len <= 0")
     return int(b.sx_min), int(b.sx_max), int(b.sy_min), int(b.sy_max)
+
+
+def raster_shape(box):
+    """gndt_raster_shape: (width, height) of the image of an inclusive box of signed column indices — the non-zero integers of each
+    axis (host, no GPU)."""
+    b = CropBox(*[int(v) for v in box])
+    w, h = C.c_uint32(), C.c_uint32()
+    rc = _lib.lib().gndt_raster_shape(C.byref(b), C.byref(w), C.byref(h))
+    if rc:
+        raise GndtError(rc, "raster_shape: min > max, an index beyond +-65535, an axis without a non-zero index or more than 2^31 pixels")
+    return int(w.value), int(h.value)
+
+
+def _first_nonzero(lo):
+    return 1 if lo == 0 else int(lo)
+
+
+def _column_centre(o, grid_len, s):
+    """World coordinate of the centre of column s on an axis (no index 0): o + sign(s) * (|s| - 0.5) * grid_len"""
+    return float(o) + (1.0 if s > 0 else -1.0) * (abs(s) - 0.5) * float(grid_len)
 
 
 def device_info(device=0):

@@ -463,6 +463,45 @@ int gndt_crop(gndt_handle* h, const gndt_crop_box* box, int32_t mode);
  * to it.  GNDT_ERR_INVALID: a null pointer, grid_len not > 0, a non-finite value, lo > hi on an axis. */
 int gndt_crop_box_from_world(const float origin[3], float grid_len, const float lo_xy[2], const float hi_xy[2], gndt_crop_box* out);
 
+/* ---- raster export: one pixel per column of a box, the slope a consumer stands on -------------------------------------------
+ * The map over a window as a 2-D image (an occupancy grid, a costmap layer, an elevation map, a bird's-eye-view tensor), the
+ * reference's showBottom / showSlopeList (map2D.h:980-1284: one cell per column, coloured by its slope's height), without exporting
+ * every row.  The region is a gndt_crop_box (a world rectangle reaches it through gndt_crop_box_from_world).
+ * Geometry: signed indices skip 0, so the image is `width` x `height`, the non-zero integers of [sx_min, sx_max] x [sy_min, sy_max].
+ * Pixel (i, j) sits at j * width + i; i runs over those sx ascending, j over those sy ascending (row-major, row 0 at the smallest y:
+ * the nav_msgs/OccupancyGrid convention).  Pixels are grid_len apart everywhere, across the origin too: the centre of column s is
+ * origin + sign(s) * (|s| - 0.5) * grid_len.
+ * Selection, among the rows of the pixel's column that have GNDT_FLAG_SLOPE:
+ *   GNDT_RASTER_LOWEST     the least sz (the reference's bottom: the ground under a bridge)
+ *   GNDT_RASTER_HIGHEST    the greatest sz (the deck)
+ *   GNDT_RASTER_NEAREST_Z  the least fabsf(mean_z - z_ref) in fp32, a tie going to the smaller sz: GNDT_QUERY_NEAREST_SLOPE's rule
+ *                          (the same code), for every pixel at once
+ * A column without a slope gives an empty pixel (row GNDT_NO_ROW, z and rough quiet NaN, h FLT_MAX, state 0); its `nodes` layer still
+ * counts the column's nodes, so "observed, nothing to stand on" (nodes > 0) stays apart from "never observed" (nodes == 0).  A box
+ * that covers no column of the map is not an error: every pixel is empty.
+ * GNDT_ERR_INVALID: a null handle or box, every layer pointer NULL, an unknown mode, a non-finite z_ref with NEAREST_Z, min > max on an
+ * axis, an index beyond +-65535, an axis without a non-zero index ([0, 0]), width * height > 2^31, no finished build, h or state
+ * without a cost map of the current grid (the rule of gndt_cost_export), a stream under hipGraph capture (a raster is not recorded).
+ * Order and lifetime are the point queries': the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a
+ * re-run), then builds or reuses the queries' column index (the same index, under the same rule).  Row numbers stay valid until the
+ * next build, update, remove, crop or reset.  A sharded map rasterises the rows this rank holds. */
+enum { GNDT_RASTER_LOWEST = 0, GNDT_RASTER_HIGHEST = 1, GNDT_RASTER_NEAREST_Z = 2 };
+typedef struct {
+    uint32_t* row;    /* selected slope's row (gndt_cells order), GNDT_NO_ROW where none      */
+    float*    z;      /* its mean z;                          quiet NaN where none           */
+    float*    rough;  /* its Slope::rough;                    quiet NaN where none           */
+    uint32_t* nodes;  /* the column's node count (any node);  0 = column not in the map      */
+    float*    h;      /* cost map h of the row;               FLT_MAX where none             */
+    uint32_t* state;  /* cost map state of the row;           0 where none                   */
+} gndt_raster_layers;  /* every pointer optional (NULL = not written); at least one non-NULL; each width * height elements */
+/* Host, no handle, no GPU: the image size of a box.  GNDT_ERR_INVALID for the box errors above (and null pointers). */
+int gndt_raster_shape(const gndt_crop_box* box, uint32_t* width, uint32_t* height);
+/* Device layers; enqueued on `hip_stream` (NULL = the handle's stream, the rules of gndt_build_device) and not awaited. */
+int gndt_raster_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_ref, const gndt_raster_layers* out_dev,
+                       void* hip_stream);
+/* Host layers, through a device scratch the handle owns and grows; synchronous. */
+int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_ref, const gndt_raster_layers* out_host);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */

@@ -1,0 +1,353 @@
+"""GPU tier: raster export (gndt_raster_device / gndt_raster, TwoDmap.raster).  On every path that writes rows the raster in all three
+modes is the numpy restatement over the handle's own export, bit for bit; on the bridge LOWEST and HIGHEST differ exactly on the
+multi-slope columns; NEAREST_Z is the query's nearest_slope at the pixel centres; the cost layers are cost_export gathered at the rows
+and are refused after an update; the host variant equals the device variant; boxes larger than, outside of and inside one column of the
+map, every refused argument, a capturing stream and a raster right after a build; and the S2 map's full box."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from grid_ndt_amd import scenes
+from tests import query_ref as qr
+from tests import raster_ref as rr
+
+pytestmark = pytest.mark.gpu
+
+ATOMIC, PARTITION, EXACT, TWO_LEVEL, TILE, AUTO = 1, 2, 3, 4, 5, 0
+TERRAIN = scenes.TERRAIN_PARAMS
+MAP_LAYERS = ("row", "z", "rough", "nodes")
+ERR_INVALID = 1
+
+
+def _handle(P, strategy=AUTO, **kw):
+    import grid_ndt_amd as g
+    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
+    m.setInterval(P["slope_interval"])
+    return m
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+
+
+def _np(t):
+    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
+
+
+def _box_of(cells):
+    return int(cells["sx"].min()), int(cells["sx"].max()), int(cells["sy"].min()), int(cells["sy"].max())
+
+
+def _z_refs(cells):
+    z = np.asarray(cells["mean"], np.float32)[(cells["flags"] & 2) != 0, 2]
+    return [float(np.median(z)), float(np.percentile(z, 90)) + 0.1]
+
+
+def _assert_raster(m, cells, box, layers=MAP_LAYERS, host=False):
+    """every mode (NEAREST_Z at two heights) against the restatement over `cells`"""
+    for mode in ("lowest", "highest", "nearest_z"):
+        for z_ref in (_z_refs(cells) if mode == "nearest_z" else [None]):
+            got = m.raster(box, mode, z_ref, layers=layers, host=host)
+            want = rr.raster(cells, box, mode, 0.0 if z_ref is None else z_ref)
+            for k in layers:
+                assert rr.same(_np(got[k]), want[k]), (box, mode, z_ref, k)
+
+
+def _path(name):
+    """-> a function that builds the map of path `name` on a fresh handle and returns it"""
+    if name in ("atomic", "partition_one_level", "exact", "two_level", "auto"):
+        # (one level: a cloud of at most 512 buckets, as tests/test_gpu_fold_clear.py takes it)
+        P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08) if name == "partition_one_level" else TERRAIN
+        cloud = scenes.uniform_box(300_001, half_xy=20.0) if name == "partition_one_level" else scenes.terrain_cloud(300_000)
+        strategy = {"atomic": ATOMIC, "partition_one_level": PARTITION, "exact": EXACT, "two_level": TWO_LEVEL, "auto": AUTO}[name]
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(P, strategy)
+            m.setCloudFirst(cloud[0])
+            m.create2DMap("slope", t)
+            m.sync()
+            want = {"partition_one_level": "partition_one_level", "exact": "partition_exact"}.get(name)
+            assert want is None or m.STRATEGY_NAMES[m.last_strategy()] == want
+            return m
+        return make
+    if name == "tile":
+        cloud, P = scenes.depth_frame(), scenes.DEPTH_PARAMS
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(P, TILE)
+            m.setCloudFirst(cloud[0])
+            m.create2DMap("slope", t)
+            assert m.STRATEGY_NAMES[m.last_strategy()] == "tile"
+            return m
+        return make
+    if name == "blocked":
+        P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
+        cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
+        t = _dev(cloud[1:])
+
+        def make():
+            m = _handle(P)
+            m.setCloudFirst(cloud[0])
+            for _ in range(2):
+                m.create2DMap("slope", t)
+                m.sync()
+            assert m.STRATEGY_NAMES[m.last_strategy()] == "partition_blocked"
+            return m
+        return make
+    cloud = scenes.terrain_cloud(240_000)
+    cuts = [1, 90_000, 170_000, cloud.shape[0]]
+
+    def make():
+        m = _handle(TERRAIN, ATOMIC)
+        m.setCloudFirst(cloud[0])
+        if name == "deferred":
+            m.set_deferred_emit(True)
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            m.change2DMap("slope", _dev(cloud[a:b]))
+        if name == "removed":
+            m.del2DMap("slope", _dev(cloud[170_000:]))
+        if name == "cropped":
+            c = m.export()
+            x0, x1, y0, y1 = _box_of(c)
+            m.crop_box(((x0 + x1) // 2 or 1, x1, y0, (y0 + y1) // 2 or 1), "drop_inside")
+        return m
+    return make
+
+
+@pytest.mark.parametrize("name", ["atomic", "partition_one_level", "exact", "two_level", "blocked", "tile", "auto", "updates", "deferred",
+                                  "removed", "cropped"])
+def test_raster_is_the_restatement_on_every_path(name):
+    m = _path(name)()
+    cells = m.export()
+    assert cells["num_nodes"] > 100
+    x0, x1, y0, y1 = _box_of(cells)
+    _assert_raster(m, cells, (x0, x1, y0, y1))
+    # a window through the origin's columns
+    _assert_raster(m, cells, (max(x0, -40), min(x1, 40), max(y0, -30), min(y1, 30)))
+
+
+def _bridge():
+    cloud = scenes.bridge_ground()
+    m = _handle(scenes.BRIDGE_PARAMS)
+    m.setCloudFirst(cloud[0])
+    m.create2DMap("slope", _dev(cloud[1:]))
+    return m, cloud
+
+
+def test_bridge_lowest_and_highest_differ_on_exactly_the_multi_slope_columns():
+    m, _ = _bridge()
+    cells = m.export()
+    box = _box_of(cells)
+    assert box[0] < 0 < box[1]
+    lo, hi = m.raster(box, "lowest", layers=MAP_LAYERS), m.raster(box, "highest", layers=MAP_LAYERS)
+    slope = (cells["flags"] & 2) != 0
+    xs, ys = rr.axis(box[0], box[1]), rr.axis(box[2], box[3])
+    count = np.zeros((ys.size, xs.size), np.int64)
+    np.add.at(count, (np.searchsorted(ys, cells["sy"][slope]), np.searchsorted(xs, cells["sx"][slope])), 1)
+    multi = count > 1
+    assert int((_np(lo["nodes"]) > 0).sum()) == 9600 and multi.sum() == 5076
+    assert ((_np(lo["row"]) != _np(hi["row"])) == multi).all()
+    near = m.raster(box, "nearest_z", 3.0, layers=MAP_LAYERS)          # the deck's height (scenes.bridge_ground)
+    deck = multi & (np.abs(_np(hi["z"]) - np.float32(3.0)) < np.float32(0.05))
+    assert deck.sum() > 1000 and (np.abs(_np(near["z"])[deck] - np.float32(3.0)) < np.float32(0.05)).all()
+    for mode in ("lowest", "highest", "nearest_z"):
+        want = rr.raster(cells, box, mode, 3.0)
+        got = {"lowest": lo, "highest": hi, "nearest_z": near}[mode]
+        for k in MAP_LAYERS:
+            assert rr.same(_np(got[k]), want[k]), (mode, k)
+
+
+def test_nearest_z_is_the_nearest_slope_query_at_the_pixel_centres():
+    import torch
+    m, cloud = _bridge()
+    cells = m.export()
+    box = _box_of(cells)
+    g = np.float32(m.gridLen)
+    for z_ref in (1.0, 2.2, 3.0):
+        r = m.raster(box, "nearest_z", z_ref, layers=("row",))
+        H, W = r["row"].shape
+        cx = (np.float32(r["x0"]) + np.arange(W, dtype=np.float32) * g).astype(np.float32)
+        cy = (np.float32(r["y0"]) + np.arange(H, dtype=np.float32) * g).astype(np.float32)
+        X, Y = np.meshgrid(cx, cy)
+        pts = np.stack([X.ravel(), Y.ravel(), np.full(X.size, np.float32(z_ref))], 1).astype(np.float32)
+        sx, sy, _, _, ok = qr.keys(pts, m.cloudFirst, m.gridLen, m.zLen)
+        # every centre keys back to its own column
+        assert ok.all() and (sx.reshape(H, W) == rr.axis(box[0], box[1])[None, :]).all()
+        assert (sy.reshape(H, W) == rr.axis(box[2], box[3])[:, None]).all()
+        q = m.query(torch.from_numpy(pts).cuda(), "nearest_slope")
+        assert (_np(q).reshape(H, W) == _np(r["row"])).all()
+
+
+def test_cost_layers_are_the_cost_map_at_the_rows_and_refused_after_an_update():
+    import grid_ndt_amd as g
+    CP = scenes.COST_PARAMS
+    site = scenes.drivable_site(200_000)
+    m = _handle(CP, ATOMIC)
+    m.setCloudFirst(site[0])
+    m.create2DMap("slope", _dev(site[1:]))
+    m.computeCost(scenes.DRIVABLE_GOAL)
+    cells = m.export()
+    cost = m.cost_export()
+    box = _box_of(cells)
+    for mode in ("lowest", "highest", "nearest_z"):
+        for host in (False, True):
+            got = m.raster(box, mode, 0.3, layers=("row", "h", "state"), host=host)
+            row = _np(got["row"]).astype(np.int64)
+            hit = row >= 0
+            assert hit.any() and (~hit).any()
+            h, st = _np(got["h"]), _np(got["state"])
+            assert np.array_equal(h[hit].view(np.uint32), cost["h"][row[hit]].view(np.uint32))
+            assert (st[hit] == cost["state"][row[hit]]).all()
+            assert (h[~hit] == rr.FLT_MAX).all() and (st[~hit] == 0).all()
+    m.change2DMap("slope", _dev(site[1:1000]))
+    for layers in (("row", "h"), ("state",)):
+        with pytest.raises(g.GndtError) as e:
+            m.raster(box, "lowest", layers=layers)
+        assert e.value.code == ERR_INVALID
+    m.raster(box, "lowest", layers=("row", "z"))             # the map layers still work
+
+
+def test_host_variant_equals_device_variant():
+    m = _path("removed")()
+    cells = m.export()
+    box = _box_of(cells)
+    for mode, z in (("lowest", None), ("highest", None), ("nearest_z", 0.5)):
+        d = m.raster(box, mode, z, layers=MAP_LAYERS)
+        h = m.raster(box, mode, z, layers=MAP_LAYERS, host=True)
+        for k in MAP_LAYERS:
+            assert isinstance(h[k], np.ndarray) and rr.same(h[k], _np(d[k])), (mode, k)
+        assert (h["x0"], h["y0"], h["res"]) == (d["x0"], d["y0"], d["res"])
+    # a smaller raster after a larger one reuses the scratch; a larger one grows it
+    small = (box[0], box[0] + 3, box[2], box[2] + 2)
+    _assert_raster(m, cells, small, host=True)
+    _assert_raster(m, cells, (box[0] - 20, box[1] + 20, box[2] - 20, box[3] + 20), host=True)
+
+
+def test_edge_boxes():
+    m = _path("atomic")()
+    cells = m.export()
+    x0, x1, y0, y1 = _box_of(cells)
+    big = (x0 - 13, x1 + 9, y0 - 5, y1 + 11)
+    _assert_raster(m, cells, big)
+    r = m.raster(big, "lowest", layers=("row", "nodes"))
+    row, nodes = _np(r["row"]), _np(r["nodes"])
+    assert (row[:5] == -1).all() and (nodes[:5] == 0).all() and (row[:, -9:] == -1).all()
+    # outside the map: every pixel empty, no error
+    out = m.raster((x1 + 100, x1 + 140, y0, y0 + 10), "highest", layers=MAP_LAYERS)
+    assert (_np(out["row"]) == -1).all() and (_np(out["nodes"]) == 0).all() and np.isnan(_np(out["z"])).all()
+    # one pixel
+    sl = np.flatnonzero(cells["flags"] & 2)
+    r0 = int(sl[len(sl) // 7])
+    one = (int(cells["sx"][r0]),) * 2 + (int(cells["sy"][r0]),) * 2
+    p = m.raster(one, "nearest_z", float(cells["mean"][r0, 2]), layers=MAP_LAYERS)
+    assert _np(p["row"]).shape == (1, 1) and int(_np(p["row"])[0, 0]) == r0
+    _assert_raster(m, cells, one)
+    # touching 0: (0, 3) is the columns 1..3
+    _assert_raster(m, cells, (0, 3, -2, 0))
+    assert m.raster((0, 3, -2, 0), layers=("row",))["row"].shape == (2, 3)
+
+
+def _raw(m, box, mode=0, z_ref=0.0, layers=None, stream=None, host=False):
+    """the C entry points with explicit layer pointers (None: the row layer only)"""
+    import torch
+    from grid_ndt_amd._lib import CropBox, RasterLayers
+    w, h = (1, 1) if box is None else (max(1, len(rr.axis(box[0], box[1]))), max(1, len(rr.axis(box[2], box[3]))))
+    if host:
+        buf = np.zeros(w * h, np.uint32)
+        ptr = buf.ctypes.data
+    else:
+        buf = torch.zeros(w * h, dtype=torch.int32, device="cuda")
+        ptr = buf.data_ptr()
+    L = RasterLayers(*([ptr, 0, 0, 0, 0, 0] if layers is None else layers(ptr)))
+    b = None if box is None else C.byref(CropBox(*box))
+    if host:
+        return m._L.gndt_raster(m._h, b, mode, z_ref, C.byref(L))
+    s = C.c_void_p(0 if stream is None else (stream.cuda_stream or 1))
+    rc = m._L.gndt_raster_device(m._h, b, mode, z_ref, C.byref(L), s)
+    torch.cuda.synchronize()
+    return rc
+
+
+def test_refused_arguments():
+    import torch
+    import grid_ndt_amd as g
+    m = _path("atomic")()
+    cells = m.export()
+    ok = (int(cells["sx"][0]), int(cells["sx"][0]) + 2, int(cells["sy"][0]), int(cells["sy"][0]) + 2)
+    for host in (False, True):
+        assert _raw(m, ok, host=host) == 0
+        assert _raw(m, None, host=host) == ERR_INVALID                                   # null box
+        assert _raw(m, ok, layers=lambda p: [0] * 6, host=host) == ERR_INVALID           # no layer
+        assert _raw(m, ok, mode=3, host=host) == ERR_INVALID                             # unknown mode
+        assert _raw(m, ok, mode=-1, host=host) == ERR_INVALID
+        for z in (float("nan"), float("inf"), float("-inf")):
+            assert _raw(m, ok, mode=2, z_ref=z, host=host) == ERR_INVALID              # NEAREST_Z without a finite z_ref
+            assert _raw(m, ok, mode=0, z_ref=z, host=host) == 0                        # (not looked at by the other modes)
+        for box in ((3, 2, 1, 1), (1, 1, 3, 2), (-65536, 1, 1, 2), (1, 2, 1, 65536), (0, 0, 1, 2), (1, 2, 0, 0),
+                    (1, 32769, -32768, 32768)):
+            assert _raw(m, box, host=host) == ERR_INVALID, box
+        # h or state without a cost map of the current grid
+        assert _raw(m, ok, layers=lambda p: [0, 0, 0, 0, p, 0], host=host) == ERR_INVALID
+        assert _raw(m, ok, layers=lambda p: [0, 0, 0, 0, 0, p], host=host) == ERR_INVALID
+    assert m._L.gndt_raster_device(None, None, 0, 0.0, None, None) == ERR_INVALID
+    assert m._L.gndt_raster(None, None, 0, 0.0, None) == ERR_INVALID
+    # no finished build
+    e = _handle(TERRAIN)
+    e.setCloudFirst((0.0, 0.0, 0.0))
+    with pytest.raises(g.GndtError) as err:
+        e.raster((1, 2, 1, 2))
+    assert err.value.code == ERR_INVALID
+    # a capturing stream: refused, and the capture goes on
+    s = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    x = torch.zeros(16, device="cuda")
+    from grid_ndt_amd._lib import CropBox, RasterLayers
+    out = torch.zeros(9, dtype=torch.int32, device="cuda")
+    L = RasterLayers(out.data_ptr(), 0, 0, 0, 0, 0)
+    box = CropBox(*ok)
+    with g.graph_capture(graph, stream=s):
+        rc = m._L.gndt_raster_device(m._h, C.byref(box), 0, 0.0, C.byref(L), C.c_void_p(s.cuda_stream))
+        x.add_(1.0)
+    assert rc == ERR_INVALID
+    graph.replay()
+    torch.cuda.synchronize()
+    assert float(x[0]) == 1.0
+    _assert_raster(m, cells, ok)
+
+
+def test_raster_right_after_a_build_sees_that_build():
+    """no sync between the build and the raster: the raster finishes the build first (and its index follows every new build)"""
+    cloud = scenes.terrain_cloud(300_000)
+    t1, t2 = _dev(cloud[1:150_000]), _dev(cloud[1:])
+    for strategy in (PARTITION, ATOMIC):
+        m = _handle(TERRAIN, strategy)
+        m.setCloudFirst(cloud[0])
+        m.create2DMap("slope", t1)
+        m.sync()
+        box = _box_of(m.export())
+        for t in (t2, t1, t2):
+            m.create2DMap("slope", t)
+            got = m.raster(box, "highest", layers=MAP_LAYERS)
+            cells = m.export()
+            want = rr.raster(cells, box, "highest")
+            for k in MAP_LAYERS:
+                assert rr.same(_np(got[k]), want[k]), (strategy, k)
+
+
+def test_s2_full_box():
+    """bench.py's S2 map (10 M uniform points, 0.5 m cells): its full box (200 m / 0.5 m, one more column where the origin is off the
+    lattice), every mode, every map layer"""
+    cloud = scenes.uniform_box(10_000_001)
+    P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
+    m = _handle(P, max_nodes_hint=1 << 20)
+    m.setCloudFirst(cloud[0])
+    m.create2DMap("slope", _dev(cloud[1:]))
+    cells = m.export()
+    box = _box_of(cells)
+    W, H = len(rr.axis(box[0], box[1])), len(rr.axis(box[2], box[3]))
+    assert min(W, H) >= 400 and m.raster(box, layers=("row",))["row"].shape == (H, W)
+    _assert_raster(m, cells, box)
