@@ -27,6 +27,7 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_TILE_RATIO: if (!(value >= 1.0)) return GNDT_ERR_INVALID; t.tile_ratio = value; return GNDT_OK;
         case GNDT_DEBUG_COST_ONE_WORKGROUP: t.cost_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_QUERY_ILP: if (!(value == 1.0 || value == 2.0 || value == 4.0)) return GNDT_ERR_INVALID; t.query_ilp = (int)value; return GNDT_OK;
+        case GNDT_DEBUG_CLEAR_EXTENT: if (!(value == 0.0 || value == 1.0)) return GNDT_ERR_INVALID; t.clear_extent = value != 0.0; return GNDT_OK;
         default: return GNDT_ERR_INVALID;
     }
 }
@@ -325,6 +326,7 @@ void gndt_destroy(gndt_handle* h) {
     free_query(h);
     free_raster(h);
     free_crop(h);
+    free_clear(h);
     void* ptrs[] = {h->out.sx, h->out.sy, h->out.sz, h->out.count, h->out.first_idx, h->out.mean, h->out.cov,
                     h->out.rough, h->out.normal, h->out.flags, h->st_key, h->st_sums, h->st_count, h->st_first,
                     h->stage, h->d_cnt, h->packed, h->d_nvalid};

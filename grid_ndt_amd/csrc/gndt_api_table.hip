@@ -289,6 +289,17 @@ int grow_table(gndt_handle* h, uint32_t new_cap, hipStream_t s) {
 
 }  // namespace
 
+// The tail of gndt_remove_device and gndt_clear_rays*, after fetch_counters: nodes left with no point (n_dead) are dropped — statistics
+// out, fresh table, merge back (k_stats_merge skips entries without points) — and every row is re-finalised.
+int drop_dead_and_finalize(gndt_handle* h, hipStream_t s) {
+    if (h->h_cnt->n_dead) {
+        HIP_TRY(h, hipMemsetAsync(&h->d_cnt->n_dead, 0, sizeof(uint32_t), s));
+        const int rc = grow_table(h, h->cap, s);
+        if (rc) return rc;
+    }
+    return do_finalize(h, s);
+}
+
 // gndt_reserve: a node table for `nodes` nodes (what a table that holds a map already is grown to, its contents kept)
 int reserve_table(gndt_handle* h, uint64_t nodes, hipStream_t s) {
     const uint32_t want = cap_for_nodes(nodes);
@@ -614,12 +625,7 @@ int gndt_remove_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t str
         HIP_TRY(h, hipMemsetAsync(&h->d_cnt->err_remove, 0, sizeof(uint32_t), s));
         return GNDT_ERR_INVALID;
     }
-    if (h->h_cnt->n_dead) {
-        // drop the empty nodes: statistics out, fresh table, merge back (k_stats_merge skips entries without points)
-        HIP_TRY(h, hipMemsetAsync(&h->d_cnt->n_dead, 0, sizeof(uint32_t), s));
-        if ((rc = grow_table(h, h->cap, s))) return rc;
-    }
-    return do_finalize(h, s);
+    return drop_dead_and_finalize(h, s);
 }
 
 int gndt_remove(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes) {

@@ -8,6 +8,7 @@
 //   gndt_api_cost.hip   cost-map flood over the finished grid
 //   gndt_api_query.hip  batched point queries against the finished grid
 //   gndt_api_crop.hip   region crop: the columns outside (or inside) a box leave the map
+//   gndt_api_clear.hip  free-space clearing: nodes that sensor rays pass through leave the map
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
@@ -215,6 +216,14 @@ struct gndt_handle {
         OutView spare{};  uint32_t* spare_ncol = nullptr;  uint64_t spare_cap = 0, spare_ncol_cap = 0;
         uint32_t* tiles = nullptr;  uint64_t tiles_cap = 0;
     } crop;
+    // free-space clearing (gndt_ray.hpp): per-row pass counts and protection bits, the per-column level extents (at each column's first
+    // row), the device copies of a host call's input and the call's counters {rays, skipped, protected rows}; grown on demand
+    struct Clear {
+        uint32_t* passes = nullptr;  void* ext = nullptr;  uint64_t rows_cap = 0;    // ext: gndt::LevelExtent[rows]
+        uint64_t ext_serial = 0;        // result_serial the extents were computed for (0 = none)
+        void* in = nullptr;  uint64_t in_cap = 0;          // bytes
+        unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;   // [3], device and pinned
+    } clear;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -366,6 +375,8 @@ struct Tuning {
     bool verbose = false;        // GNDT_DEBUG_VERBOSE      stderr line per resolved two-level build
     bool cost_one_workgroup = true;   // GNDT_DEBUG_COST_ONE_WORKGROUP   0: every layer of the flood its own launch
     int query_ilp = 1;           // GNDT_DEBUG_QUERY_ILP           queries a thread of k_query works on at once (1, 2 or 4)
+    bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
+                                 //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
 };
 const Tuning& tuning();
 void tuning_force_stamps(bool on);   // bench.py --stamps flips this after the timed run
@@ -490,6 +501,7 @@ int do_reset(gndt_handle* h, hipStream_t s);
 int zero_device_now(gndt_handle* h, void* p, size_t bytes);
 int partition_recheck_after_replay(gndt_handle* h);
 int reserve_table(gndt_handle* h, uint64_t nodes, hipStream_t s);
+int drop_dead_and_finalize(gndt_handle* h, hipStream_t s);   // gndt_remove* / gndt_clear_rays*: drop the nodes left empty, re-finalise every row
 int table_refinalize(gndt_handle* h);      // the regular finalisation after the small-map one gave up (gndt_sync)
 int table_emit_pending(gndt_handle* h);    // deferred-emit mode: the ordering + emit pass the frames since the last read left out (gndt_sync)
 int build_atomic(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, hipStream_t s, bool tile = false,
@@ -522,5 +534,7 @@ gndt::QueryView query_view(gndt_handle* h);
 void free_raster(gndt_handle* h);
 // ---- gndt_api_crop.hip ----
 void free_crop(gndt_handle* h);
+// ---- gndt_api_clear.hip ----
+void free_clear(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cells, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, Stats
+from ._lib import Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -644,6 +644,40 @@ class TwoDmap:
         out.update(x0=_column_centre(self.cloudFirst[0], self.gridLen, sx0), y0=_column_centre(self.cloudFirst[1], self.gridLen, sy0),
                    res=self.gridLen)
         return out
+
+    # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
+    CLEAR_PROTECTED = 0x80000000
+
+    def clear_rays(self, origin, points, max_range=0.0, end_margin=0.0, min_passes=1, count_only=False, passes=False, stream=None):
+        """Drop every node that at least `min_passes` rays from the sensor `origin` (xyz) to the end `points` ([N,3] or [N,4] float32)
+        pass through, unless an end point lies in it (include/gndt.h "free-space clearing" defines the walk).  max_range > 0 walks at
+        most that far from the origin, end_margin leaves the last metres before every end point.  count_only=True changes nothing: the
+        dry run.  A torch CUDA tensor is walked on the device (enqueued on `stream`, default torch's current stream), a host array
+        through gndt_clear_rays.  Returns the stats dict {rays, skipped, protected_rows, cleared}; with passes=True also the per-row
+        words of the map as it was before the call (bits 0-30 the pass count, bit 31 CLEAR_PROTECTED): a torch int32 tensor on the device
+        for device points, a numpy uint32 array otherwise: (stats, passes).  The stats are awaited, so the call always waits."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        o = (C.c_float * 3)(*[float(v) for v in origin[:3]])
+        prm = ClearParams(float(max_range), float(end_margin), int(min_passes), 1 if count_only else 0)
+        st = ClearStats()
+        ptr, n, stride, on_dev, keep = self._as_input(points)
+        rows = None
+        if on_dev:
+            if passes:
+                import torch
+                nodes = self.sync()[0]
+                rows = torch.zeros(nodes, dtype=torch.int32, device=keep.device)
+            self._check(self._L.gndt_clear_rays_device(self._h, o, C.c_void_p(ptr if n else 0), n, stride, C.byref(prm),
+                                                       C.c_void_p(rows.data_ptr() if rows is not None and rows.numel() else 0),
+                                                       C.byref(st), _stream_ptr(stream)))
+        else:
+            if passes:
+                rows = np.zeros(self.sync()[0], np.uint32)
+            self._check(self._L.gndt_clear_rays(self._h, o, C.c_void_p(ptr if n else 0), n, stride, C.byref(prm),
+                                                C.c_void_p(rows.ctypes.data if rows is not None and rows.size else 0), C.byref(st)))
+        out = {"rays": int(st.rays), "skipped": int(st.skipped), "protected_rows": int(st.protected_rows), "cleared": int(st.cleared)}
+        return (out, rows) if passes else out
 
     # ---- results ----
     def sync(self):

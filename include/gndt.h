@@ -207,7 +207,7 @@ int gndt_finalize_device(gndt_handle* h, void* hip_stream);
 /* ---- results --------------------------------------------------------------------------------- */
 /* Waits for the handle's pending work, reports counts and any deferred device-side error. */
 int gndt_sync(gndt_handle* h, uint64_t* num_nodes, uint64_t* num_columns, uint64_t* num_slopes);
-/* Device-resident SoA of the last build/finalize; valid until the next build/update/remove/crop/destroy. */
+/* Device-resident SoA of the last build/finalize; valid until the next build/update/remove/crop/clear/destroy. */
 int gndt_export_device(gndt_handle* h, gndt_cells* out);
 /* Copies into caller-allocated host arrays sized from gndt_sync's num_nodes (NULL arrays skipped). */
 int gndt_export(gndt_handle* h, gndt_cells* out_host);
@@ -502,6 +502,69 @@ int gndt_raster_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, f
 /* Host layers, through a device scratch the handle owns and grows; synchronous. */
 int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_ref, const gndt_raster_layers* out_host);
 
+/* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
+ * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
+ * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
+ * One call takes a sensor origin o (finite and keyed by the codec) and n end points p_i in map coordinates (stride 12 or 16, like
+ * gndt_build_device).  Every finite end point whose key is in the codec's range defines one ray (stats.rays); the others are skipped
+ * (stats.skipped).
+ * The walk of a ray is a DEFINITION, not an approximation (tests restate it in numpy, bit for bit):
+ *   - cut point: e = o + d * min(1, max_range / |d|, max(0, |d| - end_margin) / |d|), d = p - o, all in fp64 (e = p when nothing
+ *     is cut; max_range = 0: no limit).  A ray with |d| = 0 walks only the origin's voxel.
+ *   - first and last column: the codec's (sx, sy) of o and of e (point_key / axis_index in fp32, exactly as the build keys points).
+ *   - steps: exactly |dx| + |dy| unit steps between them, measured in lattice cells (signed indices skip 0: positive index s is the
+ *     cell between the planes s - 1 and s, negative index s the cell between s and s + 1, in grid_len from the map origin).  Each step
+ *     crosses the lattice plane the segment meets first: crossing parameter t = (o_axis + k * grid_len - o_ray) / d_axis in fp64,
+ *     clamped to [0, 1], with o_axis the map origin and d_axis the uncut direction; an axis whose index has reached the last column's
+ *     is not stepped again; a tie steps x first.
+ *   - levels: in every column the ray walks every level between its level at the column's entry and at its exit, inclusive (0 skipped):
+ *     the first column's entry level is the codec's sz of o, the last column's exit level the codec's sz of e, a crossing's level is the
+ *     codec's rule in fp64 at the ray's z there: sign(z - oz) * max(1, ceil(|z - oz| / z_len)).  Both ends' voxels are walked.
+ * A node is PASSED by a ray when the walk visits its (sx, sy, sz).  A node is PROTECTED when the GNDT_QUERY_NODE lookup of some ray's
+ * UNCUT end point p_i names it (something was seen in it in this call; the query's own code).
+ * Clearing: a node leaves the map when its passes are >= min_passes and it is not protected — with everything it has, with or without
+ * statistics or a slope.  By definition
+ *     clear  ==  gndt_remove of every point ever added to the nodes that leave,
+ * so survivors keep first_idx and their place in the order, the stream position stays, every row is re-finalised (the labels of the
+ * touched columns change as isSlope says they must), and a cleared node that receives points again is a new node.  Clearing needs the
+ * additive node table, as gndt_remove does (strategy ATOMIC / TILE or a map built by gndt_update*); otherwise GNDT_ERR_INVALID and the
+ * map is unchanged.
+ * GNDT_CLEAR_COUNT_ONLY: the same walk, and nothing changes — a dry run, and a read-only "which parts of the map does this scan see
+ * through" query.  It works on every map that has rows (PARTITION-built and sharded ones: the rows this rank holds), as queries do.
+ * passes_out (optional, num_nodes u32, indexed by the rows as they were BEFORE the call): bits 0-30 the pass count, bit 31
+ * (GNDT_CLEAR_PROTECTED) a protected row.  Count-only: exact counts (n < 2^31, so they cannot saturate).  While clearing the kernel
+ * stops adding to a row once it has min_passes, and adds nothing to a protected row: the count of a row that is not protected is
+ * min(exact, min_passes), that of a protected row 0.
+ * stats (optional): rays, skipped points, protected rows, nodes cleared (0 in count-only mode).
+ * GNDT_ERR_INVALID: null handle, origin or params, null points with n > 0, n >= 2^31, a non-finite origin or one without a key, a
+ * negative or non-finite max_range / end_margin, min_passes == 0, unknown flags, a stride other than 12 / 16, no finished build, a
+ * stream under hipGraph capture (a clear is not recorded), clearing without the node table.  There is no CPU path: without a device
+ * the call fails like every compute entry point.  n == 0 returns GNDT_OK and changes nothing.
+ * Order and lifetime are gndt_crop's:
+ *   - the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a re-run), then builds or reuses the point
+ *     queries' column index;
+ *   - clearing makes a new map: the cost map is invalid until the next gndt_compute_cost (gndt_cost_export* refuse it), the query index
+ *     is rebuilt, device pointers from gndt_export_device and row numbers from gndt_query* are invalid, and a graph recorded before
+ *     the clear and replayed after it is reported stale by gndt_sync (GNDT_ERR_CAPACITY).  Capture again after the clear.
+ * Clearing waits for the device, as gndt_remove does: deaths are only known there.  A count-only gndt_clear_rays_device is enqueued on
+ * `hip_stream` (NULL = the handle's stream, the rules of gndt_build_device) and not awaited unless `stats` is non-NULL.
+ * gndt_clear_rays takes host points and a host passes_out and is synchronous. */
+enum { GNDT_CLEAR_COUNT_ONLY = 1 };
+#define GNDT_CLEAR_PROTECTED 0x80000000u
+typedef struct gndt_clear_params {
+    float max_range;      /* > 0: walk at most this far from the origin; 0 = no limit            */
+    float end_margin;     /* >= 0: the last end_margin metres before an end point are not walked */
+    uint32_t min_passes;  /* >= 1 */
+    uint32_t flags;       /* GNDT_CLEAR_* */
+} gndt_clear_params;
+typedef struct gndt_clear_stats {
+    uint64_t rays, skipped, protected_rows, cleared;   /* cleared = 0 in count-only mode */
+} gndt_clear_stats;
+int gndt_clear_rays_device(gndt_handle* h, const float origin_xyz[3], const void* xyz_dev, size_t n, size_t stride_bytes,
+                           const gndt_clear_params* p, uint32_t* passes_out_dev, gndt_clear_stats* stats, void* hip_stream);
+int gndt_clear_rays(gndt_handle* h, const float origin_xyz[3], const void* xyz_host, size_t n, size_t stride_bytes,
+                    const gndt_clear_params* p, uint32_t* passes_out_host, gndt_clear_stats* stats);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
@@ -585,11 +648,14 @@ int gndt_debug_enable_stamps(int on);
  *                                 value >= 1                                                                        default 48
  *   GNDT_DEBUG_COST_ONE_WORKGROUP value == 0: gndt_compute_cost launches every layer on its own, the one-workgroup kernel that walks
  *                                 the narrow layers is not used (tests run the flood both ways)                     default 1
- *   GNDT_DEBUG_QUERY_ILP          independent queries one thread of gndt_query* works on at once: 1, 2 or 4       default 1 */
+ *   GNDT_DEBUG_QUERY_ILP          independent queries one thread of gndt_query* works on at once: 1, 2 or 4       default 1
+ *   GNDT_DEBUG_CLEAR_EXTENT       value == 1: gndt_clear_rays* read the rows of a walked column only if the column's level extent
+ *                                 meets the ray's level range (tools/measure_clear.py A/Bs the two; same results)  default 0 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
 #define GNDT_DEBUG_QUERY_ILP 4
+#define GNDT_DEBUG_CLEAR_EXTENT 5
 int gndt_debug_set_option(int option, double value);
 /* The bucket kernel finds a node through a 21-bit fingerprint of its key and confirms it with the key itself; a bucket in
  * which a fingerprint named the wrong node (~1 in 10^4) is accumulated a second time with every probe confirmed.  Tests narrow
