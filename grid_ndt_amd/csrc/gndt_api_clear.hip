@@ -12,7 +12,7 @@ namespace gndt_host {
 
 void free_clear(gndt_handle* h) {
     auto& c = h->clear;
-    void* ptrs[] = {c.passes, c.ext, c.in, c.d_stats};
+    void* ptrs[] = {c.passes, c.ext, c.d_stats};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (c.h_stats) (void)hipHostFree(c.h_stats);
@@ -42,18 +42,12 @@ int clear_check_args(gndt_handle* h, const float* origin, const void* xyz, size_
     return GNDT_OK;
 }
 
-// The handle's state, in crop's order: no capture, what gndt_sync finishes first, a finished map, the node table when clearing
+// The handle's state, in crop's order: no capture, a finished map (points outside the key range are only reported), the node table
+// when clearing
 int clear_sync(gndt_handle* h, bool count_only, hipStream_t s) {
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &cap);
-        if (cap != hipStreamCaptureStatusNone) { h->err = "gndt_clear_rays: a clear is not recorded into a hipGraph"; return GNDT_ERR_INVALID; }
-    }
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to clear"; return GNDT_ERR_INVALID; }
-    const int rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc && rc != GNDT_ERR_KEY_RANGE) return rc;
-    if (!h->results_valid) { h->err = "no finished build to clear"; return GNDT_ERR_INVALID; }
+    int rc = refuse_capture(h, s, "gndt_clear_rays: a clear is not recorded into a hipGraph");
+    if (!rc) rc = finished_map(h, "no finished build to clear", true);
+    if (rc) return rc;
     if (!count_only && (!h->map_in_table || h->cap == 0)) {
         h->err = "gndt_clear_rays needs the additive node table (strategy ATOMIC / TILE or a map built by gndt_update*); "
                  "GNDT_CLEAR_COUNT_ONLY works on every map";
@@ -67,15 +61,9 @@ int clear_buffers(gndt_handle* h, uint64_t rows) {
     auto& c = h->clear;
     if (!c.d_stats) HIP_TRY(h, hipMalloc(&c.d_stats, 4 * sizeof(unsigned long long)));
     if (!c.h_stats) HIP_TRY(h, hipHostMalloc(&c.h_stats, 4 * sizeof(unsigned long long)));
-    if (rows > c.rows_cap) {
-        if (c.passes) (void)hipFree(c.passes);     // (the clear's own scratch: never recorded into a graph)
-        if (c.ext) (void)hipFree(c.ext);
-        c.passes = nullptr; c.ext = nullptr; c.rows_cap = 0; c.ext_serial = 0;
-        HIP_TRY(h, hipMalloc(&c.passes, rows * 4));
-        HIP_TRY(h, hipMalloc(&c.ext, rows * sizeof(LevelExtent)));
-        c.rows_cap = rows;
-    }
-    return GNDT_OK;
+    if (rows * sizeof(LevelExtent) > c.ext_cap) c.ext_serial = 0;      // (a new buffer holds no extents)
+    const int rc = grow_scratch(h, c.passes, c.passes_cap, rows * 4);
+    return rc ? rc : grow_scratch(h, c.ext, c.ext_cap, rows * sizeof(LevelExtent));
 }
 
 // Protect, walk, tally (and while clearing, kill) on the current map; the counters go to the pinned mirror.  Waits for nothing.
@@ -89,9 +77,8 @@ int clear_launch(gndt_handle* h, const float* origin, const float* xyz, uint64_t
     if (rows) HIP_TRY(h, hipMemsetAsync(passes, 0, rows * 4, s));
     const QueryView Q = query_view(h);
     LevelExtent* E = static_cast<LevelExtent*>(c.ext);
-    // the extents: kept while the map is the one they were computed for (the query index's rule: never on a handle that has recorded a
-    // hipGraph, whose replays rewrite the map unseen)
-    if (ext && rows && !(c.ext_serial && c.ext_serial == h->result_serial && !h->ever_captured)) {
+    // the extents: kept while the map is the one they were computed for (map_current)
+    if (ext && rows && !map_current(h, c.ext_serial)) {
         hipLaunchKernelGGL(k_clear_extent, dim3(grid_for(rows, 256, 2048)), dim3(256), 0, s, Q, (uint32_t)rows, E);
         HIP_TRY(h, hipGetLastError());
         c.ext_serial = h->result_serial;
@@ -140,7 +127,7 @@ int clear_finish(gndt_handle* h, hipStream_t s) {
         h->results_valid = false;
         if ((rc = drop_dead_and_finalize(h, s))) return rc;
     }
-    // the map is new: cost map, query index and row numbers are stale; a graph recorded before this call is reported stale when replayed
+    // the map is new: cost map, column index and row numbers are stale; a graph recorded before this call is reported stale when replayed
     ++h->result_serial;
     ++h->realloc_gen;
     h->last_stream = s;
@@ -167,7 +154,7 @@ int gndt_clear_rays_device(gndt_handle* h, const float origin_xyz[3], const void
     if ((rc = clear_sync(h, count_only, s))) return rc;
     zero_stats(stats);
     if (n == 0) return GNDT_OK;
-    if ((rc = query_index(h, s))) return rc;           // (the stream first: use_stream)
+    if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
     if ((rc = clear_buffers(h, h->res_nodes))) return rc;
     uint32_t* passes = passes_out_dev ? passes_out_dev : h->clear.passes;
     if ((rc = clear_launch(h, origin_xyz, static_cast<const float*>(xyz_dev), n, (uint32_t)(stride_bytes / 4), p, passes, s))) return rc;
@@ -191,19 +178,15 @@ int gndt_clear_rays(gndt_handle* h, const float origin_xyz[3], const void* xyz_h
     if ((rc = clear_sync(h, count_only, s))) return rc;
     zero_stats(stats);
     if (n == 0) return GNDT_OK;
-    if ((rc = query_index(h, s))) return rc;
+    if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
     const uint64_t rows = h->res_nodes;
     if ((rc = clear_buffers(h, rows))) return rc;
     auto& c = h->clear;
     const uint64_t in_bytes = (uint64_t)n * stride_bytes;
-    if (in_bytes > c.in_cap) {
-        if (c.in) (void)hipFree(c.in);
-        c.in = nullptr; c.in_cap = 0;
-        HIP_TRY(h, hipMalloc(&c.in, in_bytes));
-        c.in_cap = in_bytes;
-    }
-    HIP_TRY(h, hipMemcpyAsync(c.in, xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = clear_launch(h, origin_xyz, static_cast<const float*>(c.in), n, (uint32_t)(stride_bytes / 4), p, c.passes, s))) return rc;
+    void* in = nullptr;
+    if ((rc = stage_pieces(h, &in_bytes, &in, 1))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(in, xyz_host, in_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = clear_launch(h, origin_xyz, static_cast<const float*>(in), n, (uint32_t)(stride_bytes / 4), p, c.passes, s))) return rc;
     if (passes_out_host && rows) HIP_TRY(h, hipMemcpyAsync(passes_out_host, c.passes, rows * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     if (!count_only && (rc = clear_finish(h, s))) return rc;

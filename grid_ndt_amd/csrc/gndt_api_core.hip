@@ -32,25 +32,20 @@ int tuning_set_option(int option, double value) {
     }
 }
 
+int alloc_rows(gndt_handle* h, OutView& v, uint64_t rows) {
+    for (const RowArray& a : row_arrays(v)) HIP_TRY(h, hipMalloc(a.p, rows * a.elem));
+    return GNDT_OK;
+}
+
 int ensure_out(gndt_handle* h, uint64_t n) {
     if (n <= h->out_cap) return GNDT_OK;
     GNDT_NO_CAPTURE(h, "the result arrays");
-    void* ptrs[] = {h->out.sx, h->out.sy, h->out.sz, h->out.count, h->out.first_idx, h->out.mean, h->out.cov,
-                    h->out.rough, h->out.normal, h->out.flags};
-    for (void* p : ptrs) release_device(h, p);
+    for (const RowArray& a : row_arrays(h->out)) release_device(h, *a.p);
     h->out = OutView{};
     h->out_cap = 0;
-    uint64_t c = std::max<uint64_t>(1024, n + n / 8);
-    HIP_TRY(h, hipMalloc(&h->out.sx, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.sy, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.sz, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.count, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.first_idx, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.mean, c * 12));
-    HIP_TRY(h, hipMalloc(&h->out.cov, c * 24));
-    HIP_TRY(h, hipMalloc(&h->out.rough, c * 4));
-    HIP_TRY(h, hipMalloc(&h->out.normal, c * 12));
-    HIP_TRY(h, hipMalloc(&h->out.flags, c * 4));
+    const uint64_t c = std::max<uint64_t>(1024, n + n / 8);
+    const int rc = alloc_rows(h, h->out, c);
+    if (rc) return rc;
     h->out_cap = c;
     return GNDT_OK;
 }
@@ -83,6 +78,42 @@ int check_ready(gndt_handle* h) {
     h->capturing = false;              // (use_stream, which every call that enqueues work makes next, sets it for the call's stream)
     if (!h->origin_set) { h->err = "gndt_set_origin must be called first (setCloudFirst, receiver.cpp:145)"; return GNDT_ERR_INVALID; }
     HIP_TRY(h, hipSetDevice(h->device));
+    return GNDT_OK;
+}
+
+// Every reader of the finished map (export, flood, query, raster, crop, clear) starts here.  gndt_sync leaves results_valid false only
+// where it returns GNDT_ERR_CAPACITY (a replay of stale buffers, the small-map fallback of a replay, a replayed build out of room), so
+// the second look matters to the callers that go on after a GNDT_ERR_KEY_RANGE.
+int finished_map(gndt_handle* h, const char* no_map_err, bool key_range_ok) {
+    { const int prc = partition_resolve(h); if (prc) return prc; }
+    if (!h->results_valid) { h->err = no_map_err; return GNDT_ERR_INVALID; }
+    const int rc = gndt_sync(h, nullptr, nullptr, nullptr);
+    if (rc && !(key_range_ok && rc == GNDT_ERR_KEY_RANGE)) return rc;
+    if (!h->results_valid) { h->err = no_map_err; return GNDT_ERR_INVALID; }
+    return GNDT_OK;
+}
+
+// The consumers refuse a stream under hipGraph capture: they wait for the stream or allocate
+int refuse_capture(gndt_handle* h, hipStream_t s, const char* msg) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s, &cap);
+    if (cap == hipStreamCaptureStatusNone) return GNDT_OK;
+    h->err = msg;
+    return GNDT_ERR_INVALID;
+}
+
+// Safe to share: gndt_query, gndt_raster and gndt_clear_rays run on own_stream and synchronise before they return
+int stage_pieces(gndt_handle* h, const uint64_t* bytes, void** piece, int count) {
+    auto aligned = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
+    uint64_t total = 0;
+    for (int k = 0; k < count; ++k) total += aligned(bytes[k]);
+    const int rc = grow_scratch(h, h->io, h->io_cap, total);
+    if (rc) return rc;
+    char* p = static_cast<char*>(h->io);
+    for (int k = 0; k < count; ++k) {
+        piece[k] = bytes[k] ? p : nullptr;
+        p += aligned(bytes[k]);
+    }
     return GNDT_OK;
 }
 
@@ -323,13 +354,11 @@ void gndt_destroy(gndt_handle* h) {
     free_table(h);
     free_part(h);
     free_cost(h);
-    free_query(h);
-    free_raster(h);
     free_crop(h);
     free_clear(h);
-    void* ptrs[] = {h->out.sx, h->out.sy, h->out.sz, h->out.count, h->out.first_idx, h->out.mean, h->out.cov,
-                    h->out.rough, h->out.normal, h->out.flags, h->st_key, h->st_sums, h->st_count, h->st_first,
-                    h->stage, h->d_cnt, h->packed, h->d_nvalid};
+    for (const RowArray& a : row_arrays(h->out))
+        if (*a.p) (void)hipFree(*a.p);
+    void* ptrs[] = {h->st_key, h->st_sums, h->st_count, h->st_first, h->stage, h->d_cnt, h->packed, h->d_nvalid, h->index.buf, h->io};
     if (h->h_nvalid) (void)hipHostFree(h->h_nvalid);
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -493,10 +522,7 @@ int gndt_sync(gndt_handle* h, uint64_t* num_nodes, uint64_t* num_columns, uint64
 
 int gndt_export_device(gndt_handle* h, gndt_cells* out) {
     if (!h || !out) return GNDT_ERR_INVALID;
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to export"; return GNDT_ERR_INVALID; }
-    int rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc) return rc;
+    if (const int rc = finished_map(h, "no finished build to export", false)) return rc;
     out->num_nodes = h->res_nodes; out->num_columns = h->res_columns; out->num_slopes = h->res_slopes;
     out->sx = h->out.sx; out->sy = h->out.sy; out->sz = h->out.sz;
     out->count = h->out.count; out->first_idx = h->out.first_idx;
@@ -507,27 +533,18 @@ int gndt_export_device(gndt_handle* h, gndt_cells* out) {
 
 int gndt_export(gndt_handle* h, gndt_cells* o) {
     if (!h || !o) return GNDT_ERR_INVALID;
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to export"; return GNDT_ERR_INVALID; }
-    int rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc) return rc;
+    if (const int rc = finished_map(h, "no finished build to export", false)) return rc;
     const uint64_t n = h->res_nodes;
     o->num_nodes = n; o->num_columns = h->res_columns; o->num_slopes = h->res_slopes;
-    struct { void* dst; const void* src; size_t elem; } copies[] = {
-        {o->sx, h->out.sx, 4}, {o->sy, h->out.sy, 4}, {o->sz, h->out.sz, 4}, {o->count, h->out.count, 4},
-        {o->first_idx, h->out.first_idx, 4}, {o->mean, h->out.mean, 12}, {o->cov, h->out.cov, 24},
-        {o->rough, h->out.rough, 4}, {o->normal, h->out.normal, 12}, {o->flags, h->out.flags, 4}};
-    for (auto& c : copies)
-        if (c.dst && n) HIP_TRY(h, hipMemcpy(c.dst, c.src, n * c.elem, hipMemcpyDeviceToHost));
+    const auto src = row_arrays(h->out), dst = row_arrays(*o);
+    for (size_t k = 0; k < src.size(); ++k)
+        if (*dst[k].p && n) HIP_TRY(h, hipMemcpy(*dst[k].p, *src[k].p, n * src[k].elem, hipMemcpyDeviceToHost));
     return GNDT_OK;
 }
 
 int gndt_export_host(gndt_handle* h, gndt_cells* o) {
     if (!h || !o) return GNDT_ERR_INVALID;
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to export"; return GNDT_ERR_INVALID; }
-    int rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc) return rc;
+    if (const int rc = finished_map(h, "no finished build to export", false)) return rc;
     const uint64_t n = h->res_nodes;
     const uint64_t rows = std::max<uint64_t>(n, 1);
     if (rows > h->exp_rows) {
@@ -540,15 +557,12 @@ int gndt_export_host(gndt_handle* h, gndt_cells* o) {
     // ten arrays, one after the other in the pinned mirror (every one of them 4-byte elements: no alignment gaps needed)
     char* base = static_cast<char*>(h->exp_host);
     const uint64_t cap = h->exp_rows;
-    struct { const void* src; size_t elem; void** dst; } copies[] = {
-        {h->out.sx, 4, (void**)&o->sx}, {h->out.sy, 4, (void**)&o->sy}, {h->out.sz, 4, (void**)&o->sz}, {h->out.count, 4, (void**)&o->count},
-        {h->out.first_idx, 4, (void**)&o->first_idx}, {h->out.mean, 12, (void**)&o->mean}, {h->out.cov, 24, (void**)&o->cov},
-        {h->out.rough, 4, (void**)&o->rough}, {h->out.normal, 12, (void**)&o->normal}, {h->out.flags, 4, (void**)&o->flags}};
+    const auto src = row_arrays(h->out), dst = row_arrays(*o);
     size_t off = 0;
-    for (auto& c : copies) {
-        *c.dst = base + off;
-        if (n) HIP_TRY(h, hipMemcpyAsync(base + off, c.src, n * c.elem, hipMemcpyDeviceToHost, h->last_stream));
-        off += cap * c.elem;
+    for (size_t k = 0; k < src.size(); ++k) {
+        *dst[k].p = base + off;
+        if (n) HIP_TRY(h, hipMemcpyAsync(base + off, *src[k].p, n * src[k].elem, hipMemcpyDeviceToHost, h->last_stream));
+        off += cap * src[k].elem;
     }
     HIP_TRY(h, hipStreamSynchronize(h->last_stream));
     o->num_nodes = n; o->num_columns = h->res_columns; o->num_slopes = h->res_slopes;

@@ -10,11 +10,60 @@ namespace gndt_host {
 
 void free_cost(gndt_handle* h) {
     auto& c = h->cost;
-    void* ptrs[] = {c.h_bits, c.state, c.f[0], c.f[1], c.ctab_key, c.ctab_val, c.nbr, c.edges, c.d_cc};
+    void* ptrs[] = {c.h_bits, c.state, c.f[0], c.f[1], c.nbr, c.edges, c.d_cc};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (c.h_cc) (void)hipHostFree(c.h_cc);
     c = gndt_handle::Cost{};
+}
+
+int cost_counters(gndt_handle* h) {
+    auto& c = h->cost;
+    if (!c.d_cc) HIP_TRY(h, hipMalloc(&c.d_cc, sizeof(CostCounters)));
+    if (!c.h_cc) HIP_TRY(h, hipHostMalloc(&c.h_cc, sizeof(CostCounters)));
+    return GNDT_OK;
+}
+
+int cost_map_check(gndt_handle* h) {
+    if (!h->results_valid || h->cost.serial == 0 || h->cost.serial != h->result_serial) {
+        h->err = "no cost map for the current grid (call gndt_compute_cost after the build)";
+        return GNDT_ERR_INVALID;
+    }
+    return GNDT_OK;
+}
+
+namespace {
+uint32_t index_slots(const gndt_handle* h) { return pow2_ceil(std::max<uint64_t>(1024, 2 * h->res_columns)); }     // load <= 1/2
+bool index_current(const gndt_handle* h) { return map_current(h, h->index.serial) && h->index.mask == index_slots(h) - 1; }
+}  // namespace
+
+// One index per map, whoever needs it first.  It depends on the map alone; what depends on the robot as well (the flood's tables_kept)
+// is kept on top of it.  Its builds count columns beyond the flood's range into the flood's counters (range_error), which only a
+// build zeroes: a flood on an index a query built still reports them.
+int column_index(gndt_handle* h, hipStream_t s, bool flood) {
+    auto& ix = h->index;
+    const bool current = index_current(h);
+    if (current && !flood) return GNDT_OK;
+    const uint32_t tsize = index_slots(h);
+    if (!current) {
+        ix.serial = 0;
+        int rc = cost_counters(h);
+        if (!rc) rc = grow_scratch(h, ix.buf, ix.bytes, (uint64_t)tsize * 12);
+        if (rc) return rc;
+        ix.key = static_cast<uint64_t*>(ix.buf);
+        ix.val = reinterpret_cast<uint32_t*>(ix.key + tsize);
+        ix.mask = tsize - 1;
+    }
+    const uint32_t slots = current ? 0u : tsize;       // (k_cost_clear: 0 = the table is kept)
+    const uint64_t rows = h->res_nodes, reset = flood ? rows : 0;
+    hipLaunchKernelGGL(k_cost_clear, dim3(grid_for(std::max<uint64_t>(reset, slots))), dim3(256), 0, s, flood ? h->cost.h_bits : nullptr,
+                       flood ? h->cost.state : nullptr, (uint32_t)reset, ix.key, slots, h->cost.d_cc);
+    if (!current && rows)
+        hipLaunchKernelGGL(k_cost_columns, dim3(grid_for(rows)), dim3(256), 0, s, h->out.sx, h->out.sy, h->part.row_ncol, (uint32_t)rows,
+                           ix.key, ix.val, ix.mask, h->cost.d_cc);
+    HIP_TRY(h, hipGetLastError());
+    if (!current) ix.serial = h->result_serial;
+    return GNDT_OK;
 }
 
 }  // namespace gndt_host
@@ -27,18 +76,12 @@ int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot*
     int rc = check_ready(h);
     if (rc) return rc;
     if (!goal_xyz) { h->err = "null goal"; return GNDT_ERR_INVALID; }
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to flood (computeCost runs after create2DMap, receiver.cpp:160, 171)"; return GNDT_ERR_INVALID; }
-    rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc) return rc;
+    if ((rc = finished_map(h, "no finished build to flood (computeCost runs after create2DMap, receiver.cpp:160, 171)", false))) return rc;
     hipStream_t s = stream_of(h, hip_stream);
     auto& c = h->cost;
     c.serial = 0;
     const uint64_t n = h->res_nodes, K = h->res_columns;
-    if (!c.d_cc) {
-        HIP_TRY(h, hipMalloc(&c.d_cc, sizeof(CostCounters)));
-        HIP_TRY(h, hipHostMalloc(&c.h_cc, sizeof(CostCounters)));
-    }
+    if ((rc = cost_counters(h))) return rc;
     if (n > c.node_cap) {
         for (uint32_t** a : {&c.h_bits, &c.state, &c.f[0], &c.f[1], &c.nbr}) { if (*a) (void)hipFree(*a); *a = nullptr; }
         if (c.edges) (void)hipFree(c.edges);
@@ -53,42 +96,28 @@ int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot*
         HIP_TRY(h, hipMalloc(&c.edges, cap * 4 * sizeof(CostEdge)));
         c.node_cap = cap;
     }
-    const uint32_t tsize = pow2_ceil(std::max<uint64_t>(1024, 2 * K));
-    if (tsize > c.ctab_size) {
-        if (c.ctab_key) (void)hipFree(c.ctab_key);
-        if (c.ctab_val) (void)hipFree(c.ctab_val);
-        c.ctab_key = nullptr; c.ctab_val = nullptr; c.ctab_size = 0;
-        c.tables_serial = 0;
-        HIP_TRY(h, hipMalloc(&c.ctab_key, (size_t)tsize * 8));
-        HIP_TRY(h, hipMalloc(&c.ctab_val, (size_t)tsize * 4));
-        c.ctab_size = tsize;
-    }
     Robot R{0.25f, 0.15f, 100.f, 30.f};   // receiver.cpp:33, robot.h:38-46
     if (robot) R = Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
     c.ring_n = cost_ring_depth(R.r, h->P.grid_len);
+    // What depends on the map and the robot only — every row's neighbour columns / own column / CostEdge records, CollisionCheck's
+    // verdict for every slope — is kept from one flood to the next on top of the map's column index: the planner asks for a new goal
+    // on the same map (receiver.cpp:160-176 floods once per goal message), and those passes are 50 of bridge_ground's 430 us.
+    const float robot4[4] = {R.r, R.reach, R.rough, R.angle};
+    const bool tables_kept = K && index_current(h) && map_current(h, c.tables_serial) && std::memcmp(robot4, c.tables_robot, sizeof(robot4)) == 0;
+    c.tables_serial = 0;
+    if ((rc = column_index(h, s, true))) return rc;
     CostView V;
     V.sx = h->out.sx; V.sy = h->out.sy; V.sz = h->out.sz;
     V.mean = h->out.mean; V.normal = h->out.normal; V.rough = h->out.rough; V.flags = h->out.flags;
     V.row_ncol = h->part.row_ncol;
-    V.ctab_key = c.ctab_key; V.ctab_val = c.ctab_val; V.ctab_mask = c.ctab_size - 1;
+    V.ctab_key = h->index.key; V.ctab_val = h->index.val; V.ctab_mask = h->index.mask;
     V.nbr = nullptr; V.self = nullptr;
     V.slope_interval = h->P.slope_interval; V.demand_true = h->P.demand == GNDT_DEMAND_TRUE ? 1 : 0;
     // the goal's key through the same codec the build uses (transMortonXYZ, map2D.h:1293)
     const PointKey gk = point_key(goal_xyz[0], goal_xyz[1], goal_xyz[2], h->origin[0], h->origin[1], h->origin[2],
                                   h->P.grid_len, h->P.z_len);
-    // What depends on the map and the robot only — the column index, every row's neighbour columns / own column / CostEdge records,
-    // CollisionCheck's verdict for every slope — is kept from one flood to the next: the planner asks for a new goal on the same map
-    // (receiver.cpp:160-176 floods once per goal message), and those passes are 50 of bridge_ground's 430 us.
-    const float robot4[4] = {R.r, R.reach, R.rough, R.angle};
-    // (Not on a handle that has recorded a hipGraph: a replay rewrites the map without the host's serial moving.)
-    const bool tables_kept = K && !h->ever_captured && c.tables_serial == h->result_serial && std::memcmp(robot4, c.tables_robot, sizeof(robot4)) == 0;
-    c.tables_serial = 0;
     uint32_t* self = c.nbr + 8 * c.node_cap;
-    hipLaunchKernelGGL(k_cost_clear, dim3(grid_for(std::max<uint64_t>(n, tables_kept ? 0 : c.ctab_size))), dim3(256), 0, s, c.h_bits,
-                       c.state, (uint32_t)n, c.ctab_key, tables_kept ? 0u : c.ctab_size, c.d_cc);
     if (K && !tables_kept) {
-        hipLaunchKernelGGL(k_cost_columns, dim3(grid_for(n)), dim3(256), 0, s, h->out.sx, h->out.sy, h->part.row_ncol,
-                           (uint32_t)n, c.ctab_key, c.ctab_val, c.ctab_size - 1, c.d_cc);
         // the per-map tables (gndt_cost.hpp): neighbour columns, own column, and CollisionCheck's verdict for every slope — with a
         // robot wider than a cell after ring_n rounds of "the extreme over my steps" over the whole map instead of a ring per slope
         uint32_t* step = c.nbr + 10 * c.node_cap;
@@ -180,10 +209,7 @@ int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot*
 
 static int cost_ready(gndt_handle* h, gndt_cost_stats* st) {
     if (!h) return GNDT_ERR_INVALID;
-    if (!h->results_valid || h->cost.serial == 0 || h->cost.serial != h->result_serial) {
-        h->err = "no cost map for the current grid (call gndt_compute_cost after the build)";
-        return GNDT_ERR_INVALID;
-    }
+    if (const int rc = cost_map_check(h)) return rc;
     if (st) {
         const CostCounters* cc = h->cost.h_cc;
         st->goal_status = cc->goal_status; st->ring = (uint32_t)h->cost.ring_n; st->levels = cc->levels; st->ring_store = (uint32_t)h->cost.ring_store;

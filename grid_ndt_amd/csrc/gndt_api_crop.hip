@@ -9,8 +9,8 @@ namespace gndt_host {
 
 namespace {
 void release_rows(gndt_handle* h, OutView& v, uint32_t*& ncol) {
-    void* ptrs[] = {v.sx, v.sy, v.sz, v.count, v.first_idx, v.mean, v.cov, v.rough, v.normal, v.flags, ncol};
-    for (void* p : ptrs) release_device(h, p);
+    for (const RowArray& a : row_arrays(v)) release_device(h, *a.p);
+    release_device(h, ncol);
     v = OutView{};
     ncol = nullptr;
 }
@@ -18,9 +18,9 @@ void release_rows(gndt_handle* h, OutView& v, uint32_t*& ncol) {
 
 void free_crop(gndt_handle* h) {
     auto& c = h->crop;
-    void* ptrs[] = {c.spare.sx, c.spare.sy, c.spare.sz, c.spare.count, c.spare.first_idx, c.spare.mean, c.spare.cov, c.spare.rough,
-                    c.spare.normal, c.spare.flags, c.spare_ncol, c.tiles};
-    for (void* p : ptrs)
+    for (const RowArray& a : row_arrays(c.spare))
+        if (*a.p) (void)hipFree(*a.p);
+    for (void* p : {(void*)c.spare_ncol, (void*)c.tiles})
         if (p) (void)hipFree(p);
     c = gndt_handle::Crop{};
 }
@@ -34,16 +34,8 @@ int ensure_spare(gndt_handle* h) {
     if (c.spare.sx && c.spare_cap == rows && c.spare_ncol_cap == ncols) return GNDT_OK;
     release_rows(h, c.spare, c.spare_ncol);
     c.spare_cap = c.spare_ncol_cap = 0;
-    HIP_TRY(h, hipMalloc(&c.spare.sx, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.sy, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.sz, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.count, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.first_idx, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.mean, rows * 12));
-    HIP_TRY(h, hipMalloc(&c.spare.cov, rows * 24));
-    HIP_TRY(h, hipMalloc(&c.spare.rough, rows * 4));
-    HIP_TRY(h, hipMalloc(&c.spare.normal, rows * 12));
-    HIP_TRY(h, hipMalloc(&c.spare.flags, rows * 4));
+    const int rc = alloc_rows(h, c.spare, rows);
+    if (rc) return rc;
     HIP_TRY(h, hipMalloc(&c.spare_ncol, ncols * 4));
     c.spare_cap = rows;  c.spare_ncol_cap = ncols;
     return GNDT_OK;
@@ -85,12 +77,7 @@ int crop_prepare(gndt_handle* h) {
     int rc = ensure_spare(h);
     if (rc) return rc;
     const uint64_t tiles = (n + kCropTile - 1) / kCropTile;
-    if (tiles > c.tiles_cap) {
-        if (c.tiles) (void)hipFree(c.tiles);         // (the crop's own scratch: never recorded into a graph)
-        c.tiles = nullptr; c.tiles_cap = 0;
-        HIP_TRY(h, hipMalloc(&c.tiles, tiles * 4));
-        c.tiles_cap = tiles;
-    }
+    if ((rc = grow_scratch(h, c.tiles, c.tiles_cap, tiles * 4))) return rc;
     if (h->map_in_table && h->cap && h->h_cnt->num_nodes) return ensure_stats_buffers(h, h->h_cnt->num_nodes);
     return GNDT_OK;
 }
@@ -148,17 +135,9 @@ int gndt_crop_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, voi
     if (mode != GNDT_CROP_KEEP_INSIDE && mode != GNDT_CROP_DROP_INSIDE) { h->err = "gndt_crop: unknown mode"; return GNDT_ERR_INVALID; }
     if (box->sx_min > box->sx_max || box->sy_min > box->sy_max) { h->err = "gndt_crop: empty box (min > max)"; return GNDT_ERR_INVALID; }
     const hipStream_t s = stream_of(h, hip_stream);
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &cap);
-        if (cap != hipStreamCaptureStatusNone) { h->err = "gndt_crop: a crop is not recorded into a hipGraph"; return GNDT_ERR_INVALID; }
-    }
+    if ((rc = refuse_capture(h, s, "gndt_crop: a crop is not recorded into a hipGraph"))) return rc;
     // what gndt_sync finishes (a pending build, a deferred emit, a re-run) comes first; points outside the key range are only reported
-    { const int prc = partition_resolve(h); if (prc) return prc; }
-    if (!h->results_valid) { h->err = "no finished build to crop"; return GNDT_ERR_INVALID; }
-    rc = gndt_sync(h, nullptr, nullptr, nullptr);
-    if (rc && rc != GNDT_ERR_KEY_RANGE) return rc;
-    if (!h->results_valid) { h->err = "no finished build to crop"; return GNDT_ERR_INVALID; }
+    if ((rc = finished_map(h, "no finished build to crop", true))) return rc;
     if ((rc = use_stream(h, s))) return rc;
     const CropBox B{box->sx_min, box->sx_max, box->sy_min, box->sy_max, mode == GNDT_CROP_KEEP_INSIDE ? 1 : 0};
     if ((rc = crop_prepare(h))) return rc;
@@ -171,7 +150,7 @@ int gndt_crop_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, voi
         h->results_valid = true;
     }
     if ((rc = crop_rows(h, B, s))) { h->results_valid = false; return rc; }
-    // the map has changed: cost map and query index are stale, the next update takes the full finalisation, nothing deferred is left
+    // the map has changed: cost map and column index are stale, the next update takes the full finalisation, nothing deferred is left
     ++h->result_serial;
     h->incr_ok = false;
     h->emit_pending = false; h->deferred_captured = false; h->pending_words = 0;

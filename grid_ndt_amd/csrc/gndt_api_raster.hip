@@ -1,6 +1,6 @@
 // gndt_api_raster.hip — raster export (gndt_query.hpp k_raster): one pixel per column of a box of signed column indices, the slope of
 // the column a consumer stands on (the reference's showBottom / showSlopeList, include/map2D.h:980-1284), with its row, height,
-// roughness, node count and cost.  Runs after the point queries' steps (query_sync, query_index) on the queries' column index.
+// roughness, node count and cost.  Runs after the point queries' steps (query_sync) on the map's column index (column_index).
 #include "gndt_handle.hpp"
 #include "gndt_query.hpp"
 
@@ -8,11 +8,6 @@ using namespace gndt;
 using namespace gndt_host;
 
 namespace gndt_host {
-
-void free_raster(gndt_handle* h) {
-    if (h->raster.scratch) (void)hipFree(h->raster.scratch);
-    h->raster = gndt_handle::Raster{};
-}
 
 namespace {
 
@@ -58,12 +53,12 @@ void raster_launch_gather(const QueryView& Q, const gndt_crop_box& B, uint32_t w
     else raster_launch<MODE, kRasterSlope | kRasterCost>(Q, B, width, n, z_ref, o, s);
 }
 
-// Arguments checked: the queries' steps (capture, finished map, cost map, gndt_sync; the stream and the column index), then one kernel
+// Arguments checked: the queries' steps (capture, finished map, cost map, gndt_sync), the stream and the column index, then one kernel
 int raster_enqueue(gndt_handle* h, const gndt_crop_box& B, int32_t mode, float z_ref, uint32_t width, uint32_t height,
                    const gndt_raster_layers& L, hipStream_t s) {
     int rc = query_sync(h, L.h || L.state, s, "gndt_raster: a raster is not recorded into a hipGraph");
     if (rc) return rc;
-    if ((rc = query_index(h, s))) return rc;
+    if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
     const QueryView Q = query_view(h);
     const RasterOut o{L.row, L.z, L.rough, L.nodes, L.h, L.state};
     const uint32_t n = width * height;               // (<= 2^31: raster_box)
@@ -104,23 +99,13 @@ int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_
     uint32_t width = 0, height = 0;
     if ((rc = raster_args(h, box, mode, z_ref, out_host, width, height))) return rc;
     const hipStream_t s = h->own_stream;
-    // the requested layers side by side in the handle's scratch (the raster's own: never recorded into a graph, so plainly freed)
+    // the requested layers in the handle's staging
     const uint64_t n = (uint64_t)width * height;
     void* const host[6] = {out_host->row, out_host->z, out_host->rough, out_host->nodes, out_host->h, out_host->state};
-    void* dev[6] = {};
-    uint64_t bytes = 0;
-    for (int k = 0; k < 6; ++k)
-        if (host[k]) bytes += n * 4;
-    auto& r = h->raster;
-    if (bytes > r.cap) {
-        if (r.scratch) (void)hipFree(r.scratch);
-        r.scratch = nullptr; r.cap = 0;
-        HIP_TRY(h, hipMalloc(&r.scratch, bytes));
-        r.cap = bytes;
-    }
-    uint64_t off = 0;
-    for (int k = 0; k < 6; ++k)
-        if (host[k]) { dev[k] = static_cast<char*>(r.scratch) + off; off += n * 4; }
+    uint64_t bytes[6];
+    for (int k = 0; k < 6; ++k) bytes[k] = host[k] ? n * 4 : 0;
+    void* dev[6];
+    if ((rc = stage_pieces(h, bytes, dev, 6))) return rc;
     const gndt_raster_layers L{static_cast<uint32_t*>(dev[0]), static_cast<float*>(dev[1]), static_cast<float*>(dev[2]),
                                static_cast<uint32_t*>(dev[3]), static_cast<float*>(dev[4]), static_cast<uint32_t*>(dev[5])};
     if ((rc = raster_enqueue(h, *box, mode, z_ref, width, height, L, s))) return rc;

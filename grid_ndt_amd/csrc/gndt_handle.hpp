@@ -13,6 +13,7 @@
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -186,42 +187,35 @@ struct gndt_handle {
     // cost-map flood over the finished grid (gndt_cost.hpp)
     struct Cost {
         uint64_t node_cap = 0;     uint32_t *h_bits = nullptr, *state = nullptr, *f[2] = {nullptr, nullptr};
-        uint32_t ctab_size = 0;    uint64_t* ctab_key = nullptr; uint32_t* ctab_val = nullptr;
         uint32_t* nbr = nullptr;       // per-flood tables, node_cap rows each: neighbour columns (8 words), own column + collision verdict (2), ring step masks (4), ring extremes (4)
         CostEdge* edges = nullptr;     // node_cap x 4 records: what a slope does to each of its neighbour cells (gndt_cost.hpp)
-        CostCounters* d_cc = nullptr;
+        CostCounters* d_cc = nullptr;   // (also counts the column index's builds: its column range bound, cost_counters)
         CostCounters* h_cc = nullptr;   // pinned
         uint64_t serial = 0;            // result_serial the flood was computed for (0 = none)
-        uint64_t tables_serial = 0;     // result_serial the per-map tables (column index, nbr / self / edges, ring verdicts) belong to (0 = none) ...
+        uint64_t tables_serial = 0;     // result_serial the per-map-and-robot tables (nbr / self / edges, ring verdicts) belong to (0 = none) ...
         float tables_robot[4] = {0, 0, 0, 0};   // ... and the robot they were worked out for: the next goal on the same map reuses them
         int ring_n = 0, ring_store = 0;
     } cost;
-    // point queries (gndt_query.hpp): their own (sx, sy) -> first row index, apart from the flood's (whose reuse logic, tables_kept,
-    // then keeps serving one caller), and the device copies of a host query's input and answers
-    struct Query {
-        uint32_t ctab_cap = 0;     uint64_t* ctab_key = nullptr; uint32_t* ctab_val = nullptr;
-        uint32_t ctab_mask = 0;
+    // the map's column index, (sx, sy) -> first row (gndt_cost.hpp k_cost_columns): one per map, built by whichever of the flood, a
+    // query, a raster or a clear needs it first (column_index); keys (8 B a slot), then values (4 B a slot) in one buffer
+    struct ColumnIndex {
+        void* buf = nullptr;  uint64_t bytes = 0;
+        uint64_t* key = nullptr;  uint32_t* val = nullptr;  uint32_t mask = 0;
         uint64_t serial = 0;            // result_serial the index was built for (0 = none)
-        CostCounters* d_cc = nullptr;   // k_cost_columns' counters: scratch (its column range bound belongs to the flood)
-        uint64_t in_cap = 0, out_cap = 0;   // bytes
-        void* in = nullptr;  uint32_t *rows = nullptr, *h_bits = nullptr, *state = nullptr;
-    } query;
-    // raster export (gndt_api_raster.hip): the device scratch gndt_raster fills and copies from (the layers side by side), grown on demand
-    struct Raster {
-        void* scratch = nullptr;  uint64_t cap = 0;     // bytes
-    } raster;
+    } index;
+    // device staging of the host-pointer consumers (gndt_query, gndt_raster, gndt_clear_rays: stage_pieces), grown on demand
+    void* io = nullptr;  uint64_t io_cap = 0;     // bytes
     // region crop (gndt_crop.hpp): the second set of result arrays the kept rows are compacted into (then swapped with out / row_ncol:
     // same capacities), and the per-tile counts of the scan
     struct Crop {
         OutView spare{};  uint32_t* spare_ncol = nullptr;  uint64_t spare_cap = 0, spare_ncol_cap = 0;
-        uint32_t* tiles = nullptr;  uint64_t tiles_cap = 0;
+        uint32_t* tiles = nullptr;  uint64_t tiles_cap = 0;     // bytes
     } crop;
     // free-space clearing (gndt_ray.hpp): per-row pass counts and protection bits, the per-column level extents (at each column's first
-    // row), the device copies of a host call's input and the call's counters {rays, skipped, protected rows}; grown on demand
+    // row) and the call's counters {rays, skipped, protected rows}; grown on demand
     struct Clear {
-        uint32_t* passes = nullptr;  void* ext = nullptr;  uint64_t rows_cap = 0;    // ext: gndt::LevelExtent[rows]
+        uint32_t* passes = nullptr;  uint64_t passes_cap = 0;  void* ext = nullptr;  uint64_t ext_cap = 0;   // bytes; ext: gndt::LevelExtent[rows]
         uint64_t ext_serial = 0;        // result_serial the extents were computed for (0 = none)
-        void* in = nullptr;  uint64_t in_cap = 0;          // bytes
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;   // [3], device and pinned
     } clear;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
@@ -466,6 +460,30 @@ inline void release_device(gndt_handle* h, void* p, bool bump = true) {     // (
     if (h->ever_captured) h->retired.push_back(p); else (void)hipFree(p);
 }
 
+// A device buffer that a consumer owns and never records into a graph, grown to `bytes` on demand and plainly freed.  (Not grow_buf:
+// that one retires the old buffer and bumps realloc_gen, which would report unrelated recorded graphs as stale.)
+template <typename T>
+int grow_scratch(gndt_handle* h, T*& p, uint64_t& cap, uint64_t bytes) {
+    if (bytes <= cap) return GNDT_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    HIP_TRY(h, hipMalloc(&p, bytes));
+    cap = bytes;
+    return GNDT_OK;
+}
+
+// A cache of the map (the column index, the clear's level extents, the flood's per-map tables) is current while the map is the one it
+// was made for — never on a handle that has recorded a hipGraph: a replay rewrites the map without the host's serial moving
+inline bool map_current(const gndt_handle* h, uint64_t serial) { return serial && serial == h->result_serial && !h->ever_captured; }
+
+// The ten result-row arrays of an OutView or a gndt_cells (the same fields) and the bytes a row takes in each: 76 in all
+struct RowArray { void** p; size_t elem; };
+template <typename V>
+std::array<RowArray, 10> row_arrays(V& v) {
+    return {{{(void**)&v.sx, 4}, {(void**)&v.sy, 4}, {(void**)&v.sz, 4}, {(void**)&v.count, 4}, {(void**)&v.first_idx, 4},
+             {(void**)&v.mean, 12}, {(void**)&v.cov, 24}, {(void**)&v.rough, 4}, {(void**)&v.normal, 12}, {(void**)&v.flags, 4}}};
+}
+
 template <typename T>
 int grow_buf(gndt_handle* h, T*& p, uint64_t& cap, uint64_t want) {
     if (want <= cap) return GNDT_OK;
@@ -483,6 +501,13 @@ int grow_buf(gndt_handle* h, T*& p, uint64_t& cap, uint64_t want) {
 // ---- gndt_api_core.hip: shared buffers ----
 int create_handle(const gndt_params* params, gndt_handle** out, hipStream_t borrowed_stream);   // gndt_create's body
 int check_ready(gndt_handle* h);
+// A finished map for a consumer: a pending build resolved, results_valid (else no_map_err), gndt_sync; with key_range_ok a
+// GNDT_ERR_KEY_RANGE of the build does not stop the caller (crop, clear)
+int finished_map(gndt_handle* h, const char* no_map_err, bool key_range_ok);
+int refuse_capture(gndt_handle* h, hipStream_t s, const char* msg);   // GNDT_ERR_INVALID with msg when s is under hipGraph capture
+int alloc_rows(gndt_handle* h, OutView& v, uint64_t rows);            // the ten result-row arrays, `rows` rows each
+// the host-pointer consumers' staging (h->io): `count` pieces of bytes[k], 256-byte aligned (null where bytes[k] is 0)
+int stage_pieces(gndt_handle* h, const uint64_t* bytes, void** piece, int count);
 int use_stream(gndt_handle* h, hipStream_t s);     // work moves to stream s: it waits for what the handle's last stream still runs
 int ensure_out(gndt_handle* h, uint64_t n);
 int ensure_stats_buffers(gndt_handle* h, uint64_t n);
@@ -523,15 +548,16 @@ int partition_begin(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride
 int partition_resolve(gndt_handle* h);
 // ---- gndt_api_cost.hip ----
 void free_cost(gndt_handle* h);
+int cost_counters(gndt_handle* h);        // h->cost.d_cc and its pinned mirror h_cc, allocated together by whoever comes first
+int cost_map_check(gndt_handle* h);       // GNDT_ERR_INVALID unless the flood's cost map is the current map's
+// The map's column index (h->index), built on stream s unless it is current (the caller has passed use_stream, the flood excepted).
+// flood: the flood's one k_cost_clear, which also resets its h array (and clears no table when the index is current)
+int column_index(gndt_handle* h, hipStream_t s, bool flood = false);
 // ---- gndt_api_query.hip ----
-void free_query(gndt_handle* h);
-// the steps before a query's or a raster's kernel: capture, finished map, cost map when gathered (gndt_sync on the way); then the stream
-// and the column index of the current map (h->query); and the view of rows, index and cost map the kernels read
+// the steps before a query's or a raster's kernel: no capture, a finished map, the cost map when gathered; and the view of rows,
+// index and cost map the kernels read
 int query_sync(gndt_handle* h, bool gather, hipStream_t s, const char* capture_err);
-int query_index(gndt_handle* h, hipStream_t s);
 gndt::QueryView query_view(gndt_handle* h);
-// ---- gndt_api_raster.hip ----
-void free_raster(gndt_handle* h);
 // ---- gndt_api_crop.hip ----
 void free_crop(gndt_handle* h);
 // ---- gndt_api_clear.hip ----

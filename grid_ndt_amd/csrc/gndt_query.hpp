@@ -11,7 +11,7 @@
 // them before the next one waits — but measured on the S2 map (DESIGN.md "Point queries") 2 and 4 were no faster than 1: with 32 waves
 // per CU the kernel is bound by the cache lines its four random loads per query fetch (key, value, row_ncol, sz: 128-byte lines for 4-8
 // useful bytes, from L2 or the Infinity Cache), not by their latency.  The default is 1 (GNDT_DEBUG_QUERY_ILP selects 2 or 4).
-// Everything here is callable on the host as well, so that the CPU test tier runs the kernel's own code (tests/query_shim.cpp).
+// Everything here is callable on the host as well, so that the CPU test tier runs the kernel's own code (tests/consumer_shim.cpp).
 #pragma once
 #include <float.h>
 #include <math.h>

@@ -4,7 +4,7 @@
 // the codec's columns of the ray's origin and of the cut point, exactly |dx| + |dy| unit steps between them, each across the lattice
 // plane the segment meets first (fp64 crossing parameter, a tie stepping x), and in every column the levels between the ray's z at the
 // column's entry and at its exit (the codec's level of the origin / the cut point at the ends, the codec's rule in fp64 inside).
-// Everything up to the rows is callable on the host as well, so that the CPU test tier runs the kernel's own code (tests/clear_shim.cpp).
+// Everything up to the rows is callable on the host as well, so that the CPU test tier runs the kernel's own code (tests/consumer_shim.cpp).
 //
 // Kernels (gndt_api_clear.hip launches them in this order):
 //   k_clear_extent   (GNDT_DEBUG_CLEAR_EXTENT only) per column, at its first row: the least and greatest sz of its rows (the walk skips a column whose extent misses

@@ -366,7 +366,7 @@ int gndt_adopt_rows_device(gndt_handle* h, const uint32_t* rows_dev, uint64_t n_
  *   state  0 = untouched, 1 = traversable (the reference's `traversability` list), 2 = closed (collision)
  * bit-identical to the reference's sequential flood on the same grid (DESIGN.md "Cost map").
  * The call returns when the flood is complete.  Column indices must not exceed 32767 (mortonToXY's range,
- * Stopwatch.h:171-189).  `robot` NULL = RobotSphere(0.25) with robot.h:38-46's thresholds. */
+ * Stopwatch.h:171-189).  The flood builds or reuses the map's column index, which point queries, rasters and clears share.  `robot` NULL = RobotSphere(0.25) with robot.h:38-46's thresholds. */
 typedef struct gndt_robot {
     float radius;            /* RobotSphere::r            receiver.cpp:33  */
     float reachable_height;  /* getReachableHeight() 0.15  robot.h:38-39   */
@@ -414,8 +414,8 @@ int gndt_cost_export(gndt_handle* h, float* h_out, uint32_t* state_out, gndt_cos
  * state_out without a current cost map, a stream under hipGraph capture (queries are not recorded).  There is no CPU path: without a
  * device the call fails like every compute entry point.  n == 0 returns GNDT_OK and launches nothing.
  * Order: the call first finishes what gndt_compute_cost finishes (a pending build, a deferred emit, a re-run: gndt_sync), then builds
- * or reuses its column index — rebuilt after every build / update / remove, and on every call on a handle that has recorded a
- * hipGraph (a replay rewrites the map unseen) — and enqueues one kernel.  Row numbers stay valid until the next build, update, remove,
+ * or reuses the map's column index, which the flood, rasters and clears share — rebuilt after every build / update / remove, and on
+ * every call on a handle that has recorded a hipGraph (a replay rewrites the map unseen) — and enqueues one kernel.  Row numbers stay valid until the next build, update, remove,
  * crop or reset.  A sharded map answers from the rows this rank holds. */
 enum { GNDT_QUERY_NODE = 0, GNDT_QUERY_NEAREST_SLOPE = 1 };
 #define GNDT_NO_ROW 0xFFFFFFFFu
@@ -446,7 +446,7 @@ int gndt_query(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_byt
  * Order and lifetime:
  *   - the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a re-run);
  *   - the map is new: the cost map is invalid until the next gndt_compute_cost (gndt_cost_export* refuse it, as after an update), the
- *     query index is rebuilt, and device pointers from gndt_export_device and row numbers from gndt_query* are invalid;
+ *     map's column index is rebuilt, and device pointers from gndt_export_device and row numbers from gndt_query* are invalid;
  *   - a stream under hipGraph capture is refused (GNDT_ERR_INVALID: a crop is not recorded);
  *   - a graph recorded before a crop and replayed after it is reported stale by gndt_sync (GNDT_ERR_CAPACITY, as after a buffer
  *     reallocation): the crop moves the result arrays.  Capture again after the crop.
@@ -483,7 +483,7 @@ int gndt_crop_box_from_world(const float origin[3], float grid_len, const float 
  * axis, an index beyond +-65535, an axis without a non-zero index ([0, 0]), width * height > 2^31, no finished build, h or state
  * without a cost map of the current grid (the rule of gndt_cost_export), a stream under hipGraph capture (a raster is not recorded).
  * Order and lifetime are the point queries': the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a
- * re-run), then builds or reuses the queries' column index (the same index, under the same rule).  Row numbers stay valid until the
+ * re-run), then builds or reuses the map's column index (the one the queries and the flood use, under the same rule).  Row numbers stay valid until the
  * next build, update, remove, crop or reset.  A sharded map rasterises the rows this rank holds. */
 enum { GNDT_RASTER_LOWEST = 0, GNDT_RASTER_HIGHEST = 1, GNDT_RASTER_NEAREST_Z = 2 };
 typedef struct {
@@ -541,10 +541,10 @@ int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_
  * stream under hipGraph capture (a clear is not recorded), clearing without the node table.  There is no CPU path: without a device
  * the call fails like every compute entry point.  n == 0 returns GNDT_OK and changes nothing.
  * Order and lifetime are gndt_crop's:
- *   - the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a re-run), then builds or reuses the point
- *     queries' column index;
- *   - clearing makes a new map: the cost map is invalid until the next gndt_compute_cost (gndt_cost_export* refuse it), the query index
- *     is rebuilt, device pointers from gndt_export_device and row numbers from gndt_query* are invalid, and a graph recorded before
+ *   - the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a re-run), then builds or reuses the map's
+ *     column index (the one the point queries and the flood use);
+ *   - clearing makes a new map: the cost map is invalid until the next gndt_compute_cost (gndt_cost_export* refuse it), the column
+ *     index is rebuilt, device pointers from gndt_export_device and row numbers from gndt_query* are invalid, and a graph recorded before
  *     the clear and replayed after it is reported stale by gndt_sync (GNDT_ERR_CAPACITY).  Capture again after the clear.
  * Clearing waits for the device, as gndt_remove does: deaths are only known there.  A count-only gndt_clear_rays_device is enqueued on
  * `hip_stream` (NULL = the handle's stream, the rules of gndt_build_device) and not awaited unless `stats` is non-NULL.

@@ -14,18 +14,140 @@ _SO = os.path.join(_HERE, "_host_math_shim.so")
 _lib = None
 
 
+def load_shim(src, so_name, headers, signatures):
+    """tests/<src> compiled with g++ into tests/<so_name> (again when it or one of `headers` of grid_ndt_amd/csrc is newer) and loaded;
+    signatures: {function: (argtypes, restype)}"""
+    csrc = os.path.join(_ROOT, "grid_ndt_amd", "csrc")
+    src, so = os.path.join(_HERE, src), os.path.join(_HERE, so_name)
+    deps = [src] + [os.path.join(csrc, f) for f in headers]
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", csrc, "-o", so, src])
+    L = C.CDLL(so)
+    for name, (argtypes, restype) in signatures.items():
+        getattr(L, name).argtypes = argtypes
+        getattr(L, name).restype = restype
+    return L
+
+
 def shim():
     global _lib
     if _lib is None:
-        src = os.path.join(_HERE, "host_math_shim.cpp")
-        hdrs = [os.path.join(_ROOT, "grid_ndt_amd", "csrc", f) for f in ("gndt_math.hpp", "gndt_cost.hpp")]
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
-                                   os.path.join(_ROOT, "grid_ndt_amd", "csrc"), "-o", _SO, src])
-        _lib = C.CDLL(_SO)
-        _lib.shim_mean_z.restype = C.c_float
-        _lib.shim_mean_z.argtypes = [C.c_uint32, C.c_double, C.c_double]
+        _lib = load_shim("host_math_shim.cpp", os.path.basename(_SO), ("gndt_math.hpp", "gndt_cost.hpp"),
+                         {"shim_mean_z": ([C.c_uint32, C.c_double, C.c_double], C.c_float)})
     return _lib
+
+
+_clib = None
+
+
+def consumer_shim():
+    """tests/consumer_shim.cpp: the queries', the raster export's and free-space clearing's per-element code, built for the host"""
+    global _clib
+    if _clib is None:
+        vp, f, i32, u32, u64 = C.c_void_p, C.c_float, C.c_int32, C.c_uint32, C.c_uint64
+        _clib = load_shim("consumer_shim.cpp", "_consumer_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp"), {
+            "build_index": ([vp, vp, vp, u64, vp, vp, u32], None),
+            "qshim_query": ([C.c_int, C.c_int, C.c_int, vp, u32, u64] + [vp] * 8 + [u32, vp, vp, vp, f, f, u64, vp, vp, vp], C.c_int),
+            "qshim_ctab_find": ([vp, vp, u32, i32, i32], u32),
+            "rshim_index": ([i32, u32], C.c_int),
+            "rshim_count": ([i32, i32], u32),
+            "rshim_raster": ([C.c_int, u32, i32, i32, u32, u32, f] + [vp] * 9 + [u32] + [vp] * 8, C.c_int),
+            "cshim_walk": ([vp, f, f, vp, vp, f, f, vp, i32], C.c_int),
+            "cshim_passes": ([vp, f, f, vp, vp, u64, u32, f, f, C.c_int] + [vp] * 4 + [u64, vp, vp, u32, vp, vp, vp], None),
+        })
+    return _clib
+
+
+def _pow2_at_least(v, floor=1024):
+    p = floor
+    while p < v:
+        p <<= 1
+    return p
+
+
+class HostMap:
+    """The rows of an oracle map, with the per-row column sizes, the column index derived on the host — at the library's size
+    (column_index's rule: load <= 1/2), or with table="tight" the smallest table with a free slot (long probe chains: ctab_find) —
+    and a made-up cost map drawn from `seed`; run through consumer_shim()"""
+
+    def __init__(self, cloud, P, table="library", seed=11):
+        from oracle import oracle
+        from tests import query_ref as qr
+        self.origin = np.asarray(cloud[0, :3], np.float32)
+        self.P = P
+        c = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"), mode=oracle.MODE_INT_OPENMP)
+        self.cells = c
+        self.n = int(c["num_nodes"])
+        self.sx, self.sy, self.sz = (np.ascontiguousarray(c[k], np.int32) for k in ("sx", "sy", "sz"))
+        self.mean = np.ascontiguousarray(c["mean"], np.float32)
+        self.rough = np.ascontiguousarray(c["rough"], np.float32)
+        self.flags = np.ascontiguousarray(c["flags"], np.uint32)
+        self.row_ncol = qr.row_ncol(c)
+        K = int((self.row_ncol > 0).sum())
+        assert K == int(c["num_columns"])
+        self.tsize = _pow2_at_least(2 * K) if table == "library" else _pow2_at_least(K + 1, floor=1)
+        self.ctab_key = np.zeros(self.tsize, np.uint64)
+        self.ctab_val = np.zeros(self.tsize, np.uint32)
+        consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
+                                    self.ctab_val.ctypes.data, self.tsize)
+        rng = np.random.default_rng(seed)
+        self.h_bits = rng.integers(0, 0x7F7FFFFF, size=max(self.n, 1), dtype=np.uint32)
+        self.state = rng.integers(0, 3, size=max(self.n, 1), dtype=np.uint32)
+
+    def box(self):
+        return int(self.sx.min()), int(self.sx.max()), int(self.sy.min()), int(self.sy.max())
+
+    def query(self, pts, mode, ilp=1, threads=1, gather=False):
+        """query_points over n points as k_query's `threads` threads run them -> rows (int64), with gather (rows, h, state)"""
+        pts = np.ascontiguousarray(pts, np.float32)
+        n = pts.shape[0]
+        rows = np.full(n, 0xDEADBEEF, np.uint32)
+        h = np.zeros(n, np.float32)
+        st = np.full(n, 99, np.uint32)
+        o = (C.c_float * 3)(*[float(v) for v in self.origin])
+        rc = consumer_shim().qshim_query(mode, ilp, int(gather), pts.ctypes.data, pts.shape[1], n, self.sx.ctypes.data, self.sy.ctypes.data,
+                                         self.sz.ctypes.data, self.mean.ctypes.data, self.flags.ctypes.data, self.row_ncol.ctypes.data,
+                                         self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize, self.h_bits.ctypes.data,
+                                         self.state.ctypes.data, o, self.P["grid_len"], self.P["z_len"], threads, rows.ctypes.data,
+                                         h.ctypes.data, st.ctypes.data)
+        assert rc == 0
+        r = rows.view(np.int32).astype(np.int64)
+        return (r, h, st) if gather else r
+
+    def raster(self, box, mode, z_ref=0.0, gather=3, layers=("row", "z", "rough", "nodes", "h", "state")):
+        """raster_pixel over every pixel of the box -> {layer: (H, W) image}"""
+        from tests import raster_ref as rr
+        W, H = len(rr.axis(box[0], box[1])), len(rr.axis(box[2], box[3]))
+        dt = {"row": np.uint32, "z": np.float32, "rough": np.float32, "nodes": np.uint32, "h": np.float32, "state": np.uint32}
+        out = {k: np.full((H, W), 0xA5A5A5A5, np.uint32).view(dt[k]) for k in layers}
+        p = lambda k: C.c_void_p(out[k].ctypes.data if k in out else 0)
+        rc = consumer_shim().rshim_raster(mode, gather, box[0], box[2], W, W * H, z_ref, self.sx.ctypes.data,
+                                          self.sy.ctypes.data, self.sz.ctypes.data, self.mean.ctypes.data, self.rough.ctypes.data,
+                                          self.flags.ctypes.data, self.row_ncol.ctypes.data, self.ctab_key.ctypes.data, self.ctab_val.ctypes.data,
+                                          self.tsize, self.h_bits.ctypes.data, self.state.ctypes.data, p("row"), p("z"), p("rough"), p("nodes"),
+                                          p("h"), p("state"))
+        assert rc == 0
+        if "row" in out:
+            out["row"] = out["row"].view(np.int32)
+        return out
+
+    def want(self, box, mode, z_ref=0.0):
+        """the raster's numpy restatement (tests/raster_ref.py) on the same rows and cost map"""
+        from tests import raster_ref as rr
+        return rr.raster(self.cells, box, mode, z_ref, self.h_bits[:self.n], self.state[:self.n])
+
+    def passes(self, o, pts, max_range=0.0, end_margin=0.0, ext=True):
+        """count-only passes of the rays from o to pts -> (per-row words, rays, skipped)"""
+        pts = np.ascontiguousarray(pts, np.float32)
+        oo = np.ascontiguousarray(o, np.float32)
+        words = np.zeros(max(self.n, 1), np.uint32)
+        extent = np.zeros((max(self.n, 1), 2), np.int32)
+        stats = np.zeros(2, np.uint64)
+        consumer_shim().cshim_passes(self.origin.ctypes.data, self.P["grid_len"], self.P["z_len"], oo.ctypes.data, pts.ctypes.data, len(pts),
+                                     pts.shape[1], max_range, end_margin, int(ext), self.sx.ctypes.data, self.sy.ctypes.data,
+                                     self.sz.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
+                                     self.ctab_val.ctypes.data, self.tsize, extent.ctypes.data, words.ctypes.data, stats.ctypes.data)
+        return words[:self.n], int(stats[0]), int(stats[1])
 
 
 _DSO = os.path.join(_HERE, "_device_math_shim.so")

@@ -1,43 +1,13 @@
 """CPU tier: free-space clearing's code (grid_ndt_amd/csrc/gndt_ray.hpp: the walk of a ray and the count-only passes of the kernels,
-with and without the extent skip), compiled with g++ into tests/_clear_shim.so, against hand-derived walks and against the numpy
+with and without the extent skip), compiled with g++ into tests/_consumer_shim.so, against hand-derived walks and against the numpy
 restatement of the definition (tests/clear_ref.py) on maps the oracle builds; and the product entry points refuse to run without a GPU."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from grid_ndt_amd import scenes
-from oracle import oracle
 from tests import clear_ref as cr
-from tests import query_ref as qr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_HERE)
-_SO = os.path.join(_HERE, "_clear_shim.so")
-_lib = None
-
-
-def shim():
-    global _lib
-    if _lib is None:
-        src = os.path.join(_HERE, "clear_shim.cpp")
-        hdrs = [os.path.join(_ROOT, "grid_ndt_amd", "csrc", f) for f in ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp")]
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
-                                   os.path.join(_ROOT, "grid_ndt_amd", "csrc"), "-o", _SO, src])
-        L = C.CDLL(_SO)
-        vp, f = C.c_void_p, C.c_float
-        L.cshim_walk.argtypes = [vp, f, f, vp, vp, f, f, vp, C.c_int32]
-        L.cshim_walk.restype = C.c_int
-        L.cshim_passes.argtypes = [vp, f, f, vp, vp, C.c_uint64, C.c_uint32, f, f, C.c_int] + [vp] * 4 + [C.c_uint64, vp, vp, C.c_uint32,
-                                                                                                        vp, vp, vp]
-        L.cshim_passes.restype = None
-        L.cshim_build_index.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32]
-        L.cshim_build_index.restype = None
-        _lib = L
-    return _lib
+from tests.host_emulation import HostMap, consumer_shim
 
 
 def _f32(a):
@@ -49,7 +19,7 @@ def shim_walk(map_origin, grid_len, z_len, o, p, max_range=0.0, end_margin=0.0):
     mo, oo, pp = _f32(map_origin), _f32(o), _f32(p)
     cap = 1 << 16
     out = np.zeros((cap, 4), np.int32)
-    k = shim().cshim_walk(mo.ctypes.data, grid_len, z_len, oo.ctypes.data, pp.ctypes.data, max_range, end_margin, out.ctypes.data, cap)
+    k = consumer_shim().cshim_walk(mo.ctypes.data, grid_len, z_len, oo.ctypes.data, pp.ctypes.data, max_range, end_margin, out.ctypes.data, cap)
     if k < 0:
         return None
     assert k <= cap
@@ -93,39 +63,6 @@ def test_hand_derived_walks(case):
 def test_skipped_points():
     for p in ((np.nan, 0.5, 0.5), (0.5, np.inf, 0.5), (1e6, 0.5, 0.5)):
         assert shim_walk(*UNIT, O, p) is None and ref_walk(*UNIT, O, p) is None
-
-
-class HostMap:
-    """An oracle map's rows, per-row column sizes and the column index (the library's size)"""
-
-    def __init__(self, cloud, P):
-        self.origin = _f32(cloud[0, :3])
-        self.P = P
-        c = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"), mode=oracle.MODE_INT_OPENMP)
-        self.cells = c
-        self.n = int(c["num_nodes"])
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(c[k], np.int32) for k in ("sx", "sy", "sz"))
-        self.row_ncol = qr.row_ncol(c)
-        K = int((self.row_ncol > 0).sum())
-        self.tsize = 1024
-        while self.tsize < 2 * K:
-            self.tsize <<= 1
-        self.ctab_key = np.zeros(self.tsize, np.uint64)
-        self.ctab_val = np.zeros(self.tsize, np.uint32)
-        shim().cshim_build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                 self.ctab_val.ctypes.data, self.tsize)
-
-    def passes(self, o, pts, max_range=0.0, end_margin=0.0, ext=True):
-        pts = _f32(pts)
-        oo = _f32(o)
-        words = np.zeros(max(self.n, 1), np.uint32)
-        extent = np.zeros((max(self.n, 1), 2), np.int32)
-        stats = np.zeros(2, np.uint64)
-        shim().cshim_passes(self.origin.ctypes.data, self.P["grid_len"], self.P["z_len"], oo.ctypes.data, pts.ctypes.data, len(pts), pts.shape[1],
-                            max_range, end_margin, int(ext), self.sx.ctypes.data, self.sy.ctypes.data, self.sz.ctypes.data,
-                            self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize,
-                            extent.ctypes.data, words.ctypes.data, stats.ctypes.data)
-        return words[:self.n], int(stats[0]), int(stats[1])
 
 
 def _terrain():

@@ -1,92 +1,13 @@
 """CPU tier: the point queries' per-point code (grid_ndt_amd/csrc/gndt_query.hpp: query_points at ILP 1, 2 and 4, and the ctab_find
-probe behind it), compiled with g++ into tests/_query_shim.so, against plain numpy lookups of the rows (tests/query_ref.py) on maps the
+probe behind it), compiled with g++ into tests/_consumer_shim.so, against plain numpy lookups of the rows (tests/query_ref.py) on maps the
 oracle builds; and the product entry point refuses to run without a GPU."""
-import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from grid_ndt_amd import scenes
-from oracle import oracle
 from tests import query_ref as qr
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_HERE)
-_SO = os.path.join(_HERE, "_query_shim.so")
-_lib = None
-
-
-def shim():
-    global _lib
-    if _lib is None:
-        src = os.path.join(_HERE, "query_shim.cpp")
-        hdrs = [os.path.join(_ROOT, "grid_ndt_amd", "csrc", f) for f in ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp")]
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
-                                   os.path.join(_ROOT, "grid_ndt_amd", "csrc"), "-o", _SO, src])
-        L = C.CDLL(_SO)
-        vp = C.c_void_p
-        L.qshim_build_index.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32]
-        L.qshim_build_index.restype = None
-        L.qshim_query.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_uint32, C.c_uint64] + [vp] * 8 + [C.c_uint32, vp, vp, vp, C.c_float,
-                                                                                                     C.c_float, C.c_uint64, vp, vp, vp]
-        L.qshim_query.restype = C.c_int
-        L.qshim_ctab_find.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_int32]
-        L.qshim_ctab_find.restype = C.c_uint32
-        _lib = L
-    return _lib
-
-
-def _pow2_at_least(v, floor=1024):
-    p = floor
-    while p < v:
-        p <<= 1
-    return p
-
-
-class HostMap:
-    """The rows of an oracle map, with the per-row column sizes and the column index derived on the host"""
-
-    def __init__(self, cloud, P, table="library"):
-        self.origin = np.asarray(cloud[0, :3], np.float32)
-        self.P = P
-        self.cells = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"),
-                                       mode=oracle.MODE_INT_OPENMP)
-        c = self.cells
-        self.n = int(c["num_nodes"])
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(c[k], np.int32) for k in ("sx", "sy", "sz"))
-        self.mean = np.ascontiguousarray(c["mean"], np.float32)
-        self.flags = np.ascontiguousarray(c["flags"], np.uint32)
-        self.row_ncol = qr.row_ncol(c)
-        K = int((self.row_ncol > 0).sum())
-        assert K == int(c["num_columns"])
-        # the library's size (gndt_query's rule: load <= 1/2), or the smallest table with a free slot (long probe chains: ctab_find)
-        self.tsize = _pow2_at_least(2 * K) if table == "library" else _pow2_at_least(K + 1, floor=1)
-        self.ctab_key = np.zeros(self.tsize, np.uint64)
-        self.ctab_val = np.zeros(self.tsize, np.uint32)
-        shim().qshim_build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                 self.ctab_val.ctypes.data, self.tsize)
-        rng = np.random.default_rng(11)
-        self.h_bits = rng.integers(0, 0x7F7FFFFF, size=max(self.n, 1), dtype=np.uint32)
-        self.state = rng.integers(0, 3, size=max(self.n, 1), dtype=np.uint32)
-
-    def query(self, pts, mode, ilp=1, threads=1, gather=False):
-        pts = np.ascontiguousarray(pts, np.float32)
-        n = pts.shape[0]
-        rows = np.full(n, 0xDEADBEEF, np.uint32)
-        h = np.zeros(n, np.float32)
-        st = np.full(n, 99, np.uint32)
-        o = (C.c_float * 3)(*[float(v) for v in self.origin])
-        rc = shim().qshim_query(mode, ilp, int(gather), pts.ctypes.data, pts.shape[1], n, self.sx.ctypes.data, self.sy.ctypes.data,
-                                self.sz.ctypes.data, self.mean.ctypes.data, self.flags.ctypes.data, self.row_ncol.ctypes.data,
-                                self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize, self.h_bits.ctypes.data,
-                                self.state.ctypes.data, o, self.P["grid_len"], self.P["z_len"], threads, rows.ctypes.data, h.ctypes.data,
-                                st.ctypes.data)
-        assert rc == 0
-        r = rows.view(np.int32).astype(np.int64)
-        return (r, h, st) if gather else r
+from tests.host_emulation import HostMap, consumer_shim
 
 
 def _face_scene():
@@ -216,7 +137,7 @@ def test_probe_walks_past_other_columns():
     """in a full table most columns do not sit in their first slot: ctab_find must still name every column's first row"""
     _, m = _map("campus", "full")
     first = np.flatnonzero(m.row_ncol)
-    got = np.array([shim().qshim_ctab_find(m.ctab_key.ctypes.data, m.ctab_val.ctypes.data, m.tsize, int(m.sx[r]), int(m.sy[r])) for r in first])
+    got = np.array([consumer_shim().qshim_ctab_find(m.ctab_key.ctypes.data, m.ctab_val.ctypes.data, m.tsize, int(m.sx[r]), int(m.sy[r])) for r in first])
     assert (got == first).all()
 
 

@@ -1,96 +1,18 @@
 """CPU tier: the raster export's code (grid_ndt_amd/csrc/gndt_query.hpp: raster_index, raster_count and the kernel's per-pixel function
-raster_pixel at every mode and gather mask), compiled with g++ into tests/_raster_shim.so, against a numpy restatement from the rows
+raster_pixel at every mode and gather mask), compiled with g++ into tests/_consumer_shim.so, against a numpy restatement from the rows
 (tests/raster_ref.py) on maps the oracle builds; gndt_raster_shape against numpy enumeration; and the product entry points refuse to run
 without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from grid_ndt_amd import scenes
-from oracle import oracle
 from tests import query_ref as qr
 from tests import raster_ref as rr
+from tests.host_emulation import HostMap, consumer_shim
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_ROOT = os.path.dirname(_HERE)
-_SO = os.path.join(_HERE, "_raster_shim.so")
-_lib = None
 ERR_INVALID = 1
-
-
-def shim():
-    global _lib
-    if _lib is None:
-        src = os.path.join(_HERE, "raster_shim.cpp")
-        hdrs = [os.path.join(_ROOT, "grid_ndt_amd", "csrc", f) for f in ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp")]
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in [src] + hdrs):
-            subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I",
-                                   os.path.join(_ROOT, "grid_ndt_amd", "csrc"), "-o", _SO, src])
-        L = C.CDLL(_SO)
-        vp = C.c_void_p
-        L.rshim_index.argtypes = [C.c_int32, C.c_uint32]
-        L.rshim_index.restype = C.c_int
-        L.rshim_count.argtypes = [C.c_int32, C.c_int32]
-        L.rshim_count.restype = C.c_uint32
-        L.rshim_build_index.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, C.c_uint32]
-        L.rshim_build_index.restype = None
-        L.rshim_raster.argtypes = ([C.c_int, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_float] + [vp] * 9 + [C.c_uint32]
-                                   + [vp] * 8)
-        L.rshim_raster.restype = C.c_int
-        _lib = L
-    return _lib
-
-
-class HostMap:
-    """The rows of an oracle map, with the per-row column sizes, the column index (the library's size) and a made-up cost map"""
-
-    def __init__(self, cloud, P):
-        self.origin = np.asarray(cloud[0, :3], np.float32)
-        self.P = P
-        c = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"), mode=oracle.MODE_INT_OPENMP)
-        self.cells = c
-        self.n = int(c["num_nodes"])
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(c[k], np.int32) for k in ("sx", "sy", "sz"))
-        self.mean = np.ascontiguousarray(c["mean"], np.float32)
-        self.rough = np.ascontiguousarray(c["rough"], np.float32)
-        self.flags = np.ascontiguousarray(c["flags"], np.uint32)
-        self.row_ncol = qr.row_ncol(c)
-        K = int((self.row_ncol > 0).sum())
-        self.tsize = 1024
-        while self.tsize < 2 * K:
-            self.tsize <<= 1
-        self.ctab_key = np.zeros(self.tsize, np.uint64)
-        self.ctab_val = np.zeros(self.tsize, np.uint32)
-        shim().rshim_build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                 self.ctab_val.ctypes.data, self.tsize)
-        rng = np.random.default_rng(13)
-        self.h_bits = rng.integers(0, 0x7F7FFFFF, size=max(self.n, 1), dtype=np.uint32)
-        self.state = rng.integers(0, 3, size=max(self.n, 1), dtype=np.uint32)
-
-    def box(self):
-        return int(self.sx.min()), int(self.sx.max()), int(self.sy.min()), int(self.sy.max())
-
-    def raster(self, box, mode, z_ref=0.0, gather=3, layers=("row", "z", "rough", "nodes", "h", "state")):
-        W, H = len(rr.axis(box[0], box[1])), len(rr.axis(box[2], box[3]))
-        dt = {"row": np.uint32, "z": np.float32, "rough": np.float32, "nodes": np.uint32, "h": np.float32, "state": np.uint32}
-        out = {k: np.full((H, W), 0xA5A5A5A5, np.uint32).view(dt[k]) for k in layers}
-        p = lambda k: C.c_void_p(out[k].ctypes.data if k in out else 0)
-        rc = shim().rshim_raster(mode, gather, box[0], box[2], W, W * H, z_ref, self.sx.ctypes.data,
-                                 self.sy.ctypes.data, self.sz.ctypes.data, self.mean.ctypes.data, self.rough.ctypes.data,
-                                 self.flags.ctypes.data, self.row_ncol.ctypes.data, self.ctab_key.ctypes.data, self.ctab_val.ctypes.data,
-                                 self.tsize, self.h_bits.ctypes.data, self.state.ctypes.data, p("row"), p("z"), p("rough"), p("nodes"),
-                                 p("h"), p("state"))
-        assert rc == 0
-        if "row" in out:
-            out["row"] = out["row"].view(np.int32)
-        return out
-
-    def want(self, box, mode, z_ref=0.0):
-        return rr.raster(self.cells, box, mode, z_ref, self.h_bits[:self.n], self.state[:self.n])
-
 
 SCENES = {
     "bridge_ground": lambda: (scenes.bridge_ground(), scenes.BRIDGE_PARAMS),
@@ -104,7 +26,7 @@ _maps = {}
 def _map(name):
     if name not in _maps:
         cloud, P = SCENES[name]()
-        _maps[name] = HostMap(cloud, P)
+        _maps[name] = HostMap(cloud, P, seed=13)
     return _maps[name]
 
 
@@ -126,7 +48,7 @@ AXES = [(-3, 4), (0, 5), (-6, 0), (0, 1), (-1, 0), (1, 1), (-1, -1), (7, 7), (-7
 @pytest.mark.parametrize("lo,hi", AXES)
 def test_axis_index_and_count_enumerate_the_non_zero_indices(lo, hi):
     want = rr.axis(lo, hi)
-    L = shim()
+    L = consumer_shim()
     assert L.rshim_count(lo, hi) == want.size
     if want.size and want.size < 1000:
         got = [L.rshim_index(lo, i) for i in range(want.size)]
