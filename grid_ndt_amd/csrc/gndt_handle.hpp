@@ -218,6 +218,10 @@ struct gndt_handle {
         uint64_t ext_serial = 0;        // result_serial the extents were computed for (0 = none)
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;   // [3], device and pinned
     } clear;
+    // scan scoring (gndt_score.hpp): the per-tile partial sums of the poses one launch takes, grown on demand
+    struct Score {
+        void* partial = nullptr;  uint64_t partial_cap = 0;   // bytes; gndt::ScorePartial[poses of a launch][tiles]
+    } score;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -562,5 +566,7 @@ gndt::QueryView query_view(gndt_handle* h);
 void free_crop(gndt_handle* h);
 // ---- gndt_api_clear.hip ----
 void free_clear(gndt_handle* h);
+// ---- gndt_api_score.hip ----
+void free_score(gndt_handle* h);
 
 }  // namespace gndt_host

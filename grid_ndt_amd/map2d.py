@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, Stats
+from ._lib import Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -678,6 +678,65 @@ class TwoDmap:
                                                 C.c_void_p(rows.ctypes.data if rows is not None and rows.size else 0), C.byref(st)))
         out = {"rays": int(st.rays), "skipped": int(st.skipped), "protected_rows": int(st.protected_rows), "cleared": int(st.cleared)}
         return (out, rows) if passes else out
+
+    # ---- scan scoring (gndt_score_poses*: the NDT match score of a scan for a batch of poses) ----
+    @staticmethod
+    def _as_poses(poses):
+        """-> contiguous float64 [K, 12] from [K, 3, 4], [K, 4, 4] (last row dropped) or a single 3 x 4 / 4 x 4 matrix, any float dtype"""
+        try:
+            import torch
+            if isinstance(poses, torch.Tensor):
+                poses = poses.detach().cpu().numpy()
+        except ImportError:
+            pass
+        a = np.asarray(poses, dtype=np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[1] not in (3, 4) or a.shape[2] != 4:
+            raise ValueError("poses must be [K, 3, 4], [K, 4, 4] or one such matrix")
+        return np.ascontiguousarray(a[:, :3, :]).reshape(a.shape[0], 12)
+
+    def score_poses(self, points, poses, neighbourhood=1, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, per_point=None, stream=None):
+        """How well the scan `points` ([N,3] or [N,4] float32) fits the map at each of the K `poses` ([K,3,4] or [K,4,4] or one matrix,
+        map <- scan): include/gndt.h "scan scoring" defines the sum.  neighbourhood 1 scores every moved point against the node it falls
+        in, 7 also against that node's six face neighbours; 0 takes the default of min_count (max(min_points, 3)), cov_rel (0.01) and
+        cov_floor (1e-6 m^2); max_d2 > 0 leaves out candidates beyond that Mahalanobis distance squared.  Returns a dict of length-K
+        arrays: score and d2_sum (float64), matched (points with a term) and terms (int64); with per_point=k also d2 (float32, the least
+        d2 of every point at pose k, inf where it met no node) and row (int32, that node's row, -1).  A torch CUDA tensor is scored on
+        the device (torch tensors, enqueued on `stream`, default torch's current stream, not awaited); a host array through
+        gndt_score_poses (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        T = self._as_poses(poses)
+        K = T.shape[0]
+        ptr, n, stride, on_dev, keep = self._as_input(points)
+        want = per_point is not None
+        prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), int(per_point) if want else 0)
+        if on_dev:
+            import contextlib
+            import torch
+            # (the poses' upload and the outputs belong to the stream the kernels run on)
+            with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+                Td = torch.from_numpy(T).to(keep.device)
+                rec = torch.empty((K, 4), dtype=torch.int64, device=keep.device)
+                d2 = torch.empty(n, dtype=torch.float32, device=keep.device) if want else None
+                row = torch.empty(n, dtype=torch.int32, device=keep.device) if want else None
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_score_poses_device(self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), K, C.byref(prm), p(rec),
+                                                        p(d2), p(row), _stream_ptr(stream)))
+            fl = rec.view(torch.float64)       # (a view: nothing is enqueued behind the caller's stream)
+            out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+        else:
+            rec = np.zeros((K, 4), np.int64)
+            d2 = np.empty(n, np.float32) if want else None
+            row = np.empty(n, np.int32) if want else None
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_score_poses(self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), K, C.byref(prm), p(rec), p(d2), p(row)))
+            fl = rec.view(np.float64)
+            out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+        if want:
+            out.update(d2=d2, row=row)
+        return out
 
     # ---- results ----
     def sync(self):

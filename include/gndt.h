@@ -565,6 +565,65 @@ int gndt_clear_rays_device(gndt_handle* h, const float origin_xyz[3], const void
 int gndt_clear_rays(gndt_handle* h, const float origin_xyz[3], const void* xyz_host, size_t n, size_t stride_bytes,
                     const gndt_clear_params* p, uint32_t* passes_out_host, gndt_clear_stats* stats);
 
+/* ---- scan scoring: how well a scan fits the map at each of K poses -----------------------------------------------------------
+ * The map is a grid of normal distributions (count, mean, scatter per node); this call reads it as one: the NDT match score of n scan
+ * points (fp32, stride 12 or 16, like gndt_build_device) for K poses, each a row-major 3 x 4 double matrix [R | t] (nothing checks that
+ * R is a rotation).  No optimiser, no derivatives: the sum a localisation health check, a particle filter's weighting step, a pose
+ * search or a registration loop is built on.
+ * The score is a DEFINITION (tests restate it in numpy).  For pose k and point p = (x, y, z):
+ *   1. transform, in fp64, in this order, rounded once to fp32 per coordinate: q_i = (float)(((R_i0 x + R_i1 y) + R_i2 z) + t_i).
+ *      Everything after this step sees only the fp32 q: scoring cloud P at pose T and scoring fl32(T P) at the identity are the same
+ *      computation.
+ *   2. key: q's key as GNDT_QUERY_NODE keys a point (finite, and all three axes in the codec's range).  No key: the point contributes
+ *      nothing for this pose (not an error).
+ *   3. candidates: GNDT_SCORE_DIRECT1 the node with that key; GNDT_SCORE_DIRECT7 also its six face neighbours, by the index rules of the
+ *      cost flood, which skip 0: (sx -+ 1, sy, sz), (sx, sy -+ 1, sz), (sx, sy, level above / below sz).  A neighbour index beyond the
+ *      codec's range (|sx|, |sy| > 65535, |sz| >= 2^21) is no candidate.  A candidate counts when the map holds it and its
+ *      count >= min_count.
+ *   4. term of a candidate with c = count, mean m and scatter S (gndt_cells.cov, un-normalised), in fp64 from the rows' fp32 values:
+ *      C = S / (c - 1); eps = max(cov_rel * (C_xx + C_yy + C_zz) / 3, cov_floor); A = C + eps I; d = q - m; d2 = d^T A^-1 d by the
+ *      adjugate (cofactors, one division by the determinant; grid_ndt_amd/csrc/gndt_score.hpp states the evaluation order);
+ *      term = exp(-d2 / 2).  With max_d2 > 0 a candidate whose d2 > max_d2 does not count.
+ *   5. per pose: score = the sum of the terms, d2_sum = the sum of their d2, terms = how many, matched = how many points had at least
+ *      one.
+ *   6. per point, optional, for the one pose `point_pose`: the least d2 among the point's terms as fp32 (+inf: none) and that node's row
+ *      (GNDT_NO_ROW: none; equal d2: the lower row) — which points of the scan disagree with the map.
+ * Parameters, 0 = default: min_count = max(the handle's min_points, 3); cov_rel = 0.01f; cov_floor = 1e-6f (m^2); max_d2 = 0 is no
+ * gate.  eps is therefore always positive and A never singular; with cov_rel = 0.01 the condition number of A is at most 301 whatever
+ * the node's shape (a rank-1 node of three collinear points included).
+ * Results are reproducible to the bit: sums are formed per thread, then in a fixed tree per tile of 256 points, then over a pose's
+ * tiles in tile order — no floating-point atomics.  Pose k of a batch has exactly the bits a single-pose call of that pose gives, on
+ * any stream, at either stride.
+ * Order and lifetime are the point queries': the call first finishes what gndt_sync finishes (a pending build, a deferred emit, a
+ * re-run), then builds or reuses the map's column index, then enqueues its kernels on `hip_stream` (NULL = the handle's stream, the
+ * rules of gndt_build_device) and does not wait.  The map is not modified.  Row numbers stay valid until the next build, update, remove,
+ * crop, clear or reset.  A sharded map answers from the rows this rank holds (the caller adds the ranks' records).  There is no CPU
+ * path.  n == 0 with K > 0 writes K zeroed records; K == 0 returns GNDT_OK and launches nothing.
+ * GNDT_ERR_INVALID: null handle or params, null points with n > 0, null poses or out with K > 0, K > 65535, a stride other than 12 / 16,
+ * an unknown neighbourhood, point_pose >= K when a per-point output is asked for, min_count of 1 or 2 or below the handle's min_points
+ * (such nodes keep zero statistics), a negative or non-finite cov_rel, cov_floor or max_d2, no finished build, a stream under hipGraph
+ * capture (a score is not recorded). */
+enum { GNDT_SCORE_DIRECT1 = 1, GNDT_SCORE_DIRECT7 = 7 };
+typedef struct gndt_score_params {
+    int32_t neighbourhood;   /* GNDT_SCORE_DIRECT1 / GNDT_SCORE_DIRECT7                          */
+    int32_t min_count;       /* 0 = max(min_points, 3)                                           */
+    float cov_rel;           /* 0 = 0.01                                                         */
+    float cov_floor;         /* 0 = 1e-6 (m^2)                                                   */
+    float max_d2;            /* > 0: candidates beyond this d2 do not count; 0 = no gate         */
+    uint32_t point_pose;     /* the pose the per-point outputs are written for (< K)             */
+} gndt_score_params;
+typedef struct gndt_pose_score {
+    double score, d2_sum;
+    uint64_t matched, terms;
+} gndt_pose_score;           /* 32 bytes */
+/* Device points, poses ([K][12] doubles), records ([K]) and per-point outputs ([n] each, either may be NULL). */
+int gndt_score_poses_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* poses_dev, uint32_t K,
+                            const gndt_score_params* params, gndt_pose_score* out_dev, float* point_d2_dev, uint32_t* point_row_dev,
+                            void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; synchronous. */
+int gndt_score_poses(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
+                     const gndt_score_params* params, gndt_pose_score* out_host, float* point_d2_host, uint32_t* point_row_host);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
