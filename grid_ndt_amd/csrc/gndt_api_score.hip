@@ -1,21 +1,26 @@
-// gndt_api_score.hip — scan scoring (gndt_score.hpp): the NDT match score of a scan against the finished grid for a batch of poses.
+// gndt_api_score.hip — scan scoring (gndt_score.hpp): the NDT match score of a scan against the finished grid for a batch of poses,
+// and (gndt_score_derivs.hpp) that score with its gradient and Hessian with respect to a pose perturbation.
 // A reader of the map like the point queries: finished_map, the map's column index, kernels on the caller's stream, nothing awaited.
 #include <cmath>
 #include <cstring>
 
 #include "gndt_handle.hpp"
 #include "gndt_score.hpp"
+#include "gndt_score_derivs.hpp"
 
 using namespace gndt;
 using namespace gndt_host;
 
 static_assert(sizeof(gndt_pose_score) == 32 && sizeof(ScoreRecord) == sizeof(gndt_pose_score), "k_score_reduce writes gndt_pose_score records");
 static_assert(sizeof(ScorePartial) == 24, "the per-tile partial sums are 24 bytes");
+static_assert(sizeof(gndt_pose_derivs) == 248 && sizeof(ScoreDerivRecord) == sizeof(gndt_pose_derivs), "k_score_derivs_finish writes gndt_pose_derivs records");
+static_assert(sizeof(ScoreDerivPartial) == 240 && sizeof(ScoreDerivWaves) % 8 == 0, "the per-tile partial sums of the derivatives are 240 bytes");
 
 namespace gndt_host {
 
 void free_score(gndt_handle* h) {
     if (h->score.partial) (void)hipFree(h->score.partial);
+    if (h->score.dpartial) (void)hipFree(h->score.dpartial);
     h->score = gndt_handle::Score{};
 }
 
@@ -24,9 +29,10 @@ namespace {
 constexpr uint32_t kMaxPoses = 65535;                      // the grid's y limit
 constexpr uint64_t kPartialBytes = 64ull << 20;            // partial sums of one launch: a batch of poses is split to stay below this
 
-// Arguments (every GNDT_ERR_INVALID of include/gndt.h but the handle's state); R = the parameters with the defaults filled in
+// Arguments (every GNDT_ERR_INVALID of include/gndt.h but the handle's state) of a score or a derivatives call (`out`: its records;
+// no per-point outputs: point_pose is not looked at); R = the parameters with the defaults filled in
 int score_check_args(gndt_handle* h, const void* xyz, size_t n, size_t stride_bytes, const double* poses, uint32_t K,
-                     const gndt_score_params* p, const gndt_pose_score* out, const float* point_d2, const uint32_t* point_row, ScoreParams& R) {
+                     const gndt_score_params* p, const void* out, const float* point_d2, const uint32_t* point_row, ScoreParams& R) {
     if (!p) { h->err = "gndt_score_poses: null params"; return GNDT_ERR_INVALID; }
     if (n && !xyz) { h->err = "gndt_score_poses: null points"; return GNDT_ERR_INVALID; }
     if (K && (!poses || !out)) { h->err = "gndt_score_poses: null poses or out"; return GNDT_ERR_INVALID; }
@@ -107,6 +113,39 @@ int score_run(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes
     return GNDT_OK;
 }
 
+// score_run for the derivatives: k_score_derivs, the 16 waves of k_score_derivs_reduce per pose, k_score_derivs_finish.  The same
+// 64 MiB bound on a launch's partial sums (the tiles' and the 16 waves'); a pose's tiles and their order do not depend on the split.
+int score_derivs_run(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* poses, uint32_t K, int32_t nbh,
+                     const ScoreParams& R, gndt_pose_derivs* out, hipStream_t s) {
+    const uint64_t tiles64 = ((uint64_t)n + kScoreTile - 1) / kScoreTile;
+    if (tiles64 > 0x7FFFFFFFull) { h->err = "gndt_score_derivs: more than 2^39 points in one call"; return GNDT_ERR_INVALID; }
+    const uint32_t tiles = (uint32_t)tiles64;
+    const uint64_t per_pose = tiles64 * sizeof(ScoreDerivPartial);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(K, std::max<uint64_t>(1, kPartialBytes / (per_pose + sizeof(ScoreDerivWaves))));
+    const uint64_t wave_bytes = (uint64_t)chunk * sizeof(ScoreDerivWaves);
+    const int rc = grow_scratch(h, h->score.dpartial, h->score.dpartial_cap, wave_bytes + per_pose * chunk);
+    if (rc) return rc;
+    ScoreDerivWaves* waves = static_cast<ScoreDerivWaves*>(h->score.dpartial);
+    ScoreDerivPartial* partial = reinterpret_cast<ScoreDerivPartial*>(static_cast<char*>(h->score.dpartial) + wave_bytes);
+    const ScoreView S = score_view(h);
+    const float* xyz = static_cast<const float*>(xyz_dev);
+    const uint32_t sf = (uint32_t)(stride_bytes / 4);
+    for (uint32_t k0 = 0; k0 < K; k0 += chunk) {
+        const uint32_t kc = std::min(chunk, K - k0);
+        const dim3 grid(tiles, kc);
+        if (nbh == GNDT_SCORE_DIRECT1)
+            hipLaunchKernelGGL((k_score_derivs<kScoreDirect1>), grid, dim3(kScoreTile), 0, s, S, R, xyz, sf, n, poses + 12 * (size_t)k0, partial);
+        else
+            hipLaunchKernelGGL((k_score_derivs<kScoreDirect7>), grid, dim3(kScoreTile), 0, s, S, R, xyz, sf, n, poses + 12 * (size_t)k0, partial);
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_score_derivs_reduce, dim3(kDerivReduceWaves, kc), dim3(64), 0, s, partial, tiles, waves);
+        HIP_TRY(h, hipGetLastError());
+        hipLaunchKernelGGL(k_score_derivs_finish, dim3(kc), dim3(64), 0, s, waves, reinterpret_cast<ScoreDerivRecord*>(out) + k0);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return GNDT_OK;
+}
+
 }  // namespace
 
 }  // namespace gndt_host
@@ -158,6 +197,51 @@ int gndt_score_poses(gndt_handle* h, const void* xyz_host, size_t n, size_t stri
     HIP_TRY(h, hipMemcpyAsync(out_host, dev[2], out_bytes, hipMemcpyDeviceToHost, s));
     if (point_d2_host) HIP_TRY(h, hipMemcpyAsync(point_d2_host, dev[3], pt_bytes, hipMemcpyDeviceToHost, s));
     if (point_row_host) HIP_TRY(h, hipMemcpyAsync(point_row_host, dev[4], pt_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return GNDT_OK;
+}
+
+int gndt_score_derivs_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* poses_dev, uint32_t K,
+                             const gndt_score_params* params, gndt_pose_derivs* out_dev, void* hip_stream) {
+    int rc = check_ready(h);
+    if (rc) return rc;
+    ScoreParams R{};
+    if ((rc = score_check_args(h, xyz_dev, n, stride_bytes, poses_dev, K, params, out_dev, nullptr, nullptr, R))) return rc;
+    const hipStream_t s = stream_of(h, hip_stream);
+    if ((rc = score_sync(h, s)) || K == 0) return rc;
+    if ((rc = use_stream(h, s))) return rc;
+    if (n == 0) {
+        HIP_TRY(h, hipMemsetAsync(out_dev, 0, (size_t)K * sizeof(gndt_pose_derivs), s));
+        return GNDT_OK;
+    }
+    if ((rc = column_index(h, s))) return rc;
+    return score_derivs_run(h, xyz_dev, n, stride_bytes, poses_dev, K, params->neighbourhood, R, out_dev, s);
+}
+
+int gndt_score_derivs(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
+                      const gndt_score_params* params, gndt_pose_derivs* out_host) {
+    int rc = check_ready(h);
+    if (rc) return rc;
+    ScoreParams R{};
+    if ((rc = score_check_args(h, xyz_host, n, stride_bytes, poses_host, K, params, out_host, nullptr, nullptr, R))) return rc;
+    const hipStream_t s = h->own_stream;
+    if ((rc = score_sync(h, s)) || K == 0) return rc;
+    if (n == 0) {
+        memset(out_host, 0, (size_t)K * sizeof(gndt_pose_derivs));
+        return GNDT_OK;
+    }
+    if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
+    const uint64_t in_bytes = (uint64_t)n * stride_bytes, pose_bytes = (uint64_t)K * 12 * sizeof(double),
+                   out_bytes = (uint64_t)K * sizeof(gndt_pose_derivs);
+    const uint64_t bytes[3] = {in_bytes, pose_bytes, out_bytes};
+    void* dev[3];
+    if ((rc = stage_pieces(h, bytes, dev, 3))) return rc;
+    HIP_TRY(h, hipMemcpyAsync(dev[0], xyz_host, in_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(dev[1], poses_host, pose_bytes, hipMemcpyHostToDevice, s));
+    rc = score_derivs_run(h, dev[0], n, stride_bytes, static_cast<const double*>(dev[1]), K, params->neighbourhood, R,
+                          static_cast<gndt_pose_derivs*>(dev[2]), s);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpyAsync(out_host, dev[2], out_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     return GNDT_OK;
 }

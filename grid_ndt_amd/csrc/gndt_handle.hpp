@@ -221,6 +221,8 @@ struct gndt_handle {
     // scan scoring (gndt_score.hpp): the per-tile partial sums of the poses one launch takes, grown on demand
     struct Score {
         void* partial = nullptr;  uint64_t partial_cap = 0;   // bytes; gndt::ScorePartial[poses of a launch][tiles]
+        // scan score derivatives (gndt_score_derivs.hpp): ScoreDerivWaves[poses of a launch], then ScoreDerivPartial[poses][tiles]
+        void* dpartial = nullptr; uint64_t dpartial_cap = 0;
     } score;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {

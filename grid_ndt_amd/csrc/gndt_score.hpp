@@ -22,6 +22,8 @@
 // A workgroup owns kScoreTile consecutive points of one pose and adds its threads' sums in a fixed tree (the 64 lanes by __shfl_xor,
 // then the waves pairwise through LDS); k_score_reduce adds a pose's tiles in tile order per thread, then in the same tree.  No
 // floating-point atomics: a pose's record has the same bits in every run, in every batch and on every stream.
+// score_point hands every counted candidate (ScoreTerm: d, the cofactors, det, u, d2) and its term to a sink: plain scoring passes
+// ScoreNoSink, the score's derivatives (gndt_score_derivs.hpp) add their per-point sums there, on the same lookup.
 // Everything but the kernels is callable on the host as well (tests/score_shim.cpp).
 #pragma once
 #include <math.h>
@@ -64,9 +66,16 @@ GNDT_HD void score_transform(const double* T, float x, float y, float z, float& 
     qz = (float)(((T[8] * dx + T[9] * dy) + T[10] * dz) + T[11]);
 }
 
-// d2 of q against the node of `row` (the order of the header comment); false: the node is not a candidate (too few points, or beyond
-// max_d2)
-GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, float qx, float qy, float qz, double& d2) {
+// One counted candidate as a sink of score_point receives it: d = q - mean, the cofactors of A, det, u = adj(A) d and d2
+struct ScoreTerm {
+    double dx, dy, dz;
+    double c00, c01, c02, c11, c12, c22, det;
+    double ux, uy, uz, d2;
+};
+
+// The term of q against the node of `row` (the order of the header comment); false: the node is not a candidate (too few points, or
+// beyond max_d2)
+GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, float qx, float qy, float qz, ScoreTerm& t) {
     const uint32_t c = S.count[row];
     const float* m = S.Q.V.mean + 3 * (size_t)row;
     const float* s = S.cov + 6 * (size_t)row;
@@ -78,15 +87,23 @@ GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, 
                  czz = (double)s5 * r;
     const double eps = fmax(P.cov_rel * (((cxx + cyy) + czz) / 3.0), P.cov_floor);
     const double a00 = cxx + eps, a11 = cyy + eps, a22 = czz + eps, a01 = cxy, a02 = cxz, a12 = cyz;
-    const double c00 = a11 * a22 - a12 * a12, c01 = a02 * a12 - a01 * a22, c02 = a01 * a12 - a02 * a11;
-    const double c11 = a00 * a22 - a02 * a02, c12 = a01 * a02 - a00 * a12, c22 = a00 * a11 - a01 * a01;
-    const double det = (a00 * c00 + a01 * c01) + a02 * c02;
-    const double dx = (double)qx - (double)mx, dy = (double)qy - (double)my, dz = (double)qz - (double)mz;
-    const double ux = (c00 * dx + c01 * dy) + c02 * dz;
-    const double uy = (c01 * dx + c11 * dy) + c12 * dz;
-    const double uz = (c02 * dx + c12 * dy) + c22 * dz;
-    d2 = ((dx * ux + dy * uy) + dz * uz) / det;
-    return !(P.max_d2 > 0.0 && d2 > P.max_d2);
+    t.c00 = a11 * a22 - a12 * a12; t.c01 = a02 * a12 - a01 * a22; t.c02 = a01 * a12 - a02 * a11;
+    t.c11 = a00 * a22 - a02 * a02; t.c12 = a01 * a02 - a00 * a12; t.c22 = a00 * a11 - a01 * a01;
+    t.det = (a00 * t.c00 + a01 * t.c01) + a02 * t.c02;
+    t.dx = (double)qx - (double)mx; t.dy = (double)qy - (double)my; t.dz = (double)qz - (double)mz;
+    t.ux = (t.c00 * t.dx + t.c01 * t.dy) + t.c02 * t.dz;
+    t.uy = (t.c01 * t.dx + t.c11 * t.dy) + t.c12 * t.dz;
+    t.uz = (t.c02 * t.dx + t.c12 * t.dy) + t.c22 * t.dz;
+    t.d2 = ((t.dx * t.ux + t.dy * t.uy) + t.dz * t.uz) / t.det;
+    return !(P.max_d2 > 0.0 && t.d2 > P.max_d2);
+}
+
+// d2 alone
+GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, float qx, float qy, float qz, double& d2) {
+    ScoreTerm t;
+    const bool counted = score_node(S, P, row, qx, qy, qz, t);
+    d2 = t.d2;
+    return counted;
 }
 
 // The rows of column c (ncol nodes) whose levels are lv[0 .. NT): row[t], left alone where the column has no such level or !want[t].
@@ -105,22 +122,31 @@ GNDT_HD void score_walk(const CostView& V, uint32_t c, uint32_t ncol, const int*
     }
 }
 
-// One candidate row into the thread's sums and the point's best (equal d2: the lower row)
+// The sink of plain scoring: a counted candidate is looked at by nobody else
+struct ScoreNoSink {
+    GNDT_HD void operator()(uint32_t, const ScoreTerm&, double) const {}
+};
+
+// One candidate row into the thread's sums and the point's best (equal d2: the lower row); sink(row, term, exp(-d2 / 2)) for a counted one
+template <typename SINK>
 GNDT_HD void score_add(const ScoreView& S, const ScoreParams& P, uint32_t row, float qx, float qy, float qz, ScoreAcc& a, ScoreBest& b,
-                       uint32_t& found) {
+                       uint32_t& found, SINK& sink) {
     if (row == kNoRow) return;
-    double d2;
-    if (!score_node(S, P, row, qx, qy, qz, d2)) return;
-    a.score += exp(-0.5 * d2);
-    a.d2_sum += d2;
+    ScoreTerm t;
+    if (!score_node(S, P, row, qx, qy, qz, t)) return;
+    const double e = exp(-0.5 * t.d2);
+    a.score += e;
+    a.d2_sum += t.d2;
     ++a.terms;
     ++found;
-    if (d2 < b.d2 || (d2 == b.d2 && row < b.row)) { b.d2 = d2; b.row = row; }
+    if (t.d2 < b.d2 || (t.d2 == b.d2 && row < b.row)) { b.d2 = t.d2; b.row = row; }
+    sink(row, t, e);
 }
 
-// The moved point q against the map: its terms into a (matched: at least one), its nearest candidate into b
-template <int NBH>
-GNDT_HD void score_point(const ScoreView& S, const ScoreParams& P, float qx, float qy, float qz, ScoreAcc& a, ScoreBest& b) {
+// The moved point q against the map: its terms into a (matched: at least one), its nearest candidate into b, every counted candidate
+// to the sink in the candidates' order
+template <int NBH, typename SINK>
+GNDT_HD void score_point(const ScoreView& S, const ScoreParams& P, float qx, float qy, float qz, ScoreAcc& a, ScoreBest& b, SINK& sink) {
     const QueryView& Q = S.Q;
     const QueryKey k = query_key<kQueryNode>(Q, qx, qy, qz);
     uint32_t found = 0u;
@@ -134,7 +160,7 @@ GNDT_HD void score_point(const ScoreView& S, const ScoreParams& P, float qx, flo
         const int lv[1] = {k.sz};
         const bool want[1] = {true};
         score_walk<1>(Q.V, c, ncol, lv, want, row);
-        score_add(S, P, row[0], qx, qy, qz, a, b, found);
+        score_add(S, P, row[0], qx, qy, qz, a, b, found, sink);
     } else {
         // columns: the point's own, x - 1, x + 1, y - 1, y + 1 (signed indices skip 0; beyond the codec's range: no candidate)
         QueryKey kc[5];
@@ -168,13 +194,19 @@ GNDT_HD void score_point(const ScoreView& S, const ScoreParams& P, float qx, flo
         uint32_t side[4] = {kNoRow, kNoRow, kNoRow, kNoRow};
 #pragma unroll
         for (int j = 1; j < 5; ++j) score_walk<1>(Q.V, c[j], ncol[j], lv, want, side + (j - 1));
-        score_add(S, P, own[0], qx, qy, qz, a, b, found);
+        score_add(S, P, own[0], qx, qy, qz, a, b, found, sink);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) score_add(S, P, side[j], qx, qy, qz, a, b, found);
-        score_add(S, P, own[1], qx, qy, qz, a, b, found);
-        score_add(S, P, own[2], qx, qy, qz, a, b, found);
+        for (int j = 0; j < 4; ++j) score_add(S, P, side[j], qx, qy, qz, a, b, found, sink);
+        score_add(S, P, own[1], qx, qy, qz, a, b, found, sink);
+        score_add(S, P, own[2], qx, qy, qz, a, b, found, sink);
     }
     if (found) ++a.matched;
+}
+
+template <int NBH>
+GNDT_HD void score_point(const ScoreView& S, const ScoreParams& P, float qx, float qy, float qz, ScoreAcc& a, ScoreBest& b) {
+    ScoreNoSink none;
+    score_point<NBH>(S, P, qx, qy, qz, a, b, none);
 }
 
 struct ScorePartial {               // one workgroup's sums: partial[pose][tile]

@@ -738,6 +738,85 @@ class TwoDmap:
             out.update(d2=d2, row=row)
         return out
 
+    # ---- scan score derivatives (gndt_score_derivs*) and the Newton registration driven from them (registration.py) ----
+    _H_INDEX = None
+
+    @classmethod
+    def _h_index(cls):
+        """[36] positions in the record's 21 upper-triangle values of the 6 x 6 Hessian's entries, row-major"""
+        if cls._H_INDEX is None:
+            tri = {}
+            for a in range(6):
+                for b in range(a, 6):
+                    tri[(a, b)] = len(tri)
+            cls._H_INDEX = np.array([tri[(min(a, b), max(a, b))] for a in range(6) for b in range(6)], np.int64)
+        return cls._H_INDEX
+
+    def score_derivs(self, points, poses, neighbourhood=1, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, stream=None):
+        """The score of score_poses with its gradient and Hessian with respect to a left pose perturbation xi = (v, w) (include/gndt.h
+        "scan score derivatives"), for each of the K `poses`.  Arguments as score_poses (no per-point outputs).  Returns a dict of
+        score, d2_sum (float64 [K], the bits score_poses gives), matched, terms (int64 [K]), g (float64 [K, 6]) and H (float64
+        [K, 6, 6], symmetric, filled from the record's 21 values).  A torch CUDA tensor is scored on the device (torch tensors,
+        enqueued on `stream`, default torch's current stream, not awaited); a host array through gndt_score_derivs (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        T = self._as_poses(poses)
+        K = T.shape[0]
+        ptr, n, stride, on_dev, keep = self._as_input(points)
+        prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), 0)
+        if on_dev:
+            import contextlib
+            import torch
+            if stream is None:
+                ctx = contextlib.nullcontext()
+            else:
+                ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
+            with ctx:       # (the poses' upload, the outputs and the Hessian's gather belong to the stream the kernels run on)
+                Td = torch.from_numpy(T).to(keep.device)
+                rec = torch.empty((K, 31), dtype=torch.int64, device=keep.device)
+                p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+                self._check(self._L.gndt_score_derivs_device(self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), K, C.byref(prm), p(rec),
+                                                             _stream_ptr(stream)))
+                fl = rec.view(torch.float64)
+                H = fl[:, 10:31][:, torch.from_numpy(self._h_index()).to(keep.device)].reshape(K, 6, 6)
+        else:
+            rec = np.zeros((K, 31), np.int64)
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_score_derivs(self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), K, C.byref(prm), p(rec)))
+            fl = rec.view(np.float64)
+            H = fl[:, 10:31][:, self._h_index()].reshape(K, 6, 6)
+        return {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3], "g": fl[:, 4:10], "H": H}
+
+    def register(self, points, T0, neighbourhood=7, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, step_t=None, step_r=0.05,
+                 tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None):
+        """The pose near `T0` ([3, 4] / [4, 4], or [K, ...] for K starts run side by side) at which the scan `points` fits the map
+        best: registration.register's saddle-free Newton iteration, its derivatives from score_derivs and its line search from
+        score_poses.  One iteration is one call of each and two small device-to-host copies.  step_t defaults to half a cell.  Returns
+        what registration.register returns (T, reason, iterations, history; a list of those for K starts).  The default neighbourhood
+        is 7: the six neighbours smooth the score across the cell faces."""
+        from . import registration
+        kw = dict(neighbourhood=neighbourhood, min_count=min_count, cov_rel=cov_rel, cov_floor=cov_floor, max_d2=max_d2, stream=stream)
+
+        def wait():
+            if hasattr(stream, "synchronize"):
+                stream.synchronize()
+            elif stream is not None:
+                import torch
+                torch.cuda.ExternalStream(int(stream)).synchronize()
+
+        def host(out, names):
+            wait()
+            return {k: (out[k].cpu().numpy() if hasattr(out[k], "cpu") else np.asarray(out[k])) for k in names}
+
+        def evaluate(T):
+            return host(self.score_derivs(points, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
+
+        def score(T):
+            return host(self.score_poses(points, T, **kw), ("score",))["score"]
+
+        return registration.register(evaluate, score, T0, step_t=0.5 * self.gridLen if step_t is None else step_t, step_r=step_r,
+                                     tol_t=tol_t, tol_r=tol_r, max_iterations=max_iterations)
+
     # ---- results ----
     def sync(self):
         n, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()

@@ -624,6 +624,44 @@ int gndt_score_poses_device(gndt_handle* h, const void* xyz_dev, size_t n, size_
 int gndt_score_poses(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
                      const gndt_score_params* params, gndt_pose_score* out_host, float* point_d2_host, uint32_t* point_row_host);
 
+/* ---- scan score derivatives: the score of a pose with its gradient and Hessian, for K poses ------------------------------------
+ * What a registration step needs of "scan scoring": score, gradient g (6) and full Hessian H (6 x 6, not the Gauss-Newton part only)
+ * of the score with respect to a pose perturbation.  No optimiser here either (grid_ndt_amd/registration.py drives one from Python).
+ * Steps 1 to 4 of "scan scoring" hold unchanged — the transform q = fl32(T p), the key, the candidates, min_count, cov_rel, cov_floor,
+ * max_d2 and the arithmetic of A, its cofactors c_ij, det, d, u and d2 — with the same gndt_score_params (point_pose is ignored).
+ * The derivative is a DEFINITION as the score is (tests restate it in numpy), that of the FROZEN sum: every point keeps the candidate
+ * set found at the pose itself and q is treated as a real vector (neither the fp32 rounding nor the cell boundaries are
+ * differentiated).  The perturbation xi = (v, w), v, w in R^3, acts on the left, translation first:
+ *     q(xi) = Exp([w]x) q + v              (T <- [Exp(w) R | Exp(w) t + v])
+ * so at xi = 0: dq/dv_a = e_a, dq/dw_a = e_a x q, d2q/dw_a dw_b = (e_a q_b + e_b q_a) / 2 - delta_ab q, every other second derivative
+ * zero.  With B = adj(A) / det, ub = B d and e = exp(-d2 / 2) of a counted candidate, and per point the two sums over its counted
+ * candidates in the candidates' order
+ *     w3 = sum e ub  (3 values)            M = sum e (ub ub^T - B)  (symmetric, 6 values)
+ * a pose's results are sums over the points:
+ *     score = sum e                        g_v = - sum w3                       g_w = - sum q x w3
+ *     H = sum J^T M J - [0 0; 0 N],        J = [I | -[q]x] (3 x 6),             N_ab = (w3_a q_b + w3_b q_a) / 2 - delta_ab (w3 . q)
+ * g is the gradient of the score (which a registration maximises), H its Hessian; a point without a counted candidate adds nothing.
+ * grid_ndt_amd/csrc/gndt_score_derivs.hpp states the evaluation order of ub, B, the nine per-point sums and their expansion into the
+ * 6 + 21 values.
+ * The record: score, d2_sum, matched and terms have EXACTLY the bits gndt_score_poses gives for the same arguments (the same tile of
+ * 256 points, the same tree); g in the order of xi; H's upper triangle row-major (H_00 .. H_05, H_11 .. H_15, ... H_55).  All 31 values
+ * are reproducible to the bit like the score: no floating-point atomics; pose k of a batch has the bits of a single-pose call, on any
+ * stream, at either stride.
+ * Order, lifetime, stream rules, the sharded-map remark, the empty cases and every GNDT_ERR_INVALID are gndt_score_poses' (there are no
+ * per-point outputs, so point_pose is never refused).  There is no CPU path. */
+typedef struct gndt_pose_derivs {
+    double score, d2_sum;
+    uint64_t matched, terms;
+    double g[6];             /* d score / d (v, w)                                               */
+    double H[21];            /* upper triangle of d2 score / d xi d xi, row-major                 */
+} gndt_pose_derivs;          /* 248 bytes, 8-byte fields only */
+/* Device points, poses ([K][12] doubles) and records ([K]). */
+int gndt_score_derivs_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* poses_dev, uint32_t K,
+                             const gndt_score_params* params, gndt_pose_derivs* out_dev, void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; synchronous. */
+int gndt_score_derivs(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
+                      const gndt_score_params* params, gndt_pose_derivs* out_host);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
