@@ -9,6 +9,8 @@
 //   gndt_api_query.hip  batched point queries against the finished grid
 //   gndt_api_crop.hip   region crop: the columns outside (or inside) a box leave the map
 //   gndt_api_clear.hip  free-space clearing: nodes that sensor rays pass through leave the map
+//   gndt_api_score.hip  scan scoring and its derivatives
+//   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once

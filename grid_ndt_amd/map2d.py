@@ -788,12 +788,16 @@ class TwoDmap:
         return {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3], "g": fl[:, 4:10], "H": H}
 
     def register(self, points, T0, neighbourhood=7, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, step_t=None, step_r=0.05,
-                 tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None):
+                 tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None, pyramid=None):
         """The pose near `T0` ([3, 4] / [4, 4], or [K, ...] for K starts run side by side) at which the scan `points` fits the map
         best: registration.register's saddle-free Newton iteration, its derivatives from score_derivs and its line search from
         score_poses.  One iteration is one call of each and two small device-to-host copies.  step_t defaults to half a cell.  Returns
         what registration.register returns (T, reason, iterations, history; a list of those for K starts).  The default neighbourhood
-        is 7: the six neighbours smooth the score across the cell faces."""
+        is 7: the six neighbours smooth the score across the cell faces.
+        pyramid: coarser maps of the same stream, coarsest first (what self.pyramid(levels) returns) — the iteration runs on each of
+        them in turn, with step_t half of that map's own cell, every level starting from the level before; this map runs last (with
+        `step_t`, if given).  A start several cells off, beyond the score's basin on this map, is recovered that way.  The result is
+        the last level's with one more entry, levels: every level's result (registration.register_pyramid)."""
         from . import registration
         kw = dict(neighbourhood=neighbourhood, min_count=min_count, cov_rel=cov_rel, cov_floor=cov_floor, max_d2=max_d2, stream=stream)
 
@@ -808,14 +812,58 @@ class TwoDmap:
             wait()
             return {k: (out[k].cpu().numpy() if hasattr(out[k], "cpu") else np.asarray(out[k])) for k in names}
 
-        def evaluate(T):
-            return host(self.score_derivs(points, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
+        def callables(m):
+            def evaluate(T):
+                return host(m.score_derivs(points, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
 
-        def score(T):
-            return host(self.score_poses(points, T, **kw), ("score",))["score"]
+            def score(T):
+                return host(m.score_poses(points, T, **kw), ("score",))["score"]
 
-        return registration.register(evaluate, score, T0, step_t=0.5 * self.gridLen if step_t is None else step_t, step_r=step_r,
-                                     tol_t=tol_t, tol_r=tol_r, max_iterations=max_iterations)
+            return evaluate, score
+
+        own_step = 0.5 * self.gridLen if step_t is None else step_t
+        if pyramid is None:
+            evaluate, score = callables(self)
+            return registration.register(evaluate, score, T0, step_t=own_step, step_r=step_r, tol_t=tol_t, tol_r=tol_r,
+                                         max_iterations=max_iterations)
+        stages = [callables(m) + (0.5 * m.gridLen,) for m in pyramid] + [callables(self) + (own_step,)]
+        return registration.register_pyramid(stages, T0, step_r=step_r, tol_t=tol_t, tol_r=tol_r, max_iterations=max_iterations)
+
+    # ---- map pyramids (gndt_coarsen_device: a coarser map of the same point stream, from this map's node table) ----
+    def coarsen(self, factor_xy=2, factor_z=None, demand=None, into=None, stream=None):
+        """The map a build of this map's point stream at factor_xy times the cell length and factor_z (default: factor_xy) times the
+        level height would give — keys, counts, first-seen indices, order and labels exactly, statistics to fp64 rounding — computed on
+        the device from this map alone (include/gndt.h "map pyramids"): it works on a map grown by change2DMap, cropped or cleared,
+        whose points are gone.  Factors are powers of two, 1 .. 1024.  Returns a new ATOMIC-strategy TwoDmap on the same device with
+        the same interval and min_points (demand: this map's unless given), or fills `into`, an existing map at the multiplied
+        lengths, whose own map is replaced.  This map must hold its map in the node table (strategy ATOMIC / TILE, or built by
+        change2DMap); it is only read.  Enqueued on `stream` (default torch's current stream); the call waits for the device."""
+        if self._h is None:
+            raise GndtError(1, "coarsen: this map has no finished build")
+        fxy = int(factor_xy)
+        fz = fxy if factor_z is None else int(factor_z)
+        d = self._demand if demand is None else (DEMANDS[demand] if isinstance(demand, str) else int(demand))
+        if into is None:
+            # (the handle's lengths are fp32: the multiplied fp32 values, which a power of two keeps exact)
+            into = TwoDmap(float(np.float32(self.gridLen) * np.float32(fxy)), float(np.float32(self.zLen) * np.float32(fz)),
+                           device=self.device, strategy=1, min_points=self.min_points)
+            into.slope_interval = self.slope_interval
+        into._ensure(d, need_origin=False)
+        rc = self._L.gndt_coarsen_device(self._h, into._h, fxy, fz, _stream_ptr(stream))
+        if rc:
+            msg = self._L.gndt_last_error(into._h)
+            raise GndtError(rc, msg.decode() if msg else "")
+        into.cloudFirst = self.cloudFirst      # (the call gave the handle this map's origin)
+        return into
+
+    def pyramid(self, levels, factor=2):
+        """`levels` coarser maps of this one, each `factor` times the one before in all three lengths: [coarsest, ..., this map x
+        factor], the order register(pyramid=...) takes.  This map itself is not in the list."""
+        out, m = [], self
+        for _ in range(int(levels)):
+            m = m.coarsen(factor)
+            out.append(m)
+        return out[::-1]
 
     # ---- results ----
     def sync(self):

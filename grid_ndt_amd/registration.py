@@ -107,3 +107,25 @@ def register(evaluate, score, T0, step_t, step_r=0.05, tol_t=1e-4, tol_r=1e-5, m
                 out[k]["reason"] = "iterations"
         live = [k for k in live if out[k]["reason"] is None]
     return out[0] if single else out
+
+
+def register_pyramid(stages, T0, step_r=0.05, tol_t=1e-4, tol_r=1e-5, max_iterations=30):
+    """Coarse-to-fine: `register` on every stage in turn, each start's pose chained from stage to stage.  stages: a list of
+    (evaluate, score, step_t), coarsest map first (TwoDmap.register(pyramid=...) binds the maps of TwoDmap.pyramid and half of each
+    level's own cell).  The score's basin is less than a cell of the map it is taken on, so a start several fine cells off is first
+    brought within a fine cell on the coarse maps.  T0 as for `register`; K starts run side by side on every stage.  Returns the last
+    stage's result(s) with one more entry, levels: every stage's result of that start, in the order of `stages`."""
+    stages = list(stages)
+    if not stages:
+        raise ValueError("register_pyramid needs at least one stage")
+    T0 = np.asarray(T0, np.float64)
+    single = T0.ndim == 2
+    T = np.array((T0[None] if single else T0)[:, :3, :], np.float64)
+    levels = [[] for _ in range(len(T))]
+    for evaluate, score, step_t in stages:
+        res = register(evaluate, score, T, step_t=step_t, step_r=step_r, tol_t=tol_t, tol_r=tol_r, max_iterations=max_iterations)
+        for k, r in enumerate(res):
+            levels[k].append(r)
+            T[k] = r["T"]
+    out = [dict(lv[-1], levels=lv) for lv in levels]
+    return out[0] if single else out

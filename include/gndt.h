@@ -662,6 +662,32 @@ int gndt_score_derivs_device(gndt_handle* h, const void* xyz_dev, size_t n, size
 int gndt_score_derivs(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
                       const gndt_score_params* params, gndt_pose_derivs* out_host);
 
+/* ---- map pyramids: a coarser map of the same point stream, from the map alone --------------------------------------------------
+ * The scan score has a basin of less than a cell (grid_ndt_amd/registration.py); coarse-to-fine registration needs the same cloud at
+ * 2x, 4x ... the cell lengths, and a map grown by gndt_update*, cropped or cleared no longer has its points.  It does not need them:
+ * for a power-of-two factor f the coarse index of a point is a function of its fine index s (there is no index 0),
+ *     parent(s, f) = sign(s) * ceil(|s| / f)
+ * (fl32(|d| / (f L)) = fl32(|d| / L) / f exactly, and ceil(x / f) = ceil(ceil(x) / f) for x > 0), and a node's additive statistics
+ * (count, Sum v, Sum v v^T about its centre c) move to the parent's centre c' = c - d by
+ *     Sum v' = Sum v + n d,        Sum v' v'^T_ab = Sum v v^T_ab + d_a Sum v_b + d_b Sum v_a + n d_a d_b
+ * (grid_ndt_amd/csrc/gndt_coarsen.hpp states the evaluation order).  Parents add their children's statistics and counts and take the
+ * least first-seen index.  The result is the map a build of the same stream on a handle at f times the lengths gives: keys, counts,
+ * first-seen indices, order and labels exactly, statistics up to the rounding of the fp64 sums (whose order is not fixed: the adds are
+ * floating-point atomics, as the ATOMIC build's are).
+ * gndt_coarsen_device(src, dst, factor_xy, factor_z) resets `dst` (a map it held is gone), gives it `src`'s origin, fills its node table
+ * from `src`'s in one pass and finalises it with dst's own demand, slope_interval and min_points: afterwards `dst` is in the state of
+ * gndt_reset + gndt_stats_merge_device + gndt_finalize_device, and its stream position is `src`'s — a frame then given to gndt_update*
+ * on both handles keeps `dst` the coarse build of the whole stream.  Factors (1, 1) make a clone.
+ * `src` is only read: the call first finishes what gndt_sync(src) finishes (a pending build, a deferred emit, a re-run), then leaves its
+ * rows, its column index and a current cost map valid and its export bit-identical.  The kernel and the finalisation are enqueued on
+ * `hip_stream` (NULL = dst's stream, the rules of gndt_build_device); the call waits for the kernel, as gndt_stats_merge_device does.
+ * GNDT_ERR_INVALID, with `dst` unchanged: a null handle, src == dst, handles on different devices, a factor that is not a power of two
+ * in 1 .. 1024, dst.grid_len != (float)(factor_xy * src.grid_len) or dst.z_len != (float)(factor_z * src.z_len) (exact fp32), no
+ * finished build in `src`, a `src` whose map is not in the additive node table (a PARTITION build; strategy ATOMIC / TILE or a map built
+ * by gndt_update* is, as for gndt_remove), a stream under hipGraph capture (a coarsen is not recorded).  A destination table that is
+ * too small for the parents reports GNDT_ERR_CAPACITY, as elsewhere.  There is no CPU path. */
+int gndt_coarsen_device(gndt_handle* src, gndt_handle* dst, uint32_t factor_xy, uint32_t factor_z, void* hip_stream);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
