@@ -226,6 +226,10 @@ struct gndt_handle {
         // scan score derivatives (gndt_score_derivs.hpp): ScoreDerivWaves[poses of a launch], then ScoreDerivPartial[poses][tiles]
         void* dpartial = nullptr; uint64_t dpartial_cap = 0;
     } score;
+    // ray casting (gndt_cast.hpp): the call's counters {rays, skipped, hits}, device and pinned
+    struct Cast {
+        unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
+    } cast;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -572,5 +576,7 @@ void free_crop(gndt_handle* h);
 void free_clear(gndt_handle* h);
 // ---- gndt_api_score.hip ----
 void free_score(gndt_handle* h);
+// ---- gndt_api_cast.hip ----
+void free_cast(gndt_handle* h);
 
 }  // namespace gndt_host

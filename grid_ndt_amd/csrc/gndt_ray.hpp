@@ -5,6 +5,8 @@
 // plane the segment meets first (fp64 crossing parameter, a tie stepping x), and in every column the levels between the ray's z at the
 // column's entry and at its exit (the codec's level of the origin / the cut point at the ends, the codec's rule in fp64 inside).
 // Everything up to the rows is callable on the host as well, so that the CPU test tier runs the kernel's own code (tests/consumer_shim.cpp).
+// Ray casting (gndt_cast.hpp) walks the same way from an origin per ray: ray_begin's second overload checks that origin like an end
+// point, ray_next's second overload also hands out the step's crossing parameter and the column's entry and exit levels (RayCross).
 //
 // Kernels (gndt_api_clear.hip launches them in this order):
 //   k_clear_extent   (GNDT_DEBUG_CLEAR_EXTENT only) per column, at its first row: the least and greatest sz of its rows (the walk skips a column whose extent misses
@@ -58,6 +60,7 @@ GNDT_HD double ray_cross(float o_axis, float len, int k, double r, double d) {
 
 struct RayWalk {
     double r[3], d[3];           // the ray's origin and its UNCUT direction p - o, fp64
+    double f, len;               // the cut factor (e = o + d f; 1: nothing is cut) and |d|
     int lx, ly, lx1, ly1;        // the current column and the last one, as lattice cells
     int lev_in, sz_end;          // the current column's entry level; the cut point's level
     bool done;
@@ -67,11 +70,14 @@ struct RayColumn {
     int sx, sy, lo, hi;          // a column the ray walks, and the levels it walks there (lo <= hi)
 };
 
-// The ray to end point p: false if p is not finite or has no key (the point is skipped).  The sensor origin is keyed (checked by the host).
-GNDT_HD bool ray_begin(const RayGrid& G, float px, float py, float pz, RayWalk& w) {
-    if (!(isfinite(px) && isfinite(py) && isfinite(pz))) return false;
-    if (!point_key(px, py, pz, G.ox, G.oy, G.oz, G.grid_len, G.z_len).ok) return false;
-    w.r[0] = (double)G.rx; w.r[1] = (double)G.ry; w.r[2] = (double)G.rz;
+struct RayCross {                // what ray casting (gndt_cast.hpp) needs of a column visit besides RayColumn
+    double t;                    // the crossing parameter of the step that leaves the column, in units of the uncut d (the last column: the cut factor)
+    int lev_in, lev_out;         // the levels at the column's entry and exit: lo / hi in walk order
+};
+
+// The walk from the keyed, finite origin (rx, ry, rz) to the keyed, finite end point p (G.rx / ry / rz are not read)
+GNDT_HD void ray_setup(const RayGrid& G, float rx, float ry, float rz, float px, float py, float pz, RayWalk& w) {
+    w.r[0] = (double)rx; w.r[1] = (double)ry; w.r[2] = (double)rz;
     w.d[0] = (double)px - w.r[0]; w.d[1] = (double)py - w.r[1]; w.d[2] = (double)pz - w.r[2];
     // the cut point e = o + d * min(1, max_range / |d|, max(0, |d| - end_margin) / |d|), fp64; e = p when nothing is cut
     const double L = sqrt(w.d[0] * w.d[0] + w.d[1] * w.d[1] + w.d[2] * w.d[2]);
@@ -83,23 +89,44 @@ GNDT_HD bool ray_begin(const RayGrid& G, float px, float py, float pz, RayWalk& 
     float e[3] = {px, py, pz};
     if (f < 1.0)
         for (int a = 0; a < 3; ++a) e[a] = (float)(w.r[a] + w.d[a] * f);
-    const PointKey ko = point_key(G.rx, G.ry, G.rz, G.ox, G.oy, G.oz, G.grid_len, G.z_len);
+    const PointKey ko = point_key(rx, ry, rz, G.ox, G.oy, G.oz, G.grid_len, G.z_len);
     const PointKey ke = point_key(e[0], e[1], e[2], G.ox, G.oy, G.oz, G.grid_len, G.z_len);
+    w.f = f; w.len = L;
     w.lx = ray_lin(ko.sx); w.ly = ray_lin(ko.sy);
     w.lx1 = ray_lin(ke.sx); w.ly1 = ray_lin(ke.sy);
     w.lev_in = ko.sz; w.sz_end = ke.sz;
     w.done = false;
+}
+
+// A point a ray can start or end at: finite, and keyed by the codec
+GNDT_HD bool ray_point_ok(const RayGrid& G, float x, float y, float z) {
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
+    return point_key(x, y, z, G.ox, G.oy, G.oz, G.grid_len, G.z_len).ok;
+}
+
+// The ray to end point p: false if p is not finite or has no key (the point is skipped).  The sensor origin is keyed (checked by the host).
+GNDT_HD bool ray_begin(const RayGrid& G, float px, float py, float pz, RayWalk& w) {
+    if (!ray_point_ok(G, px, py, pz)) return false;
+    ray_setup(G, G.rx, G.ry, G.rz, px, py, pz, w);
     return true;
 }
 
-// The next column of the walk and its level range; false once the cut point's column has been given
-GNDT_HD bool ray_next(const RayGrid& G, RayWalk& w, RayColumn& c) {
+// The ray from an origin of its own (ray casting: one per ray, checked here like the end point)
+GNDT_HD bool ray_begin(const RayGrid& G, float rx, float ry, float rz, float px, float py, float pz, RayWalk& w) {
+    if (!ray_point_ok(G, rx, ry, rz) || !ray_point_ok(G, px, py, pz)) return false;
+    ray_setup(G, rx, ry, rz, px, py, pz, w);
+    return true;
+}
+
+// The next column of the walk, its level range and (x) the step that leaves it; false once the cut point's column has been given
+GNDT_HD bool ray_next(const RayGrid& G, RayWalk& w, RayColumn& c, RayCross& x) {
     if (w.done) return false;
     const bool mx = w.lx != w.lx1, my = w.ly != w.ly1;
     int lev_out;
     bool step_x = false;
     if (!mx && !my) {
         lev_out = w.sz_end;
+        x.t = w.f;
         w.done = true;
     } else {
         double tx = 2.0, ty = 2.0;
@@ -108,7 +135,9 @@ GNDT_HD bool ray_next(const RayGrid& G, RayWalk& w, RayColumn& c) {
         step_x = mx && (!my || tx <= ty);
         const double t = step_x ? tx : ty;
         lev_out = ray_level(w.r[2] + t * w.d[2], G.oz, G.z_len);
+        x.t = t;
     }
+    x.lev_in = w.lev_in; x.lev_out = lev_out;
     c.sx = ray_signed(w.lx); c.sy = ray_signed(w.ly);
     c.lo = w.lev_in < lev_out ? w.lev_in : lev_out;
     c.hi = w.lev_in < lev_out ? lev_out : w.lev_in;
@@ -118,6 +147,12 @@ GNDT_HD bool ray_next(const RayGrid& G, RayWalk& w, RayColumn& c) {
         w.lev_in = lev_out;
     }
     return true;
+}
+
+// The column and its level range alone (free-space clearing)
+GNDT_HD bool ray_next(const RayGrid& G, RayWalk& w, RayColumn& c) {
+    RayCross x;
+    return ray_next(G, w, c, x);
 }
 
 // A walked column -> its first row (kNoColumn: not in the map) and the rows to look at: its node count, or 0 when (EXT) the column's

@@ -73,6 +73,28 @@ struct ScoreTerm {
     double ux, uy, uz, d2;
 };
 
+// The cofactors of A and its determinant from a node's count and scatter (the order of the header comment): the one statement of it,
+// shared by score_node and ray casting's NDT mode (gndt_cast.hpp)
+GNDT_HD void score_cofactors(uint32_t c, float s0, float s1, float s2, float s3, float s4, float s5, double cov_rel, double cov_floor,
+                             ScoreTerm& t) {
+    const double r = 1.0 / (double)(c - 1u);
+    const double cxx = (double)s0 * r, cxy = (double)s1 * r, cxz = (double)s2 * r, cyy = (double)s3 * r, cyz = (double)s4 * r,
+                 czz = (double)s5 * r;
+    const double eps = fmax(cov_rel * (((cxx + cyy) + czz) / 3.0), cov_floor);
+    const double a00 = cxx + eps, a11 = cyy + eps, a22 = czz + eps, a01 = cxy, a02 = cxz, a12 = cyz;
+    t.c00 = a11 * a22 - a12 * a12; t.c01 = a02 * a12 - a01 * a22; t.c02 = a01 * a12 - a02 * a11;
+    t.c11 = a00 * a22 - a02 * a02; t.c12 = a01 * a02 - a00 * a12; t.c22 = a00 * a11 - a01 * a01;
+    t.det = (a00 * t.c00 + a01 * t.c01) + a02 * t.c02;
+}
+
+// u = adj(A) d and d2 = d^T u / det from t's d, cofactors and det
+GNDT_HD void score_d2(ScoreTerm& t) {
+    t.ux = (t.c00 * t.dx + t.c01 * t.dy) + t.c02 * t.dz;
+    t.uy = (t.c01 * t.dx + t.c11 * t.dy) + t.c12 * t.dz;
+    t.uz = (t.c02 * t.dx + t.c12 * t.dy) + t.c22 * t.dz;
+    t.d2 = ((t.dx * t.ux + t.dy * t.uy) + t.dz * t.uz) / t.det;
+}
+
 // The term of q against the node of `row` (the order of the header comment); false: the node is not a candidate (too few points, or
 // beyond max_d2)
 GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, float qx, float qy, float qz, ScoreTerm& t) {
@@ -82,19 +104,9 @@ GNDT_HD bool score_node(const ScoreView& S, const ScoreParams& P, uint32_t row, 
     const float mx = m[0], my = m[1], mz = m[2];
     const float s0 = s[0], s1 = s[1], s2 = s[2], s3 = s[3], s4 = s[4], s5 = s[5];
     if (c < P.min_count) return false;
-    const double r = 1.0 / (double)(c - 1u);
-    const double cxx = (double)s0 * r, cxy = (double)s1 * r, cxz = (double)s2 * r, cyy = (double)s3 * r, cyz = (double)s4 * r,
-                 czz = (double)s5 * r;
-    const double eps = fmax(P.cov_rel * (((cxx + cyy) + czz) / 3.0), P.cov_floor);
-    const double a00 = cxx + eps, a11 = cyy + eps, a22 = czz + eps, a01 = cxy, a02 = cxz, a12 = cyz;
-    t.c00 = a11 * a22 - a12 * a12; t.c01 = a02 * a12 - a01 * a22; t.c02 = a01 * a12 - a02 * a11;
-    t.c11 = a00 * a22 - a02 * a02; t.c12 = a01 * a02 - a00 * a12; t.c22 = a00 * a11 - a01 * a01;
-    t.det = (a00 * t.c00 + a01 * t.c01) + a02 * t.c02;
+    score_cofactors(c, s0, s1, s2, s3, s4, s5, P.cov_rel, P.cov_floor, t);
     t.dx = (double)qx - (double)mx; t.dy = (double)qy - (double)my; t.dz = (double)qz - (double)mz;
-    t.ux = (t.c00 * t.dx + t.c01 * t.dy) + t.c02 * t.dz;
-    t.uy = (t.c01 * t.dx + t.c11 * t.dy) + t.c12 * t.dz;
-    t.uz = (t.c02 * t.dx + t.c12 * t.dy) + t.c22 * t.dz;
-    t.d2 = ((t.dx * t.ux + t.dy * t.uy) + t.dz * t.uz) / t.det;
+    score_d2(t);
     return !(P.max_d2 > 0.0 && t.d2 > P.max_d2);
 }
 

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -35,6 +35,18 @@ def _stream_ptr(stream):
     if hasattr(stream, "cuda_stream"):
         return C.c_void_p(stream.cuda_stream or _HIP_STREAM_LEGACY)
     return C.c_void_p(int(stream))
+
+
+def _torch_stream_ctx(stream):
+    """torch's current stream := `stream` while tensors that the call's kernels read or write are made, so that the caching allocator
+    ties them to the stream the kernels run on.  A raw hipStream_t is wrapped (torch.cuda.ExternalStream); None: torch's current one."""
+    import contextlib
+    if stream is None:
+        return contextlib.nullcontext()
+    import torch
+    if not hasattr(stream, "cuda_stream"):
+        stream = torch.cuda.ExternalStream(int(stream))
+    return torch.cuda.stream(stream)
 
 
 class _DevArray:
@@ -678,6 +690,82 @@ class TwoDmap:
                                                 C.c_void_p(rows.ctypes.data if rows is not None and rows.size else 0), C.byref(st)))
         out = {"rays": int(st.rays), "skipped": int(st.skipped), "protected_rows": int(st.protected_rows), "cleared": int(st.cleared)}
         return (out, rows) if passes else out
+
+    # ---- ray casting (gndt_cast_rays*: the first map node along each ray of a batch) ----
+    CAST_MODES = {"voxel": 0, "ndt": 1}
+
+    def cast_rays(self, origins, ends, mode="voxel", min_count=0, max_range=0.0, min_range=0.0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0,
+                  stats=False, stream=None):
+        """Where every ray from `origins` ((3,): one origin for all; or [N,3] / [N,4] float32) to `ends` ([N,3] or [N,4] float32) first
+        hits the map (include/gndt.h "ray casting" defines the answer).  mode "voxel": the first node with count >= min_count (0 = 1)
+        the walk visits, the range to where the ray enters its voxel; "ndt": nodes with statistics (min_count 0 = max(min_points, 3)),
+        the range to the point of the ray nearest the node's distribution (cov_rel, cov_floor as in score_poses; max_d2 > 0: a node
+        the ray passes farther from than this does not stop it).  max_range > 0 walks at most that far, candidates nearer than
+        min_range do not count.  Returns {"row" (int32, -1: none), "range", "d2" (float32: inf for a miss, NaN for a skipped ray)}: torch
+        tensors for torch CUDA ends (enqueued on `stream`, default torch's current stream, not awaited), numpy arrays through
+        gndt_cast_rays otherwise.  stats=True waits and returns (that dict, {rays, skipped, hits})."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        prm = CastParams(self.CAST_MODES[mode] if isinstance(mode, str) else int(mode), int(min_count), float(max_range), float(min_range),
+                         float(cov_rel), float(cov_floor), float(max_d2), 0)
+        eptr, n, estride, on_dev, keep = self._as_input(ends)
+        st = CastStats()
+        if on_dev:
+            import torch
+            # (the origins' upload and the outputs belong to the stream the kernel runs on)
+            with _torch_stream_ctx(stream):
+                if not isinstance(origins, torch.Tensor):
+                    origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float32))
+                o = origins.to(device=keep.device, dtype=torch.float32).contiguous()
+                # (one element at least: the call wants an output pointer whatever n is)
+                buf = {k: torch.empty(max(n, 1), dtype=dt, device=keep.device)
+                       for k, dt in (("row", torch.int32), ("range", torch.float32), ("d2", torch.float32))}
+            optr, oshape = o.data_ptr(), tuple(o.shape)
+            co = CastOut(*[C.c_void_p(buf[k].data_ptr()) for k in ("row", "range", "d2")])
+        else:
+            try:
+                import torch
+                if isinstance(origins, torch.Tensor):
+                    origins = origins.detach().cpu().numpy()
+            except ImportError:
+                pass
+            o = np.ascontiguousarray(origins, dtype=np.float32)
+            buf = {k: np.empty(max(n, 1), dt) for k, dt in (("row", np.int32), ("range", np.float32), ("d2", np.float32))}
+            optr, oshape = o.ctypes.data, o.shape
+            co = CastOut(*[C.c_void_p(buf[k].ctypes.data) for k in ("row", "range", "d2")])
+        if len(oshape) == 1 and oshape[0] in (3, 4):
+            ostride = 0
+        elif len(oshape) == 2 and oshape[0] == n and oshape[1] in (3, 4):
+            ostride = 4 * oshape[1]
+        else:
+            raise ValueError("origins must be (3,) or (n, 3|4) with one row per end point")
+        stp = C.byref(st) if stats else None
+        if on_dev:
+            self._check(self._L.gndt_cast_rays_device(self._h, C.c_void_p(optr if n else 0), ostride, C.c_void_p(eptr if n else 0), n, estride,
+                                                      C.byref(prm), C.byref(co), stp, _stream_ptr(stream)))
+        else:
+            self._check(self._L.gndt_cast_rays(self._h, C.c_void_p(optr if n else 0), ostride, C.c_void_p(eptr if n else 0), n, estride,
+                                               C.byref(prm), C.byref(co), stp))
+        out = {k: v[:n] for k, v in buf.items()}
+        if stats:
+            return out, {"rays": int(st.rays), "skipped": int(st.skipped), "hits": int(st.hits)}
+        return out
+
+    def cast_scan(self, pose, directions, max_range, **kw):
+        """The scan a sensor at `pose` (3 x 4 or 4 x 4 [R | t], map <- sensor) expects of the map: one ray per row of `directions`
+        ([N,3] unit vectors in the sensor frame) from t to t + max_range * R dir.  The ends are formed on the device in float64,
+        end_a = t_a + max_range * ((R_a0 x + R_a1 y) + R_a2 z), and rounded once to float32; the origin is float32(t).  Returns
+        cast_rays' result for those rays (keyword arguments are cast_rays'): range is inf where nothing lies within max_range."""
+        import torch
+        T = self._as_poses(pose)[0].reshape(3, 4)
+        dev = f"cuda:{self.device}"
+        with _torch_stream_ctx(kw.get("stream")):
+            d = (directions if isinstance(directions, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(directions)))
+            d = d.to(device=dev, dtype=torch.float64)
+            x, y, z = d[:, 0], d[:, 1], d[:, 2]
+            ends = torch.stack([float(T[a, 3]) + float(max_range) * ((float(T[a, 0]) * x + float(T[a, 1]) * y) + float(T[a, 2]) * z)
+                                for a in range(3)], 1).to(torch.float32)
+        return self.cast_rays(np.asarray(T[:, 3], np.float32), ends, **kw)
 
     # ---- scan scoring (gndt_score_poses*: the NDT match score of a scan for a batch of poses) ----
     @staticmethod

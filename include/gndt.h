@@ -662,6 +662,75 @@ int gndt_score_derivs_device(gndt_handle* h, const void* xyz_dev, size_t n, size
 int gndt_score_derivs(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
                       const gndt_score_params* params, gndt_pose_derivs* out_host);
 
+/* ---- ray casting: the first map node along each ray of a batch, and how far away it is ----------------------------------------
+ * The expected range of a beam from a pose (a particle filter's beam model; gndt_score_poses is the likelihood-field model), line of
+ * sight and visibility, synthetic scans and depth images, and "does this return lie in front of the map or behind it" before
+ * gndt_clear_rays.  Ray i has an origin o_i and an end point p_i, both fp32 in map coordinates, d = p - o in fp64.
+ * A ray is SKIPPED when o_i or p_i has a non-finite coordinate or no key in the codec's range: not an error, counted in stats.skipped.
+ * The answer is a DEFINITION (tests restate it in numpy, bit for bit):
+ *   - walk: "free-space clearing"'s walk from o_i to the cut point e = o + d * min(1, max_range / |d|) (max_range = 0: no limit; there
+ *     is no end_margin): the same columns, |dx| + |dy| steps, tie rule, fp64 crossing parameters and level range per column.
+ *   - interval of a column visit, in units of the uncut d: t_in = 0 in the first column, otherwise the crossing parameter of the step
+ *     that entered the column; t_out = the crossing parameter of the step that leaves it, in the last column the cut factor
+ *     f = min(1, max_range / |d|); t_hi = max(t_in, t_out).
+ *   - order of levels: inside a column the levels are visited from the entry level towards the exit level, level 0 skipped.
+ *   - GNDT_CAST_VOXEL: a candidate is a row of the column with sz in the level range and count >= min_count (0 = 1; any value >= 1).
+ *     Its level the entry level: t_hit = t_in.  Otherwise t_z = the crossing of the z-plane through which the ray enters that level, by
+ *     the walk's crossing rule on the z axis (lattice plane k of z_len from the map origin, clamped to [0, 1], 1 for d_z = 0): going up
+ *     k is the level's lower plane, going down its upper plane; t_hit = min(max(t_in, t_z), t_hi).  d2 is 0.
+ *   - GNDT_CAST_NDT: a candidate also needs statistics: min_count 0 = max(min_points, 3), values below that are refused as in "scan
+ *     scoring".  A and its cofactors c_ij are exactly scoring's, from count, cov, cov_rel and cov_floor with the same defaults.  The
+ *     point of the line o + t d with the least Mahalanobis distance to the node: w_i = (c_i0 d_x + c_i1 d_y) + c_i2 d_z, g = mean - o,
+ *     t_line = ((g_x w_x + g_y w_y) + g_z w_z) / ((d_x w_x + d_y w_y) + d_z w_z), 0 for |d| = 0;
+ *     t_hit = min(max(t_line, t_in), t_hi) (a NaN t_line takes t_in); q = o + t_hit d per coordinate in fp64; d2 is the score's d2 of
+ *     q - mean with q kept in fp64.  With max_d2 > 0 a candidate whose d2 > max_d2 does not stop the ray (0: no gate).
+ *   - selection: range = t_hit * |d| (|d| the fp64 square root the walk uses).  A candidate with range < min_range (fp64 comparison)
+ *     does not count: a sensor that sits inside a mapped voxel.  The ray's answer is the first counting candidate in walk order:
+ *     columns in walk order, levels in visit order inside a column.
+ * Everything is + - x /, sqrt and ceil in fp64, no product fused with a sum, no exp, no floating-point atomics: the same bits in every
+ * run, on every stream, at every stride (grid_ndt_amd/csrc/gndt_cast.hpp states the evaluation order).
+ * Outputs per ray (each of the three arrays may be NULL, not all of them):
+ *     hit       row = the hit row      range = (float)range     d2 = 0 (VOXEL) / (float)d2 (NDT)
+ *     miss      row = GNDT_NO_ROW      range = +inf             d2 = +inf
+ *     skipped   row = GNDT_NO_ROW      range = NaN              d2 = NaN
+ * stats (optional): rays (not skipped), skipped, hits.  Asking for it makes the call wait.
+ * origin_stride_bytes is 0, 12 or 16; with 0 every ray starts at the one origin at `origins`.  end_stride_bytes is 12 or 16.
+ * Order, lifetime and stream rules are the point queries': the call first finishes what gndt_sync finishes, then builds or reuses the
+ * map's column index, then enqueues one kernel on `hip_stream` (NULL = the handle's stream, the rules of gndt_build_device) and does not
+ * wait unless `stats` is given.  The map is not modified.  It works on every map that has rows (PARTITION-built ones too: the node
+ * table is not needed); a sharded map answers from the rows this rank holds.  There is no CPU path.  n == 0 returns GNDT_OK, launches
+ * nothing and zeroes stats.
+ * GNDT_ERR_INVALID: null handle, params or out, all three output pointers null, null origins or ends with n > 0, n >= 2^31, a stride
+ * other than the above, an unknown mode, a negative or non-finite max_range, min_range, cov_rel, cov_floor or max_d2, a negative
+ * min_count, in NDT mode a min_count of 1 or 2 or below the handle's min_points, reserved != 0, no finished build, a stream under
+ * hipGraph capture (a cast is not recorded). */
+enum { GNDT_CAST_VOXEL = 0, GNDT_CAST_NDT = 1 };
+typedef struct gndt_cast_params {
+    int32_t mode;            /* GNDT_CAST_VOXEL / GNDT_CAST_NDT                                   */
+    int32_t min_count;       /* 0 = 1 (VOXEL) / max(min_points, 3) (NDT)                          */
+    float max_range;         /* > 0: walk at most this far from the origin; 0 = no limit          */
+    float min_range;         /* >= 0: candidates nearer than this do not count                    */
+    float cov_rel;           /* NDT: 0 = 0.01                                                     */
+    float cov_floor;         /* NDT: 0 = 1e-6 (m^2)                                               */
+    float max_d2;            /* NDT, > 0: candidates beyond this d2 do not stop the ray; 0 = none */
+    uint32_t reserved;       /* 0                                                                 */
+} gndt_cast_params;          /* 32 bytes */
+typedef struct gndt_cast_out {
+    uint32_t* row;           /* [n] each, NULL = not written (not all three)                      */
+    float* range;
+    float* d2;
+} gndt_cast_out;
+typedef struct gndt_cast_stats {
+    uint64_t rays, skipped, hits;
+} gndt_cast_stats;
+/* Device origins and ends; `out_dev` holds device pointers. */
+int gndt_cast_rays_device(gndt_handle* h, const void* origins_dev, size_t origin_stride_bytes, const void* ends_dev, size_t n,
+                          size_t end_stride_bytes, const gndt_cast_params* params, const gndt_cast_out* out_dev, gndt_cast_stats* stats,
+                          void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; synchronous. */
+int gndt_cast_rays(gndt_handle* h, const void* origins_host, size_t origin_stride_bytes, const void* ends_host, size_t n,
+                   size_t end_stride_bytes, const gndt_cast_params* params, const gndt_cast_out* out_host, gndt_cast_stats* stats);
+
 /* ---- map pyramids: a coarser map of the same point stream, from the map alone --------------------------------------------------
  * The scan score has a basin of less than a cell (grid_ndt_amd/registration.py); coarse-to-fine registration needs the same cloud at
  * 2x, 4x ... the cell lengths, and a map grown by gndt_update*, cropped or cleared no longer has its points.  It does not need them:
