@@ -300,6 +300,21 @@ int drop_dead_and_finalize(gndt_handle* h, hipStream_t s) {
     return do_finalize(h, s);
 }
 
+// gndt_stats_merge_device's head (gndt_merge_map_device's too): the handle ready, the call on stream *s, the map in the node table, room
+// for `nodes` more nodes in it (a populated table grows through grow_table)
+int stats_merge_head(gndt_handle* h, uint64_t nodes, void* hip_stream, hipStream_t* s) {
+    int rc = check_ready(h);
+    if (rc) return rc;
+    *s = stream_of(h, hip_stream);
+    { const int urc = use_stream(h, *s); if (urc) return urc; }
+    if (!h->map_in_table) {
+        h->err = "the current map was built by a PARTITION strategy and does not live in the node table: call gndt_reset first";
+        return GNDT_ERR_INVALID;
+    }
+    h->pending.active = false;
+    return ensure_capacity_for(h, nodes, *s);
+}
+
 // gndt_reserve: a node table for `nodes` nodes (what a table that holds a map already is grown to, its contents kept)
 int reserve_table(gndt_handle* h, uint64_t nodes, hipStream_t s) {
     const uint32_t want = cap_for_nodes(nodes);
@@ -567,15 +582,8 @@ int gndt_stats_merge_device(gndt_handle* h, const gndt_stats* in, void* hip_stre
     int rc = check_ready(h);
     if (rc) return rc;
     if (!in) return GNDT_ERR_INVALID;
-    hipStream_t s = stream_of(h, hip_stream);
-    { const int urc = use_stream(h, s); if (urc) return urc; }
-    if (!h->map_in_table) {
-        h->err = "the current map was built by a PARTITION strategy and does not live in the node table: call gndt_reset first";
-        return GNDT_ERR_INVALID;
-    }
-    h->pending.active = false;
-    rc = ensure_capacity_for(h, in->num_nodes, s);
-    if (rc) return rc;
+    hipStream_t s;
+    if ((rc = stats_merge_head(h, in->num_nodes, hip_stream, &s))) return rc;
     if (in->num_nodes) {
         hipLaunchKernelGGL(k_stats_merge, dim3(grid_for(in->num_nodes)), dim3(kBlock), 0, s, h->keys, h->acc, h->cap - 1,
                            h->node_slot, h->index_of_slot, in->key, in->sums, in->count, in->first_idx, (uint64_t)in->num_nodes,

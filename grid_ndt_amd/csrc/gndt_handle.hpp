@@ -11,6 +11,7 @@
 //   gndt_api_clear.hip  free-space clearing: nodes that sensor rays pass through leave the map
 //   gndt_api_score.hip  scan scoring and its derivatives
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
+//   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
@@ -230,6 +231,10 @@ struct gndt_handle {
     struct Cast {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
     } cast;
+    // map merge (gndt_merge.hpp): the call's tallies, device and pinned
+    struct Merge {
+        unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
+    } merge;
     // statistics exchange of a sharded build (gndt_exchange.hpp, gndt_api_dist.hip)
     struct Exchange {
         unsigned long long* d_counts = nullptr; uint64_t counts_cap = 0; unsigned long long* h_counts = nullptr;
@@ -538,6 +543,7 @@ int do_reset(gndt_handle* h, hipStream_t s);
 int zero_device_now(gndt_handle* h, void* p, size_t bytes);
 int partition_recheck_after_replay(gndt_handle* h);
 int reserve_table(gndt_handle* h, uint64_t nodes, hipStream_t s);
+int stats_merge_head(gndt_handle* h, uint64_t nodes, void* hip_stream, hipStream_t* s);   // gndt_stats_merge_device up to its kernel: room for `nodes` more
 int drop_dead_and_finalize(gndt_handle* h, hipStream_t s);   // gndt_remove* / gndt_clear_rays*: drop the nodes left empty, re-finalise every row
 int table_refinalize(gndt_handle* h);      // the regular finalisation after the small-map one gave up (gndt_sync)
 int table_emit_pending(gndt_handle* h);    // deferred-emit mode: the ordering + emit pass the frames since the last read left out (gndt_sync)
@@ -578,5 +584,7 @@ void free_clear(gndt_handle* h);
 void free_score(gndt_handle* h);
 // ---- gndt_api_cast.hip ----
 void free_cast(gndt_handle* h);
+// ---- gndt_api_merge.hip ----
+void free_merge(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -952,6 +952,44 @@ class TwoDmap:
             m = m.coarsen(factor)
             out.append(m)
         return out[::-1]
+
+    # ---- map merge (gndt_merge_map_device: another map's node table, moved by a pose, added into this map's) ----
+    def merge_from(self, other, pose=None, min_count=0, stream=None):
+        """Fold the map `other` into this one under `pose` ([3, 4] / [4, 4] [R | t], this map <- other; None = identity): every node of
+        `other` with at least min_count points (0 = 1) is moved as a Gaussian with a count and added, moment-matched, to the node of
+        this map its mean falls into (include/gndt.h "map merge").  Computed on the device from the two node tables alone: it works on
+        maps whose points are gone.  This map needs an origin and may be empty; its lengths, origin, demand and min_points may differ
+        from `other`'s, which must hold its map in the node table (strategy ATOMIC / TILE, or built by change2DMap) and is only read.
+        Afterwards every row of this map is re-finalised and change2DMap / del2DMap go on.  Enqueued on `stream` (default torch's
+        current stream); the call waits for the kernel.  Returns the tallies: source_nodes, merged_nodes, merged_points,
+        below_min_count, skipped (the moved mean has no key in this map) and new_nodes."""
+        if other._h is None:
+            raise GndtError(1, "merge_from: the other map has no finished build")
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        T = None if pose is None else self._as_poses(pose)
+        if T is not None and T.shape[0] != 1:
+            raise ValueError("merge_from takes one pose")
+        prm = MergeParams(int(min_count), 0)
+        st = MergeStats()
+        rc = self._L.gndt_merge_map_device(self._h, other._h, C.c_void_p(T.ctypes.data if T is not None else 0), C.byref(prm), C.byref(st),
+                                           _stream_ptr(stream))
+        self._check(rc)
+        return {k: int(getattr(st, k)) for k, _ in MergeStats._fields_}
+
+    def stitch(self, other, T0, **register_kw):
+        """Register the map `other` against this one from the start `T0` ([3, 4] / [4, 4], this map <- other) and fold it in at the
+        pose found: the means of `other`'s rows that have statistics are the scan of self.register(scan, T0, **register_kw), and
+        merge_from(other, pose=result["T"]) follows.  Returns (register's result, merge_from's tallies)."""
+        import torch
+        cells = other.export_device()
+        if cells["num_nodes"] == 0:
+            raise GndtError(1, "stitch: the other map is empty")
+        scan = cells["mean"][(cells["flags"] & FLAG_HAS_STATS) != 0].contiguous()
+        if np.asarray(T0).ndim != 2:
+            raise ValueError("stitch takes one start pose")
+        result = self.register(scan, T0, **register_kw)
+        return result, self.merge_from(other, pose=result["T"], stream=register_kw.get("stream"))
 
     # ---- results ----
     def sync(self):

@@ -757,6 +757,57 @@ int gndt_cast_rays(gndt_handle* h, const void* origins_host, size_t origin_strid
  * too small for the parents reports GNDT_ERR_CAPACITY, as elsewhere.  There is no CPU path. */
 int gndt_coarsen_device(gndt_handle* src, gndt_handle* dst, uint32_t factor_xy, uint32_t factor_z, void* hip_stream);
 
+/* ---- map merge: one map folded into another under a rigid transform, from the maps alone ---------------------------------------
+ * A registration returns the pose at which a submap, another robot's map or an earlier session's map fits the map being localised
+ * against; the merge uses it.  A source node is a Gaussian with a count: it is moved by the pose, the destination node its mean falls
+ * into is found, and its moment-matched statistics are added there (the standard NDT map-fusion step).  No point is needed, and a node
+ * is kept whole: one that straddles destination cells is not split (DESIGN.md 4.3h says what that costs).
+ * The answer is a definition.  Everything is fp64, no product is fused with a sum (grid_ndt_amd/csrc/gndt_merge.hpp states the
+ * evaluation order).  For every live source node (count >= 1, count >= min_count) with key k, count n, s1 = Sum v (3 values) and
+ * s2 = Sum v v^T (6 values, xx xy xz yy yz zz) about its centre c = axis centre of k at the SOURCE's origin and lengths:
+ *   1. source mean          mu_a = s1_a / (double)n,      m_a = c_a + mu_a
+ *   2. central scatter      S_ab = s2_ab - s1_a * mu_b
+ *   3. moved mean           m'_i = ((R_i0 m_x + R_i1 m_y) + R_i2 m_z) + t_i                       (the shape of scan scoring's step 1)
+ *   4. destination key      the codec's key of ((float)m'_x, (float)m'_y, (float)m'_z) at the DESTINATION's origin, grid_len and z_len;
+ *                           a non-finite coordinate or a key outside the codec's range: the node does not travel and is counted in
+ *                           `skipped` (not an error)
+ *   5. rotated scatter      W_ib = (R_i0 S_0b + R_i1 S_1b) + R_i2 S_2b   (S symmetric),   S'_ij = (W_i0 R_j0 + W_i1 R_j1) + W_i2 R_j2, i <= j
+ *                           (nothing checks that R is a rotation: any affine map moves the Gaussian this way)
+ *   6. destination centre   c' = axis centre of the destination key
+ *   7. statistics about c'  u_a = m'_a - c'_a (the fp64 m', not its fp32 rounding),  nu_a = (double)n * u_a:
+ *                           out[a] = nu_a,      out[3+ab] = S'_ab + nu_a * u_b
+ *   8. into the table       the nine sums add and the count adds; the first-seen index takes the minimum with base + first, base =
+ *                           the destination's stream position before the call
+ * The destination's stream position becomes base + the source's, whether or not any node travelled.  So a merge under the identity
+ * between handles of equal origin and lengths equals gndt_update* of the source's point stream whenever every source node's points
+ * share the cell of their mean: the merged part orders after everything the destination held, in the source's own order.  The order
+ * of the floating-point adds into one destination node is not fixed (atomics, as in the ATOMIC build and the coarsen).
+ * Afterwards `dst` is in the state of gndt_stats_merge_device + gndt_finalize_device: every row re-finalised with dst's demand,
+ * slope_interval and min_points, the cost map invalid, the column index rebuilt, device pointers from gndt_export_device and row
+ * numbers from gndt_query* invalid; a graph recorded before the merge and replayed after it is reported stale by gndt_sync
+ * (GNDT_ERR_CAPACITY, as after a crop or a clear); gndt_update* / gndt_remove* go on afterwards.  The destination may be empty (fresh, or
+ * after gndt_reset, with an origin) and may differ from the source in lengths, origin, demand and min_points.
+ * `src` is only read: the call first finishes what gndt_sync(src) and gndt_sync(dst) finish, then leaves src's rows, column index and a
+ * current cost map valid and its export bit-identical.  `pose` is host memory, row-major 3 x 4 [R | t], dst <- src; NULL = identity.
+ * The kernel and the finalisation are enqueued on `hip_stream` (NULL = dst's stream, the rules of gndt_build_device); the call waits for
+ * the kernel, as gndt_coarsen_device does, so `stats` (optional) costs nothing extra: source_nodes (live: count >= 1), merged_nodes and
+ * merged_points (what travelled), below_min_count, skipped, new_nodes (the destination's node count after minus before).
+ * GNDT_ERR_INVALID, with `dst`'s map unchanged and the text on both handles: a null handle, src == dst, handles on different devices, a
+ * non-finite pose entry, reserved != 0, a negative min_count, no finished build in `src`, a `src` whose map is not in the additive node
+ * table (the rule of gndt_coarsen_device), a `dst` without an origin, a `dst` that holds a PARTITION-built map (the rule of
+ * gndt_stats_merge_device: call gndt_reset first), base + the source's stream position > 2^32 - 2, a stream under hipGraph capture (a
+ * merge is not recorded).  A destination table that cannot be grown reports GNDT_ERR_CAPACITY or GNDT_ERR_NOMEM, as elsewhere.  A
+ * sharded map merges into the rows' owner only if the caller arranges it: the call treats `dst` as one map.  There is no CPU path. */
+typedef struct gndt_merge_params {
+    int32_t min_count;       /* source nodes with fewer points stay behind; 0 = 1                */
+    uint32_t reserved;       /* 0                                                                 */
+} gndt_merge_params;         /* 8 bytes */
+typedef struct gndt_merge_stats {
+    uint64_t source_nodes, merged_nodes, merged_points, below_min_count, skipped, new_nodes;
+} gndt_merge_stats;
+int gndt_merge_map_device(gndt_handle* dst, gndt_handle* src, const double pose[12], const gndt_merge_params* params,
+                          gndt_merge_stats* stats, void* hip_stream);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
