@@ -977,10 +977,123 @@ class TwoDmap:
         self._check(rc)
         return {k: int(getattr(st, k)) for k, _ in MergeStats._fields_}
 
-    def stitch(self, other, T0, **register_kw):
+    # ---- map-to-map scoring (gndt_score_maps*: the other map's nodes scored as Gaussians against this map) ----
+    def _maps_call(self, other, poses, prm, stream, width, per_node):
+        """the two entry points' common part: -> (records [K, width] int64 device tensor, d2, row)"""
+        import contextlib
+        import torch
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if other._h is None:
+            raise GndtError(1, "score_map: the other map has no finished build")
+        T = self._as_poses(poses)
+        K = T.shape[0]
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            ctx = contextlib.nullcontext()
+        else:
+            ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
+        with ctx:           # (the poses' upload and the outputs belong to the stream the kernels run on)
+            Td = torch.from_numpy(T).to(dev)
+            rec = torch.empty((K, width), dtype=torch.int64, device=dev)
+            d2 = row = None
+            if per_node:
+                n = other.sync()[0]
+                d2 = torch.empty(n, dtype=torch.float32, device=dev)
+                row = torch.empty(n, dtype=torch.int32, device=dev)
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            if width == 4:
+                rc = self._L.gndt_score_maps_device(self._h, other._h, p(Td), K, C.byref(prm), p(rec), p(d2), p(row), _stream_ptr(stream))
+            else:
+                rc = self._L.gndt_score_maps_derivs_device(self._h, other._h, p(Td), K, C.byref(prm), p(rec), _stream_ptr(stream))
+            self._check(rc)
+        return rec, d2, row
+
+    def score_map(self, other, poses, neighbourhood=1, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, per_node=None, stream=None):
+        """How well the map `other` fits this map at each of the K `poses` (this map <- other): every node of `other` that has
+        statistics is scored as a Gaussian against the nodes of this map its moved mean lands on, the covariance of the difference
+        being the sum of the two, `other`'s rotated by the pose (include/gndt.h "map-to-map scoring").  Arguments as score_poses;
+        min_count 0 is max(both maps' min_points, 3).  Both maps are only read and may be the same map.  Returns score_poses' dict of
+        device tensors; with per_node=k also d2 (float32, per row of `other` the least d2 at pose k: inf where it met no node, NaN
+        where the row has no statistics) and row (int32, that node's row in this map, -1).  Enqueued on `stream` (default torch's
+        current stream), not awaited."""
+        want = per_node is not None
+        prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), int(per_node) if want else 0)
+        rec, d2, row = self._maps_call(other, poses, prm, stream, 4, want)
+        import torch
+        fl = rec.view(torch.float64)
+        out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+        if want:
+            out.update(d2=d2, row=row)
+        return out
+
+    def score_map_derivs(self, other, poses, neighbourhood=1, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, stream=None):
+        """score_map's score with its gradient and Hessian with respect to a left pose perturbation xi = (v, w), which moves the means
+        and rotates the covariances of `other`'s nodes (include/gndt.h "map-to-map scoring").  Returns score_derivs' dict of device
+        tensors: score, d2_sum (the bits score_map gives), matched, terms, g [K, 6] and H [K, 6, 6]."""
+        import contextlib
+        import torch
+        prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), 0)
+        rec, _, _ = self._maps_call(other, poses, prm, stream, 31, False)
+        if stream is None:
+            ctx = contextlib.nullcontext()
+        else:
+            ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
+        with ctx:           # (the Hessian's gather runs behind the kernels)
+            fl = rec.view(torch.float64)
+            H = fl[:, 10:31][:, torch.from_numpy(self._h_index()).to(rec.device)].reshape(rec.shape[0], 6, 6)
+        return {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3], "g": fl[:, 4:10], "H": H}
+
+    def register_map(self, other, T0, neighbourhood=7, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, step_t=None, step_r=0.05,
+                     tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None, pyramid=None, other_pyramid=None):
+        """The pose near `T0` at which the map `other` fits this map best: register's iteration (registration.register, unchanged)
+        with its derivatives from score_map_derivs and its line search from score_map, so every node of `other` takes part with its
+        count's worth of shape, not as a bare point.  Arguments and result as register.  pyramid: coarser maps of this one, coarsest
+        first, as for register; other_pyramid, if given, `other`'s maps of the same levels — otherwise `other` itself is scored at
+        every level."""
+        from . import registration
+        kw = dict(neighbourhood=neighbourhood, min_count=min_count, cov_rel=cov_rel, cov_floor=cov_floor, max_d2=max_d2, stream=stream)
+
+        def host(out, names):
+            if hasattr(stream, "synchronize"):
+                stream.synchronize()
+            elif stream is not None:
+                import torch
+                torch.cuda.ExternalStream(int(stream)).synchronize()
+            return {k: out[k].cpu().numpy() for k in names}
+
+        def callables(m, o):
+            def evaluate(T):
+                return host(m.score_map_derivs(o, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
+
+            def score(T):
+                return host(m.score_map(o, T, **kw), ("score",))["score"]
+
+            return evaluate, score
+
+        own_step = 0.5 * self.gridLen if step_t is None else step_t
+        if pyramid is None:
+            evaluate, score = callables(self, other)
+            return registration.register(evaluate, score, T0, step_t=own_step, step_r=step_r, tol_t=tol_t, tol_r=tol_r,
+                                         max_iterations=max_iterations)
+        others = [other] * len(pyramid) if other_pyramid is None else list(other_pyramid)
+        if len(others) != len(pyramid):
+            raise ValueError("register_map: other_pyramid must hold one map per level of pyramid")
+        stages = [callables(m, o) + (0.5 * m.gridLen,) for m, o in zip(pyramid, others)] + [callables(self, other) + (own_step,)]
+        return registration.register_pyramid(stages, T0, step_r=step_r, tol_t=tol_t, tol_r=tol_r, max_iterations=max_iterations)
+
+    def stitch(self, other, T0, method="means", **register_kw):
         """Register the map `other` against this one from the start `T0` ([3, 4] / [4, 4], this map <- other) and fold it in at the
-        pose found: the means of `other`'s rows that have statistics are the scan of self.register(scan, T0, **register_kw), and
-        merge_from(other, pose=result["T"]) follows.  Returns (register's result, merge_from's tallies)."""
+        pose found.  method "means" (the default): the means of `other`'s rows that have statistics are the scan of
+        self.register(scan, T0, **register_kw).  method "d2d": self.register_map(other, T0, **register_kw), which scores `other`'s
+        nodes as Gaussians.  merge_from(other, pose=result["T"]) follows.  Returns (the registration's result, merge_from's tallies)."""
+        if method not in ("means", "d2d"):
+            raise ValueError("stitch: method is 'means' or 'd2d'")
+        if method == "d2d":
+            if np.asarray(T0).ndim != 2:
+                raise ValueError("stitch takes one start pose")
+            result = self.register_map(other, T0, **register_kw)
+            return result, self.merge_from(other, pose=result["T"], stream=register_kw.get("stream"))
         import torch
         cells = other.export_device()
         if cells["num_nodes"] == 0:

@@ -808,6 +808,59 @@ typedef struct gndt_merge_stats {
 int gndt_merge_map_device(gndt_handle* dst, gndt_handle* src, const double pose[12], const gndt_merge_params* params,
                           gndt_merge_stats* stats, void* hip_stream);
 
+/* ---- map-to-map scoring: how well one map's nodes fit another map at each of K poses, with derivatives ------------------------
+ * Distribution-to-distribution NDT (Stoyanov et al., IJRR 2012): every source node is scored as a Gaussian against the destination
+ * Gaussians it lands on; the covariance of the difference is the sum of the two covariances, the source's rotated by the pose.  What
+ * a registration of a submap, another robot's map or an earlier session's map needs when the points are gone (a map grown by
+ * gndt_update*, cropped, cleared or merged), and per source node the nearest destination Gaussian and its distance: what is in this
+ * submap that the map does not explain.
+ * Two handles on one device: `dst` is the map scored against, `src` supplies the nodes; both are only read and src == dst is allowed.
+ * K poses, each row-major 3 x 4 doubles [R | t], dst <- src (nothing checks that R is a rotation).
+ * The score is a DEFINITION (tests restate it in numpy).  A source row COUNTS when it has statistics (GNDT_FLAG_HAS_STATS) and its
+ * count >= min_count; the same min_count gates the destination candidates.  For pose k and counted source row r with count c_s, mean
+ * m_s (fp32) and scatter S_s (fp32, gndt_cells.cov, un-normalised):
+ *   1. q = fl32(T m_s): "scan scoring"'s step 1 to the bit, and its steps 2 and 3 give q's key and the candidates in `dst`
+ *      (GNDT_SCORE_DIRECT1 / GNDT_SCORE_DIRECT7, the same candidate order).
+ *   2. source covariance, fp64: C_s = S_s * (1 / (c_s - 1)) entry-wise; Sigma = R C_s R^T in the shape of "map merge"'s step 5:
+ *      W_ib = (R_i0 C_0b + R_i1 C_1b) + R_i2 C_2b, Sigma_ij = (W_i0 R_j0 + W_i1 R_j1) + W_i2 R_j2, i <= j.
+ *   3. per counted candidate with c_d, m_d, S_d: C_d = S_d * (1 / (c_d - 1)), P = Sigma + C_d (six values);
+ *      eps = max(cov_rel * (((P_xx + P_yy) + P_zz) / 3), cov_floor), A = P + eps I; cofactors, det, d = q - m_d, u and d2 exactly in
+ *      "scan scoring"'s order; term = exp(-d2 / 2); with max_d2 > 0 a candidate whose d2 > max_d2 does not count.  With cov_rel = 0.01
+ *      the condition number of A is at most 301; with Sigma = 0 the term has scan scoring's bits.
+ *   4. per pose: score, d2_sum, terms, and matched = counted source rows with at least one term (a gndt_pose_score).
+ *   5. per source row, optional, for the one pose `point_pose` of the parameters (read as the node pose): the least d2 as fp32 and
+ *      that destination row; +inf / GNDT_NO_ROW when the row has no term (equal d2: the lower row); NaN / GNDT_NO_ROW for a source row
+ *      that does not count.
+ * Derivatives are those of the FROZEN sum, as in "scan score derivatives": the candidate set found at the pose is kept, eps is kept, q
+ * is a real vector.  The left perturbation xi = (v, w) acts on both moments:
+ *     q(xi) = Exp([w]x) q + v,        A(xi) = Exp([w]x) Sigma Exp([w]x)^T + C_d + eps I.
+ * With G_a = [e_a]x, B = A^-1, ub = B d, e = exp(-d2 / 2) and a = 0 .. 5: d_a = e_a (translations), e_a x q (rotations); A_a = 0
+ * (translations), G_a Sigma + Sigma G_a^T (rotations); r_a = d_a - A_a ub; phi_a = 2 ub . d_a - ub^T A_a ub;
+ * phi_ab = 2 r_a^T B r_b, plus for two rotations 2 ub . (G_ab q) - ub^T A_ab ub with G_ab = (G_a G_b + G_b G_a) / 2 (so
+ * G_ab q = (e_a q_b + e_b q_a) / 2 - delta_ab q) and A_ab = G_a Sigma G_b^T + G_b Sigma G_a^T + G_ab Sigma + Sigma G_ab^T; then
+ *     g_a = sum over the pairs of -e phi_a / 2,        H_ab = sum over the pairs of e (phi_a phi_b / 4 - phi_ab / 2).
+ * grid_ndt_amd/csrc/gndt_score_maps.hpp states the evaluation order of Sigma, P, r_a, phi_a, phi_ab and the 6 + 21 values.  The record
+ * is gndt_pose_derivs; its first four fields are EXACTLY the bits the score-only call gives.
+ * Parameters are gndt_score_params with "scan scoring"'s defaults, except min_count: 0 = max(dst's min_points, src's min_points, 3),
+ * and a value of 1 or 2 or below either handle's min_points is refused.
+ * Reproducible to the bit by the score's rules: one thread per (source row, pose), the rows in row order, every row, counted or not,
+ * keeping its slot (the tile of row r is r / 256), the score's fixed tree per tile, a pose's tiles in tile order, no floating-point
+ * atomics; pose k of a batch has the bits of a single-pose call, on any stream.
+ * Order and lifetime are gndt_score_poses_device's: the call first finishes what gndt_sync finishes on both handles, builds or reuses
+ * dst's column index, enqueues on `hip_stream` (NULL = dst's stream) and does not wait; later work on either handle is ordered behind
+ * it.  It works on every map that has rows (PARTITION-built ones too); a sharded map answers from the rows this rank holds.  There is
+ * no CPU path and no host-memory variant: both maps live on the device.  No source rows with K > 0 writes K zeroed records; K == 0
+ * launches nothing.
+ * GNDT_ERR_INVALID: a null handle or params, handles on different devices, null poses or out with K > 0, K > 65535, an unknown
+ * neighbourhood, point_pose >= K when a per-node output is asked for, the min_count rule above, a negative or non-finite cov_rel,
+ * cov_floor or max_d2, no finished build in either handle, a stream under hipGraph capture (a score is not recorded; the capture
+ * goes on). */
+/* Device poses ([K][12] doubles), records ([K]) and per-node outputs ([src's rows] each, either may be NULL). */
+int gndt_score_maps_device(gndt_handle* dst, gndt_handle* src, const double* poses_dev, uint32_t K, const gndt_score_params* params,
+                           gndt_pose_score* out_dev, float* node_d2_dev, uint32_t* node_row_dev, void* hip_stream);
+int gndt_score_maps_derivs_device(gndt_handle* dst, gndt_handle* src, const double* poses_dev, uint32_t K, const gndt_score_params* params,
+                                  gndt_pose_derivs* out_dev, void* hip_stream);
+
 /* ---- input side ---------------------------------------------------------
  * Where x, y, z sit inside one raw point record: sensor_msgs::PointCloud2 fields / point_step, the records of a
  * binary .pcd, or pcl::PointXYZ itself (step 16, offsets 0, 4, 8).  Offsets are multiples of 4. */
