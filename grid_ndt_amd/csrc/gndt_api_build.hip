@@ -978,6 +978,15 @@ int gndt_debug_second_pass_buckets(gndt_handle* h, uint64_t* buckets) {
     return GNDT_OK;
 }
 
+int gndt_debug_block_layout(gndt_handle* h, int32_t out[10]) {
+    if (!h || !out) return GNDT_ERR_INVALID;
+    const auto& q = h->part;
+    const BlockMap& K = q.blk_map;
+    const int32_t v[10] = {q.blk_state, K.x0, K.y0, K.z0, K.shx, K.shy, K.shz, K.nx, K.ny, (int32_t)q.blk_buckets};
+    for (int k = 0; k < 10; ++k) out[k] = v[k];
+    return GNDT_OK;
+}
+
 int gndt_debug_enable_stamps(int on) { tuning_force_stamps(on != 0); return GNDT_OK; }
 int gndt_debug_set_option(int option, double value) { return tuning_set_option(option, value); }
 

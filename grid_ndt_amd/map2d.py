@@ -484,6 +484,15 @@ class TwoDmap:
         self._check(self._L.gndt_debug_retry_count(self._h, C.byref(r)))
         return int(r.value)
 
+    BLOCK_LAYOUT_FIELDS = ("state", "x0", "y0", "z0", "shx", "shy", "shz", "nx", "ny", "buckets")
+
+    def block_layout(self):
+        """gndt_debug_block_layout: the block layout the handle holds for blocked buckets (state 1: the next cloud of this size
+        takes them; x0, y0, z0 in contiguous indices; shx, shy, shz = log2 of a block's columns along x, y and its levels)."""
+        arr = (C.c_int32 * 10)()
+        self._check(self._L.gndt_debug_block_layout(self._h, arr))
+        return dict(zip(self.BLOCK_LAYOUT_FIELDS, (int(v) for v in arr)))
+
     def enable_stamps(self, on=True):
         self._L.gndt_debug_enable_stamps(int(bool(on)))
 

@@ -962,6 +962,12 @@ int gndt_debug_fp_clashes(gndt_handle* h, uint64_t* buckets);
 /* Buckets of the last resolved PARTITION build whose 512-slot LDS table overflowed and that were done again by the bucket kernel's
  * second pass (1024-slot tables, those buckets only) instead of the whole build being re-run (gndt_debug_retry_count). */
 int gndt_debug_second_pass_buckets(gndt_handle* h, uint64_t* buckets);
+/* The block layout the handle holds for BLOCKED buckets (GNDT_STRATEGY_PARTITION_BLOCKED), as the last resolved build decided it; waits
+ * for nothing and changes nothing.  out[0] = state (0: not looked at yet, 1: the next cloud of this size takes blocked buckets, -1: it
+ * does not), out[1..3] = smallest contiguous index of the box on x, y, z (c = s > 0 ? s - 1 : s of a signed index s; the block of margin
+ * and the level padding included), out[4..6] = log2 of a block's extent in columns along x, columns along y and levels (they sum to 9),
+ * out[7..8] = blocks along x and y, out[9] = buckets (out[7] * out[8]).  out[1..9] mean something only while out[0] == 1. */
+int gndt_debug_block_layout(gndt_handle* h, int32_t out[10]);
 /* Tests of the sharded builds: the next allocation at `site` on this handle fails once, as if the device were out of memory —
  * 1: the receive buffer of gndt_build_owned_device's exchange, 2: its column-pair buffers, 3: the buffers of
  * gndt_gather_owned_map_device, 4: the fixed-size message buffers of a communicator's first owned build (0: none).  Every rank

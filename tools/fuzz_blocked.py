@@ -30,7 +30,7 @@ def main():
         gl = float(rng.choice([0.1, 0.25, 0.5, 1.0]))
         zl = float(rng.choice([0.1, 0.25, 0.5, 1.0]))
         cols = int(rng.integers(60, 420))                      # columns along x (and about as many along y)
-        levels = float(rng.choice([1.5, 3.0, 5.0, 9.0, 20.0, 40.0]))
+        levels = float(rng.choice([0.4, 1.5, 3.0, 5.0, 9.0, 20.0, 40.0]))     # (0.4: a map of one level, or two about the origin)
         per_col = float(rng.choice([6.0, 20.0, 60.0, 150.0]))
         n = int(min(6_000_000, max(1_100_000, cols * cols * per_col)))
         demand = str(rng.choice(["slope", "true"]))
@@ -48,6 +48,7 @@ def main():
             c0[-int(n * 0.1):] = 0.0                           # the converters' zero padding: one node with a tenth of the points
         P = dict(grid_len=gl, z_len=zl, slope_interval=0.08, demand=demand)
         desc = dict(seed=a.seed, case=stats["cases"], cells=(gl, zl), cols=cols, levels=levels, points=n, demand=demand, cloud_seed=s0)
+        m = None
         try:
             m = g.TwoDmap(gl, zl)
             m.setInterval(0.08)
@@ -82,6 +83,10 @@ def main():
             del m
         except Exception as e:                                  # noqa: BLE001
             desc["error"] = repr(e)[:400]
+            try:
+                desc["block_layout"] = m.block_layout() if m is not None else None      # (which block shape the handle held)
+            except Exception as e2:                             # noqa: BLE001
+                desc["block_layout"] = repr(e2)[:200]
             stats["failures"].append(desc)
         stats["cases"] += 1
     stats["seconds"] = a.seconds
