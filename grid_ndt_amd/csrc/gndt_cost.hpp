@@ -418,7 +418,7 @@ struct CostCounters {
     uint32_t pad0, range_error;
     int32_t goal_status;      // 0 flood started, 1 no cell at the goal, 2 no slope at the goal's level
     uint32_t levels;          // layers that held at least one slope
-    uint32_t pad;
+    uint32_t goal_row;        // the row the flood was seeded at (goal_status 0): the planner's goal (gndt_plan.hpp)
     unsigned long long check_pushes;
     uint32_t wg_layers;       // layers walked by the one-workgroup kernel so far: a kernel's layer = the one-layer launches the host
                               //   has enqueued before it (an argument) + this
@@ -443,7 +443,7 @@ static __global__ void __launch_bounds__(256) k_cost_clear(uint32_t* __restrict_
         cc->frontier[0] = cc->frontier[1] = cc->frontier[2] = 0u;
         cc->traversable = cc->closed = cc->pad0 = 0u;
         if (ctab_size) cc->range_error = 0u;       // (k_cost_columns' count travels with the index it built: a kept index keeps it)
-        cc->goal_status = 1; cc->levels = 0u; cc->check_pushes = 0ull;
+        cc->goal_status = 1; cc->levels = 0u; cc->check_pushes = 0ull; cc->goal_row = 0xFFFFFFFFu;
         cc->wg_layers = 0u;
 #if defined(GNDT_COST_STAMPS)
         for (int k = 0; k < 6; ++k) cc->phase[k] = 0ull;
@@ -565,6 +565,7 @@ static __global__ void k_cost_goal(CostView V, int gx, int gy, int gz, uint32_t*
             frontier0[0] = t;
             cc->frontier[0] = 1u;
             cc->goal_status = 0;
+            cc->goal_row = t;
             return;
         }
     }

@@ -10,6 +10,7 @@
 //   gndt_api_crop.hip   region crop: the columns outside (or inside) a box leave the map
 //   gndt_api_clear.hip  free-space clearing: nodes that sensor rays pass through leave the map
 //   gndt_api_score.hip  scan scoring and its derivatives
+//   gndt_api_plan.hip   route planning: A* routes to the flood's goal for a batch of starts
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
@@ -231,6 +232,13 @@ struct gndt_handle {
     struct Cast {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
     } cast;
+    // route planning (gndt_plan.hpp): the queries' per-row state and queue spill, one slot per query of a launch; stamp: the last
+    // launch's (a row's state counts only with the launch's stamp, so nothing is cleared between launches); slot_bytes / rows: the
+    // layout the stamps in the area belong to
+    struct Plan {
+        void* scratch = nullptr;  uint64_t bytes = 0;
+        uint32_t stamp = 0;  uint64_t slot_bytes = 0, rows = 0;
+    } plan;
     // map merge (gndt_merge.hpp): the call's tallies, device and pinned
     struct Merge {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
@@ -386,6 +394,7 @@ struct Tuning {
     bool verbose = false;        // GNDT_DEBUG_VERBOSE      stderr line per resolved two-level build
     bool cost_one_workgroup = true;   // GNDT_DEBUG_COST_ONE_WORKGROUP   0: every layer of the flood its own launch
     int query_ilp = 1;           // GNDT_DEBUG_QUERY_ILP           queries a thread of k_query works on at once (1, 2 or 4)
+    int plan_lds_entries = 1024; // GNDT_DEBUG_PLAN_LDS_ENTRIES    entries of a planning query's open queue kept in LDS (64 .. 1024; the rest spills)
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
 };
@@ -586,5 +595,7 @@ void free_score(gndt_handle* h);
 void free_cast(gndt_handle* h);
 // ---- gndt_api_merge.hip ----
 void free_merge(gndt_handle* h);
+// ---- gndt_api_plan.hip ----
+void free_plan(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PointLayout, RasterLayers, Robot, ScoreParams, Stats
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -513,6 +513,7 @@ class TwoDmap:
         self._check(self._L.gndt_set_deferred_emit(self._h, int(bool(on))))
 
     DEBUG_VERBOSE, DEBUG_TILE_RATIO, DEBUG_COST_ONE_WORKGROUP, DEBUG_QUERY_ILP = 1, 2, 3, 4
+    DEBUG_PLAN_LDS_ENTRIES = 6
 
     @staticmethod
     def set_debug_option(option, value):
@@ -569,6 +570,59 @@ class TwoDmap:
         out = self._cost_stats(st)
         out.update(h=h, state=state.astype(np.uint8))
         return out
+
+    # ---- route planning (gndt_plan_routes*: AstarPlanar::findRoute, GlobalPlan.h:49-166, for a batch of starts) ----
+    ROUTE_STATUS = {0: "found", 1: "no_start", 2: "no_route", 3: "limit", 4: "no_goal"}
+    ROUTE_INFO_DTYPE = np.dtype([("status", np.int32), ("length", np.uint32), ("start_row", np.uint32), ("expansions", np.uint32),
+                                 ("queue_peak", np.uint32), ("cost", np.float32), ("h_start", np.float32), ("reserved", np.uint32)])
+
+    def plan_routes(self, starts, start_mode="node", route_cap=None, max_expansions=0, stream=None, host=False, scratch_bytes=0):
+        """The reference planner's routes from `starts` ([K,3] or [K,4] float32) to the goal of the last computeCost, one device call
+        (include/gndt.h "route planning" defines the answer).  Returns (rows, info): rows [K, route_cap] int32, each route start
+        first and goal last as rows of export(), -1 behind its end.  A route longer than route_cap (None: the map's slope count or 1024,
+        whichever is less) comes back cut to its first route_cap rows with its true length in info["length"]: call again with that;
+        info: dict of [K] arrays status (ROUTE_STATUS), length, start_row (int32, -1: none), expansions, queue_peak, cost, h_start.
+        torch CUDA starts are answered on the device (torch tensors, enqueued on `stream`, default torch's current stream, not awaited);
+        host=True or a host array goes through gndt_plan_routes (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        ptr, K, stride, on_dev, keep = self._as_input(starts)
+        if route_cap is None:
+            route_cap = max(min(int(self.sync()[2]), 1024), 1)
+        route_cap = int(route_cap)
+        prm = PlanParams(self.QUERY_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), int(max_expansions), int(scratch_bytes))
+        if on_dev and host:
+            ptr, K, stride, on_dev, keep = self._as_input(keep.detach().cpu().numpy())
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                rows = torch.empty((K, route_cap), dtype=torch.int32, device=keep.device)
+                raw = torch.empty((K, 8), dtype=torch.int32, device=keep.device)
+            self._check(self._L.gndt_plan_routes_device(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
+                                                        C.c_void_p(rows.data_ptr() if K and route_cap else 0), route_cap,
+                                                        C.c_void_p(raw.data_ptr() if K else 0), _stream_ptr(stream)))
+            info = {"status": raw[:, 0], "length": raw[:, 1], "start_row": raw[:, 2], "expansions": raw[:, 3], "queue_peak": raw[:, 4],
+                    "cost": raw[:, 5].view(torch.float32), "h_start": raw[:, 6].view(torch.float32)}
+            return rows, info
+        rows = np.empty((K, route_cap), np.int32)
+        raw = np.zeros(K, self.ROUTE_INFO_DTYPE)
+        self._check(self._L.gndt_plan_routes(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
+                                             C.c_void_p(rows.ctypes.data if K and route_cap else 0), route_cap,
+                                             C.c_void_p(raw.ctypes.data if K else 0)))
+        info = {k: raw[k] for k in ("status", "length", "expansions", "queue_peak", "cost", "h_start")}
+        info["start_row"] = raw["start_row"].view(np.int32)
+        return rows, info
+
+    def findRoute(self, start):
+        """AstarPlanar::findRoute(start -> the goal of the last computeCost): the route as a list of rows of export(), start slope
+        first and goal slope last, or None ("not find the road", GlobalPlan.h:159-163)."""
+        p = np.asarray(start, np.float32).reshape(1, -1)[:, :3]
+        rows, info = self.plan_routes(p, host=True)
+        if int(info["status"][0]) != 0:
+            return None
+        if int(info["length"][0]) > rows.shape[1]:
+            rows, info = self.plan_routes(p, host=True, route_cap=int(info["length"][0]))
+        return [int(r) for r in rows[0, :int(info["length"][0])]]
 
     # ---- point queries (the lookup of computeCost's goal, map2D.h:1291-1306, and findRoute's start / goal, GlobalPlan.h:56-61) ----
     QUERY_MODES = {"node": 0, "nearest_slope": 1}

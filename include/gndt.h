@@ -392,6 +392,58 @@ int gndt_cost_export_device(gndt_handle* h, const float** h_dev, const uint32_t*
 /* Copies into caller-allocated host arrays of num_nodes elements (NULL arrays skipped). */
 int gndt_cost_export(gndt_handle* h, float* h_out, uint32_t* state_out, gndt_cost_stats* stats);
 
+/* ---- route planning: A* routes to the flood's goal for a batch of starts ---------------------------------
+ * gndt_plan_routes* replaces AstarPlanar::findRoute (include/GlobalPlan.h:49-166; receiver.cpp:172-176, right after computeCost) for K
+ * starts at once, on the device, against the current cost map.  Per start the route is what findRoute returns on a FRESH map (every
+ * slope g = f = FLT_MAX, no father, an empty queue and closed list) whose Slope::h is the cost map — slope for slope, with the
+ * reference's quirks (DESIGN.md §4.3j "Route planning" lists them).  Queries of a batch are independent of each other and of earlier calls.
+ *   start   the row GNDT_QUERY_NODE finds for the point, if it has GNDT_FLAG_SLOPE (GlobalPlan.h:56-64); start_mode
+ *           GNDT_QUERY_NEAREST_SLOPE uses that rule instead.  None: status GNDT_ROUTE_NO_START (a non-finite coordinate, a key out of
+ *           range, no such node, a node without a slope).
+ *   goal    the slope the last gndt_compute_cost seeded.  If that flood's goal_status was not 0, every query gets GNDT_ROUTE_NO_GOAL
+ *           and no search runs.
+ *   robot   the last flood's (AccessibleNeighbors comand 2.5; 4, which also evaluates Slope::countUp, on a demand-"true" handle).
+ * Per query, gndt_route_info: status; length, the slopes of the route (start and goal included; 0 without a route); start_row;
+ * expansions, the slopes popped and expanded (a slope popped again through a stale second queue entry counts again); queue_peak, the
+ * most entries the open queue held; cost, g of the goal (FLT_MAX without a route); h_start, the cost map's h at the start (FLT_MAX
+ * without one).  route_rows[k * route_cap ..]: the route of query k as rows of gndt_cells, START FIRST, GOAL LAST; a route longer than
+ * route_cap writes its first route_cap rows (the caller sees length > route_cap), unused entries are GNDT_NO_ROW.  route_rows may be
+ * NULL with route_cap 0: only the info is written.
+ * The guard: a query that has expanded max_expansions slopes (0 = 4 * num_slopes + 1024) without popping the goal ends with
+ * GNDT_ROUTE_LIMIT and no route — the loop's bound is not obvious and the device is shared.  So does a query whose open queue holds
+ * more than 2 * num_slopes + 1024 live entries at once (its LDS and spill tiers together; the reference's queue is bounded by nothing
+ * but its expansions, which the guard bounds).
+ * Per-query state (g, f, father, closed per row; the queue's spill) lives in a scratch area the handle owns and grows: 16 bytes a row
+ * and 8 a queue entry per query.  Queries that do not fit params->scratch_bytes (0 = 256 MiB) together run in consecutive launches on
+ * the same stream; GNDT_ERR_CAPACITY if a single query does not fit.
+ * Needs a cost map of the current grid (the condition of gndt_cost_export) and the tables its flood kept, which a handle that has
+ * recorded a hipGraph does not keep.  The map, h and state are not modified.  Like queries and casts the call is enqueued and not
+ * awaited (gndt_plan_routes: synchronous), returns GNDT_OK and launches nothing for K == 0, and has no CPU path.
+ * GNDT_ERR_INVALID: a null handle or params, null starts or info with K > 0, K >= 2^31, a stride other than 12 / 16, an unknown
+ * start_mode, a non-zero reserved word, route_rows NULL with route_cap > 0 or the reverse (K > 0), no finished build, no current cost map (none,
+ * or made stale by a build / update / remove / crop since), the flood's tables not kept, a stream under hipGraph capture. */
+enum { GNDT_ROUTE_FOUND = 0, GNDT_ROUTE_NO_START = 1, GNDT_ROUTE_NO_ROUTE = 2, GNDT_ROUTE_LIMIT = 3, GNDT_ROUTE_NO_GOAL = 4 };
+typedef struct gndt_plan_params {
+    int32_t start_mode;       /* GNDT_QUERY_NODE (0, the reference's lookup) or GNDT_QUERY_NEAREST_SLOPE */
+    uint32_t max_expansions;  /* 0 = 4 * num_slopes + 1024 */
+    uint64_t scratch_bytes;   /* 0 = 256 MiB */
+    uint32_t reserved[4];     /* 0 */
+} gndt_plan_params;           /* zeros = defaults */
+typedef struct gndt_route_info {
+    int32_t status;
+    uint32_t length, start_row, expansions, queue_peak;
+    float cost, h_start;
+    uint32_t reserved;
+} gndt_route_info;            /* 32 bytes */
+/* Device memory in and out: starts (stride 12 or 16), route_rows [K * route_cap], info [K]; enqueued on `hip_stream` (NULL = the
+ * handle's stream) and not awaited.  info_dev must be 16-byte aligned (the kernel writes a record as two 16-byte stores; what hipMalloc
+ * returns is): GNDT_ERR_INVALID otherwise.  The host entry point below takes any alignment. */
+int gndt_plan_routes_device(gndt_handle* h, const void* starts_dev, size_t K, size_t stride_bytes, const gndt_plan_params* params,
+                            uint32_t* route_rows_dev, uint32_t route_cap, gndt_route_info* info_dev, void* hip_stream);
+/* Host memory in and out; returns when the answers are in place. */
+int gndt_plan_routes(gndt_handle* h, const void* starts_host, size_t K, size_t stride_bytes, const gndt_plan_params* params,
+                     uint32_t* route_rows_host, uint32_t route_cap, gndt_route_info* info_host);
+
 /* ---- point queries against the finished grid --------------------------------------------------------
  * The lookup the reference writes out wherever a consumer needs the slope at a position:
  *     transMortonXYZ(p) -> map_cell.find(morton_xy) -> map_slope.find(morton_z)
@@ -946,12 +998,15 @@ int gndt_debug_enable_stamps(int on);
  *                                 the narrow layers is not used (tests run the flood both ways)                     default 1
  *   GNDT_DEBUG_QUERY_ILP          independent queries one thread of gndt_query* works on at once: 1, 2 or 4       default 1
  *   GNDT_DEBUG_CLEAR_EXTENT       value == 1: gndt_clear_rays* read the rows of a walked column only if the column's level extent
- *                                 meets the ray's level range (tools/measure_clear.py A/Bs the two; same results)  default 0 */
+ *                                 meets the ray's level range (tools/measure_clear.py A/Bs the two; same results)  default 0
+ *   GNDT_DEBUG_PLAN_LDS_ENTRIES   entries of a planning query's open queue held in LDS, a multiple of 64 in 64 .. 1024; what does
+ *                                 not fit spills to the query's scratch (tests cap it so that a small map spills)  default 1024 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
 #define GNDT_DEBUG_QUERY_ILP 4
 #define GNDT_DEBUG_CLEAR_EXTENT 5
+#define GNDT_DEBUG_PLAN_LDS_ENTRIES 6
 int gndt_debug_set_option(int option, double value);
 /* The bucket kernel finds a node through a 21-bit fingerprint of its key and confirms it with the key itself; a bucket in
  * which a fingerprint named the wrong node (~1 in 10^4) is accumulated a second time with every probe confirmed.  Tests narrow

@@ -437,6 +437,37 @@ public:
     const gndt_cost_stats& costStats() const { return cost_stats; }
     const gndt_cells& exported() const { return host.view; }   // the rows the containers were built from
 
+    // The reference planner's route from `start` to the goal of the last computeCost, found on the device (gndt_plan_routes, gndt.h
+    // "route planning"): its rows, start slope first.  One call; a second one only for a route of more than 4096 slopes.
+    // Returns false on an ABI error (lastError); found == false is the reference's "not find the road".
+    bool planRouteRows(const Vector3f& start, std::vector<uint32_t>& rows, bool& found) {
+        found = false;
+        rows.clear();
+        if (!handle) { last_error = "planRouteRows before create2DMap"; return false; }
+        gndt_plan_params prm{};
+        gndt_route_info info{};
+        uint32_t cap = 4096;
+        for (int pass = 0; pass < 2; ++pass) {
+            rows.assign(cap, GNDT_NO_ROW);
+            const int rc = gndt_plan_routes(handle, start.d, 1, 12, &prm, rows.data(), cap, &info);
+            if (rc != GNDT_OK) { last_error = gndt_last_error(handle); rows.clear(); return false; }
+            if (info.status != GNDT_ROUTE_FOUND) { rows.clear(); return true; }
+            if (info.length <= cap) break;
+            cap = info.length;
+        }
+        rows.resize(info.length);
+        found = true;
+        return true;
+    }
+    // The Slope of result row `row` in either mode (nullptr: the row holds no slope)
+    Slope* slopeOfRow(uint32_t row) {
+        const gndt_cells& c = host.view;
+        if (row >= c.num_nodes || !(c.flags[row] & GNDT_FLAG_SLOPE)) return nullptr;
+        if (lazy_mode) return lazy_slope(row);
+        if (arena.row_slope.size() == c.num_nodes) return arena.row_slope[row];
+        return findSlope(column_key(c.sx[row], c.sy[row]), c.sz[row]);
+    }
+
     // include/map2D.h:523-526
     float TravelCost(const Vector3f& cur, const Vector3f& des, float = 0) const {
         const float dx = cur(0) - des(0), dy = cur(1) - des(1), dz = cur(2) - des(2);
@@ -647,6 +678,24 @@ public:
         }
         if (!route) return false;
         for (Slope* i = global_path.front(); i->father != nullptr; i = global_path.front()) global_path.push_front(i->father);
+        return true;
+    }
+
+    // findRoute on the device: the same route (the planner of gndt.h "route planning" is findRoute's loop, quirks included) from one
+    // gndt_plan_routes call against the map and cost map the handle holds — no containers are walked, so it serves the lazy mode as
+    // well.  global_path and the fathers along it are filled; g and f of the slopes are not.
+    bool findRouteDevice(TwoDmap& map2D) {
+        std::vector<uint32_t> rows;
+        bool found = false;
+        if (!map2D.planRouteRows(start, rows, found) || !found) return false;
+        Slope* prev = nullptr;
+        for (uint32_t row : rows) {
+            Slope* s = map2D.slopeOfRow(row);
+            if (!s) return false;
+            s->father = prev;
+            global_path.push_back(s);
+            prev = s;
+        }
         return true;
     }
 };

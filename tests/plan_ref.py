@@ -1,0 +1,183 @@
+"""Route planning's test scaffolding, shared by the CPU tier (tests/test_plan_host.py) and the GPU tier (tests/test_gpu_plan.py): a map's
+rows with the column index the shared header needs, the header itself run on the host (tests/plan_shim.cpp), the oracle's findRoute
+(oracle.compute_cost(..., start=p)["path"]) with its answers kept per start, and the scenes.  Test infrastructure only."""
+import ctypes as C
+
+import numpy as np
+
+from grid_ndt_amd import scenes
+from tests.host_emulation import HostMap, _pow2_at_least, consumer_shim, load_shim
+
+FOUND, NO_START, NO_ROUTE, LIMIT, NO_GOAL = 0, 1, 2, 3, 4
+NODE, NEAREST_SLOPE = 0, 1
+NO_ROW = 0xFFFFFFFF
+FLT_MAX = np.finfo(np.float32).max
+INFO_DTYPE = np.dtype([("status", np.int32), ("length", np.uint32), ("start_row", np.uint32), ("expansions", np.uint32),
+                       ("queue_peak", np.uint32), ("cost", np.float32), ("h_start", np.float32), ("reserved", np.uint32)])
+ROBOT_DEFAULT = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+
+_shim = None
+
+
+def shim():
+    global _shim
+    if _shim is None:
+        vp, f, u32, u64 = C.c_void_p, C.c_float, C.c_uint32, C.c_uint64
+        _shim = load_shim("plan_shim.cpp", "_plan_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_plan.hpp"), {
+            "planshim_default_expansions": ([u64], u32),
+            "planshim_queue_entries": ([u64], u32),
+            "planshim_routes": ([u64] + [vp] * 10 + [u32, vp, vp, f, f, f, C.c_int, vp, u32, C.c_int, vp, u32, u64, u32, u32, u32, vp, u32, vp, vp],
+                                C.c_int),
+        })
+    return _shim
+
+
+def info_bytes(info):
+    return np.ascontiguousarray(info).view(np.uint8).tobytes()
+
+
+class PlanMap:
+    """Rows of a map (an oracle build or an export of the device's), the flood the oracle runs on them from `goal`, and both planners."""
+
+    def __init__(self, cells, origin, P, goal, robot=None):
+        from oracle import oracle
+        from tests import query_ref as qr
+        self.cells, self.P, self.goal = cells, P, tuple(float(v) for v in goal)
+        self.origin = np.asarray(origin, np.float32)
+        self.robot = dict(ROBOT_DEFAULT)
+        self.robot.update(robot or {})
+        self.n = int(cells["num_nodes"])
+        f32, i32, u32 = np.float32, np.int32, np.uint32
+        self.sx, self.sy, self.sz = (np.ascontiguousarray(cells[k], i32) for k in ("sx", "sy", "sz"))
+        self.mean, self.normal = np.ascontiguousarray(cells["mean"], f32), np.ascontiguousarray(cells["normal"], f32)
+        self.rough, self.flags = np.ascontiguousarray(cells["rough"], f32), np.ascontiguousarray(cells["flags"], u32)
+        self.row_ncol = qr.row_ncol(cells)
+        self.tsize = _pow2_at_least(2 * int((self.row_ncol > 0).sum()))
+        self.ctab_key, self.ctab_val = np.zeros(self.tsize, np.uint64), np.zeros(self.tsize, u32)
+        consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
+                                    self.ctab_val.ctypes.data, self.tsize)
+        self.slopes = np.flatnonzero(self.flags & 2)
+        self._oracle = oracle
+        self.paths = {}
+        flood = self._flood()
+        self.rc, self.h, self.state = flood["rc"], np.ascontiguousarray(flood["h"], f32), flood["state"]
+        # the goal's row: the one slope the flood leaves at h == 0 with state != 0 is its seed (travel costs are > 0)
+        seeds = np.flatnonzero((self.h == 0) & (self.state != 0)) if self.rc == 0 else []
+        assert self.rc != 0 or len(seeds) == 1
+        self.goal_row = int(seeds[0]) if self.rc == 0 else NO_ROW
+
+    def _flood(self, start=None):
+        P = self.P
+        return self._oracle.compute_cost(self.cells, self.origin, P["grid_len"], P["z_len"], P["slope_interval"], self.goal,
+                                         demand=P.get("demand", "slope"), robot=self.robot, start=start)
+
+    def start_points(self, rows):
+        """a point per row that the NODE rule sends back to the row: the row's centroid"""
+        return np.ascontiguousarray(self.mean[np.asarray(rows, np.int64)], np.float32)
+
+    def oracle_route(self, point):
+        """AstarPlanar::findRoute from `point` on a fresh map -> list of rows (empty: no route); kept per point"""
+        key = tuple(np.asarray(point, np.float32)[:3].tolist())
+        if key not in self.paths:
+            self.paths[key] = [int(r) for r in self._flood(start=key)["path"]]
+        return self.paths[key]
+
+    def shim_routes(self, starts, mode=NODE, max_expansions=0, lds_entries=1024, queue_entries=0, route_cap=None, h=None):
+        """plan_query over every start as the kernel's wavefronts run it -> (rows [K, route_cap] uint32, info [K], tally [K, 2]:
+        pops of slopes that were already closed, entries that went in below the popped key)"""
+        starts = np.ascontiguousarray(starts, np.float32)
+        K = len(starts)
+        cap = self.n if route_cap is None else int(route_cap)
+        rows = np.full((max(K, 1), max(cap, 1)), 0xDEADBEEF, np.uint32)
+        info = np.zeros(max(K, 1), INFO_DTYPE)
+        re = np.zeros((max(K, 1), 2), np.uint32)
+        hb = np.ascontiguousarray(self.h if h is None else h, np.float32).view(np.uint32)
+        P, rb = self.P, self.robot
+        r4 = np.float32([rb["radius"], rb["reachable_height"], rb["max_rough"], rb["max_angle_deg"]])
+        rc = shim().planshim_routes(self.n, self.sx.ctypes.data, self.sy.ctypes.data, self.sz.ctypes.data, self.mean.ctypes.data,
+                                    self.normal.ctypes.data, self.rough.ctypes.data, self.flags.ctypes.data, self.row_ncol.ctypes.data,
+                                    self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize, hb.ctypes.data, self.origin.ctypes.data,
+                                    P["grid_len"], P["z_len"], P["slope_interval"], 1 if P.get("demand", "slope") == "true" else 0,
+                                    r4.ctypes.data, self.goal_row, mode, starts.ctypes.data, starts.shape[1] if K else 3, K, max_expansions,
+                                    lds_entries, queue_entries, rows.ctypes.data if cap else None, cap, info.ctypes.data, re.ctypes.data)
+        assert rc == 0
+        return rows[:K, :cap] if cap else rows[:K, :0], info[:K], re[:K]
+
+
+def route_of(rows, info, k):
+    """query k's route as a list of rows (None without one)"""
+    if info["status"][k] != FOUND:
+        return None
+    n = int(info["length"][k])
+    assert n <= rows.shape[1]
+    assert (rows[k, n:] == NO_ROW).all()
+    return [int(r) for r in rows[k, :n]]
+
+
+def host_map(cloud, P, goal, robot=None):
+    m = HostMap(cloud, P)
+    return PlanMap(m.cells, m.origin, P, goal, robot)
+
+
+# ---- scenes ------------------------------------------------------------------------------------------------------------------
+FLOOR_P = dict(grid_len=0.5, z_len=0.25, slope_interval=0.08, demand="slope")
+FLOOR_ORIGIN = np.float32([0.013, -0.021, 0.05])
+FLOOR_N = 40
+FLOOR_GOAL = (1 * 0.5 + 0.25, 2 * 0.5 + 0.25, 0.06)
+FLOOR_ROBOT = dict(radius=0.2)
+
+
+def floor_cloud(n=FLOOR_N):
+    """n x n cells of flat floor, 9 points per cell with the ripple of tests/test_planner_hand_routes.py's corridors"""
+    from tests.test_planner_hand_routes import _cells_to_cloud
+    return _cells_to_cloud([(ix, iy) for ix in range(n) for iy in range(n)])
+
+
+def find_bare_point(pm, cloud, query):
+    """a point of the cloud whose node (query(points) -> rows, the NODE rule) holds no slope"""
+    pts = np.ascontiguousarray(cloud[1::37, :3], np.float32)
+    rows = np.asarray(query(pts)).astype(np.int64)
+    ok = np.flatnonzero((rows >= 0) & ((pm.flags[np.maximum(rows, 0)] & 2) == 0))
+    assert len(ok)
+    return pts[ok[0]]
+
+
+def site_starts(pm, n_each=24, bare_point=None):
+    """The drivable site's starts: n_each traversable slopes, every closed slope, n_each unreached slopes, the goal itself, a point off
+    the map, a NaN point, a point in a node without a slope -> (points [K, 3], kinds [K])"""
+    pick = lambda rows: rows[np.linspace(0, len(rows) - 1, min(n_each, len(rows))).astype(np.int64)]
+    slope = (pm.flags & 2) != 0
+    trav = pick(np.flatnonzero(slope & (pm.state == 1) & (np.arange(pm.n) != pm.goal_row)))
+    closed = np.flatnonzero(slope & (pm.state == 2))
+    unreached = pick(np.flatnonzero(slope & (pm.state == 0)))
+    pts = [pm.start_points(trav), pm.start_points(closed), pm.start_points(unreached), pm.start_points([pm.goal_row]),
+           np.float32([[1.0e4, -1.0e4, 0.0]]), np.float32([[np.nan, 0.0, 0.0]]), np.float32(bare_point).reshape(1, 3)]
+    kinds = ["trav"] * len(trav) + ["closed"] * len(closed) + ["unreached"] * len(unreached) + ["goal", "off", "nan", "bare"]
+    return np.concatenate(pts).astype(np.float32), np.array(kinds)
+
+
+def oracle_sample(kinds, most=65):
+    """the queries whose routes are compared with the oracle's (a flood and a search each): every traversable start, the goal and the
+    three startless points, and evenly spread closed and unreached ones up to `most` in all"""
+    always = np.flatnonzero(np.isin(kinds, ("trav", "goal", "off", "nan", "bare")))
+    closed, unreached = np.flatnonzero(kinds == "closed"), np.flatnonzero(kinds == "unreached")
+    room = most - len(always)
+    n_un = min(len(unreached), 8)
+    n_cl = min(len(closed), room - n_un)
+    spread = lambda idx, n: idx[np.linspace(0, len(idx) - 1, n).astype(np.int64)] if n > 0 else idx[:0]
+    return np.concatenate([always, spread(closed, n_cl), spread(unreached, n_un)])
+
+
+SITE_RUNS = {"r025": ("slope", 0.25), "r06": ("slope", 0.6), "true": ("true", 0.25)}
+
+# bridge_ground: the deck (z = 3) spans x 5..11, y 1..5 over the ground (z = 1); both goals sit in the column at (8.02, 3.02)
+BRIDGE_GOALS = {"deck": (8.02, 3.02, 3.0), "under": (8.02, 3.02, 1.0)}
+
+
+def bridge_start_rows(pm, n=30):
+    """n traversable slopes spread over the flood of the goal, and the 392nd of 500 spread the same way: from there (goal on the deck,
+    the oracle's rows) a neighbour enters the queue BELOW the key of the slope being expanded, and the front-run test of the
+    neighbours after it has to start from that entry"""
+    trav = np.flatnonzero(((pm.flags & 2) != 0) & (pm.state == 1) & (np.arange(pm.n) != pm.goal_row))
+    spread = lambda k: trav[np.linspace(0, len(trav) - 1, k).astype(np.int64)]
+    return np.concatenate([spread(n), spread(500)[392:393]])
