@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "gndt_bucket3.hpp"
+#include "gndt_stream.hpp"
 
 namespace gndt {
 
@@ -100,7 +101,7 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         for (int j = 0; j < kBlkPer; ++j) rec[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (lo < hi) {
 #pragma unroll
-            for (int j = 0; j < kBlkPer; ++j) rec[j] = recs[min(lo + (uint32_t)(j * T + tid), hi - 1u)];
+            for (int j = 0; j < kBlkPer; ++j) rec[j] = load_once(recs + min(lo + (uint32_t)(j * T + tid), hi - 1u));      // (gndt_stream.hpp: the staging rows stay cached, not the records)
         }
         for (uint32_t ch = 0; ch < n_chunks; ++ch) {
             const uint32_t par = ch & 1u, c0 = lo + ch * kBlkChunk;
@@ -153,7 +154,7 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
                 // the next chunk's records: in flight during the walk
                 if (ch + 1u < n_chunks) {
 #pragma unroll
-                    for (int j = 0; j < kBlkPer; ++j) rec[j] = recs[min(c0 + kBlkChunk + (uint32_t)(j * T + tid), hi - 1u)];
+                    for (int j = 0; j < kBlkPer; ++j) rec[j] = load_once(recs + min(c0 + kBlkChunk + (uint32_t)(j * T + tid), hi - 1u));
                 }
                 lds_barrier();
                 // slot s's run: today's contributions (weighted records included), added in the image's order

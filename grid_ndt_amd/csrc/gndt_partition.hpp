@@ -30,6 +30,7 @@
 #include <type_traits>
 
 #include "gndt_kernels.hpp"
+#include "gndt_stream.hpp"
 
 namespace gndt {
 
@@ -732,7 +733,7 @@ __global__ void __launch_bounds__(kTileThreads) k_part2_level2(const float4* __r
         const uint32_t i = t0 + (uint32_t)j * kTileThreads + threadIdx.x;
         dig[j] = 0xFFFFFFFFu;
         if (i < have) {
-            r[j] = src[i];
+            r[j] = load_once(src + i);                    // (recs1 is done with: what stays in the last-level cache is recs2, for the bucket kernel)
             int sx, sy;
             bool kok;
             column_of_point(r[j].x, r[j].y, P, sx, sy, kok);
