@@ -363,6 +363,7 @@ void gndt_destroy(gndt_handle* h) {
     free_cast(h);
     free_merge(h);
     free_plan(h);
+    free_frontier(h);
     for (const RowArray& a : row_arrays(h->out))
         if (*a.p) (void)hipFree(*a.p);
     void* ptrs[] = {h->st_key, h->st_sums, h->st_count, h->st_first, h->stage, h->d_cnt, h->packed, h->d_nvalid, h->index.buf, h->io};

@@ -11,6 +11,7 @@
 //   gndt_api_clear.hip  free-space clearing: nodes that sensor rays pass through leave the map
 //   gndt_api_score.hip  scan scoring and its derivatives
 //   gndt_api_plan.hip   route planning: A* routes to the flood's goal for a batch of starts
+//   gndt_api_frontier.hip  frontier extraction: the slopes where the map ends, clustered
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
@@ -239,6 +240,11 @@ struct gndt_handle {
         void* scratch = nullptr;  uint64_t bytes = 0;
         uint32_t stamp = 0;  uint64_t slot_bytes = 0, rows = 0;
     } plan;
+    // frontier extraction (gndt_frontier.hpp): per row its parent in the union-find (4 B), its root's member count, then place in the
+    // list (4 B) and its open sides (1 B), and three counts per tile of rows; grown on demand
+    struct Frontier {
+        void* scratch = nullptr;  uint64_t bytes = 0;
+    } frontier;
     // map merge (gndt_merge.hpp): the call's tallies, device and pinned
     struct Merge {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
@@ -597,5 +603,7 @@ void free_cast(gndt_handle* h);
 void free_merge(gndt_handle* h);
 // ---- gndt_api_plan.hip ----
 void free_plan(gndt_handle* h);
+// ---- gndt_api_frontier.hip ----
+void free_frontier(gndt_handle* h);
 
 }  // namespace gndt_host

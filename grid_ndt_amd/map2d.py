@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -719,6 +719,102 @@ class TwoDmap:
         out.update(x0=_column_centre(self.cloudFirst[0], self.gridLen, sx0), y0=_column_centre(self.cloudFirst[1], self.gridLen, sy0),
                    res=self.gridLen)
         return out
+
+    # ---- frontier extraction (gndt_frontiers*: the slopes where the known map ends, clustered on the device) ----
+    FRONTIER_CANDIDATES = {"reached": 0, "slopes": 1}
+    FRONTIER_OPEN_RULES = {"column": 0, "level": 1}
+    FRONTIER_DTYPE = np.dtype([("label", np.int32), ("size", np.int32), ("best_row", np.int32), ("best_h", np.float32),
+                               ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
+                               ("sum_px", np.int64), ("sum_py", np.int64), ("sum_pz", np.int64), ("open_sides", np.int32), ("reserved", np.int32)])
+
+    def frontiers(self, candidates="reached", open_rule="column", level_reach=1, min_open=1, link_dz=1, min_size=1, box=None, labels=False,
+                  max_clusters=None, stream=None, host=False):
+        """Where the known map ends, as clusters (include/gndt.h "frontier extraction" defines every word).  A frontier row is a slope —
+        candidates "reached": one the last computeCost expanded; "slopes": any — with at least min_open of its four sides open:
+        open_rule "column": no such column in the map; "level": or no node of it within level_reach levels.  Frontier rows in
+        8-adjacent columns at most link_dz levels apart form a cluster.  Returns a dict with one [K] array per field of gndt_frontier
+        (label, size, best_row, best_h, sx_min, sx_max, sy_min, sy_max, sum_px, sum_py, sum_pz, open_sides) for the clusters of at
+        least min_size rows in ascending label, `counts` ([4]: those clusters, frontier rows, clusters of any size, 0) and, with
+        labels=True, `labels` (int32 per row of export(): its cluster's label, -1 for a row that is no frontier row).  box: an inclusive
+        box of signed column indices (sx_min, sx_max, sy_min, sy_max), None = the whole map.  max_clusters=None sizes the list from a
+        count-only first call (which waits for it on `stream`); a number is the list's capacity — counts[0] may exceed it.  Torch
+        tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited: the arrays then have
+        max_clusters entries, filled from the front, with size 0 behind the counts[0] the call found.  Or numpy arrays through
+        gndt_frontiers with host=True, cut to min(counts[0], max_clusters) entries."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        prm = FrontierParams(self.FRONTIER_CANDIDATES[candidates] if isinstance(candidates, str) else int(candidates),
+                             self.FRONTIER_OPEN_RULES[open_rule] if isinstance(open_rule, str) else int(open_rule),
+                             int(level_reach), int(min_open), int(link_dz), int(min_size))
+        b = C.byref(CropBox(*[int(v) for v in box])) if box is not None else None
+        n = int(self.sync()[0]) if labels else 0
+        if host:
+            counts = np.zeros(4, np.uint32)
+            label = np.empty(n, np.int32) if labels else None
+            call = lambda recs, cap: self._check(self._L.gndt_frontiers(
+                self._h, b, C.byref(prm), C.c_void_p(label.ctypes.data if labels and n else 0),
+                C.c_void_p(recs.ctypes.data if cap else 0), cap, C.c_void_p(counts.ctypes.data)))
+            if max_clusters is None:
+                call(None, 0)
+                max_clusters = int(counts[0])
+            recs = np.zeros(int(max_clusters), self.FRONTIER_DTYPE)
+            call(recs, len(recs))
+            recs = recs[:min(int(counts[0]), len(recs))]
+            out = {k: recs[k] for k in self.FRONTIER_DTYPE.names if k != "reserved"}
+        else:
+            import torch
+            dev = f"cuda:{self.device}"
+            with _torch_stream_ctx(stream):
+                counts = torch.zeros(4, dtype=torch.int32, device=dev)
+                label = torch.empty(n, dtype=torch.int32, device=dev) if labels else None
+            call = lambda recs, cap: self._check(self._L.gndt_frontiers_device(
+                self._h, b, C.byref(prm), C.c_void_p(label.data_ptr() if labels and n else 0),
+                C.c_void_p(recs.data_ptr() if cap else 0), cap, C.c_void_p(counts.data_ptr()), _stream_ptr(stream)))
+            if max_clusters is None:
+                call(None, 0)
+                with _torch_stream_ctx(stream):         # (read on the stream the count was enqueued on: the copy waits for it)
+                    max_clusters = int(counts[0].item())
+            with _torch_stream_ctx(stream):
+                recs = torch.zeros((int(max_clusters), 16), dtype=torch.int32, device=dev)
+            call(recs, recs.shape[0])
+            wide = recs.view(torch.int64)
+            out = {"label": recs[:, 0], "size": recs[:, 1], "best_row": recs[:, 2], "best_h": recs[:, 3].view(torch.float32),
+                   "sx_min": recs[:, 4], "sx_max": recs[:, 5], "sy_min": recs[:, 6], "sy_max": recs[:, 7],
+                   "sum_px": wide[:, 4], "sum_py": wide[:, 5], "sum_pz": wide[:, 6], "open_sides": recs[:, 14]}
+        out["counts"] = counts
+        if labels:
+            out["labels"] = label
+        return out
+
+    def frontier_points(self, fr, which="best"):
+        """World points [K, 3] float32 of the clusters of frontiers(), ready for plan_routes(..., start_mode="nearest_slope"): which
+        "best": the centre of the node of each cluster's best_row; "centroid": the clusters' mean position, sum_p* / size.  A column's
+        centre is origin + (lin(s) + 0.5) * grid_len with lin(s) = s - 1 for s > 0, s otherwise; the same for z with z_len.  An entry
+        of size 0 (behind the clusters found, in a list with room to spare) gives NaN, which the planner answers with "no start".
+        Torch in, torch out (best rows are looked up in export_device()); numpy in, numpy out (export())."""
+        if which not in ("best", "centroid"):
+            raise ValueError('which must be "best" or "centroid"')
+        on_dev = not isinstance(fr["size"], np.ndarray)
+        K = int(fr["size"].shape[0])
+        xp = np
+        if on_dev:
+            import torch as xp
+        if which == "centroid":
+            size = fr["size"].clip(1, None)
+            lin = [(fr[k].double() if on_dev else fr[k].astype(np.float64)) / size for k in ("sum_px", "sum_py", "sum_pz")]
+        else:
+            cells = self.export_device() if on_dev else self.export()
+            rows = fr["best_row"].long() if on_dev else fr["best_row"].astype(np.int64)
+            if K == 0 or int(cells["num_nodes"]) == 0:
+                return xp.zeros((0, 3), dtype=xp.float32, **({"device": fr["size"].device} if on_dev else {}))
+            s = [cells[k][rows] for k in ("sx", "sy", "sz")]
+            lin = [(v - (v > 0).to(v.dtype) if on_dev else v - (v > 0)) for v in s]
+            lin = [v.double() if on_dev else v.astype(np.float64) for v in lin]
+        o, steps = self.cloudFirst, (self.gridLen, self.gridLen, self.zLen)
+        cols = [o[a] + (lin[a] + 0.5) * steps[a] for a in range(3)]
+        pts = xp.stack(cols, 1).float() if on_dev else np.stack(cols, 1).astype(np.float32)
+        pts[fr["size"] == 0] = float("nan")
+        return pts
 
     # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
     CLEAR_PROTECTED = 0x80000000

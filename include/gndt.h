@@ -554,6 +554,69 @@ int gndt_raster_device(gndt_handle* h, const gndt_crop_box* box, int32_t mode, f
 /* Host layers, through a device scratch the handle owns and grows; synchronous. */
 int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_ref, const gndt_raster_layers* out_host);
 
+/* ---- frontier extraction: the slopes where the known map ends, clustered on the device --------------------------------------
+ * What an explorer, a coverage planner or a "map is complete" check asks between a flood and a planning call: where does the map end,
+ * and which of those places can the robot drive to?  The answer is a list of clusters whose best rows are ready to be planned to
+ * (gndt_plan_routes*, start_mode GNDT_QUERY_NEAREST_SLOPE at the rows' column centres).  The map cannot tell "unknown" from "seen
+ * empty": a frontier here is where the map ends.  Every definition is integer or bit-pattern arithmetic: the answer is exact and does
+ * not depend on the order threads work in.  lin(s) = s > 0 ? s - 1 : s is the position of a signed index on a line without the hole
+ * at 0 (signed indices skip 0 on all three axes).
+ *   candidate     a row with GNDT_FLAG_SLOPE, inside `box` (NULL = the whole map), and
+ *                   GNDT_FRONTIER_REACHED  with cost-map state 1 (the flood expanded it); needs a cost map of the current grid (the
+ *                                          rule of gndt_cost_export);
+ *                   GNDT_FRONTIER_SLOPES   nothing more; no cost map is read and best_h is FLT_MAX.
+ *   open side     one of the row's four neighbour columns (sx -+ 1, sy), (sx, sy -+ 1), stepping over 0, that
+ *                   GNDT_FRONTIER_OPEN_COLUMN  is not in the map (an index beyond the codec's +-65535 is not);
+ *                   GNDT_FRONTIER_OPEN_LEVEL   is not in the map or holds no node (ANY node: map_xy's view) with
+ *                                              |lin(sz_n) - lin(sz)| <= level_reach: on a two-storey map the deck's edge over the
+ *                                              ground is then a frontier of the deck.
+ *   frontier row  a candidate with at least min_open (1..4; 0 = 1) open sides.
+ *   link          two frontier rows whose columns are 8-adjacent (|lin(sx_a) - lin(sx_b)| <= 1 and |lin(sy_a) - lin(sy_b)| <= 1, not
+ *                 the same column) with |lin(sz_a) - lin(sz_b)| <= link_dz.  Two slopes of one column are never linked directly.
+ *   cluster       a connected component of the links; its label is its smallest member row.
+ * Outputs: clusters[] holds the clusters with at least min_size members in ascending label, the first cluster_cap of them (nothing is
+ * written beyond those); counts[0] is how many there are — it may exceed cluster_cap, so the caller sees the truncation and can call
+ * again (cluster_cap 0 with clusters NULL only counts) — counts[1] the frontier rows, counts[2] the clusters of any size, counts[3] 0.
+ * label[row] (optional, num_nodes entries) is the row's cluster label, GNDT_NO_ROW for a row that is no frontier row; min_size does not
+ * filter it.  A cluster's record: its label and size, the member with the least cost-map h (a tie going to the smaller row; under
+ * SLOPES that is the label) and that h, the bounds of its columns' signed indices, the sums of lin(sx), lin(sy), lin(sz) over its
+ * members (centroid = sum / size; a column's centre is origin + (lin(s) + 0.5) * grid_len) and the sum of its members' open sides.
+ * Order and lifetime are the point queries': the call first finishes what gndt_sync finishes, builds or reuses the map's column
+ * index and enqueues its kernels on `hip_stream` (NULL = the handle's stream), not awaited; gndt_frontiers is synchronous.  Row
+ * numbers stay valid until the next build, update, remove, crop or reset.  The map, h and state are not modified.  Work memory (9 bytes
+ * a row) belongs to the handle and grows with the map.  A map without rows gives four zero counts.  There is no CPU path.
+ * A sharded map answers from the rows this rank holds: the borders between ranks therefore look open.
+ * GNDT_ERR_INVALID: a null handle, params or counts, unknown candidates / open_rule, min_open > 4, a non-zero reserved word, a bad box
+ * (the raster's rules but its pixel limit: min > max on an axis, an index beyond +-65535, an axis without a non-zero index), clusters
+ * NULL with cluster_cap > 0 or the reverse, a device pointer not aligned as its type is, no finished build, REACHED without a current
+ * cost map, a stream under hipGraph capture (the call is not recorded). */
+enum { GNDT_FRONTIER_REACHED = 0, GNDT_FRONTIER_SLOPES = 1 };
+enum { GNDT_FRONTIER_OPEN_COLUMN = 0, GNDT_FRONTIER_OPEN_LEVEL = 1 };
+typedef struct gndt_frontier_params {
+    int32_t  candidates;     /* GNDT_FRONTIER_REACHED / _SLOPES */
+    int32_t  open_rule;      /* GNDT_FRONTIER_OPEN_COLUMN / _OPEN_LEVEL */
+    uint32_t level_reach;    /* OPEN_LEVEL only */
+    uint32_t min_open;       /* 0 = 1 */
+    uint32_t link_dz;        /* levels, as given (0 = same level only) */
+    uint32_t min_size;       /* clusters with fewer members are left out of the list; 0 = 1 */
+    uint32_t reserved[2];    /* 0 */
+} gndt_frontier_params;
+typedef struct gndt_frontier {      /* 64 bytes */
+    uint32_t label, size;            /* smallest member row; members */
+    uint32_t best_row; float best_h; /* the member with the least cost-map h, a tie going to the smaller row */
+    int32_t  sx_min, sx_max, sy_min, sy_max;
+    int64_t  sum_px, sum_py, sum_pz; /* sums of lin(sx), lin(sy), lin(sz) over the members */
+    uint32_t open_sides;             /* sum of the members' open sides */
+    uint32_t reserved;
+} gndt_frontier;
+/* Device memory out: label_dev [num_nodes] or NULL, clusters_dev [cluster_cap], counts_dev [4]. */
+int gndt_frontiers_device(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* params,
+                          uint32_t* label_dev /* [num_nodes] or NULL */, gndt_frontier* clusters_dev, uint32_t cluster_cap,
+                          uint32_t* counts_dev /* [4] */, void* hip_stream);
+/* Host memory out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_frontiers(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* params,
+                   uint32_t* label_host, gndt_frontier* clusters_host, uint32_t cluster_cap, uint32_t* counts_host);
+
 /* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
  * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
  * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
