@@ -42,6 +42,20 @@ struct BlockedLds {            // 43 KB: three workgroups per CU
     uint32_t n_nodes, n_cols, n_slopes, stage_base, err_range, miss;
 };
 
+// Inclusive add scan over the 64 lanes of a wave without the LDS: four shifts inside each row of 16 lanes (zero fill), then lane 15
+// of rows 0 and 2 into rows 1 and 3, then lane 31 into rows 2 and 3.  Six DPP adds, no wait — against six ds_bpermute_b32 round
+// trips with their address arithmetic for a __shfl_up scan.  FULL wave only: every lane must be active at the call (a lane that is not reads as zero and the sums behind it are wrong).  total = lane 63's value.
+__device__ __forceinline__ uint32_t full_wave_scan_add(uint32_t x, uint32_t& total) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true);       // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, true);       // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, true);       // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, true);       // row_shr:8
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);      // row_bcast:15, rows 1 and 3
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);      // row_bcast:31, rows 2 and 3
+    total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+    return x;
+}
+
 // One workgroup per bucket (the hardware's dynamic scheduling), three resident per CU.  The staging rows of a bucket are reserved with one
 // memory-side atomic whose answer takes ~3 us; to have it in time the bucket's node count is known the moment the accumulate phase
 // ends — every slot's count is in its thread's registers then: a ballot per wave — and the answer travels while the columns are
@@ -133,12 +147,11 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
                 slot_rank[j] = use ? (rs << 16) | atomicAdd(&L.hist[par][rs], 1u) : kBlkNone;
             }
             lds_barrier();
-            {   // exclusive prefix of the slots' counts: by shuffles inside a wave, the wave totals added into the later waves' entries
+            {   // exclusive prefix of the slots' counts: by DPP adds inside a wave (full_wave_scan_add: all 512 threads are here), the wave totals added into the later waves' entries
                 const uint32_t c = L.hist[par][s];
-                uint32_t incl = c;
                 const int lane = tid & 63, wv = tid >> 6;
-                for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += t; }
-                const uint32_t wtot = (uint32_t)__shfl((int)incl, 63, 64);
+                uint32_t wtot;
+                const uint32_t incl = full_wave_scan_add(c, wtot);
                 L.hist[par][s] = incl - c;
                 if (lane > wv && lane < T / 64 && wtot) atomicAdd(&L.wpre[par][lane], wtot);
                 // (the other parity's arrays were last read before the previous chunk's walk: cleared here for the next chunk)
@@ -227,14 +240,13 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
                 }
             }
         }
-        {   // exclusive prefix of the columns' node counts: by shuffles inside a wave; a column of the second wave (blocks of 128
+        {   // exclusive prefix of the columns' node counts: by DPP adds inside a wave; a column of the second wave (blocks of 128
             // columns) adds the first wave's total when it reads its entry
             const uint32_t my_col_nodes = s <= col_mask ? ncol : 0u;
-            uint32_t incl = my_col_nodes;
-            const int lane = tid & 63;
-            for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += t; }
+            uint32_t wtot;
+            const uint32_t incl = full_wave_scan_add(my_col_nodes, wtot);
             if (s <= col_mask) L.cpre[s] = incl - my_col_nodes;
-            if (lane == 63) L.wave_tot[tid >> 6] = incl;
+            if ((tid & 63) == 0) L.wave_tot[tid >> 6] = wtot;
             if (s <= col_mask && my_col_nodes) atomicAdd(&L.n_cols, 1u);
             if (tid == T - 1) L.stage_base = stage_base_reg;      // (the reservation's answer: waited for here, by one thread)
             lds_barrier();
