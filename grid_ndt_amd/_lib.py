@@ -9,7 +9,23 @@ import subprocess
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB_PATH = os.path.join(_CSRC, "libgndt.so")
+# Build variants of the library: None is the product; "poison" is the same sources and flags plus -DGNDT_POISON (gndt_handle.hpp: every
+# device and pinned host allocation filled with a byte before it is handed out), objects in a directory of its own.  A process chooses
+# its variant with the environment variable GNDT_LIB_VARIANT, read HERE (the C library reads no environment variable); unset or
+# empty, everything is the product's: same path, same commands.
+VARIANTS = {None: {"lib": "libgndt.so", "objdir": None, "flags": []},
+            "poison": {"lib": "libgndt_poison.so", "objdir": "obj_poison", "flags": ["-DGNDT_POISON"]}}
+VARIANT = os.environ.get("GNDT_LIB_VARIANT") or None
+if VARIANT not in VARIANTS:
+    raise ImportError(f"GNDT_LIB_VARIANT={VARIANT!r}: the variants are {sorted(v for v in VARIANTS if v)}")
+
+
+def lib_path(variant=None):
+    """Path of a variant's shared library (None or "": the product's libgndt.so)."""
+    return os.path.join(_CSRC, VARIANTS[variant or None]["lib"])
+
+
+LIB_PATH = lib_path(VARIANT)   # what lib() loads in this process
 SOURCES = ["gndt_api_core.hip", "gndt_api_table.hip", "gndt_api_build.hip", "gndt_api_dist.hip", "gndt_api_cost.hip", "gndt_api_query.hip",
            "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
 HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", os.path.join(_ROOT, "include", "gndt.h")]
@@ -184,17 +200,24 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"
                "-Xoffload-linker", "--discard-all"]
 
 
-def build_native(force=False, verbose=False):
-    """Compile the HIP sources into grid_ndt_amd/csrc/libgndt.so for gfx950 (cross-compiles without a GPU)."""
+def build_native(force=False, verbose=False, variant=None):
+    """Compile the HIP sources into grid_ndt_amd/csrc/libgndt.so for gfx950 (cross-compiles without a GPU).  `variant`: None = the one
+    this process loads (GNDT_LIB_VARIANT; the product if unset), "" = the product, "poison" = csrc/libgndt_poison.so."""
+    variant = VARIANT if variant is None else (variant or None)
+    V, LIB_PATH = VARIANTS[variant], lib_path(variant)
     srcs = [os.path.join(_CSRC, s) for s in SOURCES]
     deps = srcs + [h if os.path.isabs(h) else os.path.join(_CSRC, h) for h in HEADERS] + [os.path.abspath(__file__)]
     if not force and os.path.exists(LIB_PATH) and all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
         return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if V["objdir"]:
+        os.makedirs(os.path.join(_CSRC, V["objdir"]), exist_ok=True)
     objs, procs = [], []
     for src in srcs:                       # one hipcc per translation unit, side by side (8 small jobs)
         obj = os.path.splitext(src)[0] + ".o"
-        cmd = ([hipcc] + HIPCC_FLAGS + ["-I", os.path.join(_ROOT, "include"), "-I", _CSRC, "-o", obj, src]
+        if V["objdir"]:
+            obj = os.path.join(_CSRC, V["objdir"], os.path.basename(obj))
+        cmd = ([hipcc] + HIPCC_FLAGS + V["flags"] + ["-I", os.path.join(_ROOT, "include"), "-I", _CSRC, "-o", obj, src]
                + os.environ.get("GNDT_EXTRA_CXXFLAGS", "").split())
         if verbose:
             print(" ".join(cmd))
@@ -311,6 +334,8 @@ def lib():
     L.gndt_warmup.restype = C.c_int
     L.gndt_debug_set_option.argtypes = [C.c_int, C.c_double]
     L.gndt_debug_set_option.restype = C.c_int
+    L.gndt_debug_poisoned_bytes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
+    L.gndt_debug_poisoned_bytes.restype = C.c_int
     L.gndt_debug_set_fp_bits.argtypes = [C.c_int]
     L.gndt_debug_set_fp_bits.restype = C.c_int
     L.gndt_debug_fp_clashes.argtypes = [H, C.POINTER(u64)]

@@ -989,6 +989,16 @@ int gndt_debug_block_layout(gndt_handle* h, int32_t out[10]) {
 
 int gndt_debug_enable_stamps(int on) { tuning_force_stamps(on != 0); return GNDT_OK; }
 int gndt_debug_set_option(int option, double value) { return tuning_set_option(option, value); }
+int gndt_debug_poisoned_bytes(uint64_t* device_bytes, uint64_t* host_bytes) {
+#ifdef GNDT_POISON
+    if (!device_bytes || !host_bytes) return GNDT_ERR_INVALID;
+    *device_bytes = gndt_host::g_poisoned_device.load();  *host_bytes = gndt_host::g_poisoned_host.load();
+    return GNDT_OK;
+#else
+    (void)device_bytes; (void)host_bytes;
+    return GNDT_ERR_INVALID;
+#endif
+}
 
 int gndt_debug_set_fp_bits(int bits) { tuning_force_fp_bits(bits); return GNDT_OK; }
 

@@ -33,18 +33,31 @@
 
 namespace gndt { struct QueryView; }   // gndt_query.hpp
 
-// Debug build (-DGNDT_POISON): every device allocation is filled with 0xA5 before it is handed out.  A fresh process gets zeroed
-// pages from hipMalloc, which hides reads of memory the library never initialised; a process that has freed and reallocated for a
-// while does not (tools/fuzz_graph.py found two such reads only after ~100 handles).  The tests run under this build as well.
+// Debug build (-DGNDT_POISON, grid_ndt_amd/csrc/libgndt_poison.so): every device allocation and every pinned host allocation is
+// filled with one byte before it is handed out.  A fresh process gets zeroed pages from hipMalloc and hipHostMalloc, which hides
+// reads of memory the library never initialised; a process that has freed and reallocated for a while does not (tools/fuzz_graph.py
+// found two such reads only after ~100 handles).  The byte is gndt_debug_set_option(GNDT_DEBUG_POISON_BYTE, .): 0xA5 by default (as a
+// uint32 2 779 096 485: breaks indices, counts and flags, but reads as the float -2.87e-16, which a sum that starts from it survives),
+// 0x7F for the floating-point reads (3.40e38 as a float, 1.38e306 as a double, 2 139 062 143 as an int; none of the library's
+// sentinels).  gndt_debug_poisoned_bytes counts what has been filled.  tests/test_gpu_poisoned.py runs the consumers' tests under both.
 #ifdef GNDT_POISON
+#include <atomic>
 namespace gndt_host {
+inline std::atomic<int> g_poison_byte{0xA5};
+inline std::atomic<unsigned long long> g_poisoned_device{0}, g_poisoned_host{0};
 inline hipError_t poison_malloc(void** p, size_t bytes) {
     const hipError_t e = (hipMalloc)(p, bytes);
-    if (e == hipSuccess && bytes) { (void)hipMemset(*p, 0xA5, bytes); (void)hipDeviceSynchronize(); }
+    if (e == hipSuccess && bytes) { (void)hipMemset(*p, g_poison_byte.load(), bytes); (void)hipDeviceSynchronize(); g_poisoned_device += bytes; }
+    return e;
+}
+inline hipError_t poison_host_malloc(void** p, size_t bytes) {
+    const hipError_t e = (hipHostMalloc)(p, bytes);
+    if (e == hipSuccess && bytes) { std::memset(*p, g_poison_byte.load(), bytes); g_poisoned_host += bytes; }
     return e;
 }
 }  // namespace gndt_host
 #define hipMalloc(p, bytes) gndt_host::poison_malloc((void**)(p), (bytes))
+#define hipHostMalloc(p, bytes) gndt_host::poison_host_malloc((void**)(p), (bytes))
 #endif
 #include "gndt_kernels.hpp"
 #include "gndt_partition.hpp"

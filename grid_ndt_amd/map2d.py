@@ -514,6 +514,7 @@ class TwoDmap:
 
     DEBUG_VERBOSE, DEBUG_TILE_RATIO, DEBUG_COST_ONE_WORKGROUP, DEBUG_QUERY_ILP = 1, 2, 3, 4
     DEBUG_PLAN_LDS_ENTRIES = 6
+    DEBUG_POISON_BYTE = 7      # the poisoned variant of the library only (_lib.VARIANTS); the product answers GNDT_ERR_INVALID
 
     @staticmethod
     def set_debug_option(option, value):
@@ -521,6 +522,16 @@ class TwoDmap:
         rc = _lib.lib().gndt_debug_set_option(int(option), float(value))
         if rc:
             raise _lib.GndtError(rc, f"gndt_debug_set_option({option}, {value})")
+
+    @staticmethod
+    def poisoned_bytes():
+        """gndt_debug_poisoned_bytes: (device bytes, pinned host bytes) the poisoned variant of the library has filled so far in this
+        process; the product raises GNDT_ERR_INVALID."""
+        d, h = C.c_uint64(), C.c_uint64()
+        rc = _lib.lib().gndt_debug_poisoned_bytes(C.byref(d), C.byref(h))
+        if rc:
+            raise _lib.GndtError(rc, "gndt_debug_poisoned_bytes")
+        return int(d.value), int(h.value)
 
     def set_fp_bits(self, bits):
         """Narrow the bucket kernel's index fingerprint (process-wide; tests: forces its exact second pass)."""

@@ -1063,14 +1063,22 @@ int gndt_debug_enable_stamps(int on);
  *   GNDT_DEBUG_CLEAR_EXTENT       value == 1: gndt_clear_rays* read the rows of a walked column only if the column's level extent
  *                                 meets the ray's level range (tools/measure_clear.py A/Bs the two; same results)  default 0
  *   GNDT_DEBUG_PLAN_LDS_ENTRIES   entries of a planning query's open queue held in LDS, a multiple of 64 in 64 .. 1024; what does
- *                                 not fit spills to the query's scratch (tests cap it so that a small map spills)  default 1024 */
+ *                                 not fit spills to the query's scratch (tests cap it so that a small map spills)  default 1024
+ *   GNDT_DEBUG_POISON_BYTE        the -DGNDT_POISON build only (a regular build answers GNDT_ERR_INVALID): the byte every device and
+ *                                 pinned host allocation that follows is filled with before it is handed out, an integer in
+ *                                 0 .. 255.  0xA5 breaks indices, counts and flags; 0x7F also breaks floating-point reads
+ *                                 (3.40e38 as a float) and is none of the library's sentinels (tests run both)      default 0xA5 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
 #define GNDT_DEBUG_QUERY_ILP 4
 #define GNDT_DEBUG_CLEAR_EXTENT 5
 #define GNDT_DEBUG_PLAN_LDS_ENTRIES 6
+#define GNDT_DEBUG_POISON_BYTE 7
 int gndt_debug_set_option(int option, double value);
+/* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
+ * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
+int gndt_debug_poisoned_bytes(uint64_t* device_bytes, uint64_t* host_bytes);
 /* The bucket kernel finds a node through a 21-bit fingerprint of its key and confirms it with the key itself; a bucket in
  * which a fingerprint named the wrong node (~1 in 10^4) is accumulated a second time with every probe confirmed.  Tests narrow
  * the fingerprint (0 .. 21 bits, process-wide, for the builds that follow) so that this happens in every bucket;

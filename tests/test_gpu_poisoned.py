@@ -1,0 +1,233 @@
+"""The poisoned tier: the map's consumers on memory that does not start out as zeros.
+
+A fresh process gets zeroed pages from hipMalloc and hipHostMalloc, and every GPU test builds a small map on a fresh handle in a fresh
+process: memory the library forgot to initialise reads as 0 there and the answer comes out right.  The poisoned variant of the library
+(grid_ndt_amd/_lib.py VARIANTS, -DGNDT_POISON, gndt_handle.hpp) fills every device and pinned host allocation with one byte before it
+hands it out.  Two bytes: 0xA5 is 2 779 096 485 as a uint32, which breaks indices, counts and flags, but -2.87e-16 as a float, which a
+sum survives; 0x7F is 3.40e38 as a float, 1.38e306 as a double and 2 139 062 143 as an int, and none of the library's sentinels (0xFF
+would be kNoRow / kEmptyKey / kNoColumn; 0x00 is the fresh process).
+
+CPU tier: the variant cross-compiles and exports the whole boundary, the product refuses the variant's option and counter, and every
+node id of GROUPS below exists.  GPU tier: group x byte, each case ONE fresh child process (tests/poisoned_child.py, GNDT_LIB_VARIANT =
+poison) that runs the group's existing tests in-process — their references are theirs — and reports how many bytes it poisoned.  The
+children run one at a time, each under its group's time limit.  A child that is killed at its limit, ends by a signal, with status 134
+or 139, or reports an illegal memory access stops the tier: every case after it fails at once with "not started" and touches no GPU.
+
+hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground.  Nor are the
+blocked buckets: the smallest cloud that takes them has 1.1 M points (tests/blocked_scenes.py)."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+if os.environ.get("GNDT_LIB_VARIANT"):
+    pytest.skip("this process runs on a variant of the library itself (a child of this module): no children of its own", allow_module_level=True)
+
+BYTES = (0xA5, 0x7F)
+REUSE = "tests/test_gpu_scratch_reuse.py::"
+# Existing GPU tests whose maps are hand-drawn or hold at most 60 000 points, that assert no wall-clock bound and record no hipGraph, and
+# the large-then-small tests of tests/test_gpu_scratch_reuse.py in the group of their consumer.
+# measured_s: the whole child (interpreter start to exit) on the MI355X under the regular library; limit_s: three times that, rounded up
+# to 10 s (poison_malloc adds a fill and a device synchronisation to every allocation).
+GROUPS = {
+    "build": dict(measured_s=4.14, limit_s=20, ids=[
+        "tests/test_gpu_fuzz.py::test_single_points_and_tiny_clouds",
+        "tests/test_gpu_fuzz.py::test_interleaved_nodes_inside_a_wave[abab]",
+        "tests/test_gpu_fuzz.py::test_interleaved_nodes_inside_a_wave[runs]",
+        "tests/test_gpu_fuzz.py::test_interleaved_nodes_inside_a_wave[abcabc_plus_padding]",
+        "tests/test_gpu_fuzz.py::test_random_structured_clouds_every_strategy[0]",
+        "tests/test_gpu_fuzz.py::test_random_structured_clouds_every_strategy[1]",
+        "tests/test_gpu_fuzz.py::test_random_structured_clouds_every_strategy[2]",
+        "tests/test_gpu_fuzz.py::test_random_structured_clouds_every_strategy[3]",
+        "tests/test_gpu_parity.py::test_edge_inputs",
+    ]),
+    "geometry": dict(measured_s=4.42, limit_s=20, ids=[
+        REUSE + "test_query[1]",
+        REUSE + "test_query[4]",
+        REUSE + "test_raster",
+        REUSE + "test_clear",
+        REUSE + "test_cast[voxel]",
+        REUSE + "test_cast[ndt]",
+        REUSE + "test_crop",
+    ]),
+    "statistics": dict(measured_s=5.89, limit_s=20, ids=[
+        "tests/test_gpu_score.py::test_scores_equal_the_restatement[uniform_box-1]",
+        "tests/test_gpu_score.py::test_scores_equal_the_restatement[uniform_box-2]",
+        "tests/test_gpu_score.py::test_scores_equal_the_restatement[uniform_box-5]",
+        "tests/test_gpu_score.py::test_scores_equal_the_restatement[uniform_box-0]",
+        "tests/test_gpu_score_derivs.py::test_derivs_equal_the_restatement[uniform_box-1]",
+        "tests/test_gpu_score_derivs.py::test_derivs_equal_the_restatement[uniform_box-2]",
+        "tests/test_gpu_score_derivs.py::test_derivs_equal_the_restatement[uniform_box-5]",
+        "tests/test_gpu_score_derivs.py::test_derivs_equal_the_restatement[uniform_box-0]",
+        "tests/test_gpu_coarsen.py::test_smallest_shapes",
+        "tests/test_gpu_coarsen.py::test_after_remove_crop_and_clear",
+        "tests/test_gpu_merge.py::test_smallest_shapes",
+        "tests/test_gpu_merge.py::test_a_small_destination_table_grows",
+        "tests/test_gpu_merge.py::test_a_general_pose_against_the_restatement",
+        REUSE + "test_score",
+        REUSE + "test_score_derivs",
+        REUSE + "test_score_maps",
+        REUSE + "test_coarsen",
+        REUSE + "test_merge",
+    ]),
+    "flood": dict(measured_s=4.57, limit_s=20, ids=[
+        "tests/test_gpu_cost.py::test_cost_map_goal_statuses_and_lifetime",
+        "tests/test_gpu_plan.py::test_floor_all_1600_starts_in_one_call",
+        "tests/test_gpu_plan.py::test_capped_lds_tier_spills_and_gives_the_same_bytes",
+        "tests/test_gpu_frontiers.py::test_floor_ring_corners_and_nothing",
+        "tests/test_gpu_frontiers.py::test_serpentine_is_one_cluster_in_any_row_order[None]",
+        "tests/test_gpu_frontiers.py::test_serpentine_is_one_cluster_in_any_row_order[1]",
+        "tests/test_gpu_frontiers.py::test_serpentine_is_one_cluster_in_any_row_order[2]",
+        "tests/test_gpu_frontiers.py::test_serpentine_is_one_cluster_in_any_row_order[3]",
+        "tests/test_gpu_frontiers.py::test_two_storeys",
+        REUSE + "test_cost_flood[1]",
+        REUSE + "test_cost_flood[0]",
+        REUSE + "test_plan",
+        REUSE + "test_frontiers[reached]",
+        REUSE + "test_frontiers[slopes]",
+    ]),
+}
+
+
+def _env(variant=None):
+    env = dict(os.environ)
+    env.pop("GNDT_LIB_VARIANT", None)
+    if variant:
+        env["GNDT_LIB_VARIANT"] = variant
+    return env
+
+
+# ---- CPU tier --------------------------------------------------------------------------------------------------------------------------
+
+def test_variant_cross_compiles_for_gfx950_and_exports_every_declared_symbol(native_lib):
+    from grid_ndt_amd import _lib
+    path = _lib.build_native(variant="poison")
+    assert path == _lib.lib_path("poison") == os.path.join(ROOT, "grid_ndt_amd", "csrc", "libgndt_poison.so") and os.path.exists(path)
+    assert path != native_lib._name and _lib.LIB_PATH == native_lib._name       # this process itself runs on the product
+    with open(path, "rb") as f:
+        assert b"gfx950" in f.read()
+    # the rest in a process of its own that runs on the variant: the whole boundary is there (lib() binds it, symbol by symbol), and
+    # the option and the counter are the variant's.  No device is touched by either.
+    code = """
+import ctypes as C
+import grid_ndt_amd as g
+from grid_ndt_amd import _lib
+from tests.test_abi import declared_symbols
+L = _lib.lib()
+assert L._name == _lib.LIB_PATH == _lib.lib_path("poison")
+syms = declared_symbols()
+assert "gndt_debug_poisoned_bytes" in syms
+raw = C.CDLL(L._name)
+missing = [s for s in syms if not hasattr(raw, s)]
+assert not missing, missing
+T = g.TwoDmap
+for value, ok in ((0x7F, True), (0, True), (255, True), (0xA5, True), (256, False), (-1, False), (1.5, False), (float("nan"), False)):
+    try:
+        T.set_debug_option(T.DEBUG_POISON_BYTE, value)
+        assert ok, value
+    except g.GndtError as e:
+        assert not ok and e.code == 1, value
+assert T.poisoned_bytes() == (0, 0)
+h = C.c_uint64(9)
+assert L.gndt_debug_poisoned_bytes(None, C.byref(h)) == 1 and h.value == 9
+print("variant ok")
+"""
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=_env("poison"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("variant ok"), (r.stdout[-1000:], r.stderr[-2000:])
+
+
+def test_the_product_refuses_the_poison_byte_and_the_counter(native_lib):
+    import grid_ndt_amd as g
+    T = g.TwoDmap
+    assert T.DEBUG_POISON_BYTE == 7
+    for value in (0xA5, 0x7F, 0):
+        with pytest.raises(g.GndtError) as e:
+            T.set_debug_option(T.DEBUG_POISON_BYTE, value)
+        assert e.value.code == 1          # GNDT_ERR_INVALID
+    with pytest.raises(g.GndtError) as e:
+        T.poisoned_bytes()
+    assert e.value.code == 1
+    d, h = C.c_uint64(7), C.c_uint64(9)
+    assert native_lib.gndt_debug_poisoned_bytes(C.byref(d), C.byref(h)) == 1 and (d.value, h.value) == (7, 9)
+
+
+def test_the_variant_is_chosen_by_the_environment_in_python_only():
+    """GNDT_LIB_VARIANT is read by grid_ndt_amd/_lib.py: unset or empty the product, "poison" the variant, anything else refused"""
+    code = "from grid_ndt_amd import _lib; print(_lib.VARIANT, _lib.LIB_PATH)"
+    for value, want in ((None, "None " + os.path.join(ROOT, "grid_ndt_amd", "csrc", "libgndt.so")),
+                        ("", "None " + os.path.join(ROOT, "grid_ndt_amd", "csrc", "libgndt.so")),
+                        ("poison", "poison " + os.path.join(ROOT, "grid_ndt_amd", "csrc", "libgndt_poison.so"))):
+        env = _env()
+        if value is not None:
+            env["GNDT_LIB_VARIANT"] = value
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0 and r.stdout.strip() == want, (value, r.stdout, r.stderr[-500:])
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=_env("poisson"), capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "GNDT_LIB_VARIANT" in r.stderr
+
+
+def test_every_node_id_of_the_groups_is_collected():
+    ids = [i for grp in GROUPS.values() for i in grp["ids"]]
+    assert len(ids) == len(set(ids))
+    r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + ids, cwd=ROOT, env=_env(),
+                       capture_output=True, text=True, timeout=300)
+    found = {line.strip() for line in r.stdout.splitlines() if "::" in line}
+    missing = [i for i in ids if i not in found]
+    assert r.returncode == 0 and not missing, (missing, r.stdout[-2000:], r.stderr[-2000:])
+    assert len(found) == len(ids), sorted(found - set(ids))
+
+
+def test_the_limits_are_three_times_the_measured_times():
+    for name, grp in GROUPS.items():
+        assert grp["measured_s"] > 0 and grp["limit_s"] == -(-3 * grp["measured_s"] // 10) * 10, name
+
+
+# ---- GPU tier --------------------------------------------------------------------------------------------------------------------------
+
+_stopped = []        # why the tier stopped: a child ended abnormally
+
+
+def _abnormal(returncode, output):
+    if returncode is None:
+        return "killed at its time limit"
+    if returncode < 0:
+        return f"ended by signal {-returncode}"
+    if returncode in (134, 139):
+        return f"ended with status {returncode}"
+    if "illegal memory access" in output:
+        return "reported an illegal memory access"
+    return None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("byte", BYTES, ids=["0xA5", "0x7F"])
+@pytest.mark.parametrize("group", list(GROUPS))
+def test_group_under_poison(group, byte):
+    from grid_ndt_amd import _lib
+    if _stopped:
+        pytest.fail(f"not started: {_stopped[0]}", pytrace=False)
+    grp = GROUPS[group]
+    _lib.build_native(variant="poison")          # (__graft_entry__.build() has built it: nothing compiles inside the child's limit)
+    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + grp["ids"]
+    try:
+        r = subprocess.run(cmd, cwd=ROOT, env=_env("poison"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=grp["limit_s"])
+        returncode, output = r.returncode, r.stdout
+    except subprocess.TimeoutExpired as e:
+        out = e.stdout or ""
+        returncode, output = None, out.decode(errors="replace") if isinstance(out, bytes) else out
+    print(output[-6000:])
+    why = _abnormal(returncode, output)
+    if why:
+        _stopped.append(f"the child of {group} under {byte:#x} {why}")
+        pytest.fail(_stopped[0] + "\n" + output[-3000:], pytrace=False)
+    lines = [line for line in output.splitlines() if line.startswith('{"poisoned_child"')]
+    assert returncode == 0 and len(lines) == 1, (returncode, output[-3000:])
+    rep = json.loads(lines[0])
+    assert rep["exit"] == 0 and rep["byte"] == byte
+    assert rep["device_bytes"] > 0 and rep["host_bytes"] > 0, rep
+    assert rep["lib"] == _lib.lib_path("poison")
