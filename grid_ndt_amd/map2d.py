@@ -515,6 +515,7 @@ class TwoDmap:
     DEBUG_VERBOSE, DEBUG_TILE_RATIO, DEBUG_COST_ONE_WORKGROUP, DEBUG_QUERY_ILP = 1, 2, 3, 4
     DEBUG_PLAN_LDS_ENTRIES = 6
     DEBUG_POISON_BYTE = 7      # the poisoned variant of the library only (_lib.VARIANTS); the product answers GNDT_ERR_INVALID
+    DEBUG_CLEARANCE_ONE_WORKGROUP = 8
 
     @staticmethod
     def set_debug_option(option, value):
@@ -826,6 +827,81 @@ class TwoDmap:
         pts = xp.stack(cols, 1).float() if on_dev else np.stack(cols, 1).astype(np.float32)
         pts[fr["size"] == 0] = float("nan")
         return pts
+
+    # ---- clearance field (gndt_clearance*: per slope the steps to the nearest barrier, and where it is) ----
+    CLEARANCE_SOURCES = {"blocked": 1, "open": 2, "overhead": 4}
+    CLEARANCE_BEYOND = -1      # GNDT_CLEARANCE_BEYOND as the int32 the hops come back in
+
+    def clearance(self, robot=None, max_hops=32, sources=("blocked",), hops=True, nearest=True, sides=False, stream=None, host=False):
+        """How far every slope is from the nearest barrier (include/gndt.h "clearance field" defines every word).  A step goes from a
+        slope to a slope of a neighbour column that passes the flood's gates for `robot` (computeCost's dict; None = its defaults); a
+        side whose column is in the map but offers no step is blocked, a side without a column is open.  sources: which slopes count
+        as barriers, any of "blocked" (a blocked side), "open" (an open side: the map's edge), "overhead" (a surface within 2 radius
+        above), or the bit mask.  Returns a dict with, per row of export(): `hops` (int32: the steps of the shortest walk to a source,
+        0 for a source, -1 = CLEARANCE_BEYOND for more than max_hops, for none and for a row without a slope), `nearest` (int32: the
+        smallest source row that many steps away, -1 = NO_ROW), `sides` (uint8: bits 0-3 the blocked sides, 4-7 the open ones, in
+        the order left, right, forward, back; 0xFF for a row without a slope) — each only when asked for — and `counts` ([4]: sources,
+        slopes with finite hops, the largest finite hops, 0).  Torch tensors on the handle's device, enqueued on `stream` (default
+        torch's current stream) and not awaited; or numpy arrays through gndt_clearance with host=True."""
+        from ._lib import ClearanceParams
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if isinstance(sources, str):
+            sources = (sources,)
+        mask = int(sources) if not hasattr(sources, "__iter__") else sum({self.CLEARANCE_SOURCES[s] for s in sources})
+        prm = ClearanceParams(mask, int(max_hops))
+        rb = None
+        if robot is not None:
+            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+            d.update(robot)
+            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        want = {"hops": (hops, np.int32), "nearest": (nearest, np.int32), "sides": (sides, np.uint8)}
+        n = int(self.sync()[0])
+        room = max(n, 1)           # (an empty map still names its outputs: a NULL one means "not asked for")
+        out = {}
+        if host:
+            for k, (on, dt) in want.items():
+                if on:
+                    out[k] = np.empty(room, dt)
+            out["counts"] = np.zeros(4, np.int32)
+            ptr = lambda k: C.c_void_p(out[k].ctypes.data if k in out else 0)
+            self._check(self._L.gndt_clearance(self._h, rb, C.byref(prm), ptr("hops"), ptr("nearest"), ptr("sides"), ptr("counts")))
+        else:
+            import torch
+            dev = f"cuda:{self.device}"
+            with _torch_stream_ctx(stream):
+                for k, (on, dt) in want.items():
+                    if on:
+                        out[k] = torch.empty(room, dtype=torch.int32 if dt is np.int32 else torch.uint8, device=dev)
+                out["counts"] = torch.zeros(4, dtype=torch.int32, device=dev)
+            ptr = lambda k: C.c_void_p(out[k].data_ptr() if k in out else 0)
+            self._check(self._L.gndt_clearance_device(self._h, rb, C.byref(prm), ptr("hops"), ptr("nearest"), ptr("sides"), ptr("counts"),
+                                                      _stream_ptr(stream)))
+        for k in want:
+            if k in out:
+                out[k] = out[k][:n]
+        return out
+
+    def clearance_vectors(self, cl):
+        """[N, 3] float32 per row of export(): mean[nearest] - mean[row] for the `nearest` of clearance(), NaN where there is none — the
+        direction to the barrier that `hops` names (a repulsive term pushes the other way), its norm the straight-line distance.  A
+        gather and a subtraction on the exported means: torch in, torch out (export_device()); numpy in, numpy out (export())."""
+        near = cl["nearest"]
+        if isinstance(near, np.ndarray):
+            mean = self.export()["mean"]
+            none = near < 0
+            vec = mean[np.where(none, 0, near)] - mean
+            vec[none] = np.float32("nan")
+            return vec
+        import torch
+        cells = self.export_device()
+        if int(cells["num_nodes"]) == 0:
+            return torch.zeros((0, 3), dtype=torch.float32, device=near.device)
+        mean = cells["mean"]
+        none = near < 0
+        vec = mean[near.long().clamp(min=0)] - mean
+        vec[none] = float("nan")
+        return vec
 
     # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
     CLEAR_PROTECTED = 0x80000000

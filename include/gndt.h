@@ -617,6 +617,53 @@ int gndt_frontiers_device(gndt_handle* h, const gndt_crop_box* box, const gndt_f
 int gndt_frontiers(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* params,
                    uint32_t* label_host, gndt_frontier* clusters_host, uint32_t cluster_cap, uint32_t* counts_host);
 
+/* ---- clearance field: hops to the nearest barrier for every slope ------------------------------------------------------------
+ * What a planner asks after "can the robot stand here" (the flood's CollisionCheck) and "what does it cost to reach the goal from
+ * here" (h): how far is this slope from the nearest place the robot cannot go?  The answer is an inflation layer for a costmap, a
+ * direction to push trajectories away from, a way to rank a narrow passage against a wide one, and one field for robots of several
+ * widths.  Every definition is integer arithmetic except the flood's three gates, which are the flood's own code: the answer is exact
+ * and does not depend on the order threads work in.
+ *   side          (q, k): slope q (a row with GNDT_FLAG_SLOPE) towards its k-th neighbour column in the flood's order — (sx, sy - 1),
+ *                 (sx, sy + 1), (sx + 1, sy), (sx - 1, sy), stepping over index 0.  A side is
+ *                   open      the column is not in the map (an index beyond the codec's +-65535 is not);
+ *                   passable  at least one row t of the column has GNDT_FLAG_SLOPE and passes the flood's gates seen from q (the
+ *                             roughness of t, the angle between the normals, |mean_z(t) - mean_z(q)| <= reachable_height): those
+ *                             rows are the steps of q through the side;
+ *                   blocked   the column is in the map and no row passes: a wall, a kerb, a step up or down, rubble.
+ *   source        a slope for which a condition selected in params->sources (a bit mask, 0 = GNDT_CLEARANCE_BLOCKED) holds:
+ *                   GNDT_CLEARANCE_BLOCKED   at least one blocked side;
+ *                   GNDT_CLEARANCE_OPEN      at least one open side: the map's edge counts as a barrier;
+ *                   GNDT_CLEARANCE_OVERHEAD  the next slope above in its own cell lies within 2 radius and more than reachable_height
+ *                                            above it (CollisionCheck's last test; the only use of robot->radius).
+ *   hops(q)       the length of the shortest walk q -> p1 -> ... -> s along steps that ends in a source s; 0 for a source.  The graph
+ *                 is directed (the roughness gate looks only at the destination).  GNDT_CLEARANCE_BEYOND for a slope without such a
+ *                 walk of at most max_hops steps (0 = 32; above 1024 is refused: it bounds the launches of a call, and the device is
+ *                 shared) and for every row without a slope.
+ *   nearest(q)    the smallest row among the sources exactly hops(q) steps from q; GNDT_NO_ROW where hops is BEYOND.  The pair is the
+ *                 fixed point of key(q) = min(key(q), min over steps p of key(p) + 2^32) with key = hops << 32 | source row, which
+ *                 rounds over all rows at once reach exactly.
+ *   sides(q)      one byte: bits 0-3 the blocked sides, bits 4-7 the open sides, in the order above; 0xFF for a row without a slope.
+ *   counts[4]     the sources, the slopes with finite hops, the largest finite hops, 0.
+ * hops, nearest and sides have num_nodes entries; each may be NULL (it is then not written), but not all three.  `robot` NULL = the
+ * flood's defaults.  Order and lifetime are the frontier call's: the call first finishes what gndt_sync finishes, builds or reuses the
+ * map's column index and enqueues its kernels on `hip_stream` (NULL = the handle's stream), not awaited — one launch per hop, of
+ * which those behind the last hop that changed anything return at once; a map of up to 9216 rows takes every hop in one launch of one
+ * workgroup.  gndt_clearance is synchronous.  The map, h and state are not modified and no cost map is needed.  Work memory (49 bytes a
+ * row) belongs to the handle and grows with the map.  A map without rows gives four zero counts.  There is no CPU path.  A sharded
+ * map answers from the rows this rank holds: the borders between ranks therefore look open.
+ * GNDT_ERR_INVALID: a null handle, params or counts, hops, nearest and sides all NULL, unknown source bits, max_hops > 1024, a
+ * non-zero reserved word, hops_dev, nearest_dev or counts_dev not aligned to 4 bytes, no finished build, a stream under hipGraph
+ * capture (the call is not recorded). */
+#define GNDT_CLEARANCE_BEYOND 0xFFFFFFFFu
+enum { GNDT_CLEARANCE_BLOCKED = 1, GNDT_CLEARANCE_OPEN = 2, GNDT_CLEARANCE_OVERHEAD = 4 };
+typedef struct gndt_clearance_params { uint32_t sources, max_hops, reserved[6]; } gndt_clearance_params;  /* zeros = defaults */
+/* Device memory out: hops_dev, nearest_dev [num_nodes] (uint32), sides_dev [num_nodes] (bytes), each or NULL; counts_dev [4]. */
+int gndt_clearance_device(gndt_handle* h, const gndt_robot* robot, const gndt_clearance_params* params,
+                          uint32_t* hops_dev, uint32_t* nearest_dev, uint8_t* sides_dev, uint32_t* counts_dev /* [4] */, void* hip_stream);
+/* Host memory out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_clearance(gndt_handle* h, const gndt_robot* robot, const gndt_clearance_params* params,
+                   uint32_t* hops_host, uint32_t* nearest_host, uint8_t* sides_host, uint32_t* counts_host);
+
 /* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
  * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
  * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
@@ -1067,7 +1114,9 @@ int gndt_debug_enable_stamps(int on);
  *   GNDT_DEBUG_POISON_BYTE        the -DGNDT_POISON build only (a regular build answers GNDT_ERR_INVALID): the byte every device and
  *                                 pinned host allocation that follows is filled with before it is handed out, an integer in
  *                                 0 .. 255.  0xA5 breaks indices, counts and flags; 0x7F also breaks floating-point reads
- *                                 (3.40e38 as a float) and is none of the library's sentinels (tests run both)      default 0xA5 */
+ *                                 (3.40e38 as a float) and is none of the library's sentinels (tests run both)      default 0xA5
+ *   GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP value == 0: gndt_clearance* launch every hop on its own, the one-workgroup kernel that holds a
+ *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1075,6 +1124,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_CLEAR_EXTENT 5
 #define GNDT_DEBUG_PLAN_LDS_ENTRIES 6
 #define GNDT_DEBUG_POISON_BYTE 7
+#define GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP 8
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
