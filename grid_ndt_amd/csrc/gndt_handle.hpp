@@ -13,6 +13,7 @@
 //   gndt_api_plan.hip   route planning: A* routes to the flood's goal for a batch of starts
 //   gndt_api_frontier.hip  frontier extraction: the slopes where the map ends, clustered
 //   gndt_api_clearance.hip  clearance field: per slope the steps to the nearest barrier, and where it is
+//   gndt_api_walk.hip       path walks: candidate polylines driven over the map's slopes under the flood's gates
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
@@ -264,6 +265,11 @@ struct gndt_handle {
     struct Clearance {
         void* scratch = nullptr;  uint64_t bytes = 0;
     } clearance;
+    // path walks (gndt_walk.hpp), the table variant only: per row the steps table of its four sides (32 B) and what else
+    // k_clearance_steps writes (a round-0 key, 8 B, and the tall-column bits, 1 B); made again by every call that takes it
+    struct Walk {
+        void* scratch = nullptr;  uint64_t bytes = 0;
+    } walk;
     // map merge (gndt_merge.hpp): the call's tallies, device and pinned
     struct Merge {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
@@ -421,6 +427,7 @@ struct Tuning {
     int query_ilp = 1;           // GNDT_DEBUG_QUERY_ILP           queries a thread of k_query works on at once (1, 2 or 4)
     int plan_lds_entries = 1024; // GNDT_DEBUG_PLAN_LDS_ENTRIES    entries of a planning query's open queue kept in LDS (64 .. 1024; the rest spills)
     bool clearance_one_workgroup = true;   // GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP   0: every round of the clearance field its own launch
+    int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE           gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
 };
@@ -627,5 +634,7 @@ void free_plan(gndt_handle* h);
 void free_frontier(gndt_handle* h);
 // ---- gndt_api_clearance.hip ----
 void free_clearance(gndt_handle* h);
+// ---- gndt_api_walk.hip ----
+void free_walk(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats, WalkInfo, WalkParams
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -516,6 +516,7 @@ class TwoDmap:
     DEBUG_PLAN_LDS_ENTRIES = 6
     DEBUG_POISON_BYTE = 7      # the poisoned variant of the library only (_lib.VARIANTS); the product answers GNDT_ERR_INVALID
     DEBUG_CLEARANCE_ONE_WORKGROUP = 8
+    DEBUG_WALK_STEP_TABLE = 9
 
     @staticmethod
     def set_debug_option(option, value):
@@ -902,6 +903,78 @@ class TwoDmap:
         vec = mean[near.long().clamp(min=0)] - mean
         vec[none] = float("nan")
         return vec
+
+    # ---- path walks (gndt_walk_paths*: candidate polylines driven over the map's slopes under the flood's gates) ----
+    WALK_STATUS = {0: "done", 1: "no_start", 2: "blocked", 3: "left_map", 4: "overhead", 5: "too_close", 6: "limit"}
+    WALK_START_MODES = {"nearest_slope": 1, "node": 2}
+    WALK_NO_SIDE = -1          # GNDT_WALK_NO_SIDE as the int32 stop_side comes back in
+    WALK_INFO_DTYPE = np.dtype([("status", np.int32), ("stop_side", np.int32), ("steps", np.int32), ("waypoints", np.int32),
+                                ("start_row", np.int32), ("end_row", np.int32), ("length", np.float32), ("climb", np.float32),
+                                ("rough_max", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 2)])
+
+    def walk_paths(self, paths, robot=None, start_mode="nearest_slope", overhead=False, hops=None, min_hops=0, max_steps=0, rows=0,
+                   stream=None, host=False):
+        """Drive K candidate paths of T waypoints over the map (include/gndt.h "path walks" defines every word).  paths: [K, T, 3] or
+        [K, T, 4] float32, a torch CUDA tensor or a numpy array; a waypoint whose x or y is NaN ends its path.  From the slope under
+        waypoint 0 (start_mode "nearest_slope" or "node") every segment is crossed column by column, each column change a step
+        through the flood's gates for `robot` (computeCost's dict; None = its defaults) to the slope nearest in height.  overhead=True
+        also stops under a surface too low for the robot; hops (what clearance() returned, or its "hops") with min_hops stops at a
+        slope nearer than that to a barrier — the field must be of the map as it is now.  max_steps 0 = 65536.  rows > 0 also
+        returns the first `rows` slopes of every walk.  Returns a dict of [K] arrays: status (WALK_STATUS), stop_side (0..3, -1 =
+        none), steps, waypoints, start_row, end_row (-1 = none), length, climb, rough_max, hops_min (-1 = no hops given or seen), and
+        `rows` [K, rows] (int32, -1 behind a walk's end) when asked.  torch tensors on the paths' device, enqueued on `stream` (default
+        torch's current stream) and not awaited; host=True or a numpy array goes through gndt_walk_paths (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        on_dev = hasattr(paths, "is_cuda") and paths.is_cuda and not host
+        if hasattr(paths, "detach") and not on_dev:
+            paths = paths.detach().cpu().numpy()
+        if len(paths.shape) != 3 or paths.shape[2] not in (3, 4):
+            raise ValueError("paths must be [K, T, 3] or [K, T, 4]")
+        K, T, stride = int(paths.shape[0]), int(paths.shape[1]), 4 * int(paths.shape[2])
+        if isinstance(hops, dict):
+            hops = hops["hops"]
+        prm = WalkParams(self.WALK_START_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), 1 if overhead else 0,
+                         int(min_hops), int(max_steps))
+        rb = None
+        if robot is not None:
+            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+            d.update(robot)
+            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        row_cap = int(rows)
+        n = int(self.sync()[0])
+        if hops is not None and int(hops.shape[0]) != n:
+            raise ValueError(f"hops has {int(hops.shape[0])} entries, the map {n} rows: a clearance field of another map")
+        names = ("status", "stop_side", "steps", "waypoints", "start_row", "end_row", "length", "climb", "rough_max", "hops_min")
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                p = paths.contiguous().float()
+                if isinstance(hops, np.ndarray):
+                    hops = np.ascontiguousarray(hops).view(np.int32)
+                hp = None if hops is None else torch.as_tensor(hops, device=p.device).contiguous()
+                if hp is not None and hp.dtype != torch.int32:
+                    hp = hp.to(torch.int32)
+                raw = torch.zeros((max(K, 1), 12), dtype=torch.int32, device=p.device)
+                out_rows = torch.empty((K, row_cap), dtype=torch.int32, device=p.device) if row_cap else None
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_walk_paths_device(self._h, ptr(p), K, T, stride, rb, C.byref(prm), ptr(hp),
+                                                       C.c_void_p(out_rows.data_ptr()) if row_cap else None, row_cap,
+                                                       C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
+            raw = raw[:K]
+            out = {k: (raw[:, i].view(torch.float32) if k in ("length", "climb", "rough_max") else raw[:, i]) for i, k in enumerate(names)}
+        else:
+            p = np.ascontiguousarray(paths, np.float32)
+            hp = None if hops is None else np.ascontiguousarray(hops.cpu().numpy() if hasattr(hops, "cpu") else hops).view(np.uint32)
+            raw = np.zeros(max(K, 1), self.WALK_INFO_DTYPE)
+            out_rows = np.empty((K, row_cap), np.int32) if row_cap else None
+            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_walk_paths(self._h, ptr(p), K, T, stride, rb, C.byref(prm), ptr(hp),
+                                                C.c_void_p(out_rows.ctypes.data) if row_cap else None, row_cap, C.c_void_p(raw.ctypes.data)))
+            out = {k: raw[k][:K] for k in names}
+        if row_cap:
+            out["rows"] = out_rows
+        return out
 
     # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
     CLEAR_PROTECTED = 0x80000000

@@ -1,0 +1,47 @@
+"""Candidate trajectories for TwoDmap.walk_paths and the choice among the walked ones: the two ends of a local planner's loop.
+
+    paths = rollouts.arcs(pose, v, omegas, dt, T)            # a DWA fan from the robot's pose
+    info = m.walk_paths(paths)                               # driven over the map on the device
+    best = rollouts.choose(info, h[info["end_row"]])         # h: the cost map of the last computeCost, per row
+
+Plain tensor arithmetic: nothing here is a hot path."""
+import numpy as np
+
+
+def arcs(pose_xyz_yaw, v, omegas, dt, T):
+    """Unicycle arcs from one pose: [K, T, 3] float32 on the pose's device (a torch tensor in, a torch tensor out; anything else numpy).
+    pose_xyz_yaw = (x, y, z, yaw); the K arcs drive at speed v with the turn rates `omegas` (rad/s), waypoint j at time j * dt, waypoint 0
+    the pose itself.  Closed form: x + v/w (sin(yaw + w t) - sin yaw), y - v/w (cos(yaw + w t) - cos yaw); the straight line where
+    |w| < 1e-6.  z is the pose's for every waypoint (a walk only reads waypoint 0's)."""
+    torch_in = hasattr(pose_xyz_yaw, "device") and hasattr(pose_xyz_yaw, "dtype") and not isinstance(pose_xyz_yaw, np.ndarray)
+    if torch_in:
+        import torch as xp
+        pose = pose_xyz_yaw.to(xp.float64)
+        w = xp.as_tensor(omegas, dtype=xp.float64, device=pose.device).reshape(-1, 1)
+        t = xp.arange(int(T), dtype=xp.float64, device=pose.device).reshape(1, -1) * float(dt)
+    else:
+        xp = np
+        pose = np.asarray(pose_xyz_yaw, np.float64)
+        w = np.asarray(omegas, np.float64).reshape(-1, 1)
+        t = np.arange(int(T), dtype=np.float64).reshape(1, -1) * float(dt)
+    x0, y0, z0, yaw = pose[0], pose[1], pose[2], pose[3]
+    straight = xp.abs(w) < 1e-6
+    ws = xp.where(straight, xp.ones_like(w), w)
+    th = yaw + w * t
+    x = xp.where(straight, x0 + v * t * xp.cos(yaw), x0 + (v / ws) * (xp.sin(th) - xp.sin(yaw)))
+    y = xp.where(straight, y0 + v * t * xp.sin(yaw), y0 - (v / ws) * (xp.cos(th) - xp.cos(yaw)))
+    z = xp.zeros_like(x) + z0
+    out = xp.stack([x, y, z], -1)
+    return out.float() if torch_in else out.astype(np.float32)
+
+
+def choose(info, h_end):
+    """The index of the path to drive: among the paths of walk_paths' `info` whose status is done (0), the one with the least h_end —
+    the cost map's h at the path's end_row, [K] — ties broken by the shorter `length`, then the lower index; -1 if no path is done."""
+    to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    status, length, h = to_np(info["status"]), to_np(info["length"]).astype(np.float64), to_np(h_end).astype(np.float64)
+    done = np.flatnonzero(status == 0)
+    if done.size == 0:
+        return -1
+    order = np.lexsort((done, length[done], h[done]))
+    return int(done[order[0]])

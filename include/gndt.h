@@ -664,6 +664,88 @@ int gndt_clearance_device(gndt_handle* h, const gndt_robot* robot, const gndt_cl
 int gndt_clearance(gndt_handle* h, const gndt_robot* robot, const gndt_clearance_params* params,
                    uint32_t* hops_host, uint32_t* nearest_host, uint8_t* sides_host, uint32_t* counts_host);
 
+/* ---- path walks: candidate trajectories driven over the map's slopes ----------------------------------------------------------
+ * What a local planner asks between a global route and the wheels — a DWA arc fan, MPPI rollouts, "does the route of a second ago
+ * still hold after the last update": can the robot step from slope to slope along this polyline under the flood's gates, where does
+ * it stop if not and why, how long, steep and rough is the drive, how close does it come to a barrier.  One call takes K paths of T
+ * waypoints each: floats x, y, z at stride 12 or 16, path-major (waypoint [k * T + j] is the j-th of path k).  `robot` NULL = the
+ * flood's defaults.  Per path, in this order:
+ *   1. start     waypoint 0 through the point queries' own lookup selects the start row: params->start_mode 0 or
+ *                GNDT_WALK_START_NEAREST_SLOPE (= GNDT_QUERY_NEAREST_SLOPE's value and rule), or GNDT_WALK_START_NODE
+ *                (GNDT_QUERY_NODE's lookup — that enum's value is 0, which here has to mean "the default" — and the row must have
+ *                GNDT_FLAG_SLOPE).  No row: status GNDT_WALK_NO_START (waypoints 0, both rows GNDT_NO_ROW).  q = that row; the checks
+ *                of 4 apply to it.
+ *   2. segments  for j = 1 .. T-1: a waypoint whose x or y is not finite ends the path normally (a terminator: one call holds paths
+ *                of different lengths).  A finite waypoint that point_key cannot key — with waypoint 0's z, which every point of the
+ *                path is given — ends it with GNDT_WALK_LEFT_MAP.  Otherwise the segment from waypoint j-1 to waypoint j is crossed
+ *                column by column in the column sequence of the ray walk ("free-space clearing": max_range = end_margin = 0, its
+ *                levels ignored): |dx| + |dy| unit steps, each across the lattice plane the segment meets first, fp64, a tie
+ *                stepping x.  Consecutive segments join in one column, since both key the same float point.  Every column change is
+ *                a step through one side k of q in the flood's order (the clearance field's sides; no index 0).
+ *   3. a step    through side k: among the rows t of that neighbour column that have GNDT_FLAG_SLOPE and pass the flood's gates seen
+ *                from q (the clearance field's "steps of q through the side") the one with the least fabsf(mean_z(t) - mean_z(q))
+ *                in fp32, a tie going to the smaller row.  The column is not in the map (an index beyond +-65535 is not):
+ *                GNDT_WALK_LEFT_MAP; it is and offers no step: GNDT_WALK_BLOCKED; both with stop_side = k and end_row the last
+ *                slope stood on.
+ *   4. checks    on every slope stood on, the start included, each optional: with GNDT_WALK_CHECK_OVERHEAD in params->checks the
+ *                next slope above in its own cell within 2 radius and more than reachable_height above (CollisionCheck's last
+ *                test, the clearance field's OVERHEAD) gives GNDT_WALK_OVERHEAD; with hops_dev != NULL, hops_dev[t] <
+ *                params->min_hops gives GNDT_WALK_TOO_CLOSE (overhead is tested first).  hops_dev is a gndt_clearance* `hops` output
+ *                OF THIS MAP AS IT IS NOW, num_nodes entries: the caller vouches for that — after an update, a crop or a clear the
+ *                field has to be computed again, and a stale or shorter array is read out of bounds.  hops_min is the least value
+ *                seen whether or not min_hops is set, GNDT_CLEARANCE_BEYOND without hops_dev.  The slope that fails a check has
+ *                been entered: it is end_row, counts in steps and in the sums and maxima.
+ *   5. guard     a path that has taken params->max_steps steps (0 = 65536; above 2^20 is refused: it bounds a lane's loop, and the
+ *                device is shared) and needs another ends with GNDT_WALK_LIMIT; one that needs exactly max_steps is DONE.
+ *   6. sums      in walk order, so that one thread's sequential arithmetic reproduces them: length = the sum of TravelCost(mean(q),
+ *                mean(t)) (the flood's: fp32 differences, squares and root in fp64, rounded to fp32) over the steps, added in fp64
+ *                and rounded to fp32 once; climb = the sum of fabsf(mean_z(t) - mean_z(q)) the same way; rough_max the largest
+ *                `rough` over the slopes stood on (0 without a start).
+ * waypoints counts the waypoints whose column was reached, the start included.  rows_dev (optional, NULL together with row_cap 0)
+ * receives per path row_cap entries: the slopes stood on, start first, GNDT_NO_ROW behind them; a longer walk writes its first row_cap
+ * rows and the caller sees steps + 1 > row_cap.  info is written 16 bytes at a time: info_dev must be aligned to 16 bytes.
+ * Order and lifetime are the clearance call's: the call first finishes what gndt_sync finishes, builds or reuses the map's column
+ * index and enqueues its kernel on `hip_stream` (NULL = the handle's stream), not awaited; gndt_walk_paths is synchronous and takes
+ * host memory of any alignment.  The map, h and state are not modified and no cost map is needed.  K == 0 or T == 0 returns GNDT_OK
+ * and launches nothing.  There is no CPU path.  A sharded map answers from the rows this rank holds.  Work memory (41 bytes a row)
+ * belongs to the handle and is used only when a call reads its steps from a table made once per call: on a map of up to 2048 rows
+ * per waypoint of a path (GNDT_DEBUG_WALK_STEP_TABLE); the answer does not depend on it.
+ * GNDT_ERR_INVALID: a null handle, params or info, null paths with K and T non-zero, K * T >= 2^31, a stride other than 12 or 16, an
+ * unknown start_mode or check bit, max_steps > 2^20, a non-zero reserved word, rows NULL with row_cap != 0 or the reverse, info_dev
+ * not aligned to 16 bytes or paths_dev, hops_dev, rows_dev not to 4, no finished build, a stream under hipGraph capture. */
+enum { GNDT_WALK_DONE = 0, GNDT_WALK_NO_START = 1, GNDT_WALK_BLOCKED = 2, GNDT_WALK_LEFT_MAP = 3, GNDT_WALK_OVERHEAD = 4,
+       GNDT_WALK_TOO_CLOSE = 5, GNDT_WALK_LIMIT = 6 };
+enum { GNDT_WALK_START_NEAREST_SLOPE = 1, GNDT_WALK_START_NODE = 2 };
+#define GNDT_WALK_CHECK_OVERHEAD 1u
+#define GNDT_WALK_NO_SIDE 0xFFFFFFFFu
+typedef struct gndt_walk_params {
+    int32_t start_mode;       /* 0 = GNDT_WALK_START_NEAREST_SLOPE */
+    uint32_t checks;          /* GNDT_WALK_CHECK_* bits */
+    uint32_t min_hops;        /* with hops: a slope with fewer hops ends the path (0: none does) */
+    uint32_t max_steps;       /* 0 = 65536 */
+    uint32_t reserved[4];     /* 0 */
+} gndt_walk_params;           /* 32 bytes; zeros = defaults */
+typedef struct gndt_walk_info {
+    int32_t status;           /* GNDT_WALK_* */
+    uint32_t stop_side;       /* 0..3 for BLOCKED and a LEFT_MAP of a step, else GNDT_WALK_NO_SIDE */
+    uint32_t steps;           /* column changes taken */
+    uint32_t waypoints;       /* waypoints whose column was reached, the start included */
+    uint32_t start_row, end_row;
+    float length, climb;
+    float rough_max;
+    uint32_t hops_min;
+    uint32_t reserved[2];
+} gndt_walk_info;             /* 48 bytes */
+/* Device memory in and out. */
+int gndt_walk_paths_device(gndt_handle* h, const void* paths_dev, size_t K, size_t T, size_t stride_bytes, const gndt_robot* robot,
+                           const gndt_walk_params* params, const uint32_t* hops_dev /* [num_nodes] or NULL */,
+                           uint32_t* rows_dev /* [K * row_cap] or NULL */, uint32_t row_cap, gndt_walk_info* info_dev /* [K] */,
+                           void* hip_stream);
+/* Host memory in and out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_walk_paths(gndt_handle* h, const void* paths_host, size_t K, size_t T, size_t stride_bytes, const gndt_robot* robot,
+                    const gndt_walk_params* params, const uint32_t* hops_host, uint32_t* rows_host, uint32_t row_cap,
+                    gndt_walk_info* info_host);
+
 /* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
  * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
  * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
@@ -1116,7 +1198,11 @@ int gndt_debug_enable_stamps(int on);
  *                                 0 .. 255.  0xA5 breaks indices, counts and flags; 0x7F also breaks floating-point reads
  *                                 (3.40e38 as a float) and is none of the library's sentinels (tests run both)      default 0xA5
  *   GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP value == 0: gndt_clearance* launch every hop on its own, the one-workgroup kernel that holds a
- *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1 */
+ *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1
+ *   GNDT_DEBUG_WALK_STEP_TABLE    value == 1: gndt_walk_paths* first make a per-side steps table of the whole map (the clearance
+ *                                 field's first pass) and read every step of every walk from it; 0: a walk finds its steps itself,
+ *                                 gates included (tests run the walks both ways); 2: the table for a map of up to 2048 rows per
+ *                                 waypoint of a path (num_nodes <= 2048 T), where it was measured faster          default 2 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1125,6 +1211,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_PLAN_LDS_ENTRIES 6
 #define GNDT_DEBUG_POISON_BYTE 7
 #define GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP 8
+#define GNDT_DEBUG_WALK_STEP_TABLE 9
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
