@@ -68,6 +68,45 @@ def pit_cloud(depth=36):
     return np.ascontiguousarray(np.concatenate([floor[:1], np.float32(pit), floor[1:]]))
 
 
+def lattice_cloud(W, H, walls=(), P=None):
+    """A W x H floor of tests/frontier_ref.cells_cloud's cells, one per column (ix = 0 .. W-1, iy = 0 .. H-1), the cells of `walls`
+    a metre higher: exactly W * H rows, every one a slope (a wall's top is as level as the floor), and under BLOCKED the sources are
+    the slopes on either side of a wall's outline.  P: the parameters the map is built with, which have to be the cells' own."""
+    from tests import frontier_ref as fr
+    P = fr.P if P is None else P
+    assert (P["grid_len"], P["z_len"], P["slope_interval"]) == (fr.GL, fr.ZL, fr.IV), "cells_cloud draws cells of frontier_ref.P"
+    walls = set(walls)
+    assert all(0 <= ix < W and 0 <= iy < H for ix, iy in walls)
+    return fr.cells_cloud([(ix, iy, fr.Z_FLOOR + 1.0) if (ix, iy) in walls else (ix, iy) for ix in range(W) for iy in range(H)])
+
+
+def wall(xs, ys):
+    """the cells of a straight wall: every (ix, iy) of the two ranges"""
+    return frozenset((ix, iy) for ix in xs for iy in ys)
+
+
+# The lattices of the kernel-edge tests by row count: (W, H, walls).  9216 = kClrLdsRows fills k_clearance_wg, 9217 is the first
+# launch-a-hop size, 1023 / 1024 / 1025 lie around the slot edge of its 1024 threads, 131 769 is 697 rows into the second grid-stride
+# trip of k_clearance_finish (and 4 n far into that of the steps and the rounds), 14 641 and the 41 x 25 map are the large and the
+# small map of tests/test_gpu_scratch_reuse.py.  The short walls stand near a corner, so that the far corner is many hops away.
+LATTICES = {
+    1023: (31, 33, wall([1], range(1, 4))),
+    1024: (32, 32, wall([1], range(1, 4))),
+    1025: (25, 41, wall([1], range(1, 4))),
+    2048: (32, 64, wall([1], range(1, 4))),          # kWalkTableRowsPerWaypoint: the walk's table choice at T = 1, to the row
+    9216: (96, 96, wall([1], range(1, 4))),
+    9217: (13, 709, wall([1], range(1, 4))),
+    131769: (363, 363, wall([60], range(40, 300)) | wall(range(150, 330), [200])),
+    14641: (121, 121, wall([60], range(10, 111)) | wall(range(5, 40), [30])),
+    "41x25": (41, 25, wall(range(8, 30), [12])),
+}
+
+
+def lattice(name, P=None):
+    W, H, walls = LATTICES[name]
+    return lattice_cloud(W, H, walls, P)
+
+
 class Field:
     """The step graph of the exported rows for one robot; the answers per (sources, max_hops)."""
 

@@ -235,6 +235,68 @@ def test_converged_rounds_do_no_work():
     assert run(t, None, cr.BLOCKED, 3)["worked"] == 3
 
 
+LDS_ROWS = 9216              # kClrLdsRows
+_lattices = {}
+
+
+def lattice_field(name):
+    """a lattice of clearance_ref.LATTICES through the oracle -> (cells, restatement)"""
+    from oracle import oracle
+    from tests import frontier_ref as fr
+    if name not in _lattices:
+        cells = oracle.build_grid(cr.lattice(name, fr.P), fr.GL, fr.ZL, fr.IV, "slope", mode=oracle.MODE_INT_OPENMP)
+        _lattices[name] = (cells, cr.Field(cells))
+    return _lattices[name]
+
+
+def lattice_premises(name, cells, f):
+    """What the GPU tests on the lattice `name` take for granted, asserted on any build of it (the oracle's here, the device's there):
+    the exact row count, every row a slope, the angle margin, and per lattice that the answers it is there for are not vacuous."""
+    W, H, _ = cr.LATTICES[name]
+    n = int(cells["num_nodes"])
+    assert n == W * H and (n == name or isinstance(name, str)) and ((np.asarray(cells["flags"][:n]) & 2) != 0).all(), (name, n)
+    assert f.angle_margin_deg > MARGIN, (name, f.angle_margin_deg)
+    deep = f.clearance(cr.BLOCKED, 64)
+    hops = deep["hops"]
+    assert deep["counts"][0] > 0 and (hops == 0).any(), name
+    if name in (1023, 1024, 1025, 9216, 9217):
+        # k_clearance_wg's slot edges and its limit: rows far from the wall, the map's edge a barrier of its own, one hop alone
+        assert ((hops > 32) & (hops != cr.BEYOND)).any(), name
+        for mask in (cr.BLOCKED, cr.BLOCKED | cr.OPEN):
+            assert f.clearance(mask, 64)["counts"][2] >= 6 and f.clearance(mask, 1)["counts"][2] == 1, (name, mask)
+        assert (n <= LDS_ROWS) == (name != 9217) and (n == LDS_ROWS) == (name == 9216)
+        assert (name < 9216) or (hops == cr.BEYOND).any()
+    if name == 1025:
+        depth = int(f.clearance(cr.BLOCKED, 1024)["counts"][2])
+        assert 3 < depth and (depth + 3) | 1 <= 1024 and (f.clearance(cr.BLOCKED, depth - 1)["hops"] == cr.BEYOND).any()
+    if name == 2048:
+        assert n == 2048                                   # kWalkTableRowsPerWaypoint x T at T = 1
+    if name == 9217:
+        assert 2048 * 2 < n <= 2048 * 6                    # the walk's default: inline at T = 2, the table at T = 6
+    if name == 131769:
+        # the second trip of the grid-stride loops: rows 131 072 .. n - 1 (k_clearance_finish; quads 524 288 .. of the steps and rounds)
+        assert 4 * n > 2048 * 256 and n > 512 * 256
+        tail = hops[512 * 256:]
+        assert (tail == cr.BEYOND).any() and (tail != cr.BEYOND).any() and (hops[:512 * 256] == cr.BEYOND).any() and deep["counts"][2] == 64
+    if name == 14641:
+        assert n > LDS_ROWS and tuple(deep["counts"]) == (412, 14596, 64, 0)
+        assert f.clearance(cr.BLOCKED | cr.OPEN | cr.OVERHEAD, 7)["counts"][2] == 7
+    if name == "41x25":
+        assert tuple(deep["counts"]) == (68, 1025, 22, 0) and (f.clearance(cr.BLOCKED, 3)["hops"] == cr.BEYOND).any()
+
+
+@pytest.mark.parametrize("name", list(cr.LATTICES), ids=[str(k) for k in cr.LATTICES])
+def test_lattices_have_exact_row_counts_and_the_premises_of_the_gpu_tests(name):
+    """tests/clearance_ref.lattice_cloud through the oracle: W x H rows to the row, all slopes, 28.8 degrees from the angle gate, and
+    the fields the kernel-edge, scratch-reuse and poisoned tests of the GPU tier expect of them — checked where no GPU exists"""
+    cells, f = lattice_field(name)
+    lattice_premises(name, cells, f)
+    if name == 1024:                                       # the shim runs the kernels' per-row code on one of them
+        t = Table(cells["sx"], cells["sy"], cells["sz"], cells["flags"], np.ones(f.n), cells["mean"], cells["normal"], cells["rough"])
+        for mask, max_hops in ((cr.BLOCKED, 64), (cr.BLOCKED | cr.OPEN, 1)):
+            same(run(t, None, mask, max_hops), f.clearance(mask, max_hops), (name, mask, max_hops))
+
+
 def test_no_cpu_fallback_for_clearance(native_lib):
     import torch
     if torch.cuda.is_available():

@@ -2,7 +2,9 @@
 the device; hops, nearest, sides and counts are compared for equality with the restatement (tests/clearance_ref.py) on the handle's own
 export, every scene once with the one-workgroup kernel allowed and once without it.  Hand-drawn maps whose answer is known beforehand —
 a corridor between plateaus, two storeys, a low ceiling, a column taller than the step mask — then the site and the bridge, repeat
-calls and streams, crop and update, sentinel-filled outputs, the Python interface and every refused argument.  No tolerance anywhere:
+calls and streams, crop and update, sentinel-filled outputs, the Python interface and every refused argument; and lattices with exact
+row counts at the kernels' edges — the slots and the limit of the one-workgroup kernel, max_hops at 1, at 1024 and around the field's
+depth, the second trip of the grid-stride loops.  No tolerance anywhere:
 the one step that is not IEEE arithmetic is the gates' acosf, and every compared scene keeps its angle decisions more than 1e-3 degrees
 from the threshold."""
 import contextlib
@@ -114,6 +116,9 @@ def both_paths(m, f, mask=cr.BLOCKED, max_hops=32, what="", **kw):
         a = check(m, f, mask, max_hops, what=(what, "one workgroup"), **kw)
     with one_workgroup(False):
         b = check(m, f, mask, max_hops, what=(what, "a launch a hop"), **kw)
+    for k in a:
+        if k != "tails":
+            assert a[k].tobytes() == b[k].tobytes(), (what, k)
     return a
 
 
@@ -233,6 +238,74 @@ def test_site_scenes_are_the_restatement(name):
         got = both_paths(m, f, mask, what=(name, mask))
         assert got["counts"][0] > 50 and got["counts"][2] >= 3
     both_paths(m, f, cr.BLOCKED, max_hops=3, what=(name, "3 hops"))
+
+
+# ---- kernel-edge shapes: lattices with exact row counts (tests/clearance_ref.LATTICES) ------------------------------------------------
+
+def lattice(name):
+    """a lattice map -> (m, restatement, export); its premises (tests/test_clearance_host.lattice_premises, which the CPU tier asserts
+    on the oracle's build) asserted on the device's own rows when it is first drawn"""
+    from tests.test_clearance_host import lattice_premises
+    new = ("lattice", name) not in _scenes
+    m, f, cells = drawn(("lattice", name), lambda: cr.lattice(name, fr.P))
+    if new:
+        lattice_premises(name, cells, f)
+    return m, f, cells
+
+
+@pytest.mark.parametrize("rows,max_hops", [(r, h) for r in (1023, 1024, 1025, 9216, 9217) for h in (64, 1)])
+def test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel(rows, max_hops):
+    """gndt_api_clearance.hip `wg = ... n <= kClrLdsRows`, and k_clearance_wg's `row = threadIdx.x + j * kClrWgThreads; if (row >= n)
+    break` with its one-bit-a-slot `pending` and `fresh`: 1023 / 1024 / 1025 rows end a slot one thread short, exactly and one thread
+    into the next; 9216 rows use all 144 KB of keys with the flag words right behind them; 9217 is the first map that takes a launch
+    a hop whatever the option says (both_paths then runs that path twice)."""
+    m, f, cells = lattice(rows)
+    n = int(cells["num_nodes"])
+    assert n == rows and (n < LDS_ROWS if rows < 9216 else n == LDS_ROWS if rows == 9216 else n > LDS_ROWS)
+    for mask in (cr.BLOCKED, cr.BLOCKED | cr.OPEN):
+        got = both_paths(m, f, mask, max_hops, what=(rows, mask, max_hops))
+        want = f.clearance(mask, max_hops)
+        assert (got["hops"] == 0).any() and got["counts"][2] == want["counts"][2] and got["counts"][2] >= (6 if max_hops == 64 else 1)
+        if mask == cr.BLOCKED and max_hops == 64:
+            assert ((got["hops"] > 32) & (got["hops"] != cr.BEYOND)).any()
+        if max_hops == 1:
+            assert (got["hops"] == cr.BEYOND).any() and (got["hops"] == 1).any()
+
+
+def test_max_hops_of_one_the_limit_the_depth_one_less_and_an_odd_one_behind_it():
+    """gndt_api_clearance.hip `k_clearance_finish(key[F.max_hops & 1], ...)` and the `max_hops + 1` flag words: with an odd max_hops
+    behind the field's depth the rounds stop early and the answer is read from buffer 1, which the last working round has to have
+    brought up to date (clearance_round_stores); max_hops = 1024 clears and walks 1025 of the 1032 flag words; max_hops = depth makes
+    the last round the one that finds the last ring, depth - 1 leaves that ring out.  k_clearance_wg: `last`, its `fresh` copies."""
+    m, f, cells = lattice(1025)
+    full = f.clearance(cr.BLOCKED, 1024)
+    depth = int(full["counts"][2])
+    odd = (depth + 3) | 1
+    assert 3 < depth < odd - 1 and odd & 1 and odd <= 1024           # (round depth + 1 finds nothing: round depth + 2 <= odd never works)
+    for max_hops in (1, 1024, odd, depth, depth - 1, odd):
+        got = both_paths(m, f, cr.BLOCKED, max_hops, what=("max_hops", max_hops))
+        assert got["counts"][2] == min(max_hops, depth) and got["counts"][0] == full["counts"][0]
+        ring = full["hops"] == depth
+        assert ring.any() and ((got["hops"][ring] == cr.BEYOND).all() if max_hops < depth else (got["hops"][ring] == depth).all())
+        if max_hops >= depth:
+            assert np.array_equal(got["hops"], full["hops"]) and np.array_equal(got["nearest"], full["nearest"])
+    for on in (True, False):
+        with one_workgroup(on):
+            check(m, f, cr.BLOCKED, odd, host=True, what=("odd, host", on))
+
+
+def test_the_second_trip_of_the_grid_stride_loops():
+    """k_clearance_steps and k_clearance_round `for (t0 = blockIdx.x * blockDim.x; t0 < total; t0 += gsz)` with 2048 workgroups of 256
+    threads (four lanes a row), k_clearance_finish `row += gsz` with 512 (one lane a row): on 131 769 rows all three go 697 rows into
+    their second trip — ten workgroups of live quads, one with 228 live and 28 dead lanes around the quad exchange, the rest dead.
+    Those rows hold finite and BEYOND answers (lattice_premises)."""
+    m, f, cells = lattice(131769)
+    n = int(cells["num_nodes"])
+    assert 4 * n > 2048 * 256 and n > 512 * 256 and n > LDS_ROWS
+    for host in (False, True):
+        got = check(m, f, cr.BLOCKED, 64, host=host, what=("second trip", host))
+        tail = got["hops"][512 * 256:]
+        assert (tail == cr.BEYOND).any() and (tail != cr.BEYOND).any() and got["counts"][2] == 64
 
 
 def test_repeat_calls_and_a_second_stream_give_the_same_bytes_and_change_nothing():

@@ -13,6 +13,10 @@ poison) that runs the group's existing tests in-process — their references are
 children run one at a time, each under its group's time limit.  A child that is killed at its limit, ends by a signal, with status 134
 or 139, or reports an illegal memory access stops the tier: every case after it fails at once with "not started" and touches no GPU.
 
+The groups: the build, the geometric consumers, the statistical ones, the flood and what runs on it, and "reach" — the clearance field
+and the path walks, whose scratch is cut into regions by the row count on every call and whose flag words and key slots are cleared
+only in part (tests/test_gpu_clearance.py, tests/test_gpu_walk.py: the hand-drawn maps and the lattices of up to 1025 rows).
+
 hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground.  Nor are the
 blocked buckets: the smallest cloud that takes them has 1.1 M points (tests/blocked_scenes.py)."""
 import ctypes as C
@@ -30,8 +34,13 @@ if os.environ.get("GNDT_LIB_VARIANT"):
 
 BYTES = (0xA5, 0x7F)
 REUSE = "tests/test_gpu_scratch_reuse.py::"
+CLEARANCE = "tests/test_gpu_clearance.py::"
+WALK = "tests/test_gpu_walk.py::"
 # Existing GPU tests whose maps are hand-drawn or hold at most 60 000 points, that assert no wall-clock bound and record no hipGraph, and
-# the large-then-small tests of tests/test_gpu_scratch_reuse.py in the group of their consumer.
+# the large-then-small tests of tests/test_gpu_scratch_reuse.py in the group of their consumer.  The bound on the points keeps a child
+# short — poison_malloc fills and synchronises on every allocation, and a build's buffers grow with its cloud — and is no rule about
+# the maps: the 121 x 121 lattice of the reuse tests of "reach" has 131 770 points, one column each, builds in well under a second and
+# is admitted.  The site, the bridge, the 9216- and 9217-row lattices and the grid-stride cases stay out of "reach".
 # measured_s: the whole child (interpreter start to exit) on the MI355X under the regular library; limit_s: three times that, rounded up
 # to 10 s (poison_malloc adds a fill and a device synchronisation to every allocation).
 GROUPS = {
@@ -90,6 +99,35 @@ GROUPS = {
         REUSE + "test_plan",
         REUSE + "test_frontiers[reached]",
         REUSE + "test_frontiers[slopes]",
+    ]),
+    "reach": dict(measured_s=6.83, limit_s=30, ids=[
+        CLEARANCE + "test_corridor_between_plateaus",
+        CLEARANCE + "test_two_storeys_do_not_see_each_other",
+        CLEARANCE + "test_a_low_ceiling_is_a_barrier_for_the_robot_it_is_too_low_for",
+        CLEARANCE + "test_a_step_through_a_pit_column_taller_than_the_step_mask",
+        CLEARANCE + "test_outputs_are_optional_and_nothing_is_written_beyond_the_rows",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1023-64]",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1023-1]",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1024-64]",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1024-1]",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1025-64]",
+        CLEARANCE + "test_lattices_at_the_slot_edges_and_the_limit_of_the_one_workgroup_kernel[1025-1]",
+        CLEARANCE + "test_max_hops_of_one_the_limit_the_depth_one_less_and_an_odd_one_behind_it",
+        WALK + "test_corridor_along_across_and_out_of_the_end",
+        WALK + "test_a_step_through_a_pit_column_taller_than_the_step_mask",
+        WALK + "test_two_storeys_least_dz_and_a_tie_to_the_smaller_row[low]",
+        WALK + "test_two_storeys_least_dz_and_a_tie_to_the_smaller_row[high]",
+        WALK + "test_a_low_ceiling_stops_the_walk_only_when_asked",
+        WALK + "test_lattice_corners_zero_length_segments_and_the_codecs_edge",
+        WALK + "test_wave_and_workgroup_edges_of_K_terminators_and_strides[65-33-4]",
+        WALK + "test_wave_and_workgroup_edges_of_K_terminators_and_strides[64-1-3]",
+        WALK + "test_hops_and_min_hops_against_a_real_clearance_field",
+        WALK + "test_the_default_table_choice_at_its_threshold_to_the_row",
+        REUSE + "test_clearance[1]",
+        REUSE + "test_clearance[0]",
+        REUSE + "test_walk[1]",
+        REUSE + "test_walk[0]",
+        REUSE + "test_clearance_then_walk_share_nothing",
     ]),
 }
 

@@ -12,6 +12,10 @@ rows to the bit, in buffers that never held anything else.  Each test asserts th
 themselves: their keys, counts, first-seen indices and tallies are compared exactly across the two handles, their sums by the
 restatement's derived bound on either handle.
 
+The clearance field and the path walks take lattice maps instead of the box (121 x 121 cells with two walls, then 41 x 25 with one,
+cropped by a column line on either side; tests/clearance_ref.LATTICES), on which a field is tens of hops deep and walks are long;
+their small answers equal the restatements exactly, and one test runs both consumers in turn on one used handle.
+
 Every test asserts that it is not vacuous: the small call has matches / hits / routes / clusters, and fewer than the large one."""
 import numpy as np
 import pytest
@@ -20,6 +24,7 @@ from grid_ndt_amd import scenes
 from oracle import oracle
 from tests import cast_ref as cf
 from tests import clear_ref as cr
+from tests import clearance_ref as clr
 from tests import coarsen_ref as cor
 from tests import frontier_ref as fr
 from tests import plan_ref as pr
@@ -28,6 +33,7 @@ from tests import raster_ref as rr
 from tests import score_derivs_ref as dr
 from tests import score_maps_ref as mr
 from tests import score_ref as sr
+from tests import walk_ref as wr
 
 pytestmark = pytest.mark.gpu
 
@@ -79,11 +85,11 @@ def _np(v):
     return v.cpu().numpy() if hasattr(v, "cpu") else v
 
 
-def _handle(P=BOX):
+def _handle(P=BOX, origin=None):
     import grid_ndt_amd as g
     m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=ATOMIC)
     m.setInterval(P["slope_interval"])
-    m.setCloudFirst(_origin())
+    m.setCloudFirst(_origin() if origin is None else origin)
     return m
 
 
@@ -126,21 +132,26 @@ def _same_map(a, b, what):
     return ea
 
 
-def _shrink(a, n_large):
-    """The used handle `a` is rebuilt from every eighth point and cropped to one quadrant -> (a fresh handle holding the same map, that
-    map's export).  n_large: the node count `a` held before."""
-    small = _small_body()
+def _shrink_to(a, small, crop, P=BOX, origin=None):
+    """The used handle `a` is rebuilt from the points `small` and cropped to the box `crop` -> (a fresh handle holding the same map —
+    given `a`'s own statistics — and that map's export)."""
     a.create2DMap("slope", _dev(small))
     st = {k: v.clone() for k, v in a.stats_export().items()}
-    b = _handle()
+    b = _handle(P, origin)
     b.reset("slope")
     b.stats_merge(st["key"], st["sums"], st["count"], st["first_idx"])
     b.accumulate("slope", _dev(np.zeros((0, 3), np.float32)), first_idx_base=len(small))     # (the stream position of `a`)
     b.finalize()
     _same_map(a, b, "rebuilt")
     for m in (a, b):
-        m.crop_box(QUADRANT, "keep_inside")
-    cells = _same_map(a, b, "cropped")
+        m.crop_box(crop, "keep_inside")
+    return b, _same_map(a, b, "cropped")
+
+
+def _shrink(a, n_large):
+    """The used handle `a` is rebuilt from every eighth point and cropped to one quadrant -> (a fresh handle holding the same map, that
+    map's export).  n_large: the node count `a` held before."""
+    b, cells = _shrink_to(a, _small_body(), QUADRANT)
     assert 100 < cells["num_nodes"] < n_large // 2 and (cells["sx"] >= 1).all() and (cells["sy"] >= 1).all()
     assert ((cells["flags"] & 1) != 0).sum() > 50 and ((cells["flags"] & 2) != 0).sum() > 20
     return b, cells
@@ -592,3 +603,149 @@ def test_merge():
     assert ea["num_nodes"] == eb["num_nodes"] == a.sync()[0] == len(want["key"])
     for k in ("sx", "sy", "sz", "count", "first_idx"):
         assert np.array_equal(ea[k], eb[k]), k
+
+
+# ---- the clearance field, path walks -------------------------------------------------------------------------------------------------
+# The box is useless here: its field is at most 2 hops deep on the large map and 1 on the small one, and no walk on it takes more than
+# 10 steps.  Lattices instead (tests/clearance_ref.LATTICES; the CPU tier asserts their premises on the oracle's builds): the large map
+# 121 x 121 cells with two walls — 14 641 rows, more than k_clearance_wg holds, so the large call takes a launch a hop whatever the
+# option says — the small one 41 x 25 with one wall, cropped by a column line on either side of x: 975 rows.  The pointers into
+# h->clearance.scratch and h->walk.scratch (gndt_api_clearance.hip, gndt_api_walk.hip: steps | keys | flags | tall) are computed from
+# n, so on the used handle every region of the small call lies on another region's bytes of the large one.
+
+LAT = fr.P
+LAT_CROP = (2, 40, -4096, 4096)
+OTHER_ROBOT = dict(reachable_height=0.05)
+
+
+def _lattice_body(name):
+    if ("lattice", name) not in _cache:
+        cloud = clr.lattice(name, LAT)
+        assert cloud[0].tobytes() == fr.ORIGIN.tobytes()
+        _cache[("lattice", name)] = cloud[1:]
+    return _cache[("lattice", name)]
+
+
+def _lattice_large():
+    """-> (a handle that holds the large lattice, its export, its restatement)"""
+    a = _handle(LAT, fr.ORIGIN)
+    a.create2DMap("slope", _dev(_lattice_body(14641)))
+    a.sync()
+    cells = a.export()
+    f = clr.Field(cells)
+    assert cells["num_nodes"] == 14641 > 9216 and ((cells["flags"] & 2) != 0).all() and f.angle_margin_deg > 1e-3
+    return a, cells, f
+
+
+def _lattice_small(a):
+    b, cells = _shrink_to(a, _lattice_body("41x25"), LAT_CROP, LAT, fr.ORIGIN)
+    assert cells["num_nodes"] == 39 * 25 and ((cells["flags"] & 2) != 0).all() and cells["sx"].min() == 2 and cells["sx"].max() == 40
+    return b, cells
+
+
+def _lattice_paths(cells, K, seed, reach):
+    from tests.test_walk_host import random_paths
+    on = cells["mean"][(cells["flags"] & 2) != 0]
+    return random_paths(np.random.default_rng(seed), K, 6, on[:, :2].min(0), on[:, :2].max(0), 0.0, 0.1, reach=reach, on=on)
+
+
+def _field(got):
+    return {k: got[k] for k in ("hops", "nearest", "sides", "counts")}
+
+
+@pytest.mark.parametrize("one_workgroup", [1, 0])
+def test_clearance(one_workgroup):
+    """gndt_api_clearance.hip `key[1] = key[0] + n; flags = ...(key[1] + n); tall = ...(flags + kFlagWords)` and `if (!wg)
+    hipMemsetAsync(flags, 0, (max_hops + 1) * 4)`: after the large call the small call's keys lie on old steps, its flags on old keys,
+    its tall bytes on old keys; the one-workgroup kernel (option 1: 975 rows fit) clears no flag word at all."""
+    import tests.test_gpu_clearance as tgc
+    with tgc.one_workgroup(bool(one_workgroup)):
+        a, big, fl = _lattice_large()
+        for host in (False, True):
+            large = tgc.check(a, fl, clr.BLOCKED, 64, host=host, what=("large", host))
+            tgc.check(a, fl, clr.BLOCKED | clr.OPEN | clr.OVERHEAD, 7, host=host, what=("large, 7 hops", host))
+        assert tuple(large["counts"]) == (412, 14596, 64, 0)
+        b, cells = _lattice_small(a)
+        fs = clr.Field(cells)
+        assert fs.angle_margin_deg > 1e-3 and cells["num_nodes"] < big["num_nodes"] // 8
+        for max_hops in (3, 64):
+            got = tgc.check(a, fs, clr.BLOCKED, max_hops, what=("small", max_hops))
+            for host in (False, True):
+                (ra, ga), (rb, gb) = tgc.raw(a, clr.BLOCKED, max_hops, host=host), tgc.raw(b, clr.BLOCKED, max_hops, host=host)
+                assert ra == rb == 0 and tgc.untouched(ga) and tgc.untouched(gb)
+                _same_bytes(_field(ga), _field(gb), ("clearance", max_hops, host))
+                _same_bytes(_field(ga), _field(got), ("clearance, the restatement's", max_hops, host))
+            assert 0 < got["counts"][1] < large["counts"][1] and got["counts"][0] > 0
+            assert (got["hops"] == clr.BEYOND).any() if max_hops == 3 else got["counts"][2] >= 10
+
+
+@pytest.mark.parametrize("table", [1, 0])
+def test_walk(table):
+    """gndt_api_walk.hip `key0 = ...(step + 4 * n); flag = ...(key0 + n); tall = ...(flag + 2)` in h->walk.scratch, which only the
+    table variant touches (option 1), and stage_pieces' staging area, which both host entry points share: a large batch with the
+    large map's field, then 37 paths with the small map's.  (With min_hops = 2 no walk is ever BLOCKED — a slope beside a blocked side
+    has hops 0 and ends the walk one step earlier — so the large batch is also walked without a limit.)"""
+    import tests.test_gpu_walk as tgw
+    with tgw.step_table(bool(table)):
+        a, big, fl = _lattice_large()
+        field = a.clearance(max_hops=64)
+        paths_large = _lattice_paths(big, LARGE, 11, 3.0)
+        dev = _np(a.walk_paths(_dev(paths_large), hops=field, min_hops=2, rows=4))
+        _same_bytes(dev, a.walk_paths(paths_large, hops=field, min_hops=2, rows=4, host=True), "large, host")
+        assert {wr.DONE, wr.TOO_CLOSE, wr.LEFT_MAP} <= set(dev["status"].tolist())
+        free = _np(a.walk_paths(_dev(paths_large), hops=field, rows=4))
+        assert {wr.DONE, wr.BLOCKED} <= set(free["status"].tolist()) and free["steps"].max() > 10
+        b, cells = _lattice_small(a)
+        fa, fb = _np(a.clearance()), _np(b.clearance())
+        _same_bytes(fa, fb, "the small field")
+        hops = fa["hops"].view(np.uint32)
+        assert np.array_equal(hops, clr.Field(cells).clearance(clr.BLOCKED, 32)["hops"])
+        paths = _lattice_paths(cells, SMALL, 12, 1.5)
+        for robot in (None, OTHER_ROBOT):
+            w = wr.Walker(cells, fr.ORIGIN, fr.GL, fr.ZL, robot)
+            assert w.f.angle_margin_deg > 1e-3
+            want_info, want_rows, _ = w.walk(paths, hops=hops, min_hops=2, row_cap=6)
+            for host in (False, True):
+                ra = tgw.raw(a, paths, robot=robot, hops=hops, min_hops=2, row_cap=6, host=host)
+                rb = tgw.raw(b, paths, robot=robot, hops=hops, min_hops=2, row_cap=6, host=host)
+                assert ra[0] == rb[0] == 0 and ra[3] and rb[3], (robot, host)
+                assert ra[1].tobytes() == rb[1].tobytes() and ra[2].tobytes() == rb[2].tobytes(), (robot, host)
+                wr.same(ra[1], ra[2], want_info, want_rows, ("reuse", robot, host))
+            seen = set(want_info["status"].tolist())
+            assert len(seen) >= 3 and {wr.DONE, wr.TOO_CLOSE} <= seen and want_info["steps"].max() > 3, seen
+
+
+def test_clearance_then_walk_share_nothing():
+    """gndt_handle.hpp's h->clearance.scratch and h->walk.scratch are two areas: a walk through the table (k_clearance_steps into the
+    walk's own steps, keys and flag) between two clearance calls changes nothing for them, and a clearance call between two walks
+    nothing for those — on a handle on which both have held the large map's tables."""
+    import tests.test_gpu_clearance as tgc
+    import tests.test_gpu_walk as tgw
+    a, big, fl = _lattice_large()
+    large = tgc.check(a, fl, clr.BLOCKED, 64, what="large")
+    with tgw.step_table(True):
+        info = _np(a.walk_paths(_dev(_lattice_paths(big, LARGE, 11, 3.0)), hops=large["hops"].view(np.int32), rows=4))
+    assert {wr.DONE, wr.BLOCKED} <= set(info["status"].tolist())
+    b, cells = _lattice_small(a)
+    fs = clr.Field(cells)
+    w = wr.Walker(cells, fr.ORIGIN, fr.GL, fr.ZL, field=fs)
+    assert fs.angle_margin_deg > 1e-3
+    paths = _lattice_paths(cells, SMALL, 12, 1.5)
+
+    def walk(table, hops, min_hops):
+        want_info, want_rows, _ = w.walk(paths, hops=hops, min_hops=min_hops, row_cap=6)
+        with tgw.step_table(table):
+            rc, got_info, got_rows, untouched = tgw.raw(a, paths, hops=hops, min_hops=min_hops, row_cap=6)
+        assert rc == 0 and untouched
+        wr.same(got_info, got_rows, want_info, want_rows, ("share nothing", table))
+        assert {wr.DONE, wr.TOO_CLOSE} <= set(want_info["status"].tolist())
+
+    first = tgc.check(a, fs, clr.BLOCKED, 64, what="first")
+    walk(True, first["hops"], 2)
+    second = tgc.check(a, fs, clr.BLOCKED | clr.OPEN, 5, what="second")
+    rc, other = tgc.raw(b, clr.BLOCKED | clr.OPEN, 5)
+    assert rc == 0
+    _same_bytes(_field(second), _field(other), "the second field")
+    assert (second["hops"] == clr.BEYOND).any() and second["counts"][0] > first["counts"][0]
+    walk(False, second["hops"], 1)
+    _same_bytes(_field(tgc.check(a, fs, clr.BLOCKED, 64, what="again")), _field(first), "the first field again")

@@ -4,7 +4,8 @@ both kernel variants (the step found with the gates, the step read from the per-
 over-allocated with a sentinel tail that must stay untouched.  Hand-drawn maps whose answer is known beforehand — a corridor between
 plateaus, a pit column taller than the step mask, two storeys with an exact tie, a low ceiling — then wave and workgroup edges of K,
 terminators, strides, row caps, the codec's edge, the step guard, a real clearance field, crop / update / another robot, a second
-stream, the Python interface and every refused argument.  No tolerance anywhere: the one step that is not IEEE arithmetic is the
+stream, the Python interface and every refused argument; more paths than one trip of the kernel's grid-stride loop, and the table
+choice left at its default on both sides of its threshold and at it.  No tolerance anywhere: the one step that is not IEEE arithmetic is the
 gates' acosf, and every compared scene keeps its angle decisions more than 1e-3 degrees from the threshold."""
 import contextlib
 import ctypes as C
@@ -276,6 +277,93 @@ def test_wave_and_workgroup_edges_of_K_terminators_and_strides(K, T, sf):
     assert info["status"][0] != wr.NO_START
     if T > 2 and K > 4:
         assert info["waypoints"][4] <= 1 and info["waypoints"][3] <= T // 2
+
+
+def test_more_paths_than_one_trip_of_the_grid_stride_loop():
+    """k_walk_paths `for (p = blockIdx.x * blockDim.x + threadIdx.x; p < K; p += gsz)` with at most 8192 workgroups of 64 lanes: 65
+    paths more than one trip holds, so one wavefront and one lane of a second come round again.  The batch repeats 4099 distinct
+    paths (a prime: no repeat shares its lane with its original), the restatement walks those once and is tiled the same way."""
+    from tests.test_walk_host import random_paths
+    m, w, cells = drawn("ground", _ground)
+    D, K = 4099, 8192 * 64 + 65
+    assert K > 8192 * 64
+    base = random_paths(np.random.default_rng(4099), D, 2, (-3.0, -3.0), (3.0, 3.0), 0.1, 0.2, reach=0.9)
+    assert len(np.unique(base.reshape(D, -1).view(np.uint32), axis=0)) == D
+    paths = np.resize(base, (K, 2, 3))
+    assert paths[D].tobytes() == base[0].tobytes() and paths[K - 1].tobytes() == base[(K - 1) % D].tobytes()
+    info_d, rows_d, _ = w.walk(base, row_cap=1)
+    tile = np.arange(K) % D
+    want_info, want_rows = info_d[tile], rows_d[tile]
+    assert {wr.DONE, wr.LEFT_MAP} <= set(info_d["status"].tolist()) and info_d["steps"].max() >= 2
+    for table in (False, True):
+        with step_table(table):
+            rc, info, rows, untouched = raw(m, paths, row_cap=1)
+        assert rc == 0 and untouched, table
+        assert info[:K - D].tobytes() == info[D:].tobytes() and rows[:K - D].tobytes() == rows[D:].tobytes(), table
+        wr.same(info, rows, want_info, want_rows, ("grid stride", table))
+
+
+def _three_ways(m, w, paths, what, **kw):
+    """one call with the table option at its default, against the restatement; the same call forced to either variant: the same bytes"""
+    want_info, want_rows, _ = w.walk(paths, **kw)
+    rc, info, rows, untouched = raw(m, paths, **kw)
+    assert rc == 0 and untouched, (what, m._L.gndt_last_error(m._h))
+    wr.same(info, rows, want_info, want_rows, (what, "default"))
+    for table in (False, True):
+        with step_table(table):
+            rc, i2, r2, untouched = raw(m, paths, **kw)
+        assert rc == 0 and untouched and i2.tobytes() == info.tobytes() and r2.tobytes() == rows.tobytes(), (what, table)
+    return want_info
+
+
+def _lattice_paths(cells, K, seed, reach):
+    from tests.test_walk_host import random_paths
+    on = cells["mean"][(cells["flags"] & 2) != 0]
+    return random_paths(np.random.default_rng(seed), K, 2, on[:, :2].min(0), on[:, :2].max(0), 0.0, 0.1, reach=reach, on=on)
+
+
+def test_the_default_table_choice_on_both_sides_of_its_threshold():
+    """gndt_api_walk.hip `table = ... mode == 2 && n <= kWalkTableRowsPerWaypoint * T`, with the option left at its default of 2: on
+    9217 rows T = 2 walks inline (n > 4096) and T = 6 through the table (n <= 12288).  The T = 6 paths are the T = 2 ones with the
+    last waypoint repeated.  Every other comparing test forces the option."""
+    m, w, cells = drawn("lattice 9217", lambda: cr.lattice(9217, fr.P))
+    n = int(cells["num_nodes"])
+    assert n == 9217 and 2048 * 2 < n <= 2048 * 6
+    p2 = _lattice_paths(cells, 96, 17, 2.5)
+    p6 = np.ascontiguousarray(np.concatenate([p2, np.repeat(p2[:, 1:], 4, axis=1)], axis=1))
+    assert p6.shape == (96, 6, 3)
+    i2 = _three_ways(m, w, p2, "T = 2: inline", row_cap=4)
+    i6 = _three_ways(m, w, p6, "T = 6: the table", row_cap=4)
+    assert {wr.DONE, wr.LEFT_MAP} <= set(i2["status"].tolist()) and i2["steps"].max() >= 4
+    for k in ("status", "steps", "end_row", "length"):
+        assert np.array_equal(i2[k], i6[k]), k              # (padding changes `waypoints` alone)
+
+
+def test_the_default_table_choice_at_its_threshold_to_the_row():
+    """gndt_api_walk.hip `n <= kWalkTableRowsPerWaypoint * T` at equality: 2048 rows and T = 1 take the table by the `=`, and so do the
+    2047 rows left when one column is dropped; both against the restatement and the forced variants.  Under the poisoned variant of
+    the library (tests/test_gpu_poisoned.py), which counts what it allocates, the default call at equality is also seen to make the
+    table: the walk's scratch of 41 bytes a row and 8 is the one allocation between an inline call and it."""
+    import grid_ndt_amd as g
+    from grid_ndt_amd import _lib
+    m = _build(cr.lattice(2048, fr.P), fr.P)
+    for left in (2048, 2047):
+        cells = m.export()
+        n = int(cells["num_nodes"])
+        assert n == left and ((cells["flags"] & 2) != 0).all() and (n == 2048 * 1 if left == 2048 else n < 2048 * 1)
+        w = wr.Walker(cells, fr.ORIGIN, fr.P["grid_len"], fr.P["z_len"])
+        assert w.f.angle_margin_deg > MARGIN
+        paths = np.ascontiguousarray(_lattice_paths(cells, 96, left, 1.0)[:, :1])
+        if _lib.VARIANT == "poison" and left == 2048:
+            with step_table(False):
+                assert raw(m, paths)[0] == 0                # (the column index is made here)
+            before = g.TwoDmap.poisoned_bytes()[0]
+            assert raw(m, paths)[0] == 0
+            assert g.TwoDmap.poisoned_bytes()[0] - before == n * 41 + 8
+        info = _three_ways(m, w, paths, ("T = 1", left), row_cap=2)
+        assert {wr.DONE, wr.NO_START} <= set(info["status"].tolist()) and (info["steps"] == 0).all()
+        if left == 2048:
+            m.crop_box((5, 5, 7, 7), "drop_inside")
 
 
 def test_hops_and_min_hops_against_a_real_clearance_field():
