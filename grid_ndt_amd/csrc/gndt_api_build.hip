@@ -170,7 +170,7 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     // partition (large clouds), never for records / statistics / a re-run after a blocked attempt failed.
     // (not under hipGraph capture either: a recorded build is replayed on OTHER clouds, and one that leaves the box cannot be re-run)
     const bool blocked = tuning().blocked && q.blk_state == 1 && !P.no_block && !P.records && !P.stats_only && attempt == 0 && !h->capturing && !P.captured &&
-                         !tuning().bucket_slots && q.two_level_ok && n >= (1u << 20) &&
+                         !tuning().bucket_slots && q.two_level_ok && n >= tuning().blocked_min_points &&
                          h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && n <= q.blk_n + q.blk_n / 4 && n + n / 4 >= q.blk_n;
     P.blocked = blocked;
     if (blocked) gp.blk = q.blk_map;

@@ -33,6 +33,9 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_PLAN_LDS_ENTRIES:
             if (!(value >= 64.0 && value <= 1024.0) || value != (double)(int)value || ((int)value & 63)) return GNDT_ERR_INVALID;
             t.plan_lds_entries = (int)value; return GNDT_OK;
+        case GNDT_DEBUG_BLOCKED_MIN_POINTS:
+            if (!(value >= 65536.0 && value <= 1048576.0) || value != (double)(int)value) return GNDT_ERR_INVALID;
+            t.blocked_min_points = (uint32_t)value; return GNDT_OK;
 #ifdef GNDT_POISON
         case GNDT_DEBUG_POISON_BYTE:
             if (!(value >= 0.0 && value <= 255.0) || value != (double)(int)value) return GNDT_ERR_INVALID;

@@ -430,6 +430,7 @@ struct Tuning {
     int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE           gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
+    uint32_t blocked_min_points = 1u << 20;   // GNDT_DEBUG_BLOCKED_MIN_POINTS   points from which a build may take BLOCKED buckets (65 536 .. 2^20; tests lower it)
 };
 const Tuning& tuning();
 void tuning_force_stamps(bool on);   // bench.py --stamps flips this after the timed run

@@ -517,6 +517,7 @@ class TwoDmap:
     DEBUG_POISON_BYTE = 7      # the poisoned variant of the library only (_lib.VARIANTS); the product answers GNDT_ERR_INVALID
     DEBUG_CLEARANCE_ONE_WORKGROUP = 8
     DEBUG_WALK_STEP_TABLE = 9
+    DEBUG_BLOCKED_MIN_POINTS = 10   # points from which a build may take blocked buckets: 65 536 .. 1 048 576 (the default; tests lower it)
 
     @staticmethod
     def set_debug_option(option, value):

@@ -1202,7 +1202,10 @@ int gndt_debug_enable_stamps(int on);
  *   GNDT_DEBUG_WALK_STEP_TABLE    value == 1: gndt_walk_paths* first make a per-side steps table of the whole map (the clearance
  *                                 field's first pass) and read every step of every walk from it; 0: a walk finds its steps itself,
  *                                 gates included (tests run the walks both ways); 2: the table for a map of up to 2048 rows per
- *                                 waypoint of a path (num_nodes <= 2048 T), where it was measured faster          default 2 */
+ *                                 waypoint of a path (num_nodes <= 2048 T), where it was measured faster          default 2
+ *   GNDT_DEBUG_BLOCKED_MIN_POINTS points from which a build may take BLOCKED buckets (GNDT_STRATEGY_PARTITION_BLOCKED), an integer in
+ *                                 65 536 .. 1 048 576.  A tuning choice of the host, not a limit of the kernel: tests lower it and ask
+ *                                 for GNDT_STRATEGY_PARTITION_TWO_LEVEL to reach the blocked kernel with small clouds  default 1 048 576 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1212,6 +1215,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_POISON_BYTE 7
 #define GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP 8
 #define GNDT_DEBUG_WALK_STEP_TABLE 9
+#define GNDT_DEBUG_BLOCKED_MIN_POINTS 10
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */

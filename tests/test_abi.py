@@ -65,9 +65,13 @@ def test_library_reads_no_environment_variable_and_options_are_calls(native_lib)
     import grid_ndt_amd as g
     T = g.TwoDmap
     for opt, val in ((T.DEBUG_VERBOSE, 1), (T.DEBUG_VERBOSE, 0), (T.DEBUG_TILE_RATIO, 32.0), (T.DEBUG_TILE_RATIO, 48.0),
-                     (T.DEBUG_COST_ONE_WORKGROUP, 0), (T.DEBUG_COST_ONE_WORKGROUP, 1)):
+                     (T.DEBUG_COST_ONE_WORKGROUP, 0), (T.DEBUG_COST_ONE_WORKGROUP, 1),
+                     (T.DEBUG_BLOCKED_MIN_POINTS, 65536), (T.DEBUG_BLOCKED_MIN_POINTS, 131072), (T.DEBUG_BLOCKED_MIN_POINTS, 1 << 20)):
         T.set_debug_option(opt, val)
-    for opt, val in ((0, 1), (99, 1), (T.DEBUG_TILE_RATIO, 0.5), (T.DEBUG_TILE_RATIO, float("nan"))):
+    assert T.DEBUG_BLOCKED_MIN_POINTS == 10
+    for opt, val in ((0, 1), (99, 1), (T.DEBUG_TILE_RATIO, 0.5), (T.DEBUG_TILE_RATIO, float("nan")),
+                     (T.DEBUG_BLOCKED_MIN_POINTS, 65535), (T.DEBUG_BLOCKED_MIN_POINTS, (1 << 20) + 1), (T.DEBUG_BLOCKED_MIN_POINTS, 1.5),
+                     (T.DEBUG_BLOCKED_MIN_POINTS, 131072.5), (T.DEBUG_BLOCKED_MIN_POINTS, float("nan")), (T.DEBUG_BLOCKED_MIN_POINTS, -1)):
         with pytest.raises(g.GndtError) as e:
             T.set_debug_option(opt, val)
         assert e.value.code == 1   # GNDT_ERR_INVALID

@@ -17,8 +17,13 @@ The groups: the build, the geometric consumers, the statistical ones, the flood 
 and the path walks, whose scratch is cut into regions by the row count on every call and whose flag words and key slots are cleared
 only in part (tests/test_gpu_clearance.py, tests/test_gpu_walk.py: the hand-drawn maps and the lattices of up to 1025 rows).
 
-hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground.  Nor are the
-blocked buckets: the smallest cloud that takes them has 1.1 M points (tests/blocked_scenes.py)."""
+The group "blocked" is the blocked bucket kernel (gndt_blocked.hpp) reached with 131 072-point boxes through the lowered floor
+(tests/test_gpu_blocked_small.py): three block shapes, four fuzzed boxes and the layout's lifetime on one handle — Part::raw, the
+order arrays, the buckets' ranges, both cursor levels, the extent words of blocked_decide, the re-run after a miss and the one after the
+staging rows ran out, on poisoned memory.  Its large-then-small test stays out: a 1.1 M-point build would spend the child's time in
+poison_malloc's fills.
+
+hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground."""
 import ctypes as C
 import json
 import os
@@ -36,6 +41,7 @@ BYTES = (0xA5, 0x7F)
 REUSE = "tests/test_gpu_scratch_reuse.py::"
 CLEARANCE = "tests/test_gpu_clearance.py::"
 WALK = "tests/test_gpu_walk.py::"
+BLOCKED_SMALL = "tests/test_gpu_blocked_small.py::"
 # Existing GPU tests whose maps are hand-drawn or hold at most 60 000 points, that assert no wall-clock bound and record no hipGraph, and
 # the large-then-small tests of tests/test_gpu_scratch_reuse.py in the group of their consumer.  The bound on the points keeps a child
 # short — poison_malloc fills and synchronises on every allocation, and a build's buffers grow with its cloud — and is no rule about
@@ -128,6 +134,17 @@ GROUPS = {
         REUSE + "test_walk[1]",
         REUSE + "test_walk[0]",
         REUSE + "test_clearance_then_walk_share_nothing",
+    ]),
+    "blocked": dict(measured_s=5.23, limit_s=20, ids=[
+        BLOCKED_SMALL + "test_every_block_shape_small[flat_1-slope]",
+        BLOCKED_SMALL + "test_every_block_shape_small[levels_4_at_interval-slope]",
+        BLOCKED_SMALL + "test_every_block_shape_small[levels_32_moved_origin-slope]",
+        BLOCKED_SMALL + "test_fuzzed_boxes[108]",
+        BLOCKED_SMALL + "test_fuzzed_boxes[133]",
+        BLOCKED_SMALL + "test_fuzzed_boxes[142]",
+        BLOCKED_SMALL + "test_fuzzed_boxes[232]",
+        BLOCKED_SMALL + "test_staging_rows_run_out_inside_a_small_blocked_build",
+        BLOCKED_SMALL + "test_layout_lifetime_on_one_handle",
     ]),
 }
 
