@@ -11,8 +11,10 @@ namespace gndt_host {
 
 // prefix of the per-word column weights -> row of every staged node -> SoA rows (marks m0+1 .. m0+5)
 // `grouped`: the staging rows of a column are adjacent (k_bucket_direct): the destination pass works per column
+// `col_records`: records of Part::col_tab that k_bucket_blocked has just written (0: none — the pass finds the columns among the nodes);
+//                only with words > Tuning::place_emit_words: k_place_emit_rows reads ord_cf, which such a bucket kernel does not write
 int launch_order_and_emit(gndt_handle* h, uint64_t words, int m0, hipStream_t s, bool grouped, bool counters_to_host, bool tab_end, uint32_t advance,
-                          bool partial) {
+                          bool partial, uint32_t col_records) {
     auto& q = h->part;
     // (small clouds, staging rows grouped by column: the destination pass scans the word weights itself — gndt_partition.hpp)
     const bool dest_scans = grouped && !partial && !tab_end && words <= kDestScanMax && tuning().dest_scans;
@@ -48,7 +50,13 @@ int launch_order_and_emit(gndt_handle* h, uint64_t words, int m0, hipStream_t s,
         mark(h, m0 + 5, s);
         return GNDT_OK;
     }
-    if (grouped && dest_scans)
+    if (grouped && col_records && dest_scans)       // (a BLOCKED build: one thread per record of the bucket kernel's column table)
+        hipLaunchKernelGGL(k_order_dest_table<true>, dim3(grid_for(col_records)), dim3(kBlock), 0, s, (const uint4*)q.col_tab, col_records, q.bitmap, q.word_base,
+                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+    else if (grouped && col_records)
+        hipLaunchKernelGGL(k_order_dest_table<false>, dim3(grid_for(col_records)), dim3(kBlock), 0, s, (const uint4*)q.col_tab, col_records, q.bitmap, q.word_base,
+                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+    else if (grouped && dest_scans)
         hipLaunchKernelGGL(k_order_dest_columns<true>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
                            q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
     else if (grouped)
@@ -238,6 +246,14 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         if ((rc = ensure_raw(h, std::max<uint64_t>(P.rows_floor, nodes_est + nodes_est / 8)))) return rc;
         if ((rc = ensure_out(h, q.stage_cap))) return rc;
     }
+    // BLOCKED builds that order and emit in two kernels: the bucket kernel leaves a record per column of every block and the ordering
+    // pass runs over those (k_order_dest_table); it then writes neither ord_cf nor ord_idx.  Who reads those two arrays: k_order_dest,
+    // k_order_dest_columns and k_place_emit_rows (launch_order_and_emit: none of them is launched behind such a build — the small-cloud
+    // kernel is why `words` is looked at here) and the table path's own passes, which write both arrays themselves before every read
+    // (gndt_api_table.hip; the incremental finalisation keeps row_of, not them).  Nothing reads them after the build that wrote them.
+    const bool col_dest = blocked && tuning().column_dest && words > (uint64_t)tuning().place_emit_words;
+    const uint32_t col_records = col_dest ? q.blk_buckets << (q.blk_map.shx + q.blk_map.shy) : 0u;      // (at most 2^18 blocks of at most 2^9 columns)
+    if (col_dest && (rc = grow_buf(h, q.col_tab, q.col_tab_cap, (uint64_t)col_records))) return rc;
     BucketRanges ranges{nullptr, nullptr, nullptr, 0u};
     const float4* bucket_recs = nullptr;
     if (two) {
@@ -480,7 +496,7 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
                        RL_, TODO_)
         if (blocked)        // (gndt_blocked.hpp: a block of the box per bucket, the table addressed by the key)
             hipLaunchKernelGGL(k_bucket_blocked<512>, bgrid, dim3(512), 0, s, bucket_recs, ranges, B, gp, q.raw, (uint32_t)rows_cap, q.ord_cf, q.ord_idx, order,
-                               h->d_cnt, q.d_pc, dbg);
+                               h->d_cnt, q.d_pc, dbg, col_dest ? q.col_tab : (uint4*)nullptr);
         else if (bslots == 1024) { if (P.stats_only) GNDT_LAUNCH_DIRECT(1024, 1024, true, bgrid, (uint32_t*)nullptr, (const uint32_t*)nullptr); else GNDT_LAUNCH_DIRECT(1024, 1024, false, bgrid, (uint32_t*)nullptr, (const uint32_t*)nullptr); }
         else if (wide)
             hipLaunchKernelGGL((k_bucket_direct<GNDT_DIRECT_THREADS, 512, false, 1, 6>), bgrid, dim3(GNDT_DIRECT_THREADS), 0, s, bucket_recs, ranges, B, gp, q.raw,
@@ -496,7 +512,7 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     HIP_TRY(h, hipGetLastError());
     mark(h, 5, s);
     // (the counters and overflow flags come back with the last kernel: k_emit_rows stores them into the host's pinned mirrors)
-    if (!P.stats_only && (rc = launch_order_and_emit(h, words, 5, s, grouped, true))) return rc;
+    if (!P.stats_only && (rc = launch_order_and_emit(h, words, 5, s, grouped, true, false, 0u, false, col_records))) return rc;
     if (P.stats_only) {
         HIP_TRY(h, hipMemcpyAsync(q.h_pc, q.d_pc, sizeof(PartCounters), hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipMemcpyAsync(h->h_cnt, h->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, s));

@@ -36,6 +36,10 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_BLOCKED_MIN_POINTS:
             if (!(value >= 65536.0 && value <= 1048576.0) || value != (double)(int)value) return GNDT_ERR_INVALID;
             t.blocked_min_points = (uint32_t)value; return GNDT_OK;
+        case GNDT_DEBUG_COLUMN_DEST: if (!(value == 0.0 || value == 1.0)) return GNDT_ERR_INVALID; t.column_dest = value != 0.0; return GNDT_OK;
+        case GNDT_DEBUG_PLACE_EMIT_WORDS:
+            if (!(value >= 0.0 && value <= 16777216.0) || value != (double)(int)value) return GNDT_ERR_INVALID;
+            t.place_emit_words = (int)value; return GNDT_OK;
 #ifdef GNDT_POISON
         case GNDT_DEBUG_POISON_BYTE:
             if (!(value >= 0.0 && value <= 255.0) || value != (double)(int)value) return GNDT_ERR_INVALID;
@@ -133,7 +137,7 @@ int stage_pieces(gndt_handle* h, const uint64_t* bytes, void** piece, int count)
 void free_part(gndt_handle* h) {
     auto& q = h->part;
     void* ptrs[] = {q.recs, q.recs1, q.cursors, q.range_lo, q.range_hi, q.range_cap, q.hist, q.totals, q.bucket_base, q.stage, q.ord_cf, q.ord_idx, q.inv, q.row_of, q.row_ncol, q.raw,
-                    q.bitmap, q.word_weight, q.word_base, q.bsum_words, q.ncol_at, q.d_pc, q.dbg, q.cursors_alt, q.d_pc_alt};
+                    q.bitmap, q.word_weight, q.word_base, q.bsum_words, q.ncol_at, q.d_pc, q.dbg, q.cursors_alt, q.d_pc_alt, q.col_tab};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (q.h_pc) (void)hipHostFree(q.h_pc);

@@ -12,7 +12,7 @@
 // already 20 x the mean).  The host takes this kernel when the map of the previous build on the handle says so (partition_launch); a
 // record that does not belong to its bucket's block (the cloud outgrew the box) raises PartCounters::blk_miss and the build is
 // re-run with hashed buckets — the kernel is an optimisation of the same map, never another answer.
-// Same outputs as k_bucket_direct: RawNode staging rows (a column's rows adjacent, first-seen order), ord_cf / ord_idx, the columns'
+// Same outputs as k_bucket_direct: RawNode staging rows (a column's rows adjacent, first-seen order), ord_cf / ord_idx (or the column table in their place), the columns'
 // votes in the bitmap / word weights, node / column / slope counts.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -62,12 +62,23 @@ __device__ __forceinline__ uint32_t full_wave_scan_add(uint32_t x, uint32_t& tot
 // worked out.  (Built and measured on the way, profiles/r06_ablation.txt 8: the count
 // after the accumulate phase: ~5 k of 58 k cycles per bucket waiting; the rows of a bucket written behind the NEXT bucket's
 // accumulate phase from registers: slower — the held row spills, and every vector-memory wait that follows stores waits for them.)
+//
+// col_tab (nullable): the COLUMN TABLE, one 16-byte record {first-seen index, first staging row, nodes, 0} per column `col` of bucket
+// b at (b << (shx + shy)) + col, for the ordering pass that runs over columns (gndt_partition.hpp k_order_dest_table).  A block's
+// columns are known by position, so the table needs no reservation and no search.  With it the kernel writes neither ord_cf nor
+// ord_idx (who reads those: partition_launch, gndt_api_build.hip).  The table is NOT cleared between builds, a re-used handle holds
+// the last build's records: every bucket therefore writes ALL 2^(shx + shy) records of its block in every build — nodes = 0 for a
+// column without nodes (margin blocks and lo == hi take the ordinary path and write zeros' worth of columns), and zero records on
+// both early ways out (a record outside the block, the staging rows run out).  The grid stride covers every bucket, so the pass never
+// meets a record of another build and needs no flag to tell; what it reads of a build that is re-run is as consistent as its rows.
+// (Round 10 also sent the staging rows out through the dead record image, in whole lines: 1.7 us of the kernel, inside its run-to-run
+//  spread — built, measured, taken out again: profiles/r10_ablation.txt 2.)
 template <int T>
 __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) k_bucket_blocked(const float4* __restrict__ recs, BucketRanges ranges, uint32_t num_buckets, GridParams P,
                                                       RawNode* __restrict__ stage, uint32_t stage_cap,
                                                       uint32_t* __restrict__ ord_cf, uint32_t* __restrict__ ord_idx, ColumnOrder O,
                                                       Counters* __restrict__ cnt, PartCounters* __restrict__ pc,
-                                                      unsigned long long* __restrict__ dbg) {
+                                                      unsigned long long* __restrict__ dbg, uint4* __restrict__ col_tab) {
     static_assert(T == 512, "one table slot per thread");
     __shared__ BlockedLds L;
     const int tid = threadIdx.x;
@@ -199,6 +210,7 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         GNDT_STAMPB(2);
         if (L.miss) {                                  // (uniform)
             if (tid == 0) atomicAdd(&pc->blk_miss, 1u);
+            if (col_tab && s <= col_mask) col_tab[((size_t)bucket << sh_xy) + s] = make_uint4(zero, zero, zero, zero);      // (no columns: see col_tab above; `zero`: a constant vector would be hoisted out of the bucket loop and spill)
             lds_barrier();
             continue;
         }
@@ -255,10 +267,17 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
         const uint32_t sbase = L.stage_base;
         if (sbase + M > stage_cap) {                   // uniform: the staging rows ran out, the build is re-run with more
             if (tid == 0 && M) atomicAdd(&pc->stage_overflow, M);
+            if (col_tab && s <= col_mask) col_tab[((size_t)bucket << sh_xy) + s] = make_uint4(zero, zero, zero, zero);
             lds_barrier();
             continue;
         }
-        uint32_t my_slopes = 0;
+        uint32_t my_slopes = 0, cbase = 0;
+        if (live || s <= col_mask) {                    // the column's first row inside the bucket
+            cbase = L.cpre[col];
+            for (uint32_t w = 0; w < (col >> 6); ++w) cbase += L.wave_tot[w];      // (columns 64 .. 127 of a 128-column block: behind the first wave's)
+        }
+        // the column's record, by the thread of its level-0 slot, live or not (ncol = 0: the block has no such column)
+        if (col_tab && s <= col_mask) col_tab[((size_t)bucket << sh_xy) + s] = make_uint4(cfirst, sbase + cbase, ncol, 0u);
         if (live) {
             uint32_t fl = (my_n >= (uint32_t)P.min_points) ? 1u : 0u;
             if (fl) {
@@ -272,12 +291,12 @@ __global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(6, 6))) 
             for (int j = 0; j < 9; ++j) row.sum[j] = sums[j];
             row.info = fl | (icol << 3);
             row.ncol = ncol;
-            uint32_t cbase = L.cpre[col];
-            for (uint32_t w = 0; w < (col >> 6); ++w) cbase += L.wave_tot[w];      // (columns 64 .. 127 of a 128-column block: behind the first wave's)
             const uint32_t dst = sbase + cbase + icol;
             stage[dst] = row;
-            ord_cf[dst] = cfirst;
-            ord_idx[dst] = icol ? icol : (kOrdHeadFlag | ncol);       // (a column's first row carries the column's size)
+            if (!col_tab) {                             // (the node-order passes' keys: gndt_partition.hpp)
+                ord_cf[dst] = cfirst;
+                ord_idx[dst] = icol ? icol : (kOrdHeadFlag | ncol);       // (a column's first row carries the column's size)
+            }
             if (icol == 0) note_column(O, cfirst, ncol);
         }
         if (my_slopes) atomicAdd(&L.n_slopes, my_slopes);

@@ -194,6 +194,10 @@ struct gndt_handle {
         // clouds of that size take them, -1 = no (or a blocked build failed)
         int blk_state = 0;  uint64_t blk_n = 0;  BlockMap blk_map{};  uint32_t blk_buckets = 0;
         uint32_t* d_extent = nullptr;  uint32_t* h_extent = nullptr;      // k_key_extent's seven words and their pinned mirror
+        // the blocked kernel's column table (gndt_blocked.hpp, col_tab): blk_buckets << (shx + shy) 16-byte records, one per column of every
+        // block, written whole by every blocked build that the per-column ordering pass follows (k_order_dest_table); sized by
+        // partition_launch for the layout blocked_decide fixed (a blocked build is never recorded into a hipGraph: it may allocate)
+        uint4* col_tab = nullptr;  uint64_t col_tab_cap = 0;
         int good_slots = 0; uint64_t good_est = 0, good_n = 0;   // table size / estimate that worked last time
         int good_load = 0;          //   ... and the table load (percent) if it had to be lowered (0: the default)
         int load_pct = 60;          // average LDS-table load (percent) the bucket count aims at
@@ -431,6 +435,9 @@ struct Tuning {
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
     uint32_t blocked_min_points = 1u << 20;   // GNDT_DEBUG_BLOCKED_MIN_POINTS   points from which a build may take BLOCKED buckets (65 536 .. 2^20; tests lower it)
+    bool column_dest = true;     // GNDT_DEBUG_COLUMN_DEST         BLOCKED builds that end in the two-kernel tail: the ordering pass runs over the
+                                 //   bucket kernel's column table (k_order_dest_table); 0: over the staged nodes (k_order_dest_columns, ord_cf / ord_idx)
+                                 // GNDT_DEBUG_PLACE_EMIT_WORDS sets place_emit_words (above)
 };
 const Tuning& tuning();
 void tuning_force_stamps(bool on);   // bench.py --stamps flips this after the timed run
@@ -602,7 +609,7 @@ int sketch_nodes(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_by
 // partial: incremental finalisation — only rows from the first changed column on are placed and gathered again, touched rows in
 //          front of it are emitted where they are (k_order_dest / k_emit_rows, gndt_partition.hpp)
 int launch_order_and_emit(gndt_handle* h, uint64_t words, int m0, hipStream_t s, bool grouped = false, bool counters_to_host = false,
-                          bool tab_end = false, uint32_t advance = 0, bool partial = false);
+                          bool tab_end = false, uint32_t advance = 0, bool partial = false, uint32_t col_records = 0);
 int partition_launch(gndt_handle* h, gndt_handle::Pending& P);
 int partition_begin(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, hipStream_t s, bool records = false, uint64_t index_range = 0,
                     const void* records2 = nullptr, size_t n2 = 0);

@@ -955,6 +955,63 @@ static __global__ void __launch_bounds__(kBlock) k_order_dest_columns(const uint
     }
 }
 
+// BLOCKED builds (gndt_blocked.hpp): the same pass over COLUMNS.  The bucket kernel knows every column of its block by position and
+// leaves one 16-byte record per column — {first-seen index, first staging row, nodes, 0}; nodes == 0: the block has no such column —
+// in a table addressed by (bucket, column).  One thread per record: nobody reads the order key of every staged node to find the
+// column heads (796 k loads for 160 k heads on the bench scene), and a head's place is three dependent round trips — the record,
+// {bitmap word, word base}, ncol_at — where k_order_dest_columns takes four.  Same arithmetic for the row, same inv.
+// Every record of the table belongs to THIS build: k_bucket_blocked writes all of its block's records, zeros where it leaves early.
+// (row + nodes <= num_nodes holds for every record of a build that raised no flag; the comparison keeps a write inside inv whatever
+//  the table holds.)
+template <bool SCAN>
+static __global__ void __launch_bounds__(kBlock) k_order_dest_table(const uint4* __restrict__ col_tab, uint32_t n_records,
+                                                                    const uint32_t* __restrict__ bitmap, uint32_t* __restrict__ word_base,
+                                                                    const uint32_t* __restrict__ ncol_at, uint32_t* __restrict__ inv,
+                                                                    const Counters* __restrict__ cnt, const PartCounters* __restrict__ pc,
+                                                                    const uint32_t* __restrict__ word_weight, uint32_t words) {
+    if (pc->lds_overflow | pc->stage_overflow | pc->index_overflow | pc->part_overflow) return;
+    const uint32_t n = cnt->num_nodes;
+    __shared__ uint32_t s_base[SCAN ? kDestScanMax : 1];
+    __shared__ uint32_t s_wave[kBlock / 64];
+    if (SCAN) {            // (as in k_order_dest_columns: the prefix of the word weights, worked out by every workgroup in LDS)
+        for (uint32_t j = threadIdx.x; j < words; j += kBlock) s_base[j] = word_weight[j];
+        __syncthreads();
+        const uint32_t per = ((words + kBlock - 1u) / kBlock) | 1u;
+        const uint32_t j0 = min(threadIdx.x * per, words), j1 = min(j0 + per, words);
+        uint32_t sum = 0;
+        for (uint32_t j = j0; j < j1; ++j) sum += s_base[j];
+        uint32_t incl = sum;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)incl, off, 64); if (lane >= off) incl += t; }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t run = incl - sum;
+        for (int w = 0; w < wave; ++w) run += s_wave[w];
+        for (uint32_t j = j0; j < j1; ++j) { const uint32_t v = s_base[j]; s_base[j] = run; run += v; }
+        __syncthreads();
+        if (blockIdx.x == 0) for (uint32_t j = threadIdx.x; j < words; j += kBlock) word_base[j] = s_base[j];
+    }
+    for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n_records; c += gridDim.x * blockDim.x) {
+        const uint4 rec = col_tab[c];                              // {cfirst, first staging row, ncol, 0}
+        const uint32_t cf = rec.x, first = rec.y, nc = rec.z;
+        if (nc == 0u) continue;
+        const uint32_t w = cf >> 5;
+        uint32_t m = bitmap[w] & ((1u << (cf & 31u)) - 1u);        // columns first seen earlier inside the same word
+        uint32_t row = SCAN ? s_base[w] : word_base[w];
+        while (m) {                                                // (four of the walk's loads in flight: a wave waits for its longest walk)
+            uint32_t a[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a[q] = 0u;
+                if (m) { a[q] = ncol_at[(w << 5) + (uint32_t)__builtin_ctz(m)]; m &= m - 1u; }
+            }
+            row += a[0] + a[1] + a[2] + a[3];
+        }
+        if (row + nc > n) continue;
+        for (uint32_t k = 0; k < nc; ++k) inv[row + k] = first + k;
+    }
+}
+
 // destination row of every staged node (see ColumnOrder), as the inverse permutation the emit kernel gathers by
 // `row_of` (nullable): the row of every staged node, kept for the incremental finalisation.  `partial`: only the nodes of columns
 // from bitmap word cnt->first_word on are placed again — nothing in front of that word moved in this frame (gndt_table.hpp).

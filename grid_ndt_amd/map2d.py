@@ -518,6 +518,8 @@ class TwoDmap:
     DEBUG_CLEARANCE_ONE_WORKGROUP = 8
     DEBUG_WALK_STEP_TABLE = 9
     DEBUG_BLOCKED_MIN_POINTS = 10   # points from which a build may take blocked buckets: 65 536 .. 1 048 576 (the default; tests lower it)
+    DEBUG_COLUMN_DEST = 11          # blocked builds with the two-kernel tail: 1 (the default) orders by the column table, 0 by the staged nodes
+    DEBUG_PLACE_EMIT_WORDS = 12     # bitmap words up to which ordering and emit are one kernel: 0 .. 2^24 (16 384 by default; 0: always two)
 
     @staticmethod
     def set_debug_option(option, value):

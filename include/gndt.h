@@ -1205,7 +1205,13 @@ int gndt_debug_enable_stamps(int on);
  *                                 waypoint of a path (num_nodes <= 2048 T), where it was measured faster          default 2
  *   GNDT_DEBUG_BLOCKED_MIN_POINTS points from which a build may take BLOCKED buckets (GNDT_STRATEGY_PARTITION_BLOCKED), an integer in
  *                                 65 536 .. 1 048 576.  A tuning choice of the host, not a limit of the kernel: tests lower it and ask
- *                                 for GNDT_STRATEGY_PARTITION_TWO_LEVEL to reach the blocked kernel with small clouds  default 1 048 576 */
+ *                                 for GNDT_STRATEGY_PARTITION_TWO_LEVEL to reach the blocked kernel with small clouds  default 1 048 576
+ *   GNDT_DEBUG_COLUMN_DEST        value == 0: a BLOCKED build that orders and emits in two kernels finds its rows' places from the staged
+ *                                 nodes (ord_cf / ord_idx, as every other build does) instead of from the bucket kernel's column
+ *                                 table; same map either way (tests build both and compare)                          default 1
+ *   GNDT_DEBUG_PLACE_EMIT_WORDS   PARTITION builds of clouds with up to this many column-order bitmap words (32 points each) order and
+ *                                 emit in ONE kernel, larger ones in two; an integer in 0 .. 2^24, 0 = always two kernels (tests send
+ *                                 small clouds through the two kernels of a production-size build)                   default 16 384 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1216,6 +1222,8 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP 8
 #define GNDT_DEBUG_WALK_STEP_TABLE 9
 #define GNDT_DEBUG_BLOCKED_MIN_POINTS 10
+#define GNDT_DEBUG_COLUMN_DEST 11
+#define GNDT_DEBUG_PLACE_EMIT_WORDS 12
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
