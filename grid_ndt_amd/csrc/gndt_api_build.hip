@@ -1,5 +1,6 @@
 // gndt_api_build.hip — strategy PARTITION (gndt_partition.hpp, gndt_bucket3.hpp): launch, pending-build resolution, gndt_build*.
 #include <atomic>
+#include <type_traits>
 
 #include "gndt_handle.hpp"
 #include "gndt_bucket3.hpp"
@@ -16,8 +17,11 @@ namespace gndt_host {
 int launch_order_and_emit(gndt_handle* h, uint64_t words, int m0, hipStream_t s, bool grouped, bool counters_to_host, bool tab_end, uint32_t advance,
                           bool partial, uint32_t col_records) {
     auto& q = h->part;
-    // (small clouds, staging rows grouped by column: the destination pass scans the word weights itself — gndt_partition.hpp)
-    const bool dest_scans = grouped && !partial && !tab_end && words <= kDestScanMax && tuning().dest_scans;
+    // (small clouds, staging rows grouped by column: the destination pass scans the word weights itself instead of one or two scan
+    //  launches in front of it — gndt_partition.hpp; 200 k-point campus frame 0.0549 -> 0.0535 ms, bridge_ground 0.0647 -> 0.0646: r05 ablation 6h)
+    const bool dest_scans = grouped && !partial && !tab_end && words <= kDestScanMax;
+    // the kernels that come as a <true> / <false> pair on dest_scans: `launch` is called with the one constant that applies
+    auto with_dest_scans = [&](auto launch) { if (dest_scans) launch(std::true_type{}); else launch(std::false_type{}); };
     if (dest_scans) {
     } else if (words <= kScanSmallMax) {
         hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, s, (const uint32_t*)q.word_weight, (uint32_t)words, q.word_base);
@@ -38,30 +42,25 @@ int launch_order_and_emit(gndt_handle* h, uint64_t words, int m0, hipStream_t s,
     if (grouped && !partial && !tab_end && words <= (uint64_t)tuning().place_emit_words) {
         // small clouds: the ordering pass and the emit pass as one kernel in scatter form (gndt_partition.hpp)
         mark(h, m0 + 4, s);
-        if (dest_scans)
-            hipLaunchKernelGGL(k_place_emit_rows<true>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, (const RawNode*)q.raw, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
+        with_dest_scans([&](auto scans) {
+            hipLaunchKernelGGL(k_place_emit_rows<decltype(scans)::value>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, (const RawNode*)q.raw, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
                                q.ncol_at, h->out, q.row_ncol, h->d_cnt, q.d_pc, counters_to_host ? h->h_cnt : (Counters*)nullptr,
                                counters_to_host ? q.h_pc : (PartCounters*)nullptr, h->cur_capture_id, h->pending.gp, (const uint32_t*)q.word_weight, (uint32_t)words);
-        else
-            hipLaunchKernelGGL(k_place_emit_rows<false>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, (const RawNode*)q.raw, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
-                               q.ncol_at, h->out, q.row_ncol, h->d_cnt, q.d_pc, counters_to_host ? h->h_cnt : (Counters*)nullptr,
-                               counters_to_host ? q.h_pc : (PartCounters*)nullptr, h->cur_capture_id, h->pending.gp, (const uint32_t*)q.word_weight, (uint32_t)words);
+        });
         HIP_TRY(h, hipGetLastError());
         mark(h, m0 + 5, s);
         return GNDT_OK;
     }
-    if (grouped && col_records && dest_scans)       // (a BLOCKED build: one thread per record of the bucket kernel's column table)
-        hipLaunchKernelGGL(k_order_dest_table<true>, dim3(grid_for(col_records)), dim3(kBlock), 0, s, (const uint4*)q.col_tab, col_records, q.bitmap, q.word_base,
-                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
-    else if (grouped && col_records)
-        hipLaunchKernelGGL(k_order_dest_table<false>, dim3(grid_for(col_records)), dim3(kBlock), 0, s, (const uint4*)q.col_tab, col_records, q.bitmap, q.word_base,
-                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
-    else if (grouped && dest_scans)
-        hipLaunchKernelGGL(k_order_dest_columns<true>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
-                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+    if (grouped && col_records)       // (a BLOCKED build: one thread per record of the bucket kernel's column table)
+        with_dest_scans([&](auto scans) {
+            hipLaunchKernelGGL(k_order_dest_table<decltype(scans)::value>, dim3(grid_for(col_records)), dim3(kBlock), 0, s, (const uint4*)q.col_tab, col_records, q.bitmap, q.word_base,
+                               q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+        });
     else if (grouped)
-        hipLaunchKernelGGL(k_order_dest_columns<false>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
-                           q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+        with_dest_scans([&](auto scans) {
+            hipLaunchKernelGGL(k_order_dest_columns<decltype(scans)::value>, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
+                               q.ncol_at, q.inv, h->d_cnt, q.d_pc, (const uint32_t*)q.word_weight, (uint32_t)words);
+        });
     else
         hipLaunchKernelGGL(k_order_dest, dim3(grid_for(q.stage_cap)), dim3(kBlock), 0, s, q.ord_cf, q.ord_idx, q.bitmap, q.word_base,
                            q.ncol_at, q.inv, h->d_cnt, q.d_pc, tab_end ? q.row_of : (uint32_t*)nullptr, partial ? 1u : 0u);
@@ -155,6 +154,91 @@ static FoldClear fold_clear_begin(gndt_handle* h, const gndt_handle::Pending& P,
     return FoldClear{q.cursors_alt, (uint32_t)(kMaxFan + 2 * q.cur_cap), q.d_pc_alt, q.bitmap, q.word_weight, clean ? words : 0ull};
 }
 
+// totals / bucket_base of the exact counting partition, for B buckets
+static int ensure_bucket_totals(gndt_handle* h, uint64_t B) {
+    auto& q = h->part;
+    if (B <= q.bucket_cap) return GNDT_OK;
+    GNDT_NO_CAPTURE(h, "the bucket totals");
+    release_device(h, q.totals);
+    release_device(h, q.bucket_base);
+    q.totals = q.bucket_base = nullptr; q.bucket_cap = 0;
+    HIP_TRY(h, hipMalloc(&q.totals, (size_t)B * 4));
+    HIP_TRY(h, hipMalloc(&q.bucket_base, ((size_t)B + 1) * 4));
+    q.bucket_cap = (uint32_t)B;
+    return GNDT_OK;
+}
+
+// What every kind of partition starts with (marks 0 .. 1): the table reset, and k_part_clear over the column order, the counters and
+// the `ncursors` words at `cursors` — unless the level-1 kernel of the build before this one has left all that clean (fold.words: FoldClear)
+static int partition_prelude(gndt_handle* h, hipStream_t s, uint64_t words, uint32_t* cursors, uint32_t ncursors, const FoldClear& fold) {
+    auto& q = h->part;
+    int rc;
+    mark(h, 0, s);
+    // the HBM node table is not used by this strategy, but a previous atomic build may sit in it
+    // (a build recorded into a hipGraph always records the reset: its replays must not depend on what the table held at capture time)
+    if (h->table_dirty || h->capturing) { if ((rc = do_reset(h, s))) return rc; }
+    h->results_valid = false;
+    if (!fold.words) {
+        hipLaunchKernelGGL(k_part_clear, dim3(grid_for(words, 256, 512)), dim3(256), 0, s, h->d_cnt, q.d_pc, q.bitmap, q.word_weight, (uint64_t)words,
+                           cursors, ncursors);
+        HIP_TRY(h, hipGetLastError());
+    }
+    mark(h, 1, s);
+    return GNDT_OK;
+}
+
+// Level 1 of a build, `a` being everything but the input and the grid: points in one launch; records, the two segments one after the
+// other into the same regions (the cursors carry on; only the last launch lays the buckets out).  (Records come without FoldClear.)
+static void launch_level1_of_build(const gndt_handle::Pending& P, Level1Launch a, hipStream_t s) {
+    const uint64_t tile = (uint64_t)kTileThreads * (a.small_tiles ? kTilePerSmall : kTilePer1);
+    auto input = [&](const void* in, uint64_t n) {
+        a.in = static_cast<const float*>(in);
+        a.n = n;
+        a.grid = dim3(std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)((n + tile - 1) / tile), kL1Wgs)));     // persistent workgroups (2 resident per CU)
+    };
+    if (!P.records) { input(P.xyz, P.n); launch_level1<Level1Input::Points>(a, s); return; }
+    uint32_t* const lay_lo = a.range_lo;
+    if (P.n) { input(P.xyz, P.n); a.range_lo = P.n2 ? nullptr : lay_lo; launch_level1<Level1Input::Records>(a, s); }
+    if (P.n2) { input(P.xyz2, P.n2); a.range_lo = lay_lo; launch_level1<Level1Input::Records>(a, s); }
+}
+
+// The bucket pass of a build (gndt_bucket3.hpp, gndt_blocked.hpp) and, when asked for, the second pass behind it
+struct BucketLaunch {
+    const float4* recs;  BucketRanges ranges;  uint32_t B;  GridParams gp;
+    int slots;              // the LDS tables of the pass: 512 or 1024 slots
+    bool blocked;           // k_bucket_blocked: a block of the box per bucket, the table addressed by the key
+    bool wide;              // 512 slots: one record per thread at three workgroups per CU
+    bool stats_only;
+    bool second_pass;       // 512 slots: overflowing buckets are queued (Part::range_hi) and done again with 1024 slots
+    uint64_t rows_cap;      // staging rows the order arrays AND the records hold
+    uint32_t interleave;
+    uint4* col_tab;         // blocked: the column table the ordering pass runs over (null: none)
+};
+template <int T, int H, bool STATS, int... MORE>      // (MORE: records per thread, waves per SIMD — the kernel's own defaults when left out)
+static void enqueue_bucket_direct(gndt_handle* h, const BucketLaunch& a, dim3 grid, uint32_t* retry_list, const uint32_t* todo_list, hipStream_t s) {
+    auto& q = h->part;
+    hipLaunchKernelGGL((k_bucket_direct<T, H, STATS, MORE...>), grid, dim3(T), 0, s, a.recs, a.ranges, a.B, a.gp, q.raw, (uint32_t)(STATS ? h->st_cap : a.rows_cap),
+                       q.ord_cf, q.ord_idx, ColumnOrder{q.bitmap, q.word_weight, q.ncol_at}, h->d_cnt, q.d_pc, tuning().stamps ? q.dbg : nullptr,
+                       StatsOut{h->st_key, h->st_sums, h->st_count, h->st_first}, (1u << tuning().fp_bits) - 1u, a.interleave, retry_list, todo_list);
+}
+static void launch_buckets(gndt_handle* h, const BucketLaunch& a, hipStream_t s) {
+    auto& q = h->part;
+    // one workgroup per bucket: 512 persistent workgroups measured 8 % slower, the hardware's dynamic workgroup scheduling balances
+    // uneven buckets better than a static stride
+    const dim3 grid(a.B);
+    uint32_t* const rlist = a.second_pass ? q.range_hi : (uint32_t*)nullptr;
+    if (a.blocked)
+        hipLaunchKernelGGL(k_bucket_blocked<512>, grid, dim3(512), 0, s, a.recs, a.ranges, a.B, a.gp, q.raw, (uint32_t)a.rows_cap, q.ord_cf, q.ord_idx,
+                           ColumnOrder{q.bitmap, q.word_weight, q.ncol_at}, h->d_cnt, q.d_pc, tuning().stamps ? q.dbg : nullptr, a.col_tab);
+    else if (a.slots == 1024) { if (a.stats_only) enqueue_bucket_direct<1024, 1024, true>(h, a, grid, nullptr, nullptr, s); else enqueue_bucket_direct<1024, 1024, false>(h, a, grid, nullptr, nullptr, s); }
+    else if (a.wide) enqueue_bucket_direct<GNDT_DIRECT_THREADS, 512, false, 1, 6>(h, a, grid, rlist, nullptr, s);
+    else { if (a.stats_only) enqueue_bucket_direct<GNDT_DIRECT_THREADS, 512, true>(h, a, grid, rlist, nullptr, s); else enqueue_bucket_direct<GNDT_DIRECT_THREADS, 512, false>(h, a, grid, rlist, nullptr, s); }
+    if (a.second_pass) {
+        const dim3 rgrid(std::min<uint32_t>(a.B, 256u));       // (one 1024-thread workgroup per CU; all of them leave at once when nothing is queued)
+        if (a.stats_only) enqueue_bucket_direct<1024, 1024, true>(h, a, rgrid, nullptr, rlist, s); else enqueue_bucket_direct<1024, 1024, false>(h, a, rgrid, nullptr, rlist, s);
+    }
+}
+
 // One attempt of the PARTITION build: every launch plus the asynchronous read-back of the counters and overflow
 // flags; no host wait.  Returns GNDT_OK, an error, or -1 when the partition path cannot hold this input.
 int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
@@ -164,8 +248,7 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     const int attempt = P.attempt;
     uint64_t& nodes_est = P.nodes_est;
     uint64_t& stage_want = P.stage_want;
-    const int env_slots = tuning().bucket_slots, part_wgs = kPartWgs;
-    const uint32_t nwg = (uint32_t)std::min<uint64_t>((uint64_t)part_wgs, std::max<uint64_t>(1, n / 8192));
+    const uint32_t nwg = (uint32_t)std::min<uint64_t>((uint64_t)kPartWgs, std::max<uint64_t>(1, n / 8192));
     const uint64_t words = ((P.index_range ? (size_t)P.index_range : n) + 31) / 32 + 1;
     int rc;
     // identical consecutive points travel as weighted records whose index word gives up two bits (gndt_partition.hpp);
@@ -178,60 +261,57 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     // partition (large clouds), never for records / statistics / a re-run after a blocked attempt failed.
     // (not under hipGraph capture either: a recorded build is replayed on OTHER clouds, and one that leaves the box cannot be re-run)
     const bool blocked = tuning().blocked && q.blk_state == 1 && !P.no_block && !P.records && !P.stats_only && attempt == 0 && !h->capturing && !P.captured &&
-                         !tuning().bucket_slots && q.two_level_ok && n >= tuning().blocked_min_points &&
-                         h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && n <= q.blk_n + q.blk_n / 4 && n + n / 4 >= q.blk_n;
+                         q.two_level_ok && n >= tuning().blocked_min_points &&
+                         h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && within_quarter(n, q.blk_n);
     P.blocked = blocked;
     if (blocked) gp.blk = q.blk_map;
-    const float* p = static_cast<const float*>(P.xyz);
-    const float* p2 = static_cast<const float*>(P.xyz2);
     // table size and bucket count for this attempt: 512-slot tables unless that needs too many buckets
     // attempt 0: 512-slot tables; an overflow first doubles the table (same estimate), then raises the estimate
-    int bslots = env_slots ? env_slots : (attempt == 0 ? 512 : 1024);
+    int bslots = attempt == 0 ? 512 : 1024;
     // Node-heavy clouds (a few points per node) get their bucket count from the NODES: estimate / (slots x load).  From 2 M points
     // on any such count fills the chip, and fuller tables with fewer buckets are faster (size sweep, round 3: load 75 against 60
     // gains 3-11 % on 3-30 M-point clouds of 0.05-0.2 m voxels, S2z 0.84 -> 0.79 ms, S3 32 M 1.50 -> 1.47; a million points lose
     // 4-13 % with it: fewer buckets than CUs want).  The estimate carries a 20 % margin, so 75 % is ~62 % of the slots really used.
     int load_pct = P.load_pct ? P.load_pct : q.load_pct;
-    if (!P.load_pct && n >= (1u << 21)) load_pct = std::max(load_pct, tuning().bucket_load_large);
+    if (!P.load_pct && n >= (1u << 21)) load_pct = std::max(load_pct, kBucketLoadLarge);
     // (which bucket kernel this build gets — gndt_bucket3.hpp: three workgroups per CU for clouds without locality — also sizes its buckets)
-    const bool wide_hint = tuning().bucket_three_wgs && !P.stats_only && tuning().interleave < 0 && !(q.pair_ratio < 0.0 || q.pair_ratio > 0.02);
+    const bool wide_hint = tuning().bucket_three_wgs && !P.stats_only && !(q.pair_ratio < 0.0 || q.pair_ratio > 0.02);
     // (its buckets are sized by the POINTS — 4000 each — unless the nodes really fill the tables: the estimate carries a 20-30 % margin
     //  and the second pass takes the tables that overflow all the same; with the 75 % rule the bench scene's hint made 2 730 buckets
     //  of 3 660 points where 2 500 of 4 000 are 4 % faster)
-    if (wide_hint && bslots == 512 && !P.load_pct && tuning().retry_pass) load_pct = std::max(load_pct, 90);
+    if (wide_hint && bslots == 512 && !P.load_pct) load_pct = std::max(load_pct, 90);
     uint64_t Bw = buckets_for(n, nodes_est, bslots, load_pct, wide_hint && bslots == 512);
     // Clouds with few points per node (a million points in half a million nodes): the NODES size the bucket count, and 512-slot
     // tables — which since round 3 hold 512 nodes and no longer overflow on such clouds — would get buckets of a few hundred
     // points, all per-bucket overhead (size sweep: 0.217 against 0.186 ms).  Below 900 points per bucket the 1024-slot tables
     // are taken from the start, if they still fill the chip.
-    if (!env_slots && attempt == 0 && P.est_reliable && n / std::max<uint64_t>(Bw, 1) < 900) {
+    if (attempt == 0 && P.est_reliable && n / std::max<uint64_t>(Bw, 1) < 900) {
         const uint64_t b1024 = buckets_for(n, nodes_est, 1024, load_pct);
         if (b1024 >= 384) { bslots = 1024; Bw = b1024; }
     }
     if (blocked) { bslots = 512; Bw = q.blk_buckets; }       // (one bucket per block of the box)
     // Two-level partition (no counting passes) for large builds; the exact single-level counting partition for small
     // ones, when asked for (GNDT_STRATEGY_PARTITION_EXACT), and after a region overflowed once on this handle.
-    const int env_two = tuning().two_level;
     bool two = h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && q.two_level_ok &&
                (n >= (1u << 20) || h->P.strategy == GNDT_STRATEGY_PARTITION_TWO_LEVEL);
-    if (env_two == 0 || n == 0) two = false;
+    if (n == 0) two = false;
     if (two && Bw > (uint64_t)kMaxFan * kMaxFan) {         // more buckets than two levels address: larger tables, fewer buckets
-        if (!env_slots) { bslots = 1024; Bw = buckets_for(n, nodes_est, bslots, load_pct); }
+        bslots = 1024; Bw = buckets_for(n, nodes_est, bslots, load_pct);
         if (Bw > (uint64_t)kMaxFan * kMaxFan) two = false;
     }
     if (!two) {
-        if (!env_slots && Bw > kMaxBuckets) { bslots = 1024; Bw = buckets_for(n, nodes_est, bslots, load_pct); }
+        if (Bw > kMaxBuckets) { bslots = 1024; Bw = buckets_for(n, nodes_est, bslots, load_pct); }
         if (Bw > kMaxBuckets) return -1;                   // too many nodes for one partition level: atomic path
     }
     // (a cloud just above kMaxFan buckets of the small-cloud size still fits kMaxFan larger ones, if its nodes do)
-    if (!two && tuning().one_level && q.one_level_ok && h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && Bw > (uint64_t)kMaxFan &&
+    if (!two && q.one_level_ok && h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && Bw > (uint64_t)kMaxFan &&
         n <= (uint64_t)kMaxFan * 2800 && (nodes_est * 100) / ((uint64_t)bslots * load_pct) <= (uint64_t)kMaxFan)
         Bw = kMaxFan;
     const uint32_t B = (uint32_t)Bw;
     // Small clouds (at most kMaxFan buckets): ONE tile-sort level writes the buckets themselves, each with a fixed room of 4 x
     // the mean fill — a third of the counting partition's time (no histogram pass, no offsets pass, coalesced copy-out).  A
     // bucket that overflows its room sends the build (and this handle from then on) to the counting partition.
-    const bool one = !two && tuning().one_level && q.one_level_ok && h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && B <= (uint32_t)kMaxFan &&
+    const bool one = !two && q.one_level_ok && h->P.strategy != GNDT_STRATEGY_PARTITION_EXACT && B <= (uint32_t)kMaxFan &&
                      n >= (1u << 14);
     P.two_level = two;
     P.one_level = one;
@@ -255,7 +335,6 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     const uint32_t col_records = col_dest ? q.blk_buckets << (q.blk_map.shx + q.blk_map.shy) : 0u;      // (at most 2^18 blocks of at most 2^9 columns)
     if (col_dest && (rc = grow_buf(h, q.col_tab, q.col_tab_cap, (uint64_t)col_records))) return rc;
     BucketRanges ranges{nullptr, nullptr, nullptr, 0u};
-    const float4* bucket_recs = nullptr;
     if (two) {
         uint32_t F2_shift = 1;                             // fan-out ~ sqrt(B) per level, F2 a power of two, both <= kMaxFan
         while (F2_shift < 9 && (1ull << (2 * F2_shift)) < B) ++F2_shift;
@@ -283,45 +362,20 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         if ((rc = ensure_cursors(h, B))) return rc;
         // (no FoldClear here: measured on the bench scene, one call, A B A B: 0.3129 | 0.3143 ms per step with it, 0.3116 | 0.3117 with the
         //  k_part_clear launch — level 1 and level 2 each a microsecond slower; the one-level partition of a small frame is where it pays)
-        const FoldClear fold{};
         uint32_t* cursor1 = q.cursors;
         uint32_t* cursor2 = q.cursors + kCursor1Words;
         uint32_t* est2 = cursor2 + B;
-        mark(h, 0, s);
-        // (a build recorded into a hipGraph always records the reset: its replays must not depend on what the table held at capture time)
-        if (h->table_dirty || h->capturing) { if ((rc = do_reset(h, s))) return rc; }
-        h->results_valid = false;
-        if (!fold.words) {
-            hipLaunchKernelGGL(k_part_clear, dim3(grid_for(words, 256, 512)), dim3(256), 0, s, h->d_cnt, q.d_pc, q.bitmap, q.word_weight, (uint64_t)words,
-                               q.cursors, (uint32_t)(kCursor1Words + 2 * B));
-            HIP_TRY(h, hipGetLastError());
-        }
-        mark(h, 1, s);
-        const uint32_t tiles1 = (uint32_t)((P.n + kTile1 - 1) / kTile1), tiles1b = (uint32_t)((P.n2 + kTile1 - 1) / kTile1);
-        const uint32_t l1_wgs = tuning().l1_wgs;   // persistent workgroups (2 resident per CU)
+        if ((rc = partition_prelude(h, s, words, q.cursors, (uint32_t)(kCursor1Words + 2 * B), FoldClear{}))) return rc;
         const bool wide = std::max(V, F2) > 256;           // LDS arrays for a fan-out of 512 (fewer resident tiles) only when needed
-        const dim3 g1(std::max<uint32_t>(1, std::min<uint32_t>(tiles1, l1_wgs))), g1b(std::max<uint32_t>(1, std::min<uint32_t>(tiles1b, l1_wgs))),
-            g2((uint32_t)((cap1 + kTile2 - 1) / kTile2), V);
+        const dim3 g2((uint32_t)((cap1 + kTile2 - 1) / kTile2), V);
+        Level1Launch l1;
+        l1.stride_floats = (int)(stride_bytes / 4);  l1.first_base = P.first_base;  l1.gp = gp;  l1.compress = compress;
+        l1.B = B;  l1.F1 = F1;  l1.F2_shift = F2_shift;  l1.replicas = R;  l1.fan512 = wide;
+        l1.cursor1 = cursor1;  l1.cap1 = cap1;  l1.cursor_shift = kCursor1Shift;  l1.est2 = est2;
+        l1.recs1 = q.recs1;  l1.cnt = h->d_cnt;  l1.pc = q.d_pc;
         // (the last level-1 workgroup to finish lays out the buckets' regions: range_lo / range_cap)
-#define GNDT_L1(SF_, FAN_)                                                                                                  \
-    hipLaunchKernelGGL((k_part2_level1<SF_, FAN_>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)n, P.first_base, gp, B, F1, F2_shift, \
-                       R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, q.range_lo,     \
-                       q.range_cap, (uint64_t)q.rec_cap, fold, kCursor1Shift)
-        // records: the two segments one after the other into the same regions (the cursors carry on; the last launch lays out)
-#define GNDT_L1R(FAN_)                                                                                                      \
-    do {                                                                                                                    \
-        if (P.n) hipLaunchKernelGGL((k_part2_level1<4, FAN_, true>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)P.n, P.first_base, gp, B, F1, \
-                                    F2_shift, R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, \
-                                    P.n2 ? (uint32_t*)nullptr : q.range_lo, q.range_cap, (uint64_t)q.rec_cap, FoldClear{}, kCursor1Shift);  \
-        if (P.n2) hipLaunchKernelGGL((k_part2_level1<4, FAN_, true>), g1b, dim3(kTileThreads), 0, s, p2, (uint64_t)P.n2, P.first_base, gp, B, \
-                                     F1, F2_shift, R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, \
-                                     q.range_lo, q.range_cap, (uint64_t)q.rec_cap, FoldClear{}, kCursor1Shift);              \
-    } while (0)
-        if (P.records) { if (wide) GNDT_L1R(512); else GNDT_L1R(256); }
-        else if (stride_bytes == 12) { if (wide) GNDT_L1(3, 512); else GNDT_L1(3, 256); }
-        else { if (wide) GNDT_L1(4, 512); else GNDT_L1(4, 256); }
-#undef GNDT_L1
-#undef GNDT_L1R
+        l1.range_lo = q.range_lo;  l1.range_cap = q.range_cap;  l1.rec_cap = q.rec_cap;
+        launch_level1_of_build(P, l1, s);
         HIP_TRY(h, hipGetLastError());
         mark(h, 2, s);
         mark(h, 3, s);
@@ -335,7 +389,6 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         mark(h, 4, s);
         ranges = BucketRanges{q.range_lo, q.range_cap, cursor2, 0u};
     } else if (one) {
-        constexpr uint64_t kTile1 = (uint64_t)kTileThreads * kTilePer1;
         const uint64_t mean = n / B + 1;
         const uint32_t cap1 = (uint32_t)std::max<uint64_t>(4 * mean, mean + 4096);
         if ((rc = grow_buf(h, q.recs1, q.rec1_cap, (uint64_t)B * cap1))) return rc;
@@ -343,51 +396,16 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         const FoldClear fold = fold_clear_begin(h, P, words);     // (may swap q.cursors / q.d_pc with their clean twins)
         uint32_t* cursor1 = q.cursors;                     // [B <= kMaxFan] the buckets' fills
         uint32_t* est2 = q.cursors + kMaxFan;              // (the kernel's sample votes: not used here, but counted; one-level: dense cursors)
-        const uint32_t F1 = B, F2_shift = 0, R = 1;
-        mark(h, 0, s);
-        // (a build recorded into a hipGraph always records the reset: its replays must not depend on what the table held at capture time)
-        if (h->table_dirty || h->capturing) { if ((rc = do_reset(h, s))) return rc; }
-        h->results_valid = false;
-        if (!fold.words) {
-            hipLaunchKernelGGL(k_part_clear, dim3(grid_for(words, 256, 512)), dim3(256), 0, s, h->d_cnt, q.d_pc, q.bitmap, q.word_weight, (uint64_t)words,
-                               q.cursors, (uint32_t)(kMaxFan + B));
-            HIP_TRY(h, hipGetLastError());
-        }
-        mark(h, 1, s);
+        if ((rc = partition_prelude(h, s, words, q.cursors, (uint32_t)(kMaxFan + B), fold))) return rc;
+        Level1Launch l1;
+        l1.stride_floats = (int)(stride_bytes / 4);  l1.first_base = P.first_base;  l1.gp = gp;  l1.compress = compress;
+        l1.B = B;  l1.F1 = B;  l1.fan512 = B > 256;                 // (one level: a region per bucket, no second fan-out)
         // small clouds: 1024-point tiles (gndt_partition.hpp: kTilePerSmall), so that the frame is a launch of a few hundred workgroups
-        const bool small_tiles = !P.records && n < (1u << 20) && tuning().small_tiles;
-        const uint64_t tile1 = small_tiles ? (uint64_t)kTileThreads * kTilePerSmall : kTile1;
-        const uint32_t tiles1 = (uint32_t)((P.n + tile1 - 1) / tile1), tiles1b = (uint32_t)((P.n2 + tile1 - 1) / tile1);
-        const uint32_t l1_wgs = tuning().l1_wgs;
-        const bool wide = B > 256;
-        const dim3 g1(std::max<uint32_t>(1, std::min<uint32_t>(tiles1, l1_wgs))), g1b(std::max<uint32_t>(1, std::min<uint32_t>(tiles1b, l1_wgs)));
-#define GNDT_L1(SF_, FAN_)                                                                                                  \
-    hipLaunchKernelGGL((k_part2_level1<SF_, FAN_>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)n, P.first_base, gp, B, F1, F2_shift, \
-                       R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, (uint32_t*)nullptr, \
-                       (uint32_t*)nullptr, 0ull, fold, 0)
-#define GNDT_L1S(SF_, FAN_)                                                                                                 \
-    hipLaunchKernelGGL((k_part2_level1<SF_, FAN_, false, false, kTilePerSmall>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)n, P.first_base, gp, B, F1, \
-                       F2_shift, R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, (uint32_t*)nullptr, \
-                       (uint32_t*)nullptr, 0ull, fold, 0)
-#define GNDT_L1R(FAN_)                                                                                                      \
-    do {                                                                                                                    \
-        if (P.n) hipLaunchKernelGGL((k_part2_level1<4, FAN_, true>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)P.n, P.first_base, gp, B, F1, \
-                                    F2_shift, R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, \
-                                    (uint32_t*)nullptr, (uint32_t*)nullptr, 0ull, FoldClear{}, 0);                              \
-        if (P.n2) hipLaunchKernelGGL((k_part2_level1<4, FAN_, true>), g1b, dim3(kTileThreads), 0, s, p2, (uint64_t)P.n2, P.first_base, gp, B, \
-                                     F1, F2_shift, R, cursor1, cap1, est2, q.recs1, h->d_cnt, q.d_pc, compress, OwnerMap{nullptr, nullptr, 0u}, \
-                                     (uint32_t*)nullptr, (uint32_t*)nullptr, 0ull, FoldClear{}, 0);                             \
-    } while (0)
-        if (small_tiles) {
-            if (stride_bytes == 12) { if (wide) GNDT_L1S(3, 512); else GNDT_L1S(3, 256); }
-            else { if (wide) GNDT_L1S(4, 512); else GNDT_L1S(4, 256); }
-        } else
-        if (P.records) { if (wide) GNDT_L1R(512); else GNDT_L1R(256); }
-        else if (stride_bytes == 12) { if (wide) GNDT_L1(3, 512); else GNDT_L1(3, 256); }
-        else { if (wide) GNDT_L1(4, 512); else GNDT_L1(4, 256); }
-#undef GNDT_L1
-#undef GNDT_L1S
-#undef GNDT_L1R
+        // instead of a few dozen (campus frame 0.0535 -> 0.0520 ms, bridge_ground 0.0648 -> 0.0608; r05 ablation 6i)
+        l1.small_tiles = !P.records && n < (1u << 20);
+        l1.cursor1 = cursor1;  l1.cap1 = cap1;  l1.est2 = est2;      // (dense cursors, no layout: every bucket has its fixed room)
+        l1.recs1 = q.recs1;  l1.cnt = h->d_cnt;  l1.pc = q.d_pc;  l1.fold = fold;
+        launch_level1_of_build(P, l1, s);
         HIP_TRY(h, hipGetLastError());
         if (fold.alt_cursors) q.alt_clean = true;          // (in stream order: the next build's level 1 runs behind this one)
         mark(h, 2, s);
@@ -395,30 +413,16 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         mark(h, 4, s);
         ranges = BucketRanges{nullptr, nullptr, cursor1, cap1};
     } else {
+    const float* p = static_cast<const float*>(P.xyz);
     if (P.n2) {                    // one array for the counting partition: the first segment goes into the room in front of the second
-        p = p2 - 4 * P.n;
+        p = static_cast<const float*>(P.xyz2) - 4 * P.n;
         if (P.n) HIP_TRY(h, hipMemcpyAsync(const_cast<float*>(p), P.xyz, P.n * 16, hipMemcpyDeviceToDevice, s));
     }
     if ((rc = grow_buf(h, q.recs, q.rec_cap, n))) return rc;
     if ((rc = ensure_cursors(h, B))) return rc;            // (for the bucket kernel's retry list)
     if ((rc = grow_buf(h, q.hist, q.hist_cap, (uint64_t)nwg * B))) return rc;
-    if (B > q.bucket_cap) {
-        GNDT_NO_CAPTURE(h, "the bucket totals");
-        release_device(h, q.totals);
-        release_device(h, q.bucket_base);
-        q.totals = q.bucket_base = nullptr; q.bucket_cap = 0;
-        HIP_TRY(h, hipMalloc(&q.totals, (size_t)B * 4));
-        HIP_TRY(h, hipMalloc(&q.bucket_base, ((size_t)B + 1) * 4));
-        q.bucket_cap = B;
-    }
-    mark(h, 0, s);
-    // the HBM node table is not used by this strategy, but a previous atomic build may sit in it
-    if (h->table_dirty || h->capturing) { if ((rc = do_reset(h, s))) return rc; }     // (as above: a captured build always records the reset)
-    h->results_valid = false;
-    hipLaunchKernelGGL(k_part_clear, dim3(grid_for(words, 256, 512)), dim3(256), 0, s, h->d_cnt, q.d_pc, q.bitmap, q.word_weight, (uint64_t)words,
-                       (uint32_t*)nullptr, 0u);
-    HIP_TRY(h, hipGetLastError());
-    mark(h, 1, s);
+    if ((rc = ensure_bucket_totals(h, B))) return rc;
+    if ((rc = partition_prelude(h, s, words, nullptr, 0u, FoldClear{}))) return rc;      // (no cursors: the counting partition has none)
     const size_t lds = (size_t)B * 4;
     if (lds > 48 * 1024) {   // beyond the default dynamic-LDS limit the kernels must be told (gfx950: 160 KiB/CU)
         HIP_TRY(h, hipFuncSetAttribute((const void*)k_part_hist<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -445,7 +449,6 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
     mark(h, 4, s);
     ranges = BucketRanges{q.bucket_base, nullptr, nullptr, 0u};
     }
-    bucket_recs = (two || !one) ? q.recs : q.recs1;
     if (tuning().stamps && q.dbg_buckets < B) {
         GNDT_NO_CAPTURE(h, "the stamp buffer");
         release_device(h, q.dbg);
@@ -455,60 +458,35 @@ int partition_launch(gndt_handle* h, gndt_handle::Pending& P) {
         q.dbg_buckets = B;
     }
     q.last_buckets = B;
-    // one workgroup per bucket by default: persistent workgroups (GNDT_BUCKET_WGS=512) measured 8 % slower, the
-    // hardware's dynamic workgroup scheduling balances uneven buckets better than a static stride
-    const uint32_t bucket_wgs = tuning().bucket_wgs;
-    const dim3 bgrid(std::min<uint32_t>(B, bucket_wgs));
-    const ColumnOrder order{q.bitmap, q.word_weight, q.ncol_at};
-    const StatsOut stats_out{h->st_key, h->st_sums, h->st_count, h->st_first};
-    unsigned long long* dbg = tuning().stamps ? q.dbg : nullptr;
     const bool grouped = true;          // k_bucket_direct stages a column's rows next to each other
-    const uint32_t fp_mask = (1u << tuning().fp_bits) - 1u;
     // record pairs interleaved over the waves (gndt_bucket3.hpp) unless the last build of this handle counted next to no adjacent
-    // records of one node: on by default — a cloud with locality gains 11-14 % of its bucket kernel, one without loses 2 %
+    // records of one node: on by default — a cloud with locality gains 11-14 % of its bucket kernel, one without loses 2 % (r05 §3)
     // (which mapping a cloud with locality gets: 1 = pairs interleaved inside 512-pair blocks, 2 = a contiguous stretch per lane;
-    //  bucket kernel S3 32 M 595 | 585 us, S3 100 M 1.691 | 1.679 ms, S5 317 | 306 us: 2)
-#ifndef GNDT_LOCALITY_MODE
-#define GNDT_LOCALITY_MODE 2
-#endif
-    const uint32_t interleave = tuning().interleave >= 0 ? (uint32_t)tuning().interleave : (q.pair_ratio < 0.0 || q.pair_ratio > 0.02 ? (uint32_t)GNDT_LOCALITY_MODE : 0u);
-    {
-        // k_bucket_direct (gndt_bucket3.hpp): 512-slot tables with two workgroups per CU, 1024-slot tables on a retry
-        // A bucket whose 512-slot table overflows (a few wall columns; the spread of a hash partition over tall columns) is queued and
-        // done again by a SECOND PASS with 1024-slot tables over the queued buckets only (round 5) — it used to send the whole build
-        // round again.  The pass is launched behind a handle's first builds, behind builds recorded into a hipGraph (a replay cannot
-        // be re-run) and for as long as the last build used it; a handle whose clouds never overflow does not pay for the launch.
-        // Round 6: a RECORDED build carries the pass only if nothing is known about this cloud size (a capture on a reserved fresh
-        // handle) or the eager build before it used it: every replay of a recorded pass over an empty list is a launch of 256 x 1024
-        // threads that all leave again (~4 us of a 52 us frame).  A replay whose tables overflow without it is
-        // reported like any replay that does not fit (GNDT_ERR_CAPACITY: build that cloud eagerly, capture again).
-        const bool known_size = q.last_n == n && q.last_est != 0;
-        const bool retry = !blocked && bslots == 512 && tuning().retry_pass && (q.retry_pass || (h->capturing && !known_size));
-        uint32_t* const rlist = retry ? q.range_hi : (uint32_t*)nullptr;
-        P.retry_pass = retry;
-        // one record per thread at three workgroups per CU for clouds without locality (interleave == 0: the last build counted next
-        // to no adjacent records of one node), two records at two workgroups per CU — with the pair folding — for the others
-        const bool wide = (interleave == 0u || tuning().bucket_three_wgs == 2) && !P.stats_only && tuning().bucket_three_wgs;
-        const uint64_t rows_cap = std::min<uint64_t>(q.stage_cap, P.stats_only ? q.stage_cap : q.raw_cap);      // staging rows the order arrays AND the records hold
-#define GNDT_LAUNCH_DIRECT(T_, H_, S_, GRID_, RL_, TODO_)                                                                       \
-    hipLaunchKernelGGL((k_bucket_direct<T_, H_, S_>), GRID_, dim3(T_), 0, s, bucket_recs, ranges, B, gp, q.raw,    \
-                       (uint32_t)(S_ ? h->st_cap : rows_cap), q.ord_cf, q.ord_idx, order, h->d_cnt, q.d_pc, dbg, stats_out, fp_mask, interleave, \
-                       RL_, TODO_)
-        if (blocked)        // (gndt_blocked.hpp: a block of the box per bucket, the table addressed by the key)
-            hipLaunchKernelGGL(k_bucket_blocked<512>, bgrid, dim3(512), 0, s, bucket_recs, ranges, B, gp, q.raw, (uint32_t)rows_cap, q.ord_cf, q.ord_idx, order,
-                               h->d_cnt, q.d_pc, dbg, col_dest ? q.col_tab : (uint4*)nullptr);
-        else if (bslots == 1024) { if (P.stats_only) GNDT_LAUNCH_DIRECT(1024, 1024, true, bgrid, (uint32_t*)nullptr, (const uint32_t*)nullptr); else GNDT_LAUNCH_DIRECT(1024, 1024, false, bgrid, (uint32_t*)nullptr, (const uint32_t*)nullptr); }
-        else if (wide)
-            hipLaunchKernelGGL((k_bucket_direct<GNDT_DIRECT_THREADS, 512, false, 1, 6>), bgrid, dim3(GNDT_DIRECT_THREADS), 0, s, bucket_recs, ranges, B, gp, q.raw,
-                               (uint32_t)rows_cap, q.ord_cf, q.ord_idx, order, h->d_cnt, q.d_pc, dbg, stats_out, fp_mask, interleave, rlist, (const uint32_t*)nullptr);
-        else { if (P.stats_only) GNDT_LAUNCH_DIRECT(GNDT_DIRECT_THREADS, 512, true, bgrid, rlist, (const uint32_t*)nullptr); else GNDT_LAUNCH_DIRECT(GNDT_DIRECT_THREADS, 512, false, bgrid, rlist, (const uint32_t*)nullptr); }
-        if (retry) {
-            const dim3 rgrid(std::min<uint32_t>(B, 256u));       // (one 1024-thread workgroup per CU; all of them leave at once when nothing is queued)
-            if (P.stats_only) GNDT_LAUNCH_DIRECT(1024, 1024, true, rgrid, (uint32_t*)nullptr, (const uint32_t*)rlist);
-            else GNDT_LAUNCH_DIRECT(1024, 1024, false, rgrid, (uint32_t*)nullptr, (const uint32_t*)rlist);
-        }
-#undef GNDT_LAUNCH_DIRECT
-    }
+    //  bucket kernel S3 32 M 595 | 585 us, S3 100 M 1.691 | 1.679 ms, S5 317 | 306 us: 2.  The host passes 0 or 2 only: the kernels'
+    //  interleave == 1 mapping is still compiled — taking it out would change device code — but nothing launches it.)
+    const uint32_t interleave = (q.pair_ratio < 0.0 || q.pair_ratio > 0.02) ? 2u : 0u;
+    // k_bucket_direct (gndt_bucket3.hpp): 512-slot tables with two workgroups per CU, 1024-slot tables on a retry
+    // A bucket whose 512-slot table overflows (a few wall columns; the spread of a hash partition over tall columns) is queued and
+    // done again by a SECOND PASS with 1024-slot tables over the queued buckets only (round 5) — it used to send the whole build
+    // round again.  The pass is launched behind a handle's first builds, behind builds recorded into a hipGraph (a replay cannot
+    // be re-run) and for as long as the last build used it; a handle whose clouds never overflow does not pay for the launch.
+    // Round 6: a RECORDED build carries the pass only if nothing is known about this cloud size (a capture on a reserved fresh
+    // handle) or the eager build before it used it: every replay of a recorded pass over an empty list is a launch of 256 x 1024
+    // threads that all leave again (~4 us of a 52 us frame).  A replay whose tables overflow without it is
+    // reported like any replay that does not fit (GNDT_ERR_CAPACITY: build that cloud eagerly, capture again).
+    const bool known_size = q.last_n == n && q.last_est != 0;
+    const bool retry = !blocked && bslots == 512 && (q.retry_pass || (h->capturing && !known_size));
+    P.retry_pass = retry;
+    BucketLaunch bk{};
+    bk.recs = (two || !one) ? q.recs : q.recs1;  bk.ranges = ranges;  bk.B = B;  bk.gp = gp;
+    bk.slots = bslots;  bk.blocked = blocked;  bk.stats_only = P.stats_only;  bk.second_pass = retry;
+    // one record per thread at three workgroups per CU for clouds without locality (interleave == 0: the last build counted next
+    // to no adjacent records of one node), two records at two workgroups per CU — with the pair folding — for the others
+    bk.wide = (interleave == 0u || tuning().bucket_three_wgs == 2) && !P.stats_only && tuning().bucket_three_wgs;
+    bk.rows_cap = std::min<uint64_t>(q.stage_cap, P.stats_only ? q.stage_cap : q.raw_cap);
+    bk.interleave = interleave;
+    bk.col_tab = col_dest ? q.col_tab : (uint4*)nullptr;
+    launch_buckets(h, bk, s);
     HIP_TRY(h, hipGetLastError());
     mark(h, 5, s);
     // (the counters and overflow flags come back with the last kernel: k_emit_rows stores them into the host's pinned mirrors)
@@ -580,14 +558,14 @@ int partition_begin(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride
     // met in two tiles counts twice) and is the better first guess (round 4: the 200 k-point campus frame has 0.37 nodes per point;
     // its first build on a fresh handle ran three times, 1.56 ms; a uniform cloud measures ratio 1 and keeps n / 4).
     uint64_t first_guess = std::max<uint64_t>(n / 4, 1024);
-    if (h->tile_ratio_seen >= 2.0 && h->tile_choice_n && n <= h->tile_choice_n + h->tile_choice_n / 4 && n + n / 4 >= h->tile_choice_n)
+    if (h->tile_ratio_seen >= 2.0 && h->tile_choice_n && within_quarter(n, h->tile_choice_n))
         first_guess = std::max<uint64_t>(1024, (uint64_t)((double)n / h->tile_ratio_seen * 1.15));
     P.nodes_est = h->P.max_nodes_hint ? h->P.max_nodes_hint : (q.nodes_learned ? q.nodes_learned : first_guess);
     P.est_reliable = h->P.max_nodes_hint != 0 || q.nodes_learned != 0;      // (not the n / 4 guess of a first build)
     // A fresh handle without a hint: count the nodes instead of guessing them (one pass, a HyperLogLog sketch: ~0.8 % standard
     // error; the estimate carries 6 % on top).  Not under hipGraph capture (the answer is awaited), not for records (their
     // producer knows), not for small clouds (a re-run costs them less than the wait).
-    if (!P.est_reliable && !records && n >= (1u << 20) && tuning().sketch) {
+    if (!P.est_reliable && !records && n >= (1u << 20)) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(s, &cap);
         if (cap == hipStreamCaptureStatusNone) {
@@ -633,6 +611,13 @@ int partition_begin(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride
     return GNDT_OK;
 }
 
+// what a replay that did not fit is reported with (after a later replay, and after the first one: partition_resolve)
+static std::string replay_capacity_error(const PartCounters& pc) {
+    return "a build replayed from a hipGraph ran out of room (LDS tables " + std::to_string(pc.lds_overflow) + ", partition regions " +
+           std::to_string(pc.part_overflow) + ", staging rows " + std::to_string(pc.stage_overflow) +
+           "): the capture is sized for the cloud it was recorded on — build this cloud eagerly (gndt_build_device + gndt_sync), then capture again";
+}
+
 // A PARTITION build captured in a hipGraph is replayed without the host: nobody starts a pending build, nobody looks at its flags.
 // They come home all the same (k_emit_rows stores them into the pinned mirrors), so the call that waits for the stream can see
 // that the build it finds on the device — necessarily a replay of the last one resolved here, while the handle's serial is still
@@ -655,9 +640,7 @@ int partition_recheck_after_replay(gndt_handle* h) {
     }
     h->results_valid = false;
     P.replay_failed = true;
-    h->err = "a build replayed from a hipGraph ran out of room (LDS tables " + std::to_string(q.h_pc->lds_overflow) + ", partition regions " +
-             std::to_string(q.h_pc->part_overflow) + ", staging rows " + std::to_string(q.h_pc->stage_overflow) +
-             "): the capture is sized for the cloud it was recorded on — build this cloud eagerly (gndt_build_device + gndt_sync), then capture again";
+    h->err = replay_capacity_error(*q.h_pc);
     return GNDT_ERR_CAPACITY;
 }
 
@@ -673,7 +656,7 @@ static void blocked_decide(gndt_handle* h, const gndt_handle::Pending& P) {
     const uint64_t n = P.n + P.n2;
     if (!tuning().blocked || P.stats_only || P.records || P.captured || !P.two_level || P.blocked || h->ever_captured) return;
     if (h->P.strategy != GNDT_STRATEGY_AUTO && h->P.strategy != GNDT_STRATEGY_PARTITION && h->P.strategy != GNDT_STRATEGY_PARTITION_TWO_LEVEL) return;
-    if (q.blk_state != 0 && n <= q.blk_n + q.blk_n / 4 && n + n / 4 >= q.blk_n) return;      // (decided for clouds of this size)
+    if (q.blk_state != 0 && within_quarter(n, q.blk_n)) return;      // (decided for clouds of this size)
     q.blk_state = -1; q.blk_n = n;
     if (!(q.pair_ratio >= 0.0 && q.pair_ratio <= 0.02)) return;                                // (clouds with locality: hot buckets, the pair folding)
     const uint64_t nodes = h->h_cnt->num_nodes;
@@ -729,7 +712,6 @@ int partition_resolve(gndt_handle* h) {
     auto& P = h->pending;
     if (!P.active) return GNDT_OK;
     auto& q = h->part;
-    const int env_slots = tuning().bucket_slots;
     int rc = GNDT_OK;
     for (;;) {
         if (hipStreamSynchronize(P.s) != hipSuccess) { P.active = false; h->err = "hipStreamSynchronize failed"; return GNDT_ERR_HIP; }
@@ -757,7 +739,7 @@ int partition_resolve(gndt_handle* h) {
             --P.attempt;                                       // one seen; after two failures the exact counting partition)
             again = true;
         } else if (q.h_pc->lds_overflow) {                            // some bucket holds too many nodes for its LDS table:
-            const bool without_retry = P.bslots == 512 && !P.retry_pass && tuning().retry_pass != 0 && !env_slots;
+            const bool without_retry = P.bslots == 512 && !P.retry_pass;
             q.retry_pass = true;                                      // (from now on overflowing buckets of this handle's clouds are done again locally)
             // (Lowering the average table load instead — more, smaller buckets — was measured: 1.19 ms against 0.80 ms with the
             // 1024-slot tables on the 3 M-node variant of the bench scene, and it does not help a hot column at all.)
@@ -768,10 +750,10 @@ int partition_resolve(gndt_handle* h) {
             const uint64_t b1024 = buckets_for(P.n + P.n2, P.nodes_est, 1024, P.load_pct ? P.load_pct : q.load_pct);
             if (without_retry) {
                 --P.attempt;                                     // the same tables once more, this time with the second pass behind them
-            } else if (P.bslots == 512 && !env_slots && P.n + P.n2 <= (1u << 20) && b1024 < 384 && (P.load_pct ? P.load_pct : q.load_pct) > 35) {
+            } else if (P.bslots == 512 && P.n + P.n2 <= (1u << 20) && b1024 < 384 && (P.load_pct ? P.load_pct : q.load_pct) > 35) {
                 P.load_pct = 35;
                 --P.attempt;                                     // (stay on the 512-slot tables)
-            } else if (P.attempt >= 1 || env_slots) {            // (attempt 0 -> 1 only switches to the 1024-slot table)
+            } else if (P.attempt >= 1) {                          // (attempt 0 -> 1 only switches to the 1024-slot table)
                 // More buckets: by 1.4x while only a few tables overflow (a cloud of tall columns — 10 M points at z = 0.1 m: one
                 // table in 5 500 — runs 15 % faster on 7 700 buckets than on the 11 000 a doubling gave it: fewer, fuller buckets
                 // amortise the per-bucket phases), doubling when many do.
@@ -804,9 +786,7 @@ int partition_resolve(gndt_handle* h) {
             P.done_serial = h->result_serial;
             P.replay_failed = true;
             h->table_dirty = false;
-            h->err = "a build replayed from a hipGraph ran out of room (LDS tables " + std::to_string(q.h_pc->lds_overflow) + ", partition regions " +
-                     std::to_string(q.h_pc->part_overflow) + ", staging rows " + std::to_string(q.h_pc->stage_overflow) +
-                     "): the capture is sized for the cloud it was recorded on — build this cloud eagerly (gndt_build_device + gndt_sync), then capture again";
+            h->err = replay_capacity_error(*q.h_pc);
             return GNDT_ERR_CAPACITY;
         }
         if (!again) {
@@ -880,7 +860,7 @@ int gndt_build_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stri
             { double r0 = 0.0; if (h->sample_pending && locality_sample_take(h, false, &r0)) adopt(r0, h->sample_n); }
             const bool stale = cap == hipStreamCaptureStatusNone && !h->sample_pending &&
                                (h->tile_choice < 0 || ++h->tile_choice_age >= 64 ||
-                                n > h->tile_choice_n + h->tile_choice_n / 4 || n + n / 4 < h->tile_choice_n);
+                                !within_quarter(n, h->tile_choice_n));
             if (stale) {
                 // A RE-sample (the cloud size changed by a quarter, or 64 builds have passed) on a handle that has room for whatever the
                 // cloud turns out to be does not WAIT for the answer (~50 us): the kernel and its copy ride in front of this build,
@@ -964,14 +944,7 @@ int gndt_reserve(gndt_handle* h, uint64_t max_points, uint64_t max_nodes) {
     if ((rc = grow_buf(h, q.recs1, q.rec1_cap, 4 * n + (1u << 24) + (uint64_t)kMaxFan * (4096 + 2 * kTile1)))) return rc;   // level-1 regions at their ceiling / one-level rooms
     const uint64_t Bexact = std::min<uint64_t>(Bmax, kMaxBuckets);
     if ((rc = grow_buf(h, q.hist, q.hist_cap, (uint64_t)kPartWgs * Bexact))) return rc;
-    if (Bexact > q.bucket_cap) {
-        release_device(h, q.totals);
-        release_device(h, q.bucket_base);
-        q.totals = q.bucket_base = nullptr; q.bucket_cap = 0;
-        HIP_TRY(h, hipMalloc(&q.totals, (size_t)Bexact * 4));
-        HIP_TRY(h, hipMalloc(&q.bucket_base, ((size_t)Bexact + 1) * 4));
-        q.bucket_cap = (uint32_t)Bexact;
-    }
+    if ((rc = ensure_bucket_totals(h, Bexact))) return rc;       // (asks about capture, like every buffer above; last_stream has been waited for: it is not capturing)
     // strategies ATOMIC / TILE (and gndt_update*): the node table
     if ((rc = reserve_table(h, std::max<uint64_t>(max_nodes, std::max<uint64_t>(1024, n / 4)), h->own_stream))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
@@ -1081,7 +1054,7 @@ int gndt_warmup(gndt_handle* h, uint64_t expected_points) {
     // (sizes within a quarter of one another make the same choices — partition levels, fan-outs, tile sizes, scans: what AUTO's own
     //  "similar cloud" rule uses — so a second handle of the process, or a second call, finds the code loaded and skips the runs)
     const uint64_t seen = known_device ? g_warm_points[h->device].load(std::memory_order_acquire) : 0;
-    const bool loaded = seen && n <= seen + seen / 4 && n + n / 4 >= seen;
+    const bool loaded = seen && within_quarter(n, seen);
     if (!loaded) {
         hipStream_t s = h->own_stream;
         float* cloud = nullptr;

@@ -12,9 +12,9 @@ namespace gndt_host {
 
 const Tuning& tuning_mut_ref();
 namespace {
-// (Round 5: twelve knobs that had lost — or never had — an A/B became constants of gndt_host::Tuning.  Round 6: the last
-//  environment reads are gone as well; the two diagnostics, AUTO's threshold and the flood's launch mode are set through
-//  gndt_debug_enable_stamps / gndt_debug_set_option, process-wide.)
+// (Round 5: twelve knobs that had lost — or never had — an A/B became constants.  Round 6: the last environment reads are gone as
+//  well; the two diagnostics, AUTO's threshold and the flood's launch mode are set through gndt_debug_enable_stamps /
+//  gndt_debug_set_option, process-wide.  Tuning holds only what those calls, a -D macro or tuning_force_* can set.)
 Tuning& tuning_storage() { static Tuning t; return t; }
 }  // namespace
 const Tuning& tuning() { return tuning_storage(); }
@@ -356,7 +356,7 @@ int create_handle(const gndt_params* params, gndt_handle** out, hipStream_t borr
         if (rc) { g_create_error = h->err; gndt_destroy(h); return rc; }
         if ((e = hipStreamSynchronize(h->own_stream)) != hipSuccess) return fail("hipStreamSynchronize", e);
     }
-    h->part.load_pct = tuning().bucket_load;
+    h->part.load_pct = kBucketLoad;
     *out = h;
     return GNDT_OK;
 }

@@ -509,6 +509,8 @@ int owner_split_launch(gndt_handle* h, const void* xyz, size_t n, size_t stride_
     const uint32_t nwg = (uint32_t)std::min<uint64_t>((uint64_t)kPartWgs, std::max<uint64_t>(1, n / 8192));
     if ((rc = grow_buf(h, q.hist, q.hist_cap, (uint64_t)nwg * W))) return rc;
     if (W > q.bucket_cap) {
+        // (partition_launch and gndt_reserve grow these through ensure_bucket_totals, which refuses under hipGraph capture; this site
+        //  never asked, and what it returns under capture stays what it was)
         release_device(h, q.totals);          // (shared with the exact partition, whose recorded builds write through them)
         release_device(h, q.bucket_base);
         q.totals = q.bucket_base = nullptr; q.bucket_cap = 0;
@@ -531,15 +533,12 @@ int owner_split_launch(gndt_handle* h, const void* xyz, size_t n, size_t stride_
         if ((rc = grow_buf(h, X.send_recs, X.send_cap, cap * W))) return rc;
         HIP_TRY(h, hipMemsetAsync(q.totals, 0, (size_t)W * 4, s));          // the runs' cursors = what every owner gets
         const uint32_t tiles = (uint32_t)((n + kTile1 - 1) / kTile1);
-        const dim3 g1(std::max<uint32_t>(1, std::min<uint32_t>(tiles, tuning().l1_wgs)));
-        if (stride_bytes == 12)
-            hipLaunchKernelGGL((k_part2_level1<3, 256, false, true>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)n, (uint32_t)first_base, gp, W, W, 0u, 1u,
-                               q.totals, (uint32_t)cap, (uint32_t*)nullptr, X.send_recs, X.d_split_cnt, q.d_pc, compress, M, (uint32_t*)nullptr,
-                               (uint32_t*)nullptr, 0ull, FoldClear{}, 0);
-        else
-            hipLaunchKernelGGL((k_part2_level1<4, 256, false, true>), g1, dim3(kTileThreads), 0, s, p, (uint64_t)n, (uint32_t)first_base, gp, W, W, 0u, 1u,
-                               q.totals, (uint32_t)cap, (uint32_t*)nullptr, X.send_recs, X.d_split_cnt, q.d_pc, compress, M, (uint32_t*)nullptr,
-                               (uint32_t*)nullptr, 0ull, FoldClear{}, 0);
+        Level1Launch l1;         // (a region per rank, dense cursors, nothing sampled, no layout)
+        l1.in = p;  l1.n = n;  l1.stride_floats = (int)(stride_bytes / 4);  l1.first_base = (uint32_t)first_base;  l1.gp = gp;  l1.compress = compress;
+        l1.B = W;  l1.F1 = W;  l1.owner = M;
+        l1.cursor1 = q.totals;  l1.cap1 = (uint32_t)cap;  l1.recs1 = X.send_recs;  l1.cnt = X.d_split_cnt;  l1.pc = q.d_pc;
+        l1.grid = dim3(std::max<uint32_t>(1, std::min<uint32_t>(tiles, kL1Wgs)));
+        launch_level1<Level1Input::OwnerSplit>(l1, s);
         HIP_TRY(h, hipGetLastError());
         X.split_cap = cap;
         uint32_t* h_base = X.h_matrix + kMatrixHostWords;
@@ -903,7 +902,7 @@ int gndt_build_owned_device(gndt_handle* h, gndt_comm* c, const void* shard_xyz_
     stamp(0);
     // 0. who owns what: everybody's samples (one fixed-size all-gather, no wait) -> the block table, identical on every rank
     X.owner_map_world = 0;
-    if (W > 1 && W <= (int)kOwnerMapMaxRanks && tuning().owner_locality) {
+    if (W > 1 && W <= (int)kOwnerMapMaxRanks) {      // (sampled block ownership; beyond that many ranks, hash ownership only)
         if (!X.owner_msg) HIP_TRY(h, hipMalloc(&X.owner_msg, (size_t)kOwnerMsgWords * 4));
         if ((rc = grow_buf(h, X.owner_msgs_all, X.owner_msgs_cap, (uint64_t)kOwnerMsgWords * W))) return rc;
         if (err || !note(owner_sample_launch(h, shard_xyz_dev, n, stride_bytes, s)))

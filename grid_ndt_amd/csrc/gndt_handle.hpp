@@ -378,37 +378,26 @@ struct gndt_handle {
 namespace gndt_host {
 using namespace gndt;
 
-// Diagnostic / tuning knobs from the environment, parsed ONCE per process (DESIGN.md "Diagnostic and tuning knobs").
+// What a process can set about the library, and nothing else: a field of Tuning is set by a gndt_debug_* call (process-wide, for the
+// calls that follow), by one of the -D macros of DESIGN §4.5 (A/B builds) or by tuning_force_*.  The library reads no environment variable.
+// Choices that lost their knob are constants here or at the place they decide, each with the measurement that set it.
 // (Folded into constants in round 4, each after losing its A/B: level-1 cursor replicas (1), workgroups of the counting partition
 //  (256), incremental updates through the tile kernel (by strategy), every rank ordering all columns instead of its slice (no).)
 constexpr int kPartWgs = 256;    // workgroups of the exact counting partition
+constexpr int kBucketLoad = 60;        // average LDS-table load (percent) that sizes the bucket count
+constexpr int kBucketLoadLarge = 75;   // the same from 2 M points on (the chip is full either way: fuller tables, fewer buckets; 85 / 92 with the second pass behind them: noise, r05 §4)
+constexpr uint32_t kL1Wgs = 2048;      // level-1 workgroups (512 are resident: 2048 of them, ~1.2 tiles each, 69 us against 75 with 1024 and 72 with 512 on the bench scene, r05 §5)
 struct Tuning {
-    // constants (each with the measurement that set it) ...
-    int bucket_load = 60;        // average LDS-table load (percent) that sizes the bucket count
-    int bucket_load_large = 75;  // the same from 2 M points on (the chip is full either way: fuller tables, fewer buckets; 85 / 92 with the second pass behind them: noise, r05 §4)
+    // set at build time (-D, each with its A/B in profiles/r06_ablation.txt) ...
 #ifndef GNDT_BUCKET_POINTS
 #define GNDT_BUCKET_POINTS 0
 #endif
     int bucket_points = GNDT_BUCKET_POINTS;       // points per bucket (0 = derived: 700 .. 3600 with the cloud's size)
-    int bucket_slots = 0;        // LDS table of the first attempt (0 = 512, 1024 on a retry)
-    int two_level = -1;          // 0 = never use the two-level partition
-    uint32_t l1_wgs = 2048;      // level-1 workgroups (512 are resident: 2048 of them, ~1.2 tiles each, 69 us against 75 with 1024 and 72 with 512 on the bench scene, r05 §5)
-    uint32_t bucket_wgs = 0xFFFFFFFFu;   // persistent bucket workgroups (default: one per bucket; 512 persistent ones measured +8 %)
-    int one_level = 1;           // small clouds: level 1 writes the buckets directly (0: counting partition)
-    int owner_locality = 1;      // owner-partitioned build: sampled block ownership (1) or hash ownership only (0)
-    int interleave = -1;         // bucket kernel: which records a lane takes — consecutive pairs (0), pairs interleaved over the waves (1), a contiguous
-                                 //   stretch of the bucket per lane (2) — or by the last build's locality (-1: 0 without, 2 with; r05 §3)
-    int sketch = 1;              // a fresh handle without a hint counts its first cloud's nodes (HyperLogLog pass) instead of guessing n / 4
-    int retry_pass = 1;          // 0: never launch the bucket kernel's second pass (an overflowing 512-slot table re-runs the build, as before round 5)
 #ifndef GNDT_PLACE_EMIT_WORDS
 #define GNDT_PLACE_EMIT_WORDS 16384
 #endif
     int place_emit_words = GNDT_PLACE_EMIT_WORDS;    // PARTITION builds of clouds with up to this many bitmap words (32 points each): ordering + emit as one kernel
                                                      //   in scatter form (gndt_partition.hpp k_place_emit_rows; 0: never)
-    int dest_scans = 1;          // small clouds: the destination pass scans the word weights itself instead of one or two scan launches in front of it
-                                 //   (200 k-point campus frame 0.0549 -> 0.0535 ms, bridge_ground 0.0647 -> 0.0646: r05 ablation 6h)
-    int small_tiles = 1;         // one-level partition of < 1 M points: 1024-point level-1 tiles (a few hundred workgroups instead of a few dozen:
-                                 //   campus frame 0.0535 -> 0.0520 ms, bridge_ground 0.0648 -> 0.0608; r05 ablation 6i)
 #ifndef GNDT_BLOCKED
 #define GNDT_BLOCKED 1
 #endif
@@ -422,7 +411,7 @@ struct Tuning {
 #endif
     int fold_clear = GNDT_FOLD_CLEAR;    // eager PARTITION builds: no k_part_clear launch — level 1 prepares the next build's cursors / counters (Part::cursors_alt)
     int fp_bits = 21;            // bits of the bucket kernel's index fingerprint (tests narrow it through gndt_debug_set_fp_bits to force clashes)
-    // ... and what gndt_debug_set_option / gndt_debug_enable_stamps can set (process-wide; the library reads no environment variable)
+    // ... and what gndt_debug_set_option / gndt_debug_enable_stamps can set (process-wide)
     double tile_ratio = 48.0;    // GNDT_DEBUG_TILE_RATIO   AUTO takes strategy TILE from this many points per partial on (sampled; the
                                  //                         measured crossover, profiles/r02_tile_calibration.json; tools/calibrate_tile.py sweeps it)
     bool stamps = false;         // gndt_debug_enable_stamps: in-kernel phase stamps of the bucket kernel
@@ -563,6 +552,52 @@ int grow_buf(gndt_handle* h, T*& p, uint64_t& cap, uint64_t want) {
     HIP_TRY(h, hipMalloc(&p, want * sizeof(T)));
     cap = want;
     return GNDT_OK;
+}
+
+// "a cloud of this size": within a quarter of `of`, either way (the blocked box, AUTO's locality sample, the warm-up)
+inline bool within_quarter(uint64_t n, uint64_t of) { return n <= of + of / 4 && n + n / 4 >= of; }
+
+// One launch of k_part2_level1 (gndt_partition.hpp) by name.  What is left at its default is what a launch without it passes.
+struct Level1Launch {
+    const float* in = nullptr;  uint64_t n = 0;  int stride_floats = 4;   // the input: points of 3 or 4 floats, or 16-byte records
+    uint32_t first_base = 0;    // global index of in[0]
+    GridParams gp{};
+    uint32_t B = 0, F1 = 0, F2_shift = 0;       // buckets (ranks), level-1 regions, log2 of the level-2 fan-out
+    uint32_t replicas = 1;      // sub-regions per region (cursor replicas)
+    bool fan512 = false;        // more than 256 regions: the LDS arrays of the large fan-out
+    bool small_tiles = false;   // points only: tiles of kTilePerSmall points per thread
+    uint32_t* cursor1 = nullptr;  uint32_t cap1 = 0;  int cursor_shift = 0;      // the regions' fills, a region's room, the cursors' spacing (log2 words)
+    uint32_t* est2 = nullptr;   // the sample votes
+    float4* recs1 = nullptr;    // the output records
+    Counters* cnt = nullptr;  PartCounters* pc = nullptr;
+    uint32_t compress = 0;
+    OwnerMap owner{nullptr, nullptr, 0u, nullptr};
+    uint32_t *range_lo = nullptr, *range_cap = nullptr;  uint64_t rec_cap = 0;   // the buckets' layout, written by the last workgroup to finish (null: none)
+    FoldClear fold{};
+    dim3 grid{1};
+};
+// What the input is decides which instantiations a translation unit carries: Points <3|4, 256|512> and the same with kTilePerSmall,
+// Records <4, 256|512, true>, OwnerSplit <3|4, 256, false, true> (gndt_api_dist.hip; at most 256 ranks).
+enum class Level1Input { Points, Records, OwnerSplit };
+template <int SF, int FAN, auto... MORE>      // (MORE: IDXW, OWNER, PER1 — the kernel's own defaults where left out)
+void enqueue_level1(const Level1Launch& a, hipStream_t s) {      // (the one place that knows the kernel's argument order)
+    hipLaunchKernelGGL((k_part2_level1<SF, FAN, MORE...>), a.grid, dim3(kTileThreads), 0, s, a.in, a.n, a.first_base, a.gp, a.B, a.F1, a.F2_shift,
+                       a.replicas, a.cursor1, a.cap1, a.est2, a.recs1, a.cnt, a.pc, a.compress, a.owner, a.range_lo, a.range_cap, a.rec_cap, a.fold, a.cursor_shift);
+}
+template <Level1Input IN>
+void launch_level1(const Level1Launch& a, hipStream_t s) {
+    const bool f3 = a.stride_floats == 3, wide = a.fan512;
+    if constexpr (IN == Level1Input::OwnerSplit) {
+        if (f3) enqueue_level1<3, 256, false, true>(a, s); else enqueue_level1<4, 256, false, true>(a, s);
+    } else if constexpr (IN == Level1Input::Records) {
+        if (wide) enqueue_level1<4, 512, true>(a, s); else enqueue_level1<4, 256, true>(a, s);
+    } else if (a.small_tiles) {
+        if (f3) { if (wide) enqueue_level1<3, 512, false, false, kTilePerSmall>(a, s); else enqueue_level1<3, 256, false, false, kTilePerSmall>(a, s); }
+        else { if (wide) enqueue_level1<4, 512, false, false, kTilePerSmall>(a, s); else enqueue_level1<4, 256, false, false, kTilePerSmall>(a, s); }
+    } else {
+        if (f3) { if (wide) enqueue_level1<3, 512>(a, s); else enqueue_level1<3, 256>(a, s); }
+        else { if (wide) enqueue_level1<4, 512>(a, s); else enqueue_level1<4, 256>(a, s); }
+    }
 }
 
 // ---- gndt_api_core.hip: shared buffers ----
