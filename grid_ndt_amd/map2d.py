@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, Stats, WalkInfo, WalkParams
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, ShortcutParams, Stats, WalkInfo, WalkParams
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -978,6 +978,129 @@ class TwoDmap:
         if row_cap:
             out["rows"] = out_rows
         return out
+
+    # ---- route shortcutting (gndt_shortcut_routes*: slope-to-slope routes string-pulled into any-angle waypoints) ----
+    SHORTCUT_STATUS = {0: "ok", 1: "empty", 2: "bad_route", 3: "limit"}
+    SHORTCUT_INFO_DTYPE = np.dtype([("status", np.int32), ("length_in", np.int32), ("waypoints", np.int32), ("path_slopes", np.int32),
+                                    ("links_tested", np.int32), ("fallback_links", np.int32), ("cost_in", np.float32),
+                                    ("cost_out", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 3)])
+
+    def shortcut_routes(self, routes, lengths=None, robot=None, window=64, overhead=False, hops=None, min_hops=0, waypoint_cap=None, path_cap=0,
+                        max_links=0, stream=None, host=False):
+        """String-pull K routes into any-angle waypoints (include/gndt.h "route shortcutting" defines every word).  routes: what
+        plan_routes() returned — its rows and its info, whose lengths are read where they lie — or a [K, route_cap] int32 rows array
+        with `lengths` ([K] int32).  From every anchor the farthest row of the next `window` (at most 256) that the robot can drive to
+        in a straight line becomes the next anchor: the link is the path walk between the two columns' centres under the flood's gates
+        for `robot` (computeCost's dict; None = its defaults), with overhead / hops / min_hops as in walk_paths; where no link holds
+        the route's own next row is kept.  waypoint_cap None = route_cap; path_cap > 0 also returns the slopes stood on; max_links 0 =
+        2^20 candidates a route.  Returns a dict of [K] arrays status (SHORTCUT_STATUS), length_in, waypoints, path_slopes,
+        links_tested, fallback_links, cost_in, cost_out, hops_min (-1 = no hops given), `waypoint_rows` [K, waypoint_cap] and with
+        path_cap `path_rows` [K, path_cap] (int32, -1 behind the end).  torch tensors on the routes' device, enqueued on `stream`
+        (default torch's current stream) and not awaited; host=True or numpy arrays go through gndt_shortcut_routes (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if isinstance(routes, (tuple, list)) and len(routes) == 2 and isinstance(routes[1], dict):
+            routes, lengths = routes[0], routes[1]["length"]
+        if lengths is None:
+            raise ValueError("shortcut_routes: rows need their lengths")
+        on_dev = hasattr(routes, "is_cuda") and routes.is_cuda and not host
+        if len(routes.shape) != 2 or int(lengths.shape[0]) != int(routes.shape[0]) or len(lengths.shape) != 1:
+            raise ValueError("routes must be [K, route_cap] and lengths [K]")
+        K, route_cap = int(routes.shape[0]), int(routes.shape[1])
+        wp_cap = route_cap if waypoint_cap is None else int(waypoint_cap)
+        path_cap = int(path_cap)
+        if isinstance(hops, dict):
+            hops = hops["hops"]
+        prm = ShortcutParams(int(window), 1 if overhead else 0, int(min_hops), int(max_links))
+        rb = None
+        if robot is not None:
+            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+            d.update(robot)
+            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        n = int(self.sync()[0])
+        if hops is not None and int(hops.shape[0]) != n:
+            raise ValueError(f"hops has {int(hops.shape[0])} entries, the map {n} rows: a clearance field of another map")
+        names = ("status", "length_in", "waypoints", "path_slopes", "links_tested", "fallback_links", "cost_in", "cost_out", "hops_min")
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                r = routes.contiguous()
+                if r.dtype != torch.int32:
+                    r = r.to(torch.int32)
+                ln = torch.as_tensor(lengths, device=r.device)
+                if ln.dtype != torch.int32 or (K > 1 and ln.stride(0) < 1):
+                    ln = ln.to(torch.int32).contiguous()
+                stride = 4 * int(ln.stride(0)) if K > 1 else 4
+                if isinstance(hops, np.ndarray):
+                    hops = np.ascontiguousarray(hops).view(np.int32)
+                hp = None if hops is None else torch.as_tensor(hops, device=r.device).contiguous()
+                if hp is not None and hp.dtype != torch.int32:
+                    hp = hp.to(torch.int32)
+                raw = torch.zeros((max(K, 1), 12), dtype=torch.int32, device=r.device)
+                wp = torch.empty((K, wp_cap), dtype=torch.int32, device=r.device)
+                out_path = torch.empty((K, path_cap), dtype=torch.int32, device=r.device) if path_cap else None
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_shortcut_routes_device(self._h, ptr(r), K, route_cap, ptr(ln), stride, rb, C.byref(prm), ptr(hp),
+                                                            C.c_void_p(wp.data_ptr() if wp.numel() else raw.data_ptr()), wp_cap,
+                                                            C.c_void_p(out_path.data_ptr()) if path_cap else None, path_cap,
+                                                            C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
+            raw = raw[:K]
+            out = {k: (raw[:, i].view(torch.float32) if k in ("cost_in", "cost_out") else raw[:, i]) for i, k in enumerate(names)}
+        else:
+            to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+            r = np.ascontiguousarray(to_np(routes))
+            r = r.view(np.int32) if r.dtype in (np.int32, np.uint32) else r.astype(np.int32)
+            ln = to_np(lengths)
+            if ln.dtype.itemsize != 4 or ln.dtype.kind not in "iu" or (K > 1 and (ln.strides[0] < 4 or ln.strides[0] % 4)):
+                ln = np.ascontiguousarray(ln, np.int32)
+            stride = int(ln.strides[0]) if K > 1 else 4
+            hp = None if hops is None else np.ascontiguousarray(to_np(hops)).view(np.uint32)
+            raw = np.zeros(max(K, 1), self.SHORTCUT_INFO_DTYPE)
+            wp = np.empty((K, wp_cap), np.int32)
+            out_path = np.empty((K, path_cap), np.int32) if path_cap else None
+            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_shortcut_routes(self._h, ptr(r), K, route_cap, ptr(ln), stride, rb, C.byref(prm), ptr(hp),
+                                                     C.c_void_p(wp.ctypes.data if wp.size else raw.ctypes.data), wp_cap,
+                                                     C.c_void_p(out_path.ctypes.data) if path_cap else None, path_cap, C.c_void_p(raw.ctypes.data)))
+            out = {k: raw[k][:K] for k in names}
+        out["waypoint_rows"] = wp
+        if path_cap:
+            out["path_rows"] = out_path
+        return out
+
+    def route_waypoints(self, rows):
+        """World points [K, cap, 3] float32 of routes of rows ([K, cap] int32, -1 behind a route's end: plan_routes' rows, or
+        shortcut_routes' waypoint_rows / path_rows): the centre of each row's column — per axis (float)(o + sign(s) (|s| - 0.5)
+        grid_len) in fp64, the points the shortcut's links run between — and the row's mean z; NaN behind the end, which is the walks'
+        terminator: the result goes into walk_paths as it is.  Torch in, torch out (export_device()); numpy in, numpy out (export())."""
+        on_dev = not isinstance(rows, np.ndarray)
+        cells = self.export_device() if on_dev else self.export()
+        o = [float(np.float32(v)) for v in self.cloudFirst]
+        g = float(np.float32(self.gridLen))
+        if on_dev:
+            import torch
+            pts = torch.full(tuple(rows.shape) + (3,), float("nan"), dtype=torch.float32, device=rows.device)
+            if int(cells["num_nodes"]) == 0 or rows.numel() == 0:
+                return pts
+            live = rows >= 0
+            at = rows.long().clamp(min=0)
+            for a, k in enumerate(("sx", "sy")):
+                s = cells[k][at].double()
+                pts[..., a] = (o[a] + torch.sign(s) * (s.abs() - 0.5) * g).float()
+            pts[..., 2] = cells["mean"][at, 2]
+            pts[~live] = float("nan")
+            return pts
+        pts = np.full(rows.shape + (3,), np.nan, np.float32)
+        if int(cells["num_nodes"]) == 0 or rows.size == 0:
+            return pts
+        live = rows >= 0
+        at = np.where(live, rows, 0).astype(np.int64)
+        for a, k in enumerate(("sx", "sy")):
+            s = cells[k][at].astype(np.float64)
+            pts[..., a] = (o[a] + np.sign(s) * (np.abs(s) - 0.5) * g).astype(np.float32)
+        pts[..., 2] = cells["mean"][at, 2]
+        pts[~live] = np.nan
+        return pts
 
     # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
     CLEAR_PROTECTED = 0x80000000

@@ -746,6 +746,81 @@ int gndt_walk_paths(gndt_handle* h, const void* paths_host, size_t K, size_t T, 
                     const gndt_walk_params* params, const uint32_t* hops_host, uint32_t* rows_host, uint32_t row_cap,
                     gndt_walk_info* info_host);
 
+/* ---- route shortcutting: any-angle waypoints from slope-to-slope routes ---------------------------------------------------------
+ * What gndt_plan_routes* returns is a staircase of 4-neighbour slopes, one waypoint a cell.  A controller wants it string-pulled: only
+ * the waypoints between which the robot can drive straight, and no corner cut closer to a barrier than the caller allows.  One call
+ * takes K routes in the layout gndt_plan_routes* writes: route_rows[k * route_cap + i], start first; its length n_k is the uint32 at
+ * lengths + k * length_stride_bytes (stride sizeof(gndt_route_info) with &info[0].length of a plan call, stride 4 for a plain array).
+ * A route need not come from the planner: any sequence of slope rows is one.  `robot` NULL = the flood's defaults.
+ * Link(a, b) for two rows:
+ *   1. both rows are < num_nodes and have GNDT_FLAG_SLOPE;
+ *   2. P_a, P_b: the centres of their columns, per axis (float)((double)o + sign(s) * (|s| - 0.5) * (double)grid_len) (no index 0);
+ *   3. both points take z = mean_z(a); the levels are ignored, as in the walks;
+ *   4. point_key of either point does not give back that row's column: the link fails;
+ *   5. the columns are more than `window` unit steps apart (|dlx| + |dly| in lattice cells): the link fails untested;
+ *   6. otherwise the link is the path walk ("path walks" 2 - 4) of the two-waypoint polyline P_a -> P_b: the ray walk's column
+ *      sequence, the step through a side, the checks on every slope stood on, a included (GNDT_WALK_CHECK_OVERHEAD in
+ *      params->checks; hops_dev with params->min_hops, under the walk call's conditions on hops_dev) —
+ *   7. except that the walk STARTS STANDING ON ROW a, not on what the start lookup finds;
+ *   8. the link HOLDS iff the walk ends GNDT_WALK_DONE ON ROW b (b's column reached on another storey is not enough).
+ * Per route with rows r[0 .. n):
+ *   1. out = [r[0]], anchor a = 0.
+ *   2. while a < n - 1: the candidates are j in (a, min(a + window, n - 1)], in groups of 64 counted from the anchor: a+1 .. a+64,
+ *      a+65 .. a+128, ...
+ *   3. the groups are evaluated from the farthest down; the first group in which a link r[a] -> r[j] holds ends the search;
+ *   4. the next anchor is the largest j of that group whose link holds;
+ *   5. no link holds in any group: the next anchor is a + 1, a FALLBACK LINK — the route's own step, kept untested, so the output
+ *      is never worse than the input;
+ *   6. links_tested counts the candidates of the groups evaluated (the group order is part of the definition);
+ *   7. before a group is evaluated, links_tested plus its size is checked against max_links: if it would exceed it the route ends
+ *      with GNDT_SHORTCUT_LIMIT and the rows from a + 1 on are appended as fallback links (the output is still a route).
+ * waypoint_rows[k * waypoint_cap ..]: the anchors, start first and goal last, GNDT_NO_ROW behind them; a longer answer writes its
+ * first waypoint_cap rows and `waypoints` says so.  path_rows (optional: NULL exactly when path_cap is 0) [k * path_cap ..]: every
+ * slope stood on along the accepted links, in order, each junction once; a fallback link contributes r[a + 1]; cut and filled the
+ * same way.  Where every link is a 4-neighbour step this is again a slope-to-slope route.
+ * gndt_shortcut_info, written 16 bytes at a time: status — GNDT_SHORTCUT_OK; _EMPTY for n = 0; _BAD_ROUTE for n > route_cap or a row
+ * that is out of range (GNDT_NO_ROW is), or holds no slope: nothing is tested and nothing but the GNDT_NO_ROW tails is written, the
+ * counts and sums are 0 but length_in; _LIMIT — length_in = n; waypoints; path_slopes; links_tested; fallback_links; cost_in, the sum
+ * of TravelCost over consecutive input rows, and cost_out, the same sum over consecutive path rows whether or not they are written,
+ * both added in order in fp64 and rounded to fp32 once; hops_min over the path's slopes, GNDT_CLEARANCE_BEYOND without hops_dev.
+ * Order, lifetime and refusals follow the walk call's: after what gndt_sync finishes, on the map's column index, enqueued on
+ * `hip_stream` (NULL = the handle's stream) and not awaited; gndt_shortcut_routes is synchronous and takes host memory of any
+ * alignment.  No cost map is needed; the map, h and state are not modified.  K == 0 returns GNDT_OK and launches nothing.  There is no
+ * CPU path.  GNDT_ERR_INVALID: a null handle, params or info, null routes or lengths with K > 0, K >= 2^31, route_cap 0 with K > 0, a
+ * stride below 4 or not a multiple of 4, window > 256 (with n anchors, window / 64 groups and up to `window` steps a lane the worst
+ * case grows with window^2 n, and the device is shared), unknown check bits, max_links > 2^24, a non-zero reserved word,
+ * waypoint_rows NULL, path_rows NULL with path_cap != 0 or the reverse, info_dev not aligned to 16 bytes or another device pointer not
+ * to 4, no finished build, a stream under hipGraph capture. */
+enum { GNDT_SHORTCUT_OK = 0, GNDT_SHORTCUT_EMPTY = 1, GNDT_SHORTCUT_BAD_ROUTE = 2, GNDT_SHORTCUT_LIMIT = 3 };
+typedef struct gndt_shortcut_params {
+    uint32_t window;          /* candidates looked at behind an anchor, and the most unit steps of a link; 0 = 64, at most 256 */
+    uint32_t checks;          /* GNDT_WALK_CHECK_* bits */
+    uint32_t min_hops;        /* with hops: a slope with fewer hops fails the link (0: none does) */
+    uint32_t max_links;       /* 0 = 2^20, at most 2^24 */
+    uint32_t reserved[4];     /* 0 */
+} gndt_shortcut_params;       /* 32 bytes; zeros = defaults */
+typedef struct gndt_shortcut_info {
+    int32_t status;           /* GNDT_SHORTCUT_* */
+    uint32_t length_in, waypoints, path_slopes;
+    uint32_t links_tested, fallback_links;
+    float cost_in, cost_out;
+    uint32_t hops_min;
+    uint32_t reserved[3];     /* 0 */
+} gndt_shortcut_info;         /* 48 bytes */
+/* Device memory in and out. */
+int gndt_shortcut_routes_device(gndt_handle* h, const uint32_t* route_rows_dev, size_t K, uint32_t route_cap,
+                                const void* lengths_dev, size_t length_stride_bytes,
+                                const gndt_robot* robot, const gndt_shortcut_params* params, const uint32_t* hops_dev /* [num_nodes] or NULL */,
+                                uint32_t* waypoint_rows_dev /* [K * waypoint_cap] */, uint32_t waypoint_cap,
+                                uint32_t* path_rows_dev /* [K * path_cap] or NULL */, uint32_t path_cap,
+                                gndt_shortcut_info* info_dev /* [K] */, void* hip_stream);
+/* Host memory in and out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_shortcut_routes(gndt_handle* h, const uint32_t* route_rows_host, size_t K, uint32_t route_cap,
+                         const void* lengths_host, size_t length_stride_bytes,
+                         const gndt_robot* robot, const gndt_shortcut_params* params, const uint32_t* hops_host,
+                         uint32_t* waypoint_rows_host, uint32_t waypoint_cap, uint32_t* path_rows_host, uint32_t path_cap,
+                         gndt_shortcut_info* info_host);
+
 /* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
  * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
  * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
