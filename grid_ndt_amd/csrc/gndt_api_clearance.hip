@@ -78,8 +78,7 @@ int clearance_enqueue(gndt_handle* h, const Robot& R, const ClearanceRule& F, ui
     key[1] = key[0] + n;
     uint32_t* flags = reinterpret_cast<uint32_t*>(key[1] + n);
     uint8_t* tall = reinterpret_cast<uint8_t*>(flags + kFlagWords);
-    CostView V = query_view(h).V;
-    V.normal = h->out.normal;
+    const CostView V = query_view(h).V;
     const bool wg = tuning().clearance_one_workgroup && n <= kClrLdsRows && clearance_lds_granted(h);
     if (!wg) HIP_TRY(h, hipMemsetAsync(flags, 0, ((uint64_t)F.max_hops + 1) * sizeof(uint32_t), s));
     // the row passes: at most 2048 workgroups of 256 threads (what the chip holds at once), grid-stride beyond
@@ -95,11 +94,6 @@ int clearance_enqueue(gndt_handle* h, const Robot& R, const ClearanceRule& F, ui
     }
     HIP_TRY(h, hipGetLastError());
     return GNDT_OK;
-}
-
-Robot clearance_robot(const gndt_robot* robot) {
-    if (!robot) return Robot{0.25f, 0.15f, 100.f, 30.f};        // the flood's defaults (gndt_compute_cost)
-    return Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
 }
 
 }  // namespace
@@ -118,7 +112,7 @@ int gndt_clearance_device(gndt_handle* h, const gndt_robot* robot, const gndt_cl
         h->err = "gndt_clearance_device: hops_dev, nearest_dev and counts_dev must be aligned to 4 bytes";
         return GNDT_ERR_INVALID;
     }
-    return clearance_enqueue(h, clearance_robot(robot), F, hops_dev, nearest_dev, sides_dev, counts_dev, stream_of(h, hip_stream));
+    return clearance_enqueue(h, robot_of(robot), F, hops_dev, nearest_dev, sides_dev, counts_dev, stream_of(h, hip_stream));
 }
 
 int gndt_clearance(gndt_handle* h, const gndt_robot* robot, const gndt_clearance_params* params, uint32_t* hops_host, uint32_t* nearest_host,
@@ -134,7 +128,7 @@ int gndt_clearance(gndt_handle* h, const gndt_robot* robot, const gndt_clearance
     const uint64_t bytes[4] = {hops_host ? rows * 4 : 0, nearest_host ? rows * 4 : 0, sides_host ? rows : 0, 4 * sizeof(uint32_t)};
     void* dev[4];
     if ((rc = stage_pieces(h, bytes, dev, 4))) return rc;
-    if ((rc = clearance_enqueue(h, clearance_robot(robot), F, static_cast<uint32_t*>(dev[0]), static_cast<uint32_t*>(dev[1]),
+    if ((rc = clearance_enqueue(h, robot_of(robot), F, static_cast<uint32_t*>(dev[0]), static_cast<uint32_t*>(dev[1]),
                                 static_cast<uint8_t*>(dev[2]), static_cast<uint32_t*>(dev[3]), s)))
         return rc;
     void* host[4] = {hops_host, nearest_host, sides_host, counts_host};

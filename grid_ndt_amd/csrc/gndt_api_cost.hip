@@ -2,6 +2,7 @@
 #include <atomic>
 
 #include "gndt_handle.hpp"
+#include "gndt_query.hpp"
 
 using namespace gndt;
 using namespace gndt_host;
@@ -96,8 +97,7 @@ int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot*
         HIP_TRY(h, hipMalloc(&c.edges, cap * 4 * sizeof(CostEdge)));
         c.node_cap = cap;
     }
-    Robot R{0.25f, 0.15f, 100.f, 30.f};   // receiver.cpp:33, robot.h:38-46
-    if (robot) R = Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
+    const Robot R = robot_of(robot);
     c.ring_n = cost_ring_depth(R.r, h->P.grid_len);
     // What depends on the map and the robot only — every row's neighbour columns / own column / CostEdge records, CollisionCheck's
     // verdict for every slope — is kept from one flood to the next on top of the map's column index: the planner asks for a new goal
@@ -106,13 +106,7 @@ int gndt_compute_cost(gndt_handle* h, const float goal_xyz[3], const gndt_robot*
     const bool tables_kept = K && index_current(h) && map_current(h, c.tables_serial) && std::memcmp(robot4, c.tables_robot, sizeof(robot4)) == 0;
     c.tables_serial = 0;
     if ((rc = column_index(h, s, true))) return rc;
-    CostView V;
-    V.sx = h->out.sx; V.sy = h->out.sy; V.sz = h->out.sz;
-    V.mean = h->out.mean; V.normal = h->out.normal; V.rough = h->out.rough; V.flags = h->out.flags;
-    V.row_ncol = h->part.row_ncol;
-    V.ctab_key = h->index.key; V.ctab_val = h->index.val; V.ctab_mask = h->index.mask;
-    V.nbr = nullptr; V.self = nullptr;
-    V.slope_interval = h->P.slope_interval; V.demand_true = h->P.demand == GNDT_DEMAND_TRUE ? 1 : 0;
+    CostView V = query_view(h).V;      // (after column_index: the index is this map's; nbr, self and edges are null until made below)
     // the goal's key through the same codec the build uses (transMortonXYZ, map2D.h:1293)
     const PointKey gk = point_key(goal_xyz[0], goal_xyz[1], goal_xyz[2], h->origin[0], h->origin[1], h->origin[2],
                                   h->P.grid_len, h->P.z_len);

@@ -52,13 +52,8 @@ int plan_sync(gndt_handle* h, hipStream_t s) {
 
 PlanView plan_view(gndt_handle* h) {
     PlanView P{};
-    CostView& V = P.V;
-    V.sx = h->out.sx; V.sy = h->out.sy; V.sz = h->out.sz;
-    V.mean = h->out.mean; V.normal = h->out.normal; V.rough = h->out.rough; V.flags = h->out.flags;
-    V.row_ncol = h->part.row_ncol;
-    V.ctab_key = h->index.key; V.ctab_val = h->index.val; V.ctab_mask = h->index.mask;
+    CostView& V = P.V = query_view(h).V;
     V.nbr = h->cost.nbr; V.self = h->cost.nbr + 8 * h->cost.node_cap; V.edges = h->cost.edges;
-    V.slope_interval = h->P.slope_interval; V.demand_true = h->P.demand == GNDT_DEMAND_TRUE ? 1 : 0;
     const float* r = h->cost.tables_robot;
     P.R = Robot{r[0], r[1], r[2], r[3]};
     P.h_bits = h->cost.h_bits;

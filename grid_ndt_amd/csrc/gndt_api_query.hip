@@ -17,13 +17,15 @@ int query_sync(gndt_handle* h, bool gather, hipStream_t s, const char* capture_e
     return rc;
 }
 
-// The rows, the column index and the cost map as the query kernels read them
+// The rows, the column index and the cost map as every consumer's kernels read them
 QueryView query_view(gndt_handle* h) {
     QueryView Q{};
-    Q.V.sx = h->out.sx; Q.V.sy = h->out.sy; Q.V.sz = h->out.sz;
-    Q.V.mean = h->out.mean; Q.V.flags = h->out.flags; Q.V.rough = h->out.rough;
-    Q.V.row_ncol = h->part.row_ncol;
-    Q.V.ctab_key = h->index.key; Q.V.ctab_val = h->index.val; Q.V.ctab_mask = h->index.mask;
+    CostView& V = Q.V;
+    V.sx = h->out.sx; V.sy = h->out.sy; V.sz = h->out.sz;
+    V.mean = h->out.mean; V.normal = h->out.normal; V.rough = h->out.rough; V.flags = h->out.flags;
+    V.row_ncol = h->part.row_ncol;
+    V.ctab_key = h->index.key; V.ctab_val = h->index.val; V.ctab_mask = h->index.mask;
+    V.slope_interval = h->P.slope_interval; V.demand_true = h->P.demand == GNDT_DEMAND_TRUE ? 1 : 0;
     Q.h_bits = h->cost.h_bits; Q.state = h->cost.state;
     Q.ox = h->origin[0]; Q.oy = h->origin[1]; Q.oz = h->origin[2];
     Q.grid_len = h->P.grid_len; Q.z_len = h->P.z_len;

@@ -42,11 +42,6 @@ int shortcut_args(gndt_handle* h, const uint32_t* routes, size_t K, uint32_t rou
     return GNDT_OK;
 }
 
-Robot shortcut_robot(const gndt_robot* robot) {
-    if (!robot) return Robot{0.25f, 0.15f, 100.f, 30.f};        // the flood's defaults (gndt_compute_cost)
-    return Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
-}
-
 // The handle's state (query_sync has run): the stream, the column index, the kernel.  Nothing is awaited.
 int shortcut_enqueue(gndt_handle* h, const Robot& R, const ShortcutRule& F, const uint32_t* routes, uint64_t K, uint32_t route_cap,
                      const void* lengths, uint64_t stride, const uint32_t* hops, uint32_t* wp, uint32_t wp_cap, uint32_t* path, uint32_t path_cap,
@@ -56,8 +51,7 @@ int shortcut_enqueue(gndt_handle* h, const Robot& R, const ShortcutRule& F, cons
     const uint64_t n = h->res_nodes;
     if (n >= 0xFFFFFFFFull) { h->err = "gndt_shortcut_routes: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
     if ((rc = column_index(h, s))) return rc;
-    QueryView Q = query_view(h);
-    Q.V.normal = h->out.normal;
+    const QueryView Q = query_view(h);
     // one route a wavefront: at most kShortcutMaxBlocks workgroups of kShortcutWaves (16 wavefronts on each of the 256 CUs), grid-stride beyond
     const dim3 grid(grid_for(K, kShortcutWaves, kShortcutMaxBlocks)), block(kShortcutThreads);
     hipLaunchKernelGGL(k_shortcut_routes, grid, block, 0, s, Q, R, F, (uint32_t)n, hops, routes, K, route_cap, static_cast<const char*>(lengths),
@@ -93,7 +87,7 @@ int gndt_shortcut_routes_device(gndt_handle* h, const uint32_t* route_rows_dev, 
     const hipStream_t s = stream_of(h, hip_stream);
     if ((rc = query_sync(h, false, s, kShortcutCapture))) return rc;
     if (K == 0) return GNDT_OK;
-    return shortcut_enqueue(h, shortcut_robot(robot), F, route_rows_dev, K, route_cap, lengths_dev, length_stride_bytes, hops_dev, waypoint_rows_dev,
+    return shortcut_enqueue(h, robot_of(robot), F, route_rows_dev, K, route_cap, lengths_dev, length_stride_bytes, hops_dev, waypoint_rows_dev,
                             waypoint_cap, path_rows_dev, path_cap, reinterpret_cast<ShortcutInfo*>(info_dev), s);
 }
 
@@ -120,7 +114,7 @@ int gndt_shortcut_routes(gndt_handle* h, const uint32_t* route_rows_host, size_t
     HIP_TRY(h, hipMemcpyAsync(dev[1], lengths.data(), bytes[1], hipMemcpyHostToDevice, s));
     if (bytes[2]) HIP_TRY(h, hipMemcpyAsync(dev[2], hops_host, bytes[2], hipMemcpyHostToDevice, s));
     // (a map without rows: hops has no entry and every route is a BAD_ROUTE)
-    if ((rc = shortcut_enqueue(h, shortcut_robot(robot), F, static_cast<const uint32_t*>(dev[0]), K, route_cap, dev[1], 4,
+    if ((rc = shortcut_enqueue(h, robot_of(robot), F, static_cast<const uint32_t*>(dev[0]), K, route_cap, dev[1], 4,
                                static_cast<const uint32_t*>(dev[2]), static_cast<uint32_t*>(dev[3]), waypoint_cap, static_cast<uint32_t*>(dev[4]),
                                path_cap, static_cast<ShortcutInfo*>(dev[5]), s)))
         return rc;

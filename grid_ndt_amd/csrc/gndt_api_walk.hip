@@ -48,11 +48,6 @@ int walk_args(gndt_handle* h, const void* paths, size_t K, size_t T, size_t stri
     return GNDT_OK;
 }
 
-Robot walk_robot(const gndt_robot* robot) {
-    if (!robot) return Robot{0.25f, 0.15f, 100.f, 30.f};        // the flood's defaults (gndt_compute_cost)
-    return Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
-}
-
 // The handle's state (query_sync has run): the stream, the column index, the steps table when the call takes that variant, the kernel.
 // Nothing is awaited.
 int walk_enqueue(gndt_handle* h, const Robot& R, const WalkRule& F, const float* paths, uint32_t sf, uint64_t K, uint32_t T, const uint32_t* hops,
@@ -62,8 +57,7 @@ int walk_enqueue(gndt_handle* h, const Robot& R, const WalkRule& F, const float*
     const uint64_t n = h->res_nodes;
     if (n >= 0xFFFFFFFFull) { h->err = "gndt_walk_paths: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
     if ((rc = column_index(h, s))) return rc;
-    QueryView Q = query_view(h);
-    Q.V.normal = h->out.normal;
+    const QueryView Q = query_view(h);
     // one wavefront a workgroup; at most 8192 of them (32 on each of the 256 CUs: what the chip holds at once), grid-stride beyond
     const dim3 grid(grid_for(K, kWalkThreads, 8192)), block(kWalkThreads);
     // Which variant: the table costs a pass over the map's rows and saves the gates on every step of a lane's chain;
@@ -111,7 +105,7 @@ int gndt_walk_paths_device(gndt_handle* h, const void* paths_dev, size_t K, size
     const hipStream_t s = stream_of(h, hip_stream);
     if ((rc = query_sync(h, false, s, kWalkCapture))) return rc;
     if (K == 0 || T == 0) return GNDT_OK;
-    return walk_enqueue(h, walk_robot(robot), F, static_cast<const float*>(paths_dev), (uint32_t)(stride_bytes / 4), K, (uint32_t)T, hops_dev, rows_dev,
+    return walk_enqueue(h, robot_of(robot), F, static_cast<const float*>(paths_dev), (uint32_t)(stride_bytes / 4), K, (uint32_t)T, hops_dev, rows_dev,
                         row_cap, reinterpret_cast<WalkInfo*>(info_dev), s);
 }
 
@@ -130,7 +124,7 @@ int gndt_walk_paths(gndt_handle* h, const void* paths_host, size_t K, size_t T, 
     HIP_TRY(h, hipMemcpyAsync(dev[0], paths_host, bytes[0], hipMemcpyHostToDevice, s));
     if (bytes[1]) HIP_TRY(h, hipMemcpyAsync(dev[1], hops_host, bytes[1], hipMemcpyHostToDevice, s));
     // (a map without rows: hops has no entry and no slope is stood on)
-    if ((rc = walk_enqueue(h, walk_robot(robot), F, static_cast<const float*>(dev[0]), (uint32_t)(stride_bytes / 4), K, (uint32_t)T,
+    if ((rc = walk_enqueue(h, robot_of(robot), F, static_cast<const float*>(dev[0]), (uint32_t)(stride_bytes / 4), K, (uint32_t)T,
                            static_cast<const uint32_t*>(dev[1]), static_cast<uint32_t*>(dev[2]), row_cap, static_cast<WalkInfo*>(dev[3]), s)))
         return rc;
     if (bytes[2]) HIP_TRY(h, hipMemcpyAsync(rows_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));

@@ -660,7 +660,12 @@ int column_index(gndt_handle* h, hipStream_t s, bool flood = false);
 // the steps before a query's or a raster's kernel: no capture, a finished map, the cost map when gathered; and the view of rows,
 // index and cost map the kernels read
 int query_sync(gndt_handle* h, bool gather, hipStream_t s, const char* capture_err);
-gndt::QueryView query_view(gndt_handle* h);
+gndt::QueryView query_view(gndt_handle* h);     // every field the handle supplies; the flood's tables (V.nbr, V.self, V.edges) are null
+// The robot of a call: the caller's, or the flood's defaults (receiver.cpp:33, robot.h:38-46)
+inline gndt::Robot robot_of(const gndt_robot* robot) {
+    if (!robot) return gndt::Robot{0.25f, 0.15f, 100.f, 30.f};
+    return gndt::Robot{robot->radius, robot->reachable_height, robot->max_rough, robot->max_angle_deg};
+}
 // ---- gndt_api_crop.hip ----
 void free_crop(gndt_handle* h);
 // ---- gndt_api_clear.hip ----

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gndt_cast.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -45,18 +46,12 @@ int castshim_walk(const float* map_origin, float grid_len, float z_len, const fl
 
 // n rays (so floats between origins, 0 = one origin; se floats between ends) against the rows and the column index (consumer_shim's
 // build_index); the parameters with the defaults filled in; stats = {rays, skipped, hits}
-int castshim_cast(int mode, const float* origins, uint32_t so, const float* ends, uint32_t se, uint64_t n, const int32_t* sx, const int32_t* sy,
-                  const int32_t* sz, const float* mean, const uint32_t* count, const float* cov, const uint32_t* row_ncol,
-                  const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const float* map_origin, float grid_len, float z_len,
-                  uint32_t min_count, float max_range, double min_range, double cov_rel, double cov_floor, double max_d2, uint32_t* row,
-                  float* range, float* d2, uint64_t* stats) {
+int castshim_cast(int mode, const float* origins, uint32_t so, const float* ends, uint32_t se, uint64_t n, const ShimMap* m, uint32_t min_count,
+                  float max_range, double min_range, double cov_rel, double cov_floor, double max_d2, uint32_t* row, float* range, float* d2,
+                  uint64_t* stats) {
     if (mode != kCastVoxel && mode != kCastNdt) return 1;
-    ScoreView S{};
-    S.Q.V.sx = sx; S.Q.V.sy = sy; S.Q.V.sz = sz; S.Q.V.mean = mean; S.Q.V.row_ncol = row_ncol;
-    S.Q.V.ctab_key = ctab_key; S.Q.V.ctab_val = ctab_val; S.Q.V.ctab_mask = ctab_size - 1;
-    S.Q.ox = map_origin[0]; S.Q.oy = map_origin[1]; S.Q.oz = map_origin[2]; S.Q.grid_len = grid_len; S.Q.z_len = z_len;
-    S.count = count; S.cov = cov;
-    const RayGrid G = grid_of(map_origin, grid_len, z_len, max_range);
+    const ScoreView S{view_of(*m), m->count, m->cov};
+    const RayGrid G = grid_of(m->origin, m->grid_len, m->z_len, max_range);
     CastParams P;
     P.min_count = min_count; P.min_range = min_range; P.cov_rel = cov_rel; P.cov_floor = cov_floor; P.max_d2 = max_d2;
     const CastOut o{row, range, d2};

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "gndt_clearance.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -19,13 +20,10 @@ uint32_t clshim_step_rows() { return kStepRows; }
 
 // robot: {radius, reachable_height, max_rough, max_angle_deg}.  hops, nearest [n], sides [n], counts [4] as gndt_clearance writes them;
 // info[0] = the rounds that did any work (mode 0) or the sweeps (mode 1).  Returns 0.
-int clshim_clearance(int mode, const float* robot, uint32_t sources, uint32_t max_hops, uint32_t n, const int32_t* sx, const int32_t* sy,
-                     const int32_t* sz, const uint32_t* flags, const uint32_t* row_ncol, const float* mean, const float* normal,
-                     const float* rough, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, uint32_t* hops,
-                     uint32_t* nearest, uint8_t* sides, uint32_t* counts, uint32_t* info) {
-    CostView V{};
-    V.sx = sx; V.sy = sy; V.sz = sz; V.flags = flags; V.row_ncol = row_ncol; V.mean = mean; V.normal = normal; V.rough = rough;
-    V.ctab_key = ctab_key; V.ctab_val = ctab_val; V.ctab_mask = ctab_size - 1;
+int clshim_clearance(int mode, const float* robot, uint32_t sources, uint32_t max_hops, const ShimMap* m, uint32_t* hops, uint32_t* nearest,
+                     uint8_t* sides, uint32_t* counts, uint32_t* info) {
+    const CostView V = view_of(*m).V;
+    const uint32_t n = (uint32_t)m->n;
     const Robot R{robot[0], robot[1], robot[2], robot[3]};
     const ClearanceRule F{sources, max_hops};
     using Ops = ClearanceSerialOps;

@@ -7,25 +7,10 @@
 // test_clear_host.py).
 #include <stdint.h>
 
-#include "gndt_query.hpp"
 #include "gndt_ray.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
-
-namespace {
-
-// The rows, the column index and the cost map as the kernels read them (null: an array the caller's code does not read)
-QueryView view_of(const int32_t* sx, const int32_t* sy, const int32_t* sz, const float* mean, const float* rough, const uint32_t* flags,
-                  const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const uint32_t* h_bits,
-                  const uint32_t* state) {
-    QueryView Q{};
-    Q.V.sx = sx; Q.V.sy = sy; Q.V.sz = sz; Q.V.mean = mean; Q.V.rough = rough; Q.V.flags = flags; Q.V.row_ncol = row_ncol;
-    Q.V.ctab_key = ctab_key; Q.V.ctab_val = ctab_val; Q.V.ctab_mask = ctab_size - 1;
-    Q.h_bits = h_bits; Q.state = state;
-    return Q;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -47,12 +32,9 @@ void build_index(const int32_t* sx, const int32_t* sy, const uint32_t* row_ncol,
 // ---- point queries ----
 
 // n queries (sf floats per point) as the kernel runs them: queries i, i + step, ... with step = the "grid" of `threads` threads
-int qshim_query(int mode, int ilp, int gather, const float* xyz, uint32_t sf, uint64_t n, const int32_t* sx, const int32_t* sy, const int32_t* sz,
-                const float* mean, const uint32_t* flags, const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val,
-                uint32_t ctab_size, const uint32_t* h_bits, const uint32_t* state, const float* origin, float grid_len, float z_len,
-                uint64_t threads, uint32_t* row_out, float* h_out, uint32_t* state_out) {
-    QueryView Q = view_of(sx, sy, sz, mean, nullptr, flags, row_ncol, ctab_key, ctab_val, ctab_size, h_bits, state);
-    Q.ox = origin[0]; Q.oy = origin[1]; Q.oz = origin[2]; Q.grid_len = grid_len; Q.z_len = z_len;
+int qshim_query(int mode, int ilp, int gather, const float* xyz, uint32_t sf, uint64_t n, const ShimMap* m, uint64_t threads,
+                uint32_t* row_out, float* h_out, uint32_t* state_out) {
+    const QueryView Q = view_of(*m);
     const uint64_t step = threads;
 #define QSHIM_RUN(ILP, MODE, G)                                                                                      \
     for (uint64_t t = 0; t < step; ++t)                                                                              \
@@ -82,11 +64,9 @@ int rshim_index(int32_t lo, uint32_t i) { return raster_index(lo, i); }
 uint32_t rshim_count(int32_t lo, int32_t hi) { return raster_count(lo, hi); }
 
 // Every pixel of a width x (n / width) image, as the kernel's threads run them (pixel p on its own); null layers are not written
-int rshim_raster(int mode, uint32_t gather, int32_t sx_lo, int32_t sy_lo, uint32_t width, uint32_t n, float z_ref, const int32_t* sx,
-                 const int32_t* sy, const int32_t* sz, const float* mean, const float* rough, const uint32_t* flags, const uint32_t* row_ncol,
-                 const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const uint32_t* h_bits, const uint32_t* state,
+int rshim_raster(int mode, uint32_t gather, int32_t sx_lo, int32_t sy_lo, uint32_t width, uint32_t n, float z_ref, const ShimMap* m,
                  uint32_t* row_out, float* z_out, float* rough_out, uint32_t* nodes_out, float* h_out, uint32_t* state_out) {
-    const QueryView Q = view_of(sx, sy, sz, mean, rough, flags, row_ncol, ctab_key, ctab_val, ctab_size, h_bits, state);
+    const QueryView Q = view_of(*m);
     const RasterOut o{row_out, z_out, rough_out, nodes_out, h_out, state_out};
 #define RSHIM_RUN(MODE, G) for (uint32_t p = 0; p < n; ++p) raster_pixel<MODE, G>(Q, sx_lo, sy_lo, width, z_ref, p, o)
 #define RSHIM_GATHER(MODE)                                                         \
@@ -128,14 +108,12 @@ int cshim_walk(const float* map_origin, float grid_len, float z_len, const float
 
 // Count-only passes of n rays (stride sf floats) against the rows and the column index (build_index)
 //; stats = {rays, skipped}
-void cshim_passes(const float* map_origin, float grid_len, float z_len, const float* o, const float* xyz, uint64_t n, uint32_t sf,
-                  float max_range, float end_margin, int use_ext, const int32_t* sx, const int32_t* sy, const int32_t* sz,
-                  const uint32_t* row_ncol, uint64_t rows, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size,
+void cshim_passes(const float* o, const float* xyz, uint64_t n, uint32_t sf, float max_range, float end_margin, int use_ext, const ShimMap* m,
                   LevelExtent* ext, uint32_t* passes, uint64_t* stats) {
-    QueryView Q = view_of(sx, sy, sz, nullptr, nullptr, nullptr, row_ncol, ctab_key, ctab_val, ctab_size, nullptr, nullptr);
-    Q.ox = map_origin[0]; Q.oy = map_origin[1]; Q.oz = map_origin[2]; Q.grid_len = grid_len; Q.z_len = z_len;
-    const RayGrid G = grid_of(map_origin, grid_len, z_len, o, max_range, end_margin);
-    for (uint64_t r = 0; r < rows; ++r) { passes[r] = 0u; clear_extent_of(Q, (uint32_t)r, ext); }
+    const QueryView Q = view_of(*m);
+    const RayGrid G = grid_of(m->origin, m->grid_len, m->z_len, o, max_range, end_margin);
+    const int32_t* sz = m->sz;
+    for (uint64_t r = 0; r < m->n; ++r) { passes[r] = 0u; clear_extent_of(Q, (uint32_t)r, ext); }
     stats[0] = stats[1] = 0;
     for (uint64_t i = 0; i < n; ++i) {          // k_clear_protect
         const float* p = xyz + i * sf;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gndt_frontier.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -17,14 +18,10 @@ int fshim_lin(int s) { return frontier_lin(s); }
 // rule: {candidates, open_rule, level_reach, min_open, link_dz, boxed, sx_min, sx_max, sy_min, sy_max}; order: the rows in the order the
 // link pass takes them (null: ascending).  label [n], open [n] (kFrontierNone for a row that is no frontier row), clusters [cap],
 // counts [4] as gndt_frontiers writes them.  Returns 0, or 1 + the row at which parent[x] <= x failed.
-int64_t fshim_frontiers(const int32_t* rule, uint32_t min_size, const uint32_t* order, uint32_t n, const int32_t* sx, const int32_t* sy,
-                        const int32_t* sz, const uint32_t* flags, const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val,
-                        uint32_t ctab_size, const uint32_t* h_bits, const uint32_t* state, uint32_t* label, uint8_t* open,
+int64_t fshim_frontiers(const int32_t* rule, uint32_t min_size, const uint32_t* order, const ShimMap* m, uint32_t* label, uint8_t* open,
                         FrontierRecord* clusters, uint32_t cap, uint32_t* counts) {
-    QueryView Q{};
-    Q.V.sx = sx; Q.V.sy = sy; Q.V.sz = sz; Q.V.flags = flags; Q.V.row_ncol = row_ncol;
-    Q.V.ctab_key = ctab_key; Q.V.ctab_val = ctab_val; Q.V.ctab_mask = ctab_size - 1;
-    Q.h_bits = h_bits; Q.state = state;
+    const QueryView Q = view_of(*m);
+    const uint32_t n = (uint32_t)m->n;
     const FrontierRule F{rule[0], rule[1], (uint32_t)rule[2], (uint32_t)rule[3], (uint32_t)rule[4], rule[5], rule[6], rule[7], rule[8], rule[9]};
     using Ops = FrontierSerialOps;
     std::vector<uint32_t> parent(n), size_at(n, 0u);

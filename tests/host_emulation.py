@@ -3,6 +3,7 @@
 It lets the CPU test tier check the kernel maths, the order-free restatement of the slope label and
 the parity tolerances against the oracle.  Test infrastructure only."""
 import ctypes as C
+import glob
 import os
 import subprocess
 
@@ -14,15 +15,47 @@ _SO = os.path.join(_HERE, "_host_math_shim.so")
 _lib = None
 
 
-def load_shim(src, so_name, headers, signatures):
-    """tests/<src> compiled with g++ into tests/<so_name> (again when it or one of `headers` of grid_ndt_amd/csrc is newer) and loaded;
-    signatures: {function: (argtypes, restype)}"""
-    csrc = os.path.join(_ROOT, "grid_ndt_amd", "csrc")
+_CSRC = os.path.join(_ROOT, "grid_ndt_amd", "csrc")
+
+
+class ShimMap(C.Structure):
+    """tests/shim_map.hpp's struct of the same name, field for field (load_shim checks it against every shim that takes one)"""
+    _fields_ = [("n", C.c_uint64), ("sx", C.c_void_p), ("sy", C.c_void_p), ("sz", C.c_void_p), ("mean", C.c_void_p), ("normal", C.c_void_p),
+                ("rough", C.c_void_p), ("flags", C.c_void_p), ("count", C.c_void_p), ("cov", C.c_void_p), ("row_ncol", C.c_void_p),
+                ("ctab_key", C.c_void_p), ("ctab_val", C.c_void_p), ("ctab_size", C.c_uint32), ("h_bits", C.c_void_p), ("state", C.c_void_p),
+                ("origin", C.c_float * 3), ("grid_len", C.c_float), ("z_len", C.c_float), ("slope_interval", C.c_float),
+                ("demand_true", C.c_int32)]
+
+
+MAP = C.POINTER(ShimMap)      # a shim's `const ShimMap*` argument
+
+
+def shim_deps(*sources):
+    """what a shim's binary is built from: its sources, tests/shim_map.hpp and every header of grid_ndt_amd/csrc (whichever of them it
+    includes, directly or not)"""
+    return list(sources) + [os.path.join(_HERE, "shim_map.hpp")] + sorted(glob.glob(os.path.join(_CSRC, "*.hpp")))
+
+
+def check_shim_map(L, mirror=ShimMap):
+    """the layout shim L was compiled with (shim_map.hpp's shim_map_layout / shim_map_fields) against the ctypes mirror"""
+    L.shim_map_fields.restype = C.c_char_p
+    words = (C.c_uint32 * 64)()
+    k = L.shim_map_layout(words)
+    names = L.shim_map_fields().decode().split()
+    assert names == [f[0] for f in mirror._fields_], ("ShimMap: the fields of tests/shim_map.hpp and of the mirror differ", names)
+    want = [C.sizeof(mirror)] + [v for f in names for v in (getattr(mirror, f).offset, getattr(mirror, f).size)]
+    assert list(words[:k]) == want, ("ShimMap: the layout of tests/shim_map.hpp and of the mirror differ", list(words[:k]), want)
+
+
+def load_shim(src, so_name, signatures):
+    """tests/<src> compiled with g++ into tests/<so_name> (again when one of shim_deps is newer) and loaded, its ShimMap checked
+    against the mirror if it takes one; signatures: {function: (argtypes, restype)}"""
     src, so = os.path.join(_HERE, src), os.path.join(_HERE, so_name)
-    deps = [src] + [os.path.join(csrc, f) for f in headers]
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", csrc, "-o", so, src])
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in shim_deps(src)):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", _CSRC, "-o", so, src])
     L = C.CDLL(so)
+    if hasattr(L, "shim_map_layout"):
+        check_shim_map(L)
     for name, (argtypes, restype) in signatures.items():
         getattr(L, name).argtypes = argtypes
         getattr(L, name).restype = restype
@@ -32,8 +65,7 @@ def load_shim(src, so_name, headers, signatures):
 def shim():
     global _lib
     if _lib is None:
-        _lib = load_shim("host_math_shim.cpp", os.path.basename(_SO), ("gndt_math.hpp", "gndt_cost.hpp"),
-                         {"shim_mean_z": ([C.c_uint32, C.c_double, C.c_double], C.c_float)})
+        _lib = load_shim("host_math_shim.cpp", os.path.basename(_SO), {"shim_mean_z": ([C.c_uint32, C.c_double, C.c_double], C.c_float)})
     return _lib
 
 
@@ -45,51 +77,87 @@ def consumer_shim():
     global _clib
     if _clib is None:
         vp, f, i32, u32, u64 = C.c_void_p, C.c_float, C.c_int32, C.c_uint32, C.c_uint64
-        _clib = load_shim("consumer_shim.cpp", "_consumer_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp"), {
+        _clib = load_shim("consumer_shim.cpp", "_consumer_shim.so", {
             "build_index": ([vp, vp, vp, u64, vp, vp, u32], None),
-            "qshim_query": ([C.c_int, C.c_int, C.c_int, vp, u32, u64] + [vp] * 8 + [u32, vp, vp, vp, f, f, u64, vp, vp, vp], C.c_int),
+            "qshim_query": ([C.c_int, C.c_int, C.c_int, vp, u32, u64, MAP, u64, vp, vp, vp], C.c_int),
             "qshim_ctab_find": ([vp, vp, u32, i32, i32], u32),
             "rshim_index": ([i32, u32], C.c_int),
             "rshim_count": ([i32, i32], u32),
-            "rshim_raster": ([C.c_int, u32, i32, i32, u32, u32, f] + [vp] * 9 + [u32] + [vp] * 8, C.c_int),
+            "rshim_raster": ([C.c_int, u32, i32, i32, u32, u32, f, MAP] + [vp] * 6, C.c_int),
             "cshim_walk": ([vp, f, f, vp, vp, f, f, vp, i32], C.c_int),
-            "cshim_passes": ([vp, f, f, vp, vp, u64, u32, f, f, C.c_int] + [vp] * 4 + [u64, vp, vp, u32, vp, vp, vp], None),
+            "cshim_passes": ([vp, vp, u64, u32, f, f, C.c_int, MAP, vp, vp, vp], None),
         })
     return _clib
 
 
-def _pow2_at_least(v, floor=1024):
-    p = floor
-    while p < v:
-        p <<= 1
-    return p
+def table_slots(columns, table="library"):
+    """the column index's slots for a map of `columns` columns: "library" = column_index's rule (a power of two, at least 1024, load
+    <= 1/2), "tight" = the smallest power of two with a free slot (long probe chains: ctab_find), a number = that many"""
+    if not isinstance(table, str):
+        assert table > columns and table & (table - 1) == 0
+        return int(table)
+    slots, least = (1024, 2 * columns) if table == "library" else (1, columns + 1)
+    while slots < least:
+        slots <<= 1
+    return slots
 
 
-class HostMap:
-    """The rows of an oracle map, with the per-row column sizes, the column index derived on the host — at the library's size
-    (column_index's rule: load <= 1/2), or with table="tight" the smallest table with a free slot (long probe chains: ctab_find) —
-    and a made-up cost map drawn from `seed`; run through consumer_shim()"""
+class MapRows:
+    """A map's rows as contiguous arrays of the dtypes the shims read (None: `cells` has no such array, a null pointer in the shim), the
+    per-row column sizes, the column index built once with table_slots(., table), the grid's origin and parameters P where the caller
+    has them, and the ShimMap that takes all of it into a shim."""
+    ROWS = (("sx", np.int32), ("sy", np.int32), ("sz", np.int32), ("mean", np.float32), ("normal", np.float32), ("rough", np.float32),
+            ("flags", np.uint32), ("count", np.uint32), ("cov", np.float32))
+    OTHERS = (("row_ncol", np.uint32), ("ctab_key", np.uint64), ("ctab_val", np.uint32), ("h_bits", np.uint32), ("state", np.uint32))
 
-    def __init__(self, cloud, P, table="library", seed=11):
-        from oracle import oracle
-        from tests import query_ref as qr
-        self.origin = np.asarray(cloud[0, :3], np.float32)
-        self.P = P
-        c = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"), mode=oracle.MODE_INT_OPENMP)
-        self.cells = c
-        self.n = int(c["num_nodes"])
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(c[k], np.int32) for k in ("sx", "sy", "sz"))
-        self.mean = np.ascontiguousarray(c["mean"], np.float32)
-        self.rough = np.ascontiguousarray(c["rough"], np.float32)
-        self.flags = np.ascontiguousarray(c["flags"], np.uint32)
-        self.row_ncol = qr.row_ncol(c)
-        K = int((self.row_ncol > 0).sum())
-        assert K == int(c["num_columns"])
-        self.tsize = _pow2_at_least(2 * K) if table == "library" else _pow2_at_least(K + 1, floor=1)
+    def __init__(self, cells, row_ncol, table="library", origin=(0.0, 0.0, 0.0), P=None, h_bits=None, state=None):
+        self.cells, self.P = cells, P or {}
+        self.origin = np.asarray(origin, np.float32)[:3]
+        for k, t in self.ROWS:
+            setattr(self, k, np.ascontiguousarray(cells[k], t) if k in cells else None)
+        self.n = int(cells["num_nodes"]) if "num_nodes" in cells else len(self.sx)
+        self.row_ncol = np.ascontiguousarray(row_ncol, np.uint32)
+        self.h_bits, self.state = h_bits, state
+        self.tsize = table_slots(int((self.row_ncol > 0).sum()), table)
         self.ctab_key = np.zeros(self.tsize, np.uint64)
         self.ctab_val = np.zeros(self.tsize, np.uint32)
         consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
                                     self.ctab_val.ctypes.data, self.tsize)
+
+    def shim_map(self, **over):
+        """the ShimMap of these rows (it keeps its arrays alive); over: a field's value in place of the map's own — an array (h_bits=...),
+        None for a null pointer, the grid of a map that was made without one (origin=..., grid_len=..., z_len=...)"""
+        P = self.P
+        val = dict(n=self.n, ctab_size=self.tsize, origin=self.origin, grid_len=P.get("grid_len", 0.0), z_len=P.get("z_len", 0.0),
+                   slope_interval=P.get("slope_interval", 0.0), demand_true=int(P.get("demand", "slope") == "true"))
+        val.update({k: getattr(self, k) for k, _ in self.ROWS + self.OTHERS})
+        assert set(over) <= set(val), over.keys()
+        val.update(over)
+        m = ShimMap()
+        m.keep = []
+        for k, t in self.ROWS + self.OTHERS:
+            a = val[k]
+            if a is not None:
+                a = np.ascontiguousarray(a)
+                assert a.dtype == t, (k, a.dtype)       # (an array of another type would be read as this one)
+                m.keep.append(a)
+                val[k] = a.ctypes.data
+        val["origin"] = (C.c_float * 3)(*[float(v) for v in val["origin"]])
+        for k, v in val.items():
+            setattr(m, k, v)
+        return m
+
+
+class HostMap(MapRows):
+    """The rows of an oracle map, with the per-row column sizes, the column index derived on the host (table_slots) and a made-up cost
+    map drawn from `seed`; run through consumer_shim()"""
+
+    def __init__(self, cloud, P, table="library", seed=11):
+        from oracle import oracle
+        from tests import query_ref as qr
+        c = oracle.build_grid(cloud, P["grid_len"], P["z_len"], P["slope_interval"], P.get("demand", "slope"), mode=oracle.MODE_INT_OPENMP)
+        super().__init__(c, qr.row_ncol(c), table, origin=cloud[0, :3], P=P)
+        assert int((self.row_ncol > 0).sum()) == int(c["num_columns"])
         rng = np.random.default_rng(seed)
         self.h_bits = rng.integers(0, 0x7F7FFFFF, size=max(self.n, 1), dtype=np.uint32)
         self.state = rng.integers(0, 3, size=max(self.n, 1), dtype=np.uint32)
@@ -104,11 +172,7 @@ class HostMap:
         rows = np.full(n, 0xDEADBEEF, np.uint32)
         h = np.zeros(n, np.float32)
         st = np.full(n, 99, np.uint32)
-        o = (C.c_float * 3)(*[float(v) for v in self.origin])
-        rc = consumer_shim().qshim_query(mode, ilp, int(gather), pts.ctypes.data, pts.shape[1], n, self.sx.ctypes.data, self.sy.ctypes.data,
-                                         self.sz.ctypes.data, self.mean.ctypes.data, self.flags.ctypes.data, self.row_ncol.ctypes.data,
-                                         self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize, self.h_bits.ctypes.data,
-                                         self.state.ctypes.data, o, self.P["grid_len"], self.P["z_len"], threads, rows.ctypes.data,
+        rc = consumer_shim().qshim_query(mode, ilp, int(gather), pts.ctypes.data, pts.shape[1], n, self.shim_map(), threads, rows.ctypes.data,
                                          h.ctypes.data, st.ctypes.data)
         assert rc == 0
         r = rows.view(np.int32).astype(np.int64)
@@ -121,11 +185,8 @@ class HostMap:
         dt = {"row": np.uint32, "z": np.float32, "rough": np.float32, "nodes": np.uint32, "h": np.float32, "state": np.uint32}
         out = {k: np.full((H, W), 0xA5A5A5A5, np.uint32).view(dt[k]) for k in layers}
         p = lambda k: C.c_void_p(out[k].ctypes.data if k in out else 0)
-        rc = consumer_shim().rshim_raster(mode, gather, box[0], box[2], W, W * H, z_ref, self.sx.ctypes.data,
-                                          self.sy.ctypes.data, self.sz.ctypes.data, self.mean.ctypes.data, self.rough.ctypes.data,
-                                          self.flags.ctypes.data, self.row_ncol.ctypes.data, self.ctab_key.ctypes.data, self.ctab_val.ctypes.data,
-                                          self.tsize, self.h_bits.ctypes.data, self.state.ctypes.data, p("row"), p("z"), p("rough"), p("nodes"),
-                                          p("h"), p("state"))
+        rc = consumer_shim().rshim_raster(mode, gather, box[0], box[2], W, W * H, z_ref, self.shim_map(), p("row"), p("z"), p("rough"),
+                                          p("nodes"), p("h"), p("state"))
         assert rc == 0
         if "row" in out:
             out["row"] = out["row"].view(np.int32)
@@ -143,10 +204,8 @@ class HostMap:
         words = np.zeros(max(self.n, 1), np.uint32)
         extent = np.zeros((max(self.n, 1), 2), np.int32)
         stats = np.zeros(2, np.uint64)
-        consumer_shim().cshim_passes(self.origin.ctypes.data, self.P["grid_len"], self.P["z_len"], oo.ctypes.data, pts.ctypes.data, len(pts),
-                                     pts.shape[1], max_range, end_margin, int(ext), self.sx.ctypes.data, self.sy.ctypes.data,
-                                     self.sz.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                     self.ctab_val.ctypes.data, self.tsize, extent.ctypes.data, words.ctypes.data, stats.ctypes.data)
+        consumer_shim().cshim_passes(oo.ctypes.data, pts.ctypes.data, len(pts), pts.shape[1], max_range, end_margin, int(ext), self.shim_map(),
+                                     extent.ctypes.data, words.ctypes.data, stats.ctypes.data)
         return words[:self.n], int(stats[0]), int(stats[1])
 
 

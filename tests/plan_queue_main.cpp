@@ -37,13 +37,19 @@ int main(int argc, char** argv) {
     const auto ctab_val = take<uint32_t>(f, tsize), h_bits = take<uint32_t>(f, n);
     const auto starts = take<float>(f, 3 * K);
     std::fclose(f);
+    ShimMap m{};
+    m.n = n;
+    m.sx = sx.data(); m.sy = sy.data(); m.sz = sz.data(); m.mean = mean.data(); m.normal = normal.data(); m.rough = rough.data();
+    m.flags = flags.data(); m.row_ncol = row_ncol.data();
+    m.ctab_key = ctab_key.data(); m.ctab_val = ctab_val.data(); m.ctab_size = (uint32_t)tsize;
+    m.h_bits = h_bits.data();
+    m.origin[0] = fl[0]; m.origin[1] = fl[1]; m.origin[2] = fl[2]; m.grid_len = fl[3]; m.z_len = fl[4]; m.slope_interval = fl[5];
+    m.demand_true = (int32_t)head[4];
     const uint32_t cap = (uint32_t)n;
     auto run = [&](uint32_t lds, uint32_t entries, std::vector<uint32_t>& route, std::vector<RouteInfo>& info) {
         route.assign((size_t)K * cap + 1, 0xDEADBEEFu);
         info.assign(K + 1, RouteInfo{});
-        return planshim_routes(n, sx.data(), sy.data(), sz.data(), mean.data(), normal.data(), rough.data(), flags.data(), row_ncol.data(),
-                               ctab_key.data(), ctab_val.data(), (uint32_t)tsize, h_bits.data(), fl.data(), fl[3], fl[4], fl[5], (int)head[4],
-                               robot.data(), (uint32_t)head[3], kQueryNode, starts.data(), 3u, K, 0u, lds, entries, route.data(), cap,
+        return planshim_routes(&m, robot.data(), (uint32_t)head[3], kQueryNode, starts.data(), 3u, K, 0u, lds, entries, route.data(), cap,
                                info.data(), nullptr);
     };
     std::vector<uint32_t> r0, r1;

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from grid_ndt_amd import scenes
-from tests.host_emulation import HostMap, _pow2_at_least, consumer_shim, load_shim
+from tests.host_emulation import MAP, HostMap, MapRows, load_shim
 
 FOUND, NO_START, NO_ROUTE, LIMIT, NO_GOAL = 0, 1, 2, 3, 4
 NODE, NEAREST_SLOPE = 0, 1
@@ -22,12 +22,11 @@ _shim = None
 def shim():
     global _shim
     if _shim is None:
-        vp, f, u32, u64 = C.c_void_p, C.c_float, C.c_uint32, C.c_uint64
-        _shim = load_shim("plan_shim.cpp", "_plan_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_plan.hpp"), {
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        _shim = load_shim("plan_shim.cpp", "_plan_shim.so", {
             "planshim_default_expansions": ([u64], u32),
             "planshim_queue_entries": ([u64], u32),
-            "planshim_routes": ([u64] + [vp] * 10 + [u32, vp, vp, f, f, f, C.c_int, vp, u32, C.c_int, vp, u32, u64, u32, u32, u32, vp, u32, vp, vp],
-                                C.c_int),
+            "planshim_routes": ([MAP, vp, u32, C.c_int, vp, u32, u64, u32, u32, u32, vp, u32, vp, vp], C.c_int),
         })
     return _shim
 
@@ -36,31 +35,21 @@ def info_bytes(info):
     return np.ascontiguousarray(info).view(np.uint8).tobytes()
 
 
-class PlanMap:
+class PlanMap(MapRows):
     """Rows of a map (an oracle build or an export of the device's), the flood the oracle runs on them from `goal`, and both planners."""
 
     def __init__(self, cells, origin, P, goal, robot=None):
         from oracle import oracle
         from tests import query_ref as qr
-        self.cells, self.P, self.goal = cells, P, tuple(float(v) for v in goal)
-        self.origin = np.asarray(origin, np.float32)
+        super().__init__(cells, qr.row_ncol(cells), origin=origin, P=P)
+        self.goal = tuple(float(v) for v in goal)
         self.robot = dict(ROBOT_DEFAULT)
         self.robot.update(robot or {})
-        self.n = int(cells["num_nodes"])
-        f32, i32, u32 = np.float32, np.int32, np.uint32
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(cells[k], i32) for k in ("sx", "sy", "sz"))
-        self.mean, self.normal = np.ascontiguousarray(cells["mean"], f32), np.ascontiguousarray(cells["normal"], f32)
-        self.rough, self.flags = np.ascontiguousarray(cells["rough"], f32), np.ascontiguousarray(cells["flags"], u32)
-        self.row_ncol = qr.row_ncol(cells)
-        self.tsize = _pow2_at_least(2 * int((self.row_ncol > 0).sum()))
-        self.ctab_key, self.ctab_val = np.zeros(self.tsize, np.uint64), np.zeros(self.tsize, u32)
-        consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                    self.ctab_val.ctypes.data, self.tsize)
         self.slopes = np.flatnonzero(self.flags & 2)
         self._oracle = oracle
         self.paths = {}
         flood = self._flood()
-        self.rc, self.h, self.state = flood["rc"], np.ascontiguousarray(flood["h"], f32), flood["state"]
+        self.rc, self.h, self.state = flood["rc"], np.ascontiguousarray(flood["h"], np.float32), flood["state"]
         # the goal's row: the one slope the flood leaves at h == 0 with state != 0 is its seed (travel costs are > 0)
         seeds = np.flatnonzero((self.h == 0) & (self.state != 0)) if self.rc == 0 else []
         assert self.rc != 0 or len(seeds) == 1
@@ -92,14 +81,11 @@ class PlanMap:
         info = np.zeros(max(K, 1), INFO_DTYPE)
         re = np.zeros((max(K, 1), 2), np.uint32)
         hb = np.ascontiguousarray(self.h if h is None else h, np.float32).view(np.uint32)
-        P, rb = self.P, self.robot
+        rb = self.robot
         r4 = np.float32([rb["radius"], rb["reachable_height"], rb["max_rough"], rb["max_angle_deg"]])
-        rc = shim().planshim_routes(self.n, self.sx.ctypes.data, self.sy.ctypes.data, self.sz.ctypes.data, self.mean.ctypes.data,
-                                    self.normal.ctypes.data, self.rough.ctypes.data, self.flags.ctypes.data, self.row_ncol.ctypes.data,
-                                    self.ctab_key.ctypes.data, self.ctab_val.ctypes.data, self.tsize, hb.ctypes.data, self.origin.ctypes.data,
-                                    P["grid_len"], P["z_len"], P["slope_interval"], 1 if P.get("demand", "slope") == "true" else 0,
-                                    r4.ctypes.data, self.goal_row, mode, starts.ctypes.data, starts.shape[1] if K else 3, K, max_expansions,
-                                    lds_entries, queue_entries, rows.ctypes.data if cap else None, cap, info.ctypes.data, re.ctypes.data)
+        rc = shim().planshim_routes(self.shim_map(h_bits=hb, state=None), r4.ctypes.data, self.goal_row, mode, starts.ctypes.data,
+                                    starts.shape[1] if K else 3, K, max_expansions, lds_entries, queue_entries,
+                                    rows.ctypes.data if cap else None, cap, info.ctypes.data, re.ctypes.data)
         assert rc == 0
         return rows[:K, :cap] if cap else rows[:K, :0], info[:K], re[:K]
 

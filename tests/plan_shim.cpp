@@ -6,27 +6,25 @@
 #include <vector>
 
 #include "gndt_plan.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
 namespace {
 
-struct ShimMap {
+// The planner's views of a map with the flood's records made for them
+struct PlanMap {
     PlanView P;
     QueryView Q;
     std::vector<CostEdge> edges;
     uint64_t num_slopes = 0;
 };
 
-void make_map(ShimMap& M, uint64_t n, const int32_t* sx, const int32_t* sy, const int32_t* sz, const float* mean, const float* normal,
-              const float* rough, const uint32_t* flags, const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val,
-              uint32_t tsize, const uint32_t* h_bits, const float* origin, float grid_len, float z_len, float slope_interval, int demand_true,
-              const float* robot4, uint32_t goal_row) {
-    CostView V{};
-    V.sx = sx; V.sy = sy; V.sz = sz; V.mean = mean; V.normal = normal; V.rough = rough; V.flags = flags;
-    V.row_ncol = row_ncol; V.ctab_key = ctab_key; V.ctab_val = ctab_val; V.ctab_mask = tsize - 1;
-    V.nbr = nullptr; V.self = nullptr; V.edges = nullptr;
-    V.slope_interval = slope_interval; V.demand_true = demand_true;
+void make_map(PlanMap& M, const ShimMap& m, const float* robot4, uint32_t goal_row) {
+    M.Q = view_of(m);
+    M.Q.state = nullptr;
+    CostView& V = M.Q.V;
+    const uint64_t n = m.n;
     const Robot R{robot4[0], robot4[1], robot4[2], robot4[3]};
     M.edges.assign(4 * (size_t)n, CostEdge{kNoColumn, 0u, 0.f, 0.f});
     for (uint32_t row = 0; row < n; ++row) {
@@ -39,10 +37,7 @@ void make_map(ShimMap& M, uint64_t n, const int32_t* sx, const int32_t* sy, cons
         }
     }
     V.edges = M.edges.data();
-    M.P.V = V; M.P.R = R; M.P.h_bits = h_bits; M.P.goal_row = goal_row; M.P.num_rows = (uint32_t)n;
-    M.Q = QueryView{};
-    M.Q.V = V; M.Q.h_bits = h_bits; M.Q.state = nullptr;
-    M.Q.ox = origin[0]; M.Q.oy = origin[1]; M.Q.oz = origin[2]; M.Q.grid_len = grid_len; M.Q.z_len = z_len;
+    M.P.V = V; M.P.R = R; M.P.h_bits = m.h_bits; M.P.goal_row = goal_row; M.P.num_rows = (uint32_t)n;
 }
 
 }  // namespace
@@ -56,15 +51,12 @@ uint32_t planshim_queue_entries(uint64_t num_slopes) { return plan_queue_entries
 // mode: kQueryNode / kQueryNearestSlope.  max_expansions 0, queue_entries 0: the library's defaults.  lds_entries: the first tier's size.
 // route: K x route_cap (may be null with 0).  info: K x 8 words (gndt_route_info).  tally: K x 2 counters (may be null): pops of closed
 // slopes, entries inserted below the popped key.
-int planshim_routes(uint64_t n, const int32_t* sx, const int32_t* sy, const int32_t* sz, const float* mean, const float* normal,
-                    const float* rough, const uint32_t* flags, const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val,
-                    uint32_t tsize, const uint32_t* h_bits, const float* origin, float grid_len, float z_len, float slope_interval,
-                    int demand_true, const float* robot4, uint32_t goal_row, int mode, const float* starts, uint32_t sf, uint64_t K,
+int planshim_routes(const ShimMap* m, const float* robot4, uint32_t goal_row, int mode, const float* starts, uint32_t sf, uint64_t K,
                     uint32_t max_expansions, uint32_t lds_entries, uint32_t queue_entries, uint32_t* route, uint32_t route_cap,
                     RouteInfo* info, uint32_t* tally) {
-    ShimMap M;
-    make_map(M, n, sx, sy, sz, mean, normal, rough, flags, row_ncol, ctab_key, ctab_val, tsize, h_bits, origin, grid_len, z_len,
-             slope_interval, demand_true, robot4, goal_row);
+    PlanMap M;
+    make_map(M, *m, robot4, goal_row);
+    const uint64_t n = m->n;
     const uint32_t entries = queue_entries ? queue_entries : plan_queue_entries(M.num_slopes);
     const uint32_t cap0 = lds_entries < entries ? lds_entries : entries, cap1 = entries - cap0;
     const uint32_t max_exp = max_expansions ? max_expansions : plan_default_expansions(M.num_slopes);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "gndt_score_maps.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -35,34 +36,21 @@ T block_tree(const T* v, uint32_t N) {
     return s[0];
 }
 
-ScoreView view(const int32_t* sx, const int32_t* sy, const int32_t* sz, const float* mean, const uint32_t* count, const float* cov,
-               const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const float* origin,
-               float grid_len, float z_len) {
-    ScoreView S{};
-    S.Q.V.sx = sx; S.Q.V.sy = sy; S.Q.V.sz = sz; S.Q.V.mean = mean; S.Q.V.row_ncol = row_ncol;
-    S.Q.V.ctab_key = ctab_key; S.Q.V.ctab_val = ctab_val; S.Q.V.ctab_mask = ctab_size - 1;
-    S.Q.ox = origin[0]; S.Q.oy = origin[1]; S.Q.oz = origin[2]; S.Q.grid_len = grid_len; S.Q.z_len = z_len;
-    S.count = count; S.cov = cov;
-    return S;
-}
-
 }  // namespace
 
 extern "C" {
 
-// K poses over the n source rows against the destination's rows and column index (consumer_shim's build_index).  out: K records of
-// 31 eight-byte fields (gndt_pose_derivs; with derivs == 0 the 27 values stay 0: k_score_maps' record in its first four fields).
-// node_d2 / node_row (may be null): the per-node outputs of pose node_pose.  node_vals (may be null): the 27 values of every source
-// row at that pose, before any reduction.
-int mshim_score_maps(int nbh, int derivs, const uint32_t* s_count, const float* s_mean, const float* s_cov, const uint32_t* s_flags, uint64_t n,
-                     const double* poses, uint32_t K, const int32_t* sx, const int32_t* sy, const int32_t* sz, const float* mean,
-                     const uint32_t* count, const float* cov, const uint32_t* row_ncol, const uint64_t* ctab_key, const uint32_t* ctab_val,
-                     uint32_t ctab_size, const float* origin, float grid_len, float z_len, uint32_t min_count, double cov_rel, double cov_floor,
-                     double max_d2, ScoreDerivRecord* out, uint32_t node_pose, float* node_d2, uint32_t* node_row, double* node_vals) {
+// K poses over the rows of the source map `src` (its count, mean, cov and flags) against the destination's rows and column index
+// (consumer_shim's build_index).  out: K records of 31 eight-byte fields (gndt_pose_derivs; with derivs == 0 the 27 values stay 0:
+// k_score_maps' record in its first four fields).  node_d2 / node_row (may be null): the per-node outputs of pose node_pose.
+// node_vals (may be null): the 27 values of every source row at that pose, before any reduction.
+int mshim_score_maps(int nbh, int derivs, const ShimMap* src, const double* poses, uint32_t K, const ShimMap* dst, uint32_t min_count,
+                     double cov_rel, double cov_floor, double max_d2, ScoreDerivRecord* out, uint32_t node_pose, float* node_d2,
+                     uint32_t* node_row, double* node_vals) {
     if (nbh != kScoreDirect1 && nbh != kScoreDirect7) return 1;
-    const ScoreView D = view(sx, sy, sz, mean, count, cov, row_ncol, ctab_key, ctab_val, ctab_size, origin, grid_len, z_len);
-    MapsSource M{};
-    M.count = s_count; M.mean = s_mean; M.cov = s_cov; M.flags = s_flags;
+    const ScoreView D{view_of(*dst), dst->count, dst->cov};
+    const MapsSource M{src->count, src->mean, src->cov, src->flags};
+    const uint64_t n = src->n;
     ScoreParams P;
     P.min_count = min_count; P.cov_rel = cov_rel; P.cov_floor = cov_floor; P.max_d2 = max_d2;
     const uint64_t tiles = (n + kScoreTile - 1) / kScoreTile;
@@ -121,11 +109,9 @@ int mshim_score_maps(int nbh, int derivs, const uint32_t* s_count, const float* 
 
 // n points q against the rows `rows` of the map: d2 of score_maps_pair with Sigma = 0 (pair_d2) and of score_node (node_d2), and
 // whether each counts
-void mshim_pair_zero_sigma(const float* q, const uint32_t* rows, uint64_t n, const float* mean, const uint32_t* count, const float* cov,
-                           uint32_t min_count, double cov_rel, double cov_floor, double max_d2, double* pair_d2, double* node_d2,
-                           uint8_t* pair_ok, uint8_t* node_ok) {
-    ScoreView D{};
-    D.Q.V.mean = mean; D.count = count; D.cov = cov;
+void mshim_pair_zero_sigma(const float* q, const uint32_t* rows, uint64_t n, const ShimMap* m, uint32_t min_count, double cov_rel,
+                           double cov_floor, double max_d2, double* pair_d2, double* node_d2, uint8_t* pair_ok, uint8_t* node_ok) {
+    const ScoreView D{view_of(*m), m->count, m->cov};
     ScoreParams P;
     P.min_count = min_count; P.cov_rel = cov_rel; P.cov_floor = cov_floor; P.max_d2 = max_d2;
     for (uint64_t i = 0; i < n; ++i) {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gndt_score.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -46,17 +47,11 @@ void sshim_transform(const double* T, const float* xyz, uint32_t sf, uint64_t n,
 // K poses over n points against the rows and the column index (consumer_shim's build_index).  out: K records.  For pose point_pose
 // (when < K) and wherever the pointer is not null: every point's least d2 and its row (the kernel's per-point outputs), and — the
 // shim's own — the number of its terms and the sum of their d2 (the thread's sums before any reduction).
-int sshim_score(int nbh, const float* xyz, uint32_t sf, uint64_t n, const double* poses, uint32_t K, const int32_t* sx, const int32_t* sy,
-                const int32_t* sz, const float* mean, const uint32_t* count, const float* cov, const uint32_t* row_ncol,
-                const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const float* origin, float grid_len, float z_len,
-                uint32_t min_count, double cov_rel, double cov_floor, double max_d2, uint32_t point_pose, ScoreRecord* out,
-                float* point_d2, uint32_t* point_row, uint32_t* point_terms, double* point_d2_sum) {
+int sshim_score(int nbh, const float* xyz, uint32_t sf, uint64_t n, const double* poses, uint32_t K, const ShimMap* m, uint32_t min_count,
+                double cov_rel, double cov_floor, double max_d2, uint32_t point_pose, ScoreRecord* out, float* point_d2, uint32_t* point_row,
+                uint32_t* point_terms, double* point_d2_sum) {
     if (nbh != kScoreDirect1 && nbh != kScoreDirect7) return 1;
-    ScoreView S{};
-    S.Q.V.sx = sx; S.Q.V.sy = sy; S.Q.V.sz = sz; S.Q.V.mean = mean; S.Q.V.row_ncol = row_ncol;
-    S.Q.V.ctab_key = ctab_key; S.Q.V.ctab_val = ctab_val; S.Q.V.ctab_mask = ctab_size - 1;
-    S.Q.ox = origin[0]; S.Q.oy = origin[1]; S.Q.oz = origin[2]; S.Q.grid_len = grid_len; S.Q.z_len = z_len;
-    S.count = count; S.cov = cov;
+    const ScoreView S{view_of(*m), m->count, m->cov};
     ScoreParams P;
     P.min_count = min_count; P.cov_rel = cov_rel; P.cov_floor = cov_floor; P.max_d2 = max_d2;
     const uint64_t tiles = (n + kScoreTile - 1) / kScoreTile;

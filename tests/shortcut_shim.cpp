@@ -4,37 +4,22 @@
 #include <stdint.h>
 
 #include "gndt_shortcut.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
 static_assert(sizeof(ShortcutInfo) == 48, "gndt_shortcut_info");
 
-namespace {
-
-QueryView view_of(const float* origin, float grid_len, float z_len, const int32_t* sx, const int32_t* sy, const int32_t* sz, const uint32_t* flags,
-                  const uint32_t* row_ncol, const float* mean, const float* normal, const float* rough, const uint64_t* ctab_key,
-                  const uint32_t* ctab_val, uint32_t ctab_size) {
-    QueryView Q{};
-    CostView& V = Q.V;
-    V.sx = sx; V.sy = sy; V.sz = sz; V.flags = flags; V.row_ncol = row_ncol; V.mean = mean; V.normal = normal; V.rough = rough;
-    V.ctab_key = ctab_key; V.ctab_val = ctab_val; V.ctab_mask = ctab_size - 1;
-    Q.ox = origin[0]; Q.oy = origin[1]; Q.oz = origin[2]; Q.grid_len = grid_len; Q.z_len = z_len;
-    return Q;
-}
-
-}  // namespace
-
 extern "C" {
 
-// robot: {radius, reachable_height, max_rough, max_angle_deg}; rule: {window, checks, min_hops, max_links} (resolved); origin: {ox, oy, oz}.
+// robot: {radius, reachable_height, max_rough, max_angle_deg}; rule: {window, checks, min_hops, max_links} (resolved).
 // lengths: the uint32 at lengths + k * length_stride.  info [K] (48 bytes each), wp [K * wp_cap], path [K * path_cap] (or null with 0) as
 // gndt_shortcut_routes writes them.  Returns 0.
-int sshim_shortcut(const float* robot, const uint32_t* rule, const float* origin, float grid_len, float z_len, uint32_t n, const int32_t* sx,
-                   const int32_t* sy, const int32_t* sz, const uint32_t* flags, const uint32_t* row_ncol, const float* mean, const float* normal,
-                   const float* rough, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const uint32_t* hops,
-                   const uint32_t* routes, uint64_t K, uint32_t route_cap, const char* lengths, uint64_t length_stride, uint32_t* wp, uint32_t wp_cap,
-                   uint32_t* path, uint32_t path_cap, ShortcutInfo* info) {
-    const QueryView Q = view_of(origin, grid_len, z_len, sx, sy, sz, flags, row_ncol, mean, normal, rough, ctab_key, ctab_val, ctab_size);
+int sshim_shortcut(const float* robot, const uint32_t* rule, const ShimMap* m, const uint32_t* hops, const uint32_t* routes, uint64_t K,
+                   uint32_t route_cap, const char* lengths, uint64_t length_stride, uint32_t* wp, uint32_t wp_cap, uint32_t* path,
+                   uint32_t path_cap, ShortcutInfo* info) {
+    const QueryView Q = view_of(*m);
+    const uint32_t n = (uint32_t)m->n;
     const Robot R{robot[0], robot[1], robot[2], robot[3]};
     const ShortcutRule P{rule[0], rule[3], WalkRule{kQueryNearestSlope, rule[1], rule[2], kWalkDefaultSteps}};
     for (uint64_t k = 0; k < K; ++k)
@@ -44,11 +29,9 @@ int sshim_shortcut(const float* robot, const uint32_t* rule, const float* origin
 }
 
 // One link on its own: 1 if Link(a, b) holds.
-int sshim_link(const float* robot, const uint32_t* rule, const float* origin, float grid_len, float z_len, uint32_t n, const int32_t* sx,
-               const int32_t* sy, const int32_t* sz, const uint32_t* flags, const uint32_t* row_ncol, const float* mean, const float* normal,
-               const float* rough, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size, const uint32_t* hops, uint32_t a,
-               uint32_t b) {
-    const QueryView Q = view_of(origin, grid_len, z_len, sx, sy, sz, flags, row_ncol, mean, normal, rough, ctab_key, ctab_val, ctab_size);
+int sshim_link(const float* robot, const uint32_t* rule, const ShimMap* m, const uint32_t* hops, uint32_t a, uint32_t b) {
+    const QueryView Q = view_of(*m);
+    const uint32_t n = (uint32_t)m->n;
     const Robot R{robot[0], robot[1], robot[2], robot[3]};
     const ShortcutRule P{rule[0], rule[3], WalkRule{kQueryNearestSlope, rule[1], rule[2], kWalkDefaultSteps}};
     return shortcut_link<false>(Q, R, P, hops, n, a, b, nullptr) ? 1 : 0;

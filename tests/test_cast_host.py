@@ -9,7 +9,7 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import cast_ref as cf
-from tests.host_emulation import HostMap, load_shim
+from tests.host_emulation import MAP, HostMap, load_shim
 
 VOXEL, NDT = cf.VOXEL, cf.NDT
 _shim = None
@@ -19,10 +19,9 @@ def shim():
     global _shim
     if _shim is None:
         vp, f, i32, u32, u64, d = C.c_void_p, C.c_float, C.c_int32, C.c_uint32, C.c_uint64, C.c_double
-        _shim = load_shim("cast_shim.cpp", "_cast_shim.so",
-                          ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_cast.hpp"), {
+        _shim = load_shim("cast_shim.cpp", "_cast_shim.so", {
             "castshim_walk": ([vp, f, f, vp, vp, f, vp, vp, i32], C.c_int),
-            "castshim_cast": ([C.c_int, vp, u32, vp, u32, u64] + [vp] * 9 + [u32, vp, f, f, u32, f, d, d, d, d] + [vp] * 4, C.c_int),
+            "castshim_cast": ([C.c_int, vp, u32, vp, u32, u64, MAP, u32, f, d, d, d, d] + [vp] * 4, C.c_int),
         })
     return _shim
 
@@ -37,16 +36,11 @@ def host_cast(m, origins, ends, mode=VOXEL, **kw):
     o, e = _f32(origins), _f32(ends)
     n = len(e)
     so = 0 if o.ndim == 1 else o.shape[1]
-    count = np.ascontiguousarray(m.cells["count"], np.uint32)
-    cov = np.ascontiguousarray(m.cells["cov"], np.float32)
     row = np.full(max(n, 1), 0xDEADBEEF, np.uint32)
     rng = np.full(max(n, 1), -1.0, np.float32)
     d2 = np.full(max(n, 1), -1.0, np.float32)
     stats = np.zeros(3, np.uint64)
-    mo = (C.c_float * 3)(*[float(v) for v in m.origin])
-    rc = shim().castshim_cast(mode, o.ctypes.data, so, e.ctypes.data, e.shape[1], n, m.sx.ctypes.data, m.sy.ctypes.data, m.sz.ctypes.data,
-                              m.mean.ctypes.data, count.ctypes.data, cov.ctypes.data, m.row_ncol.ctypes.data, m.ctab_key.ctypes.data,
-                              m.ctab_val.ctypes.data, m.tsize, mo, m.P["grid_len"], m.P["z_len"], prm["min_count"], prm["max_range"],
+    rc = shim().castshim_cast(mode, o.ctypes.data, so, e.ctypes.data, e.shape[1], n, m.shim_map(), prm["min_count"], prm["max_range"],
                               prm["min_range"], prm["cov_rel"], prm["cov_floor"], prm["max_d2"], row.ctypes.data, rng.ctypes.data,
                               d2.ctypes.data, stats.ctypes.data)
     assert rc == 0

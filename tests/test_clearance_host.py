@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from tests import clearance_ref as cr
-from tests.host_emulation import HostMap, consumer_shim, load_shim
+from tests.host_emulation import MAP, HostMap, MapRows, load_shim
 from tests.test_raster_host import SCENES
 
 MASKS = (1, 2, 3, 4, 5, 6, 7)
@@ -21,41 +21,24 @@ def shim():
     global _shim
     if _shim is None:
         vp, u32 = C.c_void_p, C.c_uint32
-        _shim = load_shim("clearance_shim.cpp", "_clearance_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_clearance.hpp"), {
+        _shim = load_shim("clearance_shim.cpp", "_clearance_shim.so", {
             "clshim_step_rows": ([], u32),
-            "clshim_clearance": ([C.c_int, vp, u32, u32, u32] + [vp] * 10 + [u32] + [vp] * 5, C.c_int),
+            "clshim_clearance": ([C.c_int, vp, u32, u32, MAP] + [vp] * 5, C.c_int),
         })
     return _shim
 
 
-class Table:
+class Table(MapRows):
     """The fields the clearance field reads, as arrays, with the column index the library would build"""
 
     def __init__(self, sx, sy, sz, flags, row_ncol, mean, normal, rough):
-        self.n = len(sx)
-        self.sx, self.sy, self.sz = (np.ascontiguousarray(a, np.int32) for a in (sx, sy, sz))
-        self.flags, self.row_ncol = np.ascontiguousarray(flags, np.uint32), np.ascontiguousarray(row_ncol, np.uint32)
-        self.mean, self.normal = np.ascontiguousarray(mean, np.float32), np.ascontiguousarray(normal, np.float32)
-        self.rough = np.ascontiguousarray(rough, np.float32)
-        self.tsize = 1024
-        while self.tsize < 2 * int((self.row_ncol > 0).sum()):
-            self.tsize *= 2
-        self.ctab_key = np.zeros(self.tsize, np.uint64)
-        self.ctab_val = np.zeros(self.tsize, np.uint32)
-        consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                    self.ctab_val.ctypes.data, self.tsize)
+        super().__init__(dict(sx=sx, sy=sy, sz=sz, flags=flags, mean=mean, normal=normal, rough=rough), row_ncol)
         self.cells = dict(num_nodes=self.n, sx=self.sx, sy=self.sy, sz=self.sz, flags=self.flags, mean=self.mean, normal=self.normal,
                           rough=self.rough)
 
 
-def table_of(m):
-    """a HostMap's rows as a Table"""
-    c = m.cells
-    return Table(c["sx"], c["sy"], c["sz"], c["flags"], m.row_ncol, c["mean"], c["normal"], c["rough"])
-
-
 def run(t, robot, mask, max_hops, mode=0):
-    """the shim's passes on table t -> dict(hops, nearest, sides, counts, worked)"""
+    """the shim's passes on t (a Table, or a HostMap: the same rows and index) -> dict(hops, nearest, sides, counts, worked)"""
     rb = dict(cr.ROBOT)
     rb.update(robot or {})
     r4 = np.array([rb["radius"], rb["reachable_height"], rb["max_rough"], rb["max_angle_deg"]], np.float32)
@@ -66,8 +49,7 @@ def run(t, robot, mask, max_hops, mode=0):
     counts = np.full(4, 0xDEADBEEF, np.uint32)
     info = np.zeros(1, np.uint32)
     p = lambda a: a.ctypes.data
-    rc = shim().clshim_clearance(mode, p(r4), mask, max_hops, n, p(t.sx), p(t.sy), p(t.sz), p(t.flags), p(t.row_ncol), p(t.mean), p(t.normal),
-                                 p(t.rough), p(t.ctab_key), p(t.ctab_val), t.tsize, p(hops), p(near), p(sides), p(counts), p(info))
+    rc = shim().clshim_clearance(mode, p(r4), mask, max_hops, t.shim_map(), p(hops), p(near), p(sides), p(counts), p(info))
     assert rc == 0
     return dict(hops=hops[:n], nearest=near[:n], sides=sides[:n], counts=counts, worked=int(info[0]))
 
@@ -101,7 +83,7 @@ def _map(name):
     if name not in _maps:
         cloud, P = SCENES[name]()
         m = HostMap(cloud, P, seed=13)
-        _maps[name] = (table_of(m), cr.Field(m.cells))
+        _maps[name] = (m, cr.Field(m.cells))
     return _maps[name]
 
 

@@ -29,7 +29,7 @@ def shim():
     global _shim
     if _shim is None:
         vp, f, u64 = C.c_void_p, C.c_float, C.c_uint64
-        _shim = load_shim("coarsen_shim.cpp", "_coarsen_shim.so", ("gndt_math.hpp", "gndt_coarsen.hpp"), {
+        _shim = load_shim("coarsen_shim.cpp", "_coarsen_shim.so", {
             "cshim_parent_index": ([C.c_int, C.c_int], C.c_int),
             "cshim_parent_keys": ([vp, u64, C.c_int, C.c_int, vp], None),
             "cshim_coarsen": ([vp, vp, vp, u64, C.c_int, C.c_int, vp, f, f, f, f, vp, vp], None),

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from tests import frontier_ref as fr
-from tests.host_emulation import HostMap, consumer_shim, load_shim
+from tests.host_emulation import MAP, HostMap, MapRows, load_shim
 from tests.test_raster_host import SCENES, _boxes
 
 _shim = None
@@ -19,9 +19,9 @@ def shim():
     global _shim
     if _shim is None:
         vp, u32 = C.c_void_p, C.c_uint32
-        _shim = load_shim("frontier_shim.cpp", "_frontier_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_frontier.hpp"), {
+        _shim = load_shim("frontier_shim.cpp", "_frontier_shim.so", {
             "fshim_lin": ([C.c_int], C.c_int),
-            "fshim_frontiers": ([vp, u32, vp, u32] + [vp] * 7 + [u32] + [vp] * 5 + [u32, vp], C.c_int64),
+            "fshim_frontiers": ([vp, u32, vp, MAP, vp, vp, vp, u32, vp], C.c_int64),
         })
     return _shim
 
@@ -39,10 +39,8 @@ def run(m, cfg, box=None, min_size=1, order=None, cap=None):
     clusters = np.full(max(cap, 1) * 16, 0xA5A5A5A5, np.uint32).view(fr.RECORD)
     counts = np.full(4, 0xDEADBEEF, np.uint32)
     o = None if order is None else np.ascontiguousarray(order, np.uint32)
-    rc = shim().fshim_frontiers(rule.ctypes.data, min_size, None if o is None else o.ctypes.data, n, m.sx.ctypes.data, m.sy.ctypes.data,
-                                m.sz.ctypes.data, m.flags.ctypes.data, m.row_ncol.ctypes.data, m.ctab_key.ctypes.data, m.ctab_val.ctypes.data,
-                                m.tsize, m.h_bits.ctypes.data, m.state.ctypes.data, label.ctypes.data, opens.ctypes.data,
-                                clusters.ctypes.data, cap, counts.ctypes.data)
+    rc = shim().fshim_frontiers(rule.ctypes.data, min_size, None if o is None else o.ctypes.data, m.shim_map(), label.ctypes.data,
+                                opens.ctypes.data, clusters.ctypes.data, cap, counts.ctypes.data)
     assert rc == 0, f"parent[x] <= x failed at row {rc - 1}"
     k = min(int(counts[0]), cap)
     return dict(label=label[:n], open=opens[:n], clusters=clusters[:k], counts=counts, tail=clusters[k:])
@@ -136,9 +134,10 @@ def test_a_short_list_is_cut_and_the_rest_untouched():
         assert (got["tail"].view(np.uint32) == 0xA5A5A5A5).all()
 
 
-class Grid:
+class Grid(MapRows):
     """A random occupancy grid as rows: side x side columns across the origin in a shuffled order, one to `levels` nodes each at random
-    levels on both sides of 0, most of them slopes; a random cost map.  No cloud, no build: the fields frontier extraction reads."""
+    levels on both sides of 0, most of them slopes; a random cost map.  No cloud, no build: the fields frontier extraction reads.
+    Its index has 2048 slots whatever the grid: not the library's rule, which gives 1024 up to 512 of the at most 576 columns."""
 
     def __init__(self, rng, side=24, levels=3):
         fill = rng.uniform(0.3, 0.9)
@@ -151,17 +150,10 @@ class Grid:
             for j, z in enumerate(zs):
                 sx.append(ix + 1 if ix >= 0 else ix); sy.append(iy + 1 if iy >= 0 else iy); sz.append(int(z))
                 ncol.append(len(zs) if j == 0 else 0)
-        self.n = len(sx)
-        self.sx, self.sy, self.sz = (np.array(a, np.int32) for a in (sx, sy, sz))
-        self.row_ncol = np.array(ncol, np.uint32)
-        self.flags = np.where(rng.random(self.n) < 0.85, 3, 1).astype(np.uint32)
-        self.tsize = 2048
-        self.ctab_key = np.zeros(self.tsize, np.uint64)
-        self.ctab_val = np.zeros(self.tsize, np.uint32)
-        consumer_shim().build_index(self.sx.ctypes.data, self.sy.ctypes.data, self.row_ncol.ctypes.data, self.n, self.ctab_key.ctypes.data,
-                                    self.ctab_val.ctypes.data, self.tsize)
-        self.h_bits = rng.integers(0, 0x7F7FFFFF, size=self.n, dtype=np.uint32)
-        self.state = rng.integers(0, 3, size=self.n, dtype=np.uint32)
+        n = len(sx)
+        flags = np.where(rng.random(n) < 0.85, 3, 1)
+        super().__init__(dict(sx=sx, sy=sy, sz=sz, flags=flags), ncol, table=2048,
+                         h_bits=rng.integers(0, 0x7F7FFFFF, size=n, dtype=np.uint32), state=rng.integers(0, 3, size=n, dtype=np.uint32))
         self.cells = dict(num_nodes=self.n, sx=self.sx, sy=self.sy, sz=self.sz, flags=self.flags)
 
 

@@ -25,7 +25,7 @@ def shim():
     global _shim
     if _shim is None:
         vp, f, u64 = C.c_void_p, C.c_float, C.c_uint64
-        _shim = load_shim("merge_shim.cpp", "_merge_shim.so", ("gndt_math.hpp", "gndt_merge.hpp"), {
+        _shim = load_shim("merge_shim.cpp", "_merge_shim.so", {
             "mshim_merge": ([vp, vp, vp, u64, vp, vp, f, f, vp, f, f, vp, vp, vp], None),
         })
     return _shim

@@ -12,7 +12,7 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import plan_ref as pr
-from tests.host_emulation import HostMap
+from tests.host_emulation import HostMap, shim_deps
 from tests.test_planner_hand_routes import GL, IV, SCENES, ZL, _cells_to_cloud, _centre, _expected_keys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -204,7 +204,7 @@ def test_queue_spill_and_compaction_under_sanitizers():
     exe = os.path.join(HERE, "_plan_queue_main")
     src = os.path.join(HERE, "plan_queue_main.cpp")
     csrc = os.path.join(os.path.dirname(HERE), "grid_ndt_amd", "csrc")
-    deps = [src, os.path.join(HERE, "plan_shim.cpp")] + [os.path.join(csrc, f) for f in ("gndt_plan.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_math.hpp")]
+    deps = shim_deps(src, os.path.join(HERE, "plan_shim.cpp"))
     if not os.path.exists(exe) or os.path.getmtime(exe) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
                                "-I", csrc, "-I", HERE, "-o", exe, src])

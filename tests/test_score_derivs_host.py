@@ -26,7 +26,7 @@ from grid_ndt_amd import registration as reg
 from grid_ndt_amd import scenes
 from tests import score_derivs_ref as dr
 from tests import score_ref as sr
-from tests.host_emulation import HostMap, load_shim
+from tests.host_emulation import MAP, HostMap, load_shim
 from tests.test_score_host import _map, five_poses, host_score, yaw
 
 # the restatement driver's own endings: (neighbourhood, start) -> final error (m, rad), iterations, reason
@@ -61,10 +61,9 @@ _shim = None
 def shim():
     global _shim
     if _shim is None:
-        vp, f, u32, u64, d = C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_double
-        _shim = load_shim("score_derivs_shim.cpp", "_score_derivs_shim.so",
-                          ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp"), {
-            "dshim_score_derivs": ([C.c_int, vp, u32, u64, vp, u32] + [vp] * 9 + [u32, vp, f, f, u32, d, d, d, vp, u32, vp], C.c_int),
+        vp, u32, u64, d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double
+        _shim = load_shim("score_derivs_shim.cpp", "_score_derivs_shim.so", {
+            "dshim_score_derivs": ([C.c_int, vp, u32, u64, vp, u32, MAP, u32, d, d, d, vp, u32, vp], C.c_int),
         })
     return _shim
 
@@ -76,17 +75,12 @@ def host_derivs(m, pts, poses, nbh=1, per_point=None, **params):
     pts = np.ascontiguousarray(pts, np.float32)
     T = np.ascontiguousarray(sr.as_poses(poses)).reshape(-1, 12)
     K, n = T.shape[0], pts.shape[0]
-    count = np.ascontiguousarray(m.cells["count"], np.uint32)
-    cov = np.ascontiguousarray(m.cells["cov"], np.float32)
     rec = np.zeros((K, 31), np.int64)
     vals = np.zeros((n, 27), np.float64)
-    o = (C.c_float * 3)(*[float(v) for v in m.origin])
     want = per_point is not None
-    rc = shim().dshim_score_derivs(nbh, pts.ctypes.data, pts.shape[1], n, T.ctypes.data, K, m.sx.ctypes.data, m.sy.ctypes.data,
-                                   m.sz.ctypes.data, m.mean.ctypes.data, count.ctypes.data, cov.ctypes.data, m.row_ncol.ctypes.data,
-                                   m.ctab_key.ctypes.data, m.ctab_val.ctypes.data, m.tsize, o, m.P["grid_len"], m.P["z_len"],
-                                   prm["min_count"], prm["cov_rel"], prm["cov_floor"], prm["max_d2"], rec.ctypes.data,
-                                   per_point if want else 0xFFFFFFFF, C.c_void_p(vals.ctypes.data if want else 0))
+    rc = shim().dshim_score_derivs(nbh, pts.ctypes.data, pts.shape[1], n, T.ctypes.data, K, m.shim_map(), prm["min_count"], prm["cov_rel"],
+                                   prm["cov_floor"], prm["max_d2"], rec.ctypes.data, per_point if want else 0xFFFFFFFF,
+                                   C.c_void_p(vals.ctypes.data if want else 0))
     assert rc == 0
     fl = rec.view(np.float64)
     H = np.zeros((K, 6, 6))

@@ -15,7 +15,7 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import query_ref as qr
 from tests import score_ref as sr
-from tests.host_emulation import HostMap, load_shim
+from tests.host_emulation import MAP, HostMap, load_shim
 
 _shim = None
 
@@ -24,9 +24,9 @@ def shim():
     global _shim
     if _shim is None:
         vp, f, u32, u64, d = C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_double
-        _shim = load_shim("score_shim.cpp", "_score_shim.so", ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_score.hpp"), {
+        _shim = load_shim("score_shim.cpp", "_score_shim.so", {
             "sshim_transform": ([vp, vp, u32, u64, vp], None),
-            "sshim_score": ([C.c_int, vp, u32, u64, vp, u32] + [vp] * 9 + [u32, vp, f, f, u32, d, d, d, u32] + [vp] * 5, C.c_int),
+            "sshim_score": ([C.c_int, vp, u32, u64, vp, u32, MAP, u32, d, d, d, u32] + [vp] * 5, C.c_int),
         })
     return _shim
 
@@ -58,19 +58,14 @@ def host_score(m, pts, poses, nbh=1, per_point=None, **params):
     pts = np.ascontiguousarray(pts, np.float32)
     T = np.ascontiguousarray(sr.as_poses(poses)).reshape(-1, 12)
     K, n = T.shape[0], pts.shape[0]
-    count = np.ascontiguousarray(m.cells["count"], np.uint32)
-    cov = np.ascontiguousarray(m.cells["cov"], np.float32)
     rec = np.zeros((K, 4), np.int64)
     d2 = np.full(n, -1.0, np.float32)
     row = np.full(n, 0xDEADBEEF, np.uint32)
     pt_terms = np.zeros(n, np.uint32)
     pt_d2 = np.zeros(n, np.float64)
-    o = (C.c_float * 3)(*[float(v) for v in m.origin])
     want = per_point is not None
     p = lambda a: C.c_void_p(a.ctypes.data if want else 0)
-    rc = shim().sshim_score(nbh, pts.ctypes.data, pts.shape[1], n, T.ctypes.data, K, m.sx.ctypes.data, m.sy.ctypes.data, m.sz.ctypes.data,
-                            m.mean.ctypes.data, count.ctypes.data, cov.ctypes.data, m.row_ncol.ctypes.data, m.ctab_key.ctypes.data,
-                            m.ctab_val.ctypes.data, m.tsize, o, m.P["grid_len"], m.P["z_len"], prm["min_count"], prm["cov_rel"],
+    rc = shim().sshim_score(nbh, pts.ctypes.data, pts.shape[1], n, T.ctypes.data, K, m.shim_map(), prm["min_count"], prm["cov_rel"],
                             prm["cov_floor"], prm["max_d2"], per_point if want else 0xFFFFFFFF, rec.ctypes.data, p(d2), p(row),
                             p(pt_terms), p(pt_d2))
     assert rc == 0

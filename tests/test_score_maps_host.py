@@ -35,7 +35,7 @@ from tests import query_ref as qr
 from tests import score_derivs_ref as dr
 from tests import score_maps_ref as mr
 from tests import score_ref as sr
-from tests.host_emulation import HostMap, load_shim
+from tests.host_emulation import MAP, HostMap, load_shim
 from tests.test_score_derivs_host import RECOVERY_SCENES, check_steps, starts
 from tests.test_score_host import SCENES, _map, five_poses, yaw
 
@@ -62,11 +62,10 @@ _shim = None
 def shim():
     global _shim
     if _shim is None:
-        vp, f, u32, u64, d = C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_double
-        _shim = load_shim("score_maps_shim.cpp", "_score_maps_shim.so",
-                          ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp"), {
-            "mshim_score_maps": ([C.c_int, C.c_int, vp, vp, vp, vp, u64, vp, u32] + [vp] * 9 + [u32, vp, f, f, u32, d, d, d, vp, u32, vp, vp, vp], C.c_int),
-            "mshim_pair_zero_sigma": ([vp, vp, u64, vp, vp, vp, u32, d, d, d, vp, vp, vp, vp], None),
+        vp, u32, u64, d = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double
+        _shim = load_shim("score_maps_shim.cpp", "_score_maps_shim.so", {
+            "mshim_score_maps": ([C.c_int, C.c_int, MAP, vp, u32, MAP, u32, d, d, d, vp, u32, vp, vp, vp], C.c_int),
+            "mshim_pair_zero_sigma": ([vp, vp, u64, MAP, u32, d, d, d, vp, vp, vp, vp], None),
         })
     return _shim
 
@@ -98,21 +97,13 @@ def host_maps(dm, sm, poses, nbh=1, derivs=True, per_node=None, **params):
     prm = mr.defaults(**params)
     T = np.ascontiguousarray(sr.as_poses(poses)).reshape(-1, 12)
     K, n = T.shape[0], sm.n
-    u32 = lambda a: np.ascontiguousarray(a, np.uint32)
-    f32 = lambda a: np.ascontiguousarray(a, np.float32)
-    s_count, s_cov, s_flags, s_mean = u32(sm.cells["count"]), f32(sm.cells["cov"]), u32(sm.cells["flags"]), f32(sm.cells["mean"])
-    count, cov = u32(dm.cells["count"]), f32(dm.cells["cov"])
     rec = np.zeros((K, 31), np.int64)
     d2 = np.full(n, -1.0, np.float32)
     row = np.full(n, 0xDEADBEEF, np.uint32)
     vals = np.zeros((n, 27), np.float64)
-    o = (C.c_float * 3)(*[float(v) for v in dm.origin])
     want = per_node is not None
     p = lambda a: C.c_void_p(a.ctypes.data if want else 0)
-    rc = shim().mshim_score_maps(nbh, int(derivs), s_count.ctypes.data, s_mean.ctypes.data, s_cov.ctypes.data, s_flags.ctypes.data, n,
-                                 T.ctypes.data, K, dm.sx.ctypes.data, dm.sy.ctypes.data, dm.sz.ctypes.data, dm.mean.ctypes.data,
-                                 count.ctypes.data, cov.ctypes.data, dm.row_ncol.ctypes.data, dm.ctab_key.ctypes.data,
-                                 dm.ctab_val.ctypes.data, dm.tsize, o, dm.P["grid_len"], dm.P["z_len"], prm["min_count"], prm["cov_rel"],
+    rc = shim().mshim_score_maps(nbh, int(derivs), sm.shim_map(), T.ctypes.data, K, dm.shim_map(), prm["min_count"], prm["cov_rel"],
                                  prm["cov_floor"], prm["max_d2"], rec.ctypes.data, per_node if want else 0xFFFFFFFF, p(d2), p(row), p(vals))
     assert rc == 0
     fl = rec.view(np.float64)
@@ -198,13 +189,12 @@ def test_zero_sigma_pair_has_score_nodes_bits(name):
     rng = np.random.default_rng(8)
     rows = rng.integers(0, m.n, size=5000).astype(np.uint32)
     q = (np.asarray(m.cells["mean"], np.float32)[rows] + rng.normal(scale=0.2, size=(len(rows), 3))).astype(np.float32)
-    count, cov, mean = (np.ascontiguousarray(m.cells[k], t) for k, t in (("count", np.uint32), ("cov", np.float32), ("mean", np.float32)))
+    count = m.count
     for gate in (0.0, 4.0):
         pd, nd = np.zeros(len(rows)), np.zeros(len(rows))
         pk, nk = np.zeros(len(rows), np.uint8), np.zeros(len(rows), np.uint8)
-        shim().mshim_pair_zero_sigma(q.ctypes.data, rows.ctypes.data, len(rows), mean.ctypes.data, count.ctypes.data, cov.ctypes.data,
-                                     prm["min_count"], prm["cov_rel"], prm["cov_floor"], gate, pd.ctypes.data, nd.ctypes.data,
-                                     pk.ctypes.data, nk.ctypes.data)
+        shim().mshim_pair_zero_sigma(q.ctypes.data, rows.ctypes.data, len(rows), m.shim_map(), prm["min_count"], prm["cov_rel"],
+                                     prm["cov_floor"], gate, pd.ctypes.data, nd.ctypes.data, pk.ctypes.data, nk.ctypes.data)
         enough = count[rows] >= prm["min_count"]
         assert enough.sum() > 1000 and np.array_equal(pk, nk)
         assert np.array_equal(pd[enough].view(np.uint64), nd[enough].view(np.uint64))

@@ -13,7 +13,7 @@ from tests import clearance_ref as cr
 from tests import plan_ref as pr
 from tests import shortcut_ref as sr
 from tests import walk_ref as wr
-from tests.host_emulation import load_shim
+from tests.host_emulation import MAP, load_shim
 from tests.test_clearance_host import FUZZ_ROBOT, MARGIN, random_table
 from tests.test_raster_host import SCENES
 from tests.test_walk_host import _map, plateau
@@ -25,10 +25,9 @@ SENTINEL = 0xDEADBEEF
 def shim():
     global _shim
     if _shim is None:
-        vp, u32, u64, f = C.c_void_p, C.c_uint32, C.c_uint64, C.c_float
-        head = [vp, vp, vp, f, f, u32] + [vp] * 10 + [u32, vp]
+        vp, u32, u64 = C.c_void_p, C.c_uint32, C.c_uint64
+        head = [vp, vp, MAP, vp]
         _shim = load_shim("shortcut_shim.cpp", "_shortcut_shim.so",
-                          ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_clearance.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp"),
                           {"sshim_shortcut": (head + [vp, u64, u32, vp, u64, vp, u32, vp, u32, vp], C.c_int),
                            "sshim_link": (head + [u32, u32], C.c_int)})
     return _shim
@@ -39,12 +38,10 @@ def _head(t, origin, grid_len, z_len, robot, window, overhead, hops, min_hops, m
     rb.update(robot or {})
     r4 = np.array([rb["radius"], rb["reachable_height"], rb["max_rough"], rb["max_angle_deg"]], np.float32)
     rule = np.array([window or sr.DEFAULT_WINDOW, 1 if overhead else 0, min_hops, max_links or sr.DEFAULT_LINKS], np.uint32)
-    o = np.ascontiguousarray(origin, np.float32)
     hp = None if hops is None else np.ascontiguousarray(hops, np.uint32)
     p = lambda a: a.ctypes.data if a is not None and a.size else None
-    keep = (r4, rule, o, hp)
-    return keep, [p(r4), p(rule), p(o), grid_len, z_len, t.n, p(t.sx), p(t.sy), p(t.sz), p(t.flags), p(t.row_ncol), p(t.mean), p(t.normal),
-                  p(t.rough), p(t.ctab_key), p(t.ctab_val), t.tsize, p(hp)]
+    keep = (r4, rule, hp)
+    return keep, [p(r4), p(rule), t.shim_map(origin=origin, grid_len=grid_len, z_len=z_len), p(hp)]
 
 
 def run(t, origin, grid_len, z_len, routes, lengths, robot=None, window=0, overhead=False, hops=None, min_hops=0, max_links=0, waypoint_cap=None,

@@ -10,8 +10,8 @@ import pytest
 
 from tests import clearance_ref as cr
 from tests import walk_ref as wr
-from tests.host_emulation import HostMap, load_shim
-from tests.test_clearance_host import FUZZ_ROBOT, MARGIN, Table, random_table, table_of, tall_corridor
+from tests.host_emulation import MAP, HostMap, load_shim
+from tests.test_clearance_host import FUZZ_ROBOT, MARGIN, Table, random_table, tall_corridor
 from tests.test_raster_host import SCENES
 
 _shim = None
@@ -21,10 +21,9 @@ MODES = {"node": 0, "nearest_slope": 1}          # kQueryNode / kQueryNearestSlo
 def shim():
     global _shim
     if _shim is None:
-        vp, u32, f = C.c_void_p, C.c_uint32, C.c_float
+        vp, u32 = C.c_void_p, C.c_uint32
         _shim = load_shim("walk_shim.cpp", "_walk_shim.so",
-                          ("gndt_math.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_clearance.hpp", "gndt_walk.hpp"),
-                          {"wshim_walk": ([C.c_int, vp, vp, vp, f, f, u32] + [vp] * 10 + [u32, vp, vp, u32, C.c_uint64, u32, vp, u32, vp], C.c_int)})
+                          {"wshim_walk": ([C.c_int, vp, vp, MAP, vp, vp, u32, C.c_uint64, u32, vp, u32, vp], C.c_int)})
     return _shim
 
 
@@ -40,12 +39,10 @@ def run(t, origin, grid_len, z_len, paths, table, robot=None, start_mode="neares
     info = np.zeros(max(K, 1), wr.INFO_DTYPE)
     info.view(np.uint32)[:] = 0xDEADBEEF
     rows = np.full((K, row_cap), 0xDEADBEEF, np.uint32)
-    o = np.ascontiguousarray(origin, np.float32)
     hp = None if hops is None else np.ascontiguousarray(hops, np.uint32)
     p = lambda a: a.ctypes.data if a is not None and a.size else None
-    rc = shim().wshim_walk(int(table), p(r4), p(rule), p(o), grid_len, z_len, t.n, p(t.sx), p(t.sy), p(t.sz), p(t.flags), p(t.row_ncol),
-                           p(t.mean), p(t.normal), p(t.rough), p(t.ctab_key), p(t.ctab_val), t.tsize, p(hp), p(paths), sf, K, T, p(rows),
-                           row_cap, p(info))
+    rc = shim().wshim_walk(int(table), p(r4), p(rule), t.shim_map(origin=origin, grid_len=grid_len, z_len=z_len), p(hp), p(paths), sf, K, T,
+                           p(rows), row_cap, p(info))
     assert rc == 0
     return info[:K], rows
 
@@ -125,7 +122,7 @@ def _map(name):
     if name not in _maps:
         cloud, P = SCENES[name]()
         m = HostMap(cloud, P, seed=13)
-        _maps[name] = (m, table_of(m), wr.Walker(m.cells, m.origin, P["grid_len"], P["z_len"]))
+        _maps[name] = (m, m, wr.Walker(m.cells, m.origin, P["grid_len"], P["z_len"]))      # (map, the table the shim runs on, walker)
     return _maps[name]
 
 

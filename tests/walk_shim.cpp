@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gndt_walk.hpp"
+#include "shim_map.hpp"
 
 using namespace gndt;
 
@@ -15,16 +16,12 @@ static_assert(sizeof(WalkInfo) == 48, "gndt_walk_info");
 extern "C" {
 
 // robot: {radius, reachable_height, max_rough, max_angle_deg}; rule: {start_mode (kQueryNode / kQueryNearestSlope), checks, min_hops,
-// max_steps (resolved)}; origin: {ox, oy, oz}.  info [K] (48 bytes each), rows [K * row_cap] as gndt_walk_paths writes them.  Returns 0.
-int wshim_walk(int table, const float* robot, const uint32_t* rule, const float* origin, float grid_len, float z_len, uint32_t n,
-               const int32_t* sx, const int32_t* sy, const int32_t* sz, const uint32_t* flags, const uint32_t* row_ncol, const float* mean,
-               const float* normal, const float* rough, const uint64_t* ctab_key, const uint32_t* ctab_val, uint32_t ctab_size,
-               const uint32_t* hops, const float* paths, uint32_t sf, uint64_t K, uint32_t T, uint32_t* rows, uint32_t row_cap, WalkInfo* info) {
-    QueryView Q{};
-    CostView& V = Q.V;
-    V.sx = sx; V.sy = sy; V.sz = sz; V.flags = flags; V.row_ncol = row_ncol; V.mean = mean; V.normal = normal; V.rough = rough;
-    V.ctab_key = ctab_key; V.ctab_val = ctab_val; V.ctab_mask = ctab_size - 1;
-    Q.ox = origin[0]; Q.oy = origin[1]; Q.oz = origin[2]; Q.grid_len = grid_len; Q.z_len = z_len;
+// max_steps (resolved)}.  info [K] (48 bytes each), rows [K * row_cap] as gndt_walk_paths writes them.  Returns 0.
+int wshim_walk(int table, const float* robot, const uint32_t* rule, const ShimMap* m, const uint32_t* hops, const float* paths, uint32_t sf,
+               uint64_t K, uint32_t T, uint32_t* rows, uint32_t row_cap, WalkInfo* info) {
+    const QueryView Q = view_of(*m);
+    const CostView& V = Q.V;
+    const uint32_t n = (uint32_t)m->n;
     const Robot R{robot[0], robot[1], robot[2], robot[3]};
     const WalkRule P{(int)rule[0], rule[1], rule[2], rule[3]};
     std::vector<ClearanceStep> step;
