@@ -900,6 +900,39 @@ int gndt_build(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_byt
     return gndt_sync(h, nullptr, nullptr, nullptr);
 }
 
+namespace {
+// gndt_reserve on a handle that holds a finished map: the result rows and their per-row column sizes grown to `rows` WITH what they
+// hold (ensure_out / ensure_stage after it find them large enough).  A PARTITION build keeps nothing its rows could be made from again.
+int grow_rows_keeping(gndt_handle* h, uint64_t rows) {
+    auto& q = h->part;
+    GNDT_NO_CAPTURE(h, "the result arrays");
+    hipStream_t s = h->own_stream;
+    if (rows > q.row_ncol_cap && q.row_ncol) {
+        uint32_t* old = q.row_ncol;
+        const uint64_t old_cap = q.row_ncol_cap;
+        uint32_t* fresh = nullptr;
+        HIP_TRY(h, hipMalloc(&fresh, rows * sizeof(uint32_t)));
+        HIP_TRY(h, hipMemcpyAsync(fresh, old, old_cap * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        q.row_ncol = fresh; q.row_ncol_cap = rows;
+        release_device(h, old);
+    }
+    if (rows > h->out_cap && h->out_cap) {
+        OutView old = h->out, fresh{};
+        const uint64_t old_cap = h->out_cap, c = std::max<uint64_t>(1024, rows + rows / 8);
+        const int rc = alloc_rows(h, fresh, c);
+        if (rc) return rc;
+        const auto src = row_arrays(old), dst = row_arrays(fresh);
+        for (size_t k = 0; k < src.size(); ++k)
+            HIP_TRY(h, hipMemcpyAsync(*dst[k].p, *src[k].p, old_cap * src[k].elem, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        h->out = fresh; h->out_cap = c;
+        for (const RowArray& a : src) release_device(h, *a.p);
+    }
+    return GNDT_OK;
+}
+}  // namespace
+
 // Every buffer a build of up to max_points points and max_nodes nodes can ask for, whatever the strategy and whatever a re-run
 // would want (both LDS table sizes, the lowest table load, node estimates up to twice max_nodes; level-1 regions at their 4 n
 // ceiling; the exact partition's histogram; the node table of strategies ATOMIC / TILE; staging rows, result rows, order arrays).
@@ -924,12 +957,16 @@ int gndt_reserve(gndt_handle* h, uint64_t max_points, uint64_t max_nodes) {
     max_nodes = std::max<uint64_t>(max_nodes, h->P.max_nodes_hint);      // (the hint is what sizes the first attempt of every build)
     auto& q = h->part;
     int rc;
+    // (what a map that is already there lives in: looked at again below)
+    const uint64_t word_cap0 = q.word_cap, stage_cap0 = q.stage_cap, stage_rows_cap0 = q.stage_rows_cap, table_gen0 = h->table_gen;
+    const bool keep_rows = h->results_valid;
     if ((rc = ensure_words(h, (std::max<uint64_t>(n, h->P.max_points_hint) + 31) / 32 + 1))) return rc;
     if ((rc = ensure_part_counters(h))) return rc;
     // rows: what a PARTITION build stages (estimate + 1/8, after two 1.4x raises) and what the table path bounds by its slots
     const uint64_t est_hi = 2 * max_nodes;
     const uint64_t rows = std::max<uint64_t>(std::max<uint64_t>(est_hi + est_hi / 8 + 1024, (uint64_t)cap_for_nodes(max_nodes) / 2 + 1),
                                              4096 + n / 4 + n / 32);      // (a build without a hint stages max(4096, n / 4) rows at least)
+    if (keep_rows && (rc = grow_rows_keeping(h, std::max<uint64_t>(rows, q.stage_cap)))) return rc;
     if ((rc = ensure_stage(h, rows))) return rc;
     if ((rc = ensure_raw(h, q.stage_cap))) return rc;           // (the PARTITION strategies' staging rows)
     if ((rc = ensure_out(h, q.stage_cap))) return rc;
@@ -949,9 +986,24 @@ int gndt_reserve(gndt_handle* h, uint64_t max_points, uint64_t max_nodes) {
     if ((rc = reserve_table(h, std::max<uint64_t>(max_nodes, std::max<uint64_t>(1024, n / 4)), h->own_stream))) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
     // (rows_bound of a table-path finalisation follows the table: cap / 2 + 1)
+    if (keep_rows && (rc = grow_rows_keeping(h, std::max<uint64_t>(std::max<uint64_t>(1024, h->cap / 2 + 1), q.stage_cap)))) return rc;
     if ((rc = ensure_stage(h, std::max<uint64_t>(1024, h->cap / 2 + 1)))) return rc;
     if ((rc = ensure_raw(h, q.stage_cap))) return rc;
     if ((rc = ensure_out(h, q.stage_cap))) return rc;
+    // A reserve in the middle of a handle's life: a buffer that grew is a fresh one, without what the old one held.  The node table
+    // keeps its contents (grow_table) and the result rows theirs (grow_rows_keeping); the column order's words and the staging rows do
+    // not, and an incremental update or a deferred emit that went on from them read whatever the new memory held
+    // (tests/stream_model.py, growth_and_reserve, the frame after the reserve: rows placed by a bitmap of stale bits, a memory fault).
+    // So the next update takes the full path, and the rows of a map in the table are made again from the table, now.
+    if (q.word_cap != word_cap0 || q.stage_cap != stage_cap0 || q.stage_rows_cap != stage_rows_cap0 || h->table_gen != table_gen0) {
+        h->incr_ok = false;
+        if (h->results_valid && h->map_in_table && h->cap) {
+            const bool small_ok = h->small_ok;
+            rc = table_refinalize(h);            // (the regular kernels, deferred frames included; waits)
+            h->small_ok = small_ok;
+            if (rc) return rc;
+        }
+    }
     return GNDT_OK;
 }
 

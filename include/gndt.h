@@ -149,7 +149,10 @@ int gndt_build_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stri
  * whatever the strategy and whatever a re-run with more room would want.  After it such a build allocates nothing: it can be
  * captured into a hipGraph on a FRESH handle (no eager warm-up), and no replay finds its buffers moved.  Without it a captured
  * call that has to grow a buffer fails with GNDT_ERR_CAPACITY before touching the allocator (allocating on a capturing stream
- * would invalidate the capture — and, on this runtime, every later capture of the process).  Waits for the handle's stream. */
+ * would invalidate the capture — and, on this runtime, every later capture of the process).  Waits for the handle's stream.
+ * On a handle that holds a map the map stays: the node table and the result rows keep their contents when they grow; where the
+ * column order's buffers had to move, the rows of a map in the table are made again from it before the call returns, and the next
+ * gndt_update* relabels every column. */
 int gndt_reserve(gndt_handle* h, uint64_t max_points, uint64_t max_nodes);
 /* The reference builds ONE map per process (receiver.cpp:137-160): what its user sees is the FIRST build of a process, not the
  * steady state.  HIP resolves a kernel's code at its first launch and every buffer is allocated on first use; on a 200 k-point frame

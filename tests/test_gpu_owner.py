@@ -27,11 +27,13 @@ def _ranks(cloud, P, W, strategy=0):
     return maps
 
 
-def owner_build_on_one_gpu(cloud, P, W, bounds=None, strategy=0, locality=False):
+def owner_build_on_one_gpu(cloud, P, W, bounds=None, strategy=0, locality=False, maps=None):
     """-> (assembled global map as an export() dict, per-rank details).  `locality`: the two optional steps in front
-    (gndt_owner_sample_device on every rank, gndt_owner_map_device from everybody's messages) instead of hash ownership."""
+    (gndt_owner_sample_device on every rank, gndt_owner_map_device from everybody's messages) instead of hash ownership.
+    `maps`: the W handles of an earlier build with the same origin, instead of fresh ones."""
     import torch
-    maps = _ranks(cloud, P, W, strategy)
+    reused = maps is not None
+    maps = maps or _ranks(cloud, P, W, strategy)
     pts = torch.from_numpy(np.ascontiguousarray(cloud[1:])).cuda()
     n = int(pts.shape[0])
     bounds = bounds or [n * r // W for r in range(W + 1)]
@@ -40,6 +42,10 @@ def owner_build_on_one_gpu(cloud, P, W, bounds=None, strategy=0, locality=False)
         msgs = torch.cat([maps[r].owner_sample(demand, pts[bounds[r]:bounds[r + 1]]).clone() for r in range(W)]).contiguous()
         for r in range(W):
             maps[r].owner_map(msgs, W)
+    elif reused:
+        # (a block table stays on its handle for splits among the same W until replaced: a table for one rank is none — the hash again)
+        for r in range(W):
+            maps[r].owner_map(maps[r].owner_sample(demand, pts[bounds[r]:bounds[r + 1]]).clone(), 1)
     pieces = [[None] * W for _ in range(W)]
     kept = 0
     for r in range(W):
@@ -73,7 +79,7 @@ def owner_build_on_one_gpu(cloud, P, W, bounds=None, strategy=0, locality=False)
     assert seen.all()                                                          # the ranks' rows tile [0, N)
     glob.update(num_nodes=N, num_columns=K, num_slopes=sum(o[0]["num_slopes"] for o in outs))
     return glob, dict(owned_points=owned_points, local_nodes=[o[0]["num_nodes"] for o in outs], pairs=[int(p.shape[0]) for p in pairs],
-                      kept_fraction=kept / max(1, sum(owned_points)))
+                      kept_fraction=kept / max(1, sum(owned_points)), maps=maps, ranks=[(o[0], o[1]) for o in outs])
 
 
 @pytest.mark.parametrize("W", [1, 2, 3, 4])
@@ -208,6 +214,30 @@ def test_owner_build_of_tiny_clouds_with_ranks_that_own_nothing(n, W):
     recs = maps[0].owner_split("true", pts16, 0, n, 1)[0]
     maps[0].build_records("true", recs.clone(), n)
     parity.assert_parity(maps[0].export(), ref, demand="true", adversarial=True)
+
+
+def test_a_small_hash_owned_build_on_the_handles_of_a_large_locality_build():
+    """Large then small on the step API: W = 3 handles build a 60 000-point cloud with the sampled block table, then a 3 000-point
+    cloud of another place with hash ownership and another total_points.  Both are the oracle's maps, and every rank's rows of the
+    second — keys, counts, first indices, flags, global rows — are those of the same build on three fresh handles: nothing of the
+    first build (block table, records, column pairs, staging rows) shows through."""
+    from tests import stream_model as sm
+    W, P = 3, sm.P
+    large = np.concatenate([sm.ORIGIN[None, :], sm.patch(81, 60_000, 30.0)])
+    small = np.concatenate([sm.ORIGIN[None, :], sm.patch(82, 3_000, 8.0, (-9.0, 12.0))])
+    glob, info = owner_build_on_one_gpu(large, P, W, locality=True)
+    parity.assert_parity(glob, parity.ref_from_cloud(large, P))
+    ref = parity.ref_from_cloud(small, P)
+    again, used = owner_build_on_one_gpu(small, P, W, maps=info["maps"])
+    parity.assert_parity(again, ref)
+    fresh_glob, fresh = owner_build_on_one_gpu(small, P, W)
+    parity.assert_parity(fresh_glob, ref)
+    assert used["owned_points"] == fresh["owned_points"] and sum(used["local_nodes"]) == ref["num_nodes"] and min(used["local_nodes"]) > 0
+    for (a, grow_a), (b, grow_b) in zip(used["ranks"], fresh["ranks"]):
+        assert (a["num_nodes"], a["num_columns"], a["num_slopes"]) == (b["num_nodes"], b["num_columns"], b["num_slopes"])
+        assert np.array_equal(grow_a, grow_b)
+        for k in ("sx", "sy", "sz", "count", "first_idx", "flags"):
+            assert np.array_equal(a[k], b[k]), k
 
 
 @pytest.mark.parametrize("n", [200_000, 3_000_000])

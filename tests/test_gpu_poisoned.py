@@ -23,6 +23,14 @@ order arrays, the buckets' ranges, both cursor levels, the extent words of block
 staging rows ran out, on poisoned memory.  Its large-then-small test stays out: a 1.1 M-point build would spend the child's time in
 poison_malloc's fills.
 
+The group "stream" is the scripted handle lives of tests/test_gpu_stream_sequences.py: change2DMap, del2DMap, deferred emit,
+table and word growth in mid-stream, reserve, crop, clear, merge and the statistics round trip on one handle after the other — the
+eight arrays alloc_table does not clear, the order arrays and the staging rows behind every kind of finalisation.
+
+The group "owner" is the owner-partitioned build through its steps on W handles of one device (tests/test_gpu_owner.py: the tiny clouds
+with ranks that own nothing, and a 3 000-point hash-owned build on the handles of a 60 000-point locality build).  The threads
+communicator and RCCL stay out: poison_malloc synchronises the whole device on every allocation, and several rank threads share it.
+
 hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground."""
 import ctypes as C
 import json
@@ -42,6 +50,8 @@ REUSE = "tests/test_gpu_scratch_reuse.py::"
 CLEARANCE = "tests/test_gpu_clearance.py::"
 WALK = "tests/test_gpu_walk.py::"
 BLOCKED_SMALL = "tests/test_gpu_blocked_small.py::"
+STREAM = "tests/test_gpu_stream_sequences.py::"
+OWNER = "tests/test_gpu_owner.py::"
 # Existing GPU tests whose maps are hand-drawn or hold at most 60 000 points, that assert no wall-clock bound and record no hipGraph, and
 # the large-then-small tests of tests/test_gpu_scratch_reuse.py in the group of their consumer.  The bound on the points keeps a child
 # short — poison_malloc fills and synchronises on every allocation, and a build's buffers grow with its cloud — and is no rule about
@@ -145,6 +155,23 @@ GROUPS = {
         BLOCKED_SMALL + "test_fuzzed_boxes[232]",
         BLOCKED_SMALL + "test_staging_rows_run_out_inside_a_small_blocked_build",
         BLOCKED_SMALL + "test_layout_lifetime_on_one_handle",
+    ]),
+    "stream": dict(measured_s=6.53, limit_s=20, ids=[
+        STREAM + "test_script[small_then_stream]",
+        STREAM + "test_script[small_seen_then_tails]",
+        STREAM + "test_script[small_seen_each_tail]",
+        STREAM + "test_script[deferred_crossings]",
+        STREAM + "test_script[growth_and_reserve]",
+        STREAM + "test_script[rebuild_between]",
+        STREAM + "test_script[to_empty_and_back]",
+        STREAM + "test_script[merge_and_stats]",
+    ]),
+    "owner": dict(measured_s=7.40, limit_s=30, ids=[
+        OWNER + "test_owner_build_of_tiny_clouds_with_ranks_that_own_nothing[1-2]",
+        OWNER + "test_owner_build_of_tiny_clouds_with_ranks_that_own_nothing[7-4]",
+        OWNER + "test_owner_build_of_tiny_clouds_with_ranks_that_own_nothing[300-8]",
+        OWNER + "test_owner_build_of_tiny_clouds_with_ranks_that_own_nothing[5000-3]",
+        OWNER + "test_a_small_hash_owned_build_on_the_handles_of_a_large_locality_build",
     ]),
 }
 
