@@ -27,8 +27,8 @@ def lib_path(variant=None):
 
 LIB_PATH = lib_path(VARIANT)   # what lib() loads in this process
 SOURCES = ["gndt_api_core.hip", "gndt_api_table.hip", "gndt_api_build.hip", "gndt_api_dist.hip", "gndt_api_cost.hip", "gndt_api_query.hip",
-           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_clearance.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
-HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_clearance.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", os.path.join(_ROOT, "include", "gndt.h")]
+           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_clearance.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
+HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_clearance.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", os.path.join(_ROOT, "include", "gndt.h")]
 
 GNDT_OK = 0
 ERR_NAMES = {0: "OK", 1: "INVALID", 2: "NO_DEVICE", 3: "HIP", 4: "KEY_RANGE", 5: "CAPACITY", 6: "NOMEM", 7: "PEER"}
@@ -143,6 +143,18 @@ class ShortcutInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("length_in", C.c_uint32), ("waypoints", C.c_uint32), ("path_slopes", C.c_uint32),
                 ("links_tested", C.c_uint32), ("fallback_links", C.c_uint32), ("cost_in", C.c_float), ("cost_out", C.c_float),
                 ("hops_min", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class FootprintParams(C.Structure):
+    _fields_ = [("half_length", C.c_float), ("half_width", C.c_float), ("max_dz", C.c_float), ("height", C.c_float),
+                ("min_cells", C.c_uint32), ("min_cover", C.c_float), ("weight", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+
+class FootprintInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("flags", C.c_uint32), ("centre_row", C.c_uint32), ("cells", C.c_uint16), ("support", C.c_uint16),
+                ("gaps", C.c_uint16), ("unknown", C.c_uint16), ("z", C.c_float), ("normal", C.c_float * 3), ("along", C.c_float),
+                ("across", C.c_float), ("rms", C.c_float), ("step_max", C.c_float), ("bump_max", C.c_float), ("headroom", C.c_float),
+                ("reserved", C.c_uint32)]
 
 
 class MergeParams(C.Structure):
@@ -346,6 +358,8 @@ def lib():
                                               C.c_uint32, vp, vp]
     L.gndt_shortcut_routes.argtypes = [H, vp, sz, C.c_uint32, vp, sz, C.POINTER(Robot), C.POINTER(ShortcutParams), vp, vp, C.c_uint32, vp,
                                        C.c_uint32, vp]
+    L.gndt_footprint_poses_device.argtypes = [H, vp, sz, sz, C.POINTER(Robot), C.POINTER(FootprintParams), vp, C.c_uint32, vp, vp]
+    L.gndt_footprint_poses.argtypes = [H, vp, sz, sz, C.POINTER(Robot), C.POINTER(FootprintParams), vp, C.c_uint32, vp]
     L.gndt_coarsen_device.argtypes = [H, H, C.c_uint32, C.c_uint32, vp]
     L.gndt_merge_map_device.argtypes = [H, H, vp, C.POINTER(MergeParams), C.POINTER(MergeStats), vp]
     L.gndt_trans_morton_xyz.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float), C.c_char_p,
@@ -421,7 +435,7 @@ def lib():
                  "gndt_export", "gndt_stats_export_device", "gndt_stats_merge_device", "gndt_trans_morton_xyz",
                  "gndt_compute_cost", "gndt_cost_export_device", "gndt_cost_export", "gndt_query_device", "gndt_query",
                  "gndt_crop_device", "gndt_crop", "gndt_crop_box_from_world", "gndt_raster_shape", "gndt_raster_device", "gndt_raster", "gndt_clear_rays_device", "gndt_clear_rays",
-                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_clearance_device", "gndt_clearance", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_coarsen_device", "gndt_merge_map_device",
+                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_clearance_device", "gndt_clearance", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
                  "gndt_shard_stats_device", "gndt_finalize_stats_device",
                  "gndt_pcd_read", "gndt_pack_points_device", "gndt_build_cloud", "gndt_get_origin",
                  "gndt_count_morton", "gndt_morton_to_xy", "gndt_device_info", "gndt_set_profiling", "gndt_get_phase_times"):

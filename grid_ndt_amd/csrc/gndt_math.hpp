@@ -180,6 +180,11 @@ GNDT_HD int pick_min_eigen(const double e[3]) {
 //      which no known input produces, starts again from just left of the lowest possible root);
 //   4. eigenvector = largest cross product of two rows of (A - x I); rank-deficient fall-backs below.
 // c = xx,xy,xz,yy,yz,zz.  Returns lambda (>= 0 up to rounding) and a unit vector.
+// kTrigStart = false leaves step 2 out: Newton starts just left of the lowest possible root, so nothing but +, x, / and sqrt in fp64
+// enters the result and a host returns the device's bits (acosf and cosf differ between libm implementations in their last bit, and
+// the iterate Newton stops at keeps a trace of where it started).  The price is iterations: the distance shrinks by a third or more
+// each time until the root is separated, then quadratically; 128 bound the loop, a flat scatter takes four or five.
+template <bool kTrigStart = true>
 GNDT_HD void min_eigenpair_sym3(const double c[6], double& lambda, double v[3]) {
     double s = fmax(fmax(fabs(c[0]), fabs(c[3])), fabs(c[5]));
     s = fmax(s, fmax(fmax(fabs(c[1]), fabs(c[2])), fabs(c[4])));
@@ -204,27 +209,29 @@ GNDT_HD void min_eigenpair_sym3(const double c[6], double& lambda, double v[3]) 
     const double c2 = a00 + a11 + a22;
     const double c1 = (a00 * a11 - a01 * a01) + (a00 * a22 - a02 * a02) + (a11 * a22 - a12 * a12);
     const double c0 = a00 * (a11 * a22 - a12 * a12) - a01 * (a01 * a22 - a12 * a02) + a02 * (a01 * a12 - a11 * a02);
-    // fp32 start value
-    const float q = (float)c2 * (1.0f / 3.0f);
-    const float b00 = (float)a00 - q, b11 = (float)a11 - q, b22 = (float)a22 - q;
-    const float f01 = (float)a01, f02 = (float)a02, f12 = (float)a12;
-    const float p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0f * (f01 * f01 + f02 * f02 + f12 * f12);
-    double lam;
-    if (p2 < 1e-12f) {
-        lam = (double)q - 1e-5;                    // (numerically) isotropic
-    } else {
-        const float p = sqrtf(p2 * (1.0f / 6.0f));
-        const float ip = 1.0f / p;
-        const float d00 = b00 * ip, d11 = b11 * ip, d22 = b22 * ip, d01 = f01 * ip, d02 = f02 * ip, d12 = f12 * ip;
-        float r = 0.5f * (d00 * (d11 * d22 - d12 * d12) - d01 * (d01 * d22 - d12 * d02) + d02 * (d01 * d12 - d11 * d02));
-        r = fminf(1.0f, fmaxf(-1.0f, r));
-        const float phi = acosf(r) * (1.0f / 3.0f);
-        lam = (double)(q + 2.0f * p * cosf(phi + 2.0943951023931953f)) - 1e-5;
+    double lam = lo - 1e-5;
+    if constexpr (kTrigStart) {
+        // fp32 start value
+        const float q = (float)c2 * (1.0f / 3.0f);
+        const float b00 = (float)a00 - q, b11 = (float)a11 - q, b22 = (float)a22 - q;
+        const float f01 = (float)a01, f02 = (float)a02, f12 = (float)a12;
+        const float p2 = b00 * b00 + b11 * b11 + b22 * b22 + 2.0f * (f01 * f01 + f02 * f02 + f12 * f12);
+        if (p2 < 1e-12f) {
+            lam = (double)q - 1e-5;                    // (numerically) isotropic
+        } else {
+            const float p = sqrtf(p2 * (1.0f / 6.0f));
+            const float ip = 1.0f / p;
+            const float d00 = b00 * ip, d11 = b11 * ip, d22 = b22 * ip, d01 = f01 * ip, d02 = f02 * ip, d12 = f12 * ip;
+            float r = 0.5f * (d00 * (d11 * d22 - d12 * d12) - d01 * (d01 * d22 - d12 * d02) + d02 * (d01 * d12 - d11 * d02));
+            r = fminf(1.0f, fmaxf(-1.0f, r));
+            const float phi = acosf(r) * (1.0f / 3.0f);
+            lam = (double)(q + 2.0f * p * cosf(phi + 2.0943951023931953f)) - 1e-5;
+        }
     }
     // separated root: 2-4 iterations (quadratic); double/triple root: halves the error each time
-    bool restarted = false;
+    bool restarted = !kTrigStart;                  // (without the fp32 value the iteration already starts where a restart would)
     double prev = 1e300;
-    for (int it = 0; it < 26; ++it) {
+    for (int it = 0; it < (kTrigStart ? 26 : 128); ++it) {
         const double f = ((c2 - lam) * lam - c1) * lam + c0;
         const double fp = (2.0 * c2 - 3.0 * lam) * lam - c1;
         if (!(fp < 0.0)) {

@@ -1102,6 +1102,106 @@ class TwoDmap:
         pts[~live] = np.nan
         return pts
 
+    # ---- footprint poses (gndt_footprint_poses*: the plane under a rectangular vehicle, its tilt, step and headroom) ----
+    FOOT_STATUS = {0: "ok", 1: "bad_pose", 2: "no_ground", 3: "sparse"}
+    FOOT_FLAGS = {"tilt": 1, "step": 2, "cover": 4, "low": 8}
+    FOOT_WEIGHTS = {"cell": 0, "count": 1}
+    FOOT_INFO_DTYPE = np.dtype([("status", np.int32), ("flags", np.uint32), ("centre_row", np.int32), ("cells", np.uint16),
+                                ("support", np.uint16), ("gaps", np.uint16), ("unknown", np.uint16), ("z", np.float32),
+                                ("normal", np.float32, 3), ("along", np.float32), ("across", np.float32), ("rms", np.float32),
+                                ("step_max", np.float32), ("bump_max", np.float32), ("headroom", np.float32), ("reserved", np.uint32)])
+
+    def footprints(self, poses, half_length, half_width, robot=None, max_dz=0.0, height=0.0, min_cells=0, min_cover=0.0, weight="cell",
+                   rows=0, stream=None, host=False):
+        """The stance of a rectangular vehicle at K poses (include/gndt.h "footprint poses" defines every word).  poses: [K, 5] float32
+        x, y, z, hx, hy with (hx, hy) the heading as a vector of any non-zero length, or [K, 4] x, y, z, yaw, from which the vector
+        (cos yaw, sin yaw) is formed here; a torch CUDA tensor or a numpy array.  The rectangle reaches half_length along the heading
+        and half_width across it, each way.  Under it the map's slopes nearest the centre slope (within max_dz of it, 0 = any) merge
+        into one Gaussian whose flattest direction is the supporting plane.  robot: computeCost's dict (None = its defaults;
+        reachable_height and max_angle_deg are read).  height > 0 asks for the headroom verdict, min_cells (0 = 3) and min_cover for
+        the sparse status and the cover verdict, weight "cell" or "count".  rows > 0 also returns the first `rows` supports of every
+        pose in box order.  Returns a dict of [K] arrays: status (FOOT_STATUS), flags (FOOT_FLAGS bits), centre_row (-1 = none),
+        cells, support, gaps, unknown, z, normal [K, 3], along, across (rise per metre), rms, step_max, bump_max, headroom, and
+        pitch = arctan(along), roll = arctan(across), ok = (status == 0) & (flags == 0); `rows` [K, rows] (int32, -1 behind the
+        last) when asked.  torch tensors on the poses' device, enqueued on `stream` (default torch's current stream) and not
+        awaited; host=True or a numpy array goes through gndt_footprint_poses (numpy)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        on_dev = hasattr(poses, "is_cuda") and poses.is_cuda and not host
+        if hasattr(poses, "detach") and not on_dev:
+            poses = poses.detach().cpu().numpy()
+        if len(poses.shape) != 2 or poses.shape[1] not in (4, 5):
+            raise ValueError("poses must be [K, 5] (x, y, z, hx, hy) or [K, 4] (x, y, z, yaw)")
+        K = int(poses.shape[0])
+        prm = _lib.FootprintParams(float(half_length), float(half_width), float(max_dz), float(height), int(min_cells), float(min_cover),
+                                   self.FOOT_WEIGHTS[weight] if isinstance(weight, str) else int(weight))
+        rb = None
+        if robot is not None:
+            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+            d.update(robot)
+            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        row_cap = int(rows)
+        ints = {"status": 0, "flags": 1, "centre_row": 2}
+        floats = {"z": 5, "along": 9, "across": 10, "rms": 11, "step_max": 12, "bump_max": 13, "headroom": 14}
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                p = poses.float()
+                if p.shape[1] == 4:
+                    p = torch.cat([p[:, :3], torch.cos(p[:, 3:4]), torch.sin(p[:, 3:4])], 1)
+                p = p.contiguous()
+                raw = torch.zeros((max(K, 1), 16), dtype=torch.int32, device=p.device)
+                out_rows = torch.empty((K, row_cap), dtype=torch.int32, device=p.device) if row_cap else None
+            # (K = 0: an empty tensor's pointer is NULL, and rows NULL goes with a cap of 0)
+            self._check(self._L.gndt_footprint_poses_device(self._h, C.c_void_p(p.data_ptr() if K else 0), K, 20, rb, C.byref(prm),
+                                                            C.c_void_p(out_rows.data_ptr()) if row_cap and K else None, row_cap if K else 0,
+                                                            C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
+            with _torch_stream_ctx(stream):
+                raw = raw[:K]
+                out = {k: raw[:, i] for k, i in ints.items()}
+                out.update({k: raw[:, i].view(torch.float32) for k, i in floats.items()})
+                out["cells"], out["support"] = raw[:, 3] & 0xFFFF, (raw[:, 3] >> 16) & 0xFFFF
+                out["gaps"], out["unknown"] = raw[:, 4] & 0xFFFF, (raw[:, 4] >> 16) & 0xFFFF
+                out["normal"] = raw[:, 6:9].view(torch.float32)
+                out["pitch"], out["roll"] = torch.atan(out["along"]), torch.atan(out["across"])
+                out["ok"] = (out["status"] == 0) & (out["flags"] == 0)
+        else:
+            p = np.asarray(poses, np.float32)
+            if p.shape[1] == 4:
+                p = np.concatenate([p[:, :3], np.cos(p[:, 3:4]), np.sin(p[:, 3:4])], 1)
+            p = np.ascontiguousarray(p, np.float32)
+            raw = np.zeros(max(K, 1), self.FOOT_INFO_DTYPE)
+            out_rows = np.empty((K, row_cap), np.int32) if row_cap else None
+            self._check(self._L.gndt_footprint_poses(self._h, C.c_void_p(p.ctypes.data if K else 0), K, 20, rb, C.byref(prm),
+                                                     C.c_void_p(out_rows.ctypes.data) if row_cap and K else None, row_cap if K else 0,
+                                                     C.c_void_p(raw.ctypes.data)))
+            out = {k: raw[k][:K] for k in self.FOOT_INFO_DTYPE.names if k != "reserved"}
+            out["flags"] = out["flags"].view(np.int32)
+            out["pitch"], out["roll"] = np.arctan(out["along"]), np.arctan(out["across"])
+            out["ok"] = (out["status"] == 0) & (out["flags"] == 0)
+        if row_cap:
+            out["rows"] = out_rows
+        return out
+
+    def footprints_along(self, paths, half_length, half_width, **kw):
+        """footprints() at every waypoint of K paths of T waypoints ([K, T, 3|4], walk_paths' layout: a waypoint whose x or y is NaN
+        ends its path), each heading the vector to the next finite waypoint (rollouts.headings).  Returns footprints()' dict with
+        [K, T] fields (normal [K, T, 3]; rows [K, T, rows]) and `stands` [K]: every waypoint before the path's terminator is ok.  A
+        waypoint at or behind the terminator has status bad_pose and does not count against its path; another bad pose does."""
+        from . import rollouts
+        poses = rollouts.headings(paths)
+        K, T = int(poses.shape[0]), int(poses.shape[1])
+        out = self.footprints(poses.reshape(K * T, 5), half_length, half_width, **kw)
+        out = {k: v.reshape((K, T) + tuple(v.shape[1:])) for k, v in out.items()}
+        ended = poses[..., 0] != poses[..., 0]          # (headings' NaN at and behind the terminator)
+        if hasattr(out["ok"], "is_cuda") and not hasattr(ended, "is_cuda"):
+            import torch
+            ended = torch.as_tensor(ended, device=out["ok"].device)
+        elif hasattr(ended, "is_cuda") and not hasattr(out["ok"], "is_cuda"):
+            ended = ended.cpu().numpy()
+        out["stands"] = (out["ok"] | ended).all(1)
+        return out
+
     # ---- free-space clearing (gndt_clear_rays*: nodes that sensor rays pass through leave the map) ----
     CLEAR_PROTECTED = 0x80000000
 

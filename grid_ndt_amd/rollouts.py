@@ -3,6 +3,7 @@
     paths = rollouts.arcs(pose, v, omegas, dt, T)            # a DWA fan from the robot's pose
     info = m.walk_paths(paths)                               # driven over the map on the device
     best = rollouts.choose(info, h[info["end_row"]])         # h: the cost map of the last computeCost, per row
+    stance = m.footprints_along(paths[info["status"] == 0], 0.3, 0.2)   # for a vehicle: the footprint along the arcs that survive
 
 Plain tensor arithmetic: nothing here is a hot path."""
 import numpy as np
@@ -45,3 +46,39 @@ def choose(info, h_end):
         return -1
     order = np.lexsort((done, length[done], h[done]))
     return int(done[order[0]])
+
+
+def headings(paths):
+    """Footprint poses along K paths of T waypoints ([K, T, 3] or [K, T, 4], walk_paths' layout): [K, T, 5] float32 x, y, z, hx, hy
+    for TwoDmap.footprints (torch in, torch out on the same device; anything else numpy).  A path ends at its first waypoint whose x
+    or y is not finite; (hx, hy) is the vector to the next waypoint of the path, in fp32, the last waypoint repeats its predecessor's
+    heading (a path of one waypoint looks along +x), and the waypoints at and behind the end are NaN: bad poses, which
+    footprints_along leaves out of its verdict.  Two waypoints in one place give the zero vector, a bad pose that does count."""
+    torch_in = hasattr(paths, "device") and hasattr(paths, "dtype") and not isinstance(paths, np.ndarray)
+    if torch_in:
+        import torch as xp
+        p = paths[..., :3].float()
+        K, T = int(p.shape[0]), int(p.shape[1])
+        col = lambda v: xp.full((K, 1, 2), v, dtype=xp.float32, device=p.device)
+        live = xp.cumprod((xp.isfinite(p[..., 0]) & xp.isfinite(p[..., 1])).to(xp.int32), 1).bool()
+        off = xp.zeros((K, 1), dtype=xp.bool, device=p.device)
+        cat = xp.cat
+    else:
+        xp = np
+        p = np.asarray(paths, np.float32)[..., :3]
+        K, T = p.shape[0], p.shape[1]
+        col = lambda v: np.full((K, 1, 2), v, np.float32)
+        live = np.cumprod(np.isfinite(p[..., 0]) & np.isfinite(p[..., 1]), 1).astype(bool)
+        off = np.zeros((K, 1), bool)
+        cat = np.concatenate
+    if T == 0:
+        return cat([p, p[..., :2]], -1)
+    has_next = cat([live[:, 1:], off], 1)
+    step = cat([p[:, 1:, :2] - p[:, :-1, :2], col(0.0)], 1)
+    h = xp.where(has_next[..., None], step, xp.zeros_like(step))
+    ahead = col(0.0)
+    ahead[:, :, 0] = 1.0
+    prev = cat([ahead, h[:, :-1]], 1)
+    h = xp.where((live & ~has_next)[..., None], prev, h)
+    out = cat([p, h], -1)
+    return xp.where(live[..., None], out, xp.full_like(out, float("nan")))

@@ -824,6 +824,107 @@ int gndt_shortcut_routes(gndt_handle* h, const uint32_t* route_rows_host, size_t
                          uint32_t* waypoint_rows_host, uint32_t waypoint_cap, uint32_t* path_rows_host, uint32_t path_cap,
                          gndt_shortcut_info* info_host);
 
+/* ---- footprint poses: fitted plane, tilt, step and headroom under a rectangular vehicle ----------------------------------------
+ * A vehicle is not a point.  Standing at (x, y) with a heading it asks what surface its footprint rests on, how far that surface
+ * tilts along and across the heading, whether a kerb or a hole lies under it, how much of it stands on unknown ground, and what
+ * hangs over it.  Every slope of the map is a Gaussian (count, mean, scatter); the Gaussians under a rectangle merge in closed form
+ * and the smallest eigenpair of the merged scatter is the supporting plane.  One call takes K poses: five floats x, y, z, hx, hy at
+ * poses + k * stride_bytes (any multiple of 4 from 20 up).  (hx, hy) is the heading as a VECTOR of any non-zero length, not an
+ * angle: which column lies under the vehicle is then decided by + and x in fp64 alone (the library is built without contraction),
+ * and no sine or cosine of any libm enters an answer.  The rectangle reaches half_length along the heading and half_width across
+ * it, both ways.  `robot` NULL = the flood's defaults; only reachable_height and max_angle_deg are read.  Per pose, in this order:
+ *   1. pose      a non-finite field, or hx == hy == 0: status GNDT_FOOT_BAD_POSE.
+ *   2. centre    the row GNDT_QUERY_NEAREST_SLOPE finds for (x, y, z) (the point queries' own lookup).  None: GNDT_FOOT_NO_GROUND.
+ *                z0 = its mean z (fp32), (cx, cy) = its column.
+ *   3. box       n = ceil(sqrt(half_length^2 + half_width^2) / grid_len), formed once on the host in fp64 from the floats widened
+ *                (n >= 1; n > 15 is refused: (2n + 1)^2 <= 1024 bounds a lane's loop and a wavefront's table).  The box is the
+ *                (2n + 1)^2 columns around (cx, cy): per axis the n non-zero signed indices below the centre's, the centre's and
+ *                the n above (signed indices skip 0, as the raster export steps them).  Box position p = j (2n + 1) + i, i over
+ *                x ascending, j over y ascending; the centre column is p = n (2n + 1) + n.
+ *   4. inside    with the column's centre per axis o + sign(s) (|s| - 0.5) grid_len in fp64 (o and grid_len widened), all in fp64:
+ *                dx = centre_x - x, dy = centre_y - y, u = dx hx + dy hy, v = dy hx - dx hy, hh = hx hx + hy hy; the column is
+ *                under the vehicle iff u u <= (half_length half_length) hh and v v <= (half_width half_width) hh.  The centre
+ *                column is under the vehicle whatever the rounding.  `cells` counts the columns under the vehicle.
+ *   5. support   a column under the vehicle whose index lies beyond +-65535, or that holds no node, is `unknown`.  Otherwise, among
+ *                its rows with GNDT_FLAG_SLOPE and fabsf(mean_z - z0) <= max_dz in fp32 (all of them when max_dz is 0), the one
+ *                with the least fabsf(mean_z - z0), a tie going to the smaller sz (the query's rule), is its support; a column
+ *                with no such row is a `gap`.  The centre column's support is the centre row.  `support`, `gaps` and `unknown`
+ *                count these; cells = support + gaps + unknown.
+ *   6. merge     over the supports, in fp64, about the point (x, y, z0): d = mean - (x, y, z0) (each float widened first),
+ *                w = 1 (GNDT_FOOT_WEIGHT_CELL) or count (GNDT_FOOT_WEIGHT_COUNT), s = w / count;
+ *                W = sum w;  M_a = sum (w d_a);  Q_ab = sum ((w d_a) d_b + s cov_ab), cov the row's un-normalised scatter;
+ *                dbar_a = M_a / W;  S_ab = Q_ab - (W dbar_a) dbar_b.
+ *                THE ORDER OF EVERY SUM is fixed by box position alone — never by arrival, by K, or by where the pose sits in the
+ *                batch: 64 partial sums l = 0 .. 63, each starting from +0 and adding the terms of the supports at positions
+ *                p = l, l + 64, l + 128, ... in ascending p; then six rounds offset = 32, 16, 8, 4, 2, 1 in each of which every
+ *                partial l becomes partial[l] + partial[l ^ offset] (all 64 at once); the sum is partial 0.
+ *                support < min_cells (0 = 3): status GNDT_FOOT_SPARSE, the counts and centre_row are reported, flags and every
+ *                float field are 0.
+ *   7. plane     (lambda, nrm) = the smallest eigenpair of S (the build's solver without its fp32 trigonometric start value:
+ *                only +, x, / and sqrt in fp64, so that a host run of the same code returns the device's bits), nrm negated if
+ *                nrm_z < 0.
+ *                rms = sqrt(max(lambda, 0) / W);  z = (z0 + dbar_z) + (nrm_x dbar_x + nrm_y dbar_y) / nrm_z, the plane's height at
+ *                (x, y);  with rh = sqrt(hh), f = (hx / rh, hy / rh):  along = -(nrm_x f_x + nrm_y f_y) / nrm_z,
+ *                across = -(nrm_y f_x - nrm_x f_y) / nrm_z — rise per metre along the heading and to its left; fp64, rounded to
+ *                fp32 once.  The library takes no arctangent: pitch = atan(along), roll = atan(across) are the caller's.
+ *                nrm_z == 0: z = z0 + dbar_z, along = across = 0 (and GNDT_FOOT_TILT is set by 9).
+ *   8. shape     step_max: the largest fabsf(mean_z(a) - mean_z(b)) in fp32 over the supports a, b of two 4-adjacent box columns
+ *                that both have one (0 if none).  bump_max: the largest |(nrm_x e_x + nrm_y e_y) + nrm_z e_z| over the supports,
+ *                e = d - dbar, fp64, rounded once.  headroom: over the rows t of the support columns with GNDT_FLAG_HAS_STATS and
+ *                mean_z(t) > mean_z(support) + reachable_height (fp32), the least of mean_z(t) - zp, zp the plane's height at the
+ *                column's centre, (z0 + dbar_z) - (nrm_x (ex - dbar_x) + nrm_y (ey - dbar_y)) / nrm_z with (ex, ey) = (dx, dy) of
+ *                4 (z0 + dbar_z where nrm_z == 0); fp64, rounded once; FLT_MAX if there is none.
+ *   9. verdict   bits in `flags`: GNDT_FOOT_TILT nrm_z < cos(max_angle_deg) (the cosine formed once on the host in fp64);
+ *                GNDT_FOOT_STEP step_max > reachable_height; GNDT_FOOT_COVER support < min_cover * cells in fp64; GNDT_FOOT_LOW
+ *                height > 0 and headroom < height.  Status GNDT_FOOT_OK with flags 0 means "stands here".
+ * rows_dev (optional, NULL together with row_cap 0) receives per pose row_cap entries: the supports in box order, GNDT_NO_ROW behind
+ * them (all GNDT_NO_ROW for BAD_POSE and NO_GROUND); more supports than row_cap write the first row_cap and the caller sees
+ * support > row_cap.  info is written 16 bytes at a time: info_dev must be aligned to 16 bytes.  A box holds at most 961 columns, so
+ * the four counts are 16-bit.  Order, lifetime and refusals are the walk call's: the call first finishes what gndt_sync finishes,
+ * builds or reuses the map's column index and enqueues its kernel on `hip_stream` (NULL = the handle's stream), not awaited;
+ * gndt_footprint_poses is synchronous and takes host memory of any alignment.  The map, h and state are only read and no cost map
+ * is needed.  K == 0 returns GNDT_OK and launches nothing.  There is no CPU path.  A sharded map answers from the rows this rank
+ * holds.  GNDT_ERR_INVALID: a null handle, params or info, null poses with K > 0, K * 1024 >= 2^31, a stride below 20 or not a
+ * multiple of 4, a half extent that is not finite or not greater than 0, a box beyond n = 15, max_dz, height or min_cover negative
+ * or not finite, an unknown weight, a non-zero reserved word, rows NULL with row_cap != 0 or the reverse, info_dev not aligned to 16
+ * bytes or poses_dev, rows_dev not to 4, no finished build, a stream under hipGraph capture. */
+enum { GNDT_FOOT_OK = 0, GNDT_FOOT_BAD_POSE = 1, GNDT_FOOT_NO_GROUND = 2, GNDT_FOOT_SPARSE = 3 };
+enum { GNDT_FOOT_WEIGHT_CELL = 0, GNDT_FOOT_WEIGHT_COUNT = 1 };
+#define GNDT_FOOT_TILT 1u
+#define GNDT_FOOT_STEP 2u
+#define GNDT_FOOT_COVER 4u
+#define GNDT_FOOT_LOW 8u
+typedef struct gndt_footprint_params {
+    float half_length;        /* metres along the heading, each way; finite, > 0 */
+    float half_width;         /* metres across the heading, each way; finite, > 0 */
+    float max_dz;             /* supports lie within this of the centre slope's mean z; 0 = no band */
+    float height;             /* the vehicle's height for GNDT_FOOT_LOW; 0 = no headroom verdict */
+    uint32_t min_cells;       /* fewer supports: GNDT_FOOT_SPARSE; 0 = 3 */
+    float min_cover;          /* share of `cells` that must be supports, for GNDT_FOOT_COVER; 0 = none */
+    uint32_t weight;          /* GNDT_FOOT_WEIGHT_* */
+    uint32_t reserved[5];     /* 0 */
+} gndt_footprint_params;      /* 48 bytes; zeros = defaults (the half extents have none) */
+typedef struct gndt_footprint_info {
+    int32_t status;           /* GNDT_FOOT_OK / _BAD_POSE / _NO_GROUND / _SPARSE */
+    uint32_t flags;           /* GNDT_FOOT_TILT | _STEP | _COVER | _LOW */
+    uint32_t centre_row;      /* GNDT_NO_ROW without a centre */
+    uint16_t cells, support;  /* columns under the vehicle; those with a support */
+    uint16_t gaps, unknown;   /* those in the map without a support; those not in the map */
+    float z;                  /* the plane's height at (x, y) */
+    float normal[3];          /* unit, normal[2] >= 0 */
+    float along, across;      /* rise per metre */
+    float rms;
+    float step_max, bump_max, headroom;
+    uint32_t reserved;        /* 0 */
+} gndt_footprint_info;        /* 64 bytes */
+/* Device memory in and out. */
+int gndt_footprint_poses_device(gndt_handle* h, const void* poses_dev, size_t K, size_t stride_bytes, const gndt_robot* robot,
+                                const gndt_footprint_params* params, uint32_t* rows_dev /* [K * row_cap] or NULL */, uint32_t row_cap,
+                                gndt_footprint_info* info_dev /* [K] */, void* hip_stream);
+/* Host memory in and out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_footprint_poses(gndt_handle* h, const void* poses_host, size_t K, size_t stride_bytes, const gndt_robot* robot,
+                         const gndt_footprint_params* params, uint32_t* rows_host, uint32_t row_cap, gndt_footprint_info* info_host);
+
 /* ---- free-space clearing: nodes that sensor rays pass through leave the map -------------------------------------------------
  * What was seen once and is gone now — a person, a car, an open door — leaves nodes that change its columns' labels (isSlope,
  * map2D.h:66-108) and that the cost flood routes around for as long as the map lives (the reference's changeCallback only adds).
