@@ -378,6 +378,7 @@ void gndt_destroy(gndt_handle* h) {
     free_merge(h);
     free_plan(h);
     free_frontier(h);
+    free_segment(h);
     free_clearance(h);
     free_walk(h);
     for (const RowArray& a : row_arrays(h->out))

@@ -12,6 +12,7 @@
 //   gndt_api_score.hip  scan scoring and its derivatives
 //   gndt_api_plan.hip   route planning: A* routes to the flood's goal for a batch of starts
 //   gndt_api_frontier.hip  frontier extraction: the slopes where the map ends, clustered
+//   gndt_api_segment.hip   scan segmentation: the points of a scan the map does not explain, clustered
 //   gndt_api_clearance.hip  clearance field: per slope the steps to the nearest barrier, and where it is
 //   gndt_api_walk.hip       path walks: candidate polylines driven over the map's slopes under the flood's gates
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
@@ -264,6 +265,12 @@ struct gndt_handle {
     struct Frontier {
         void* scratch = nullptr;  uint64_t bytes = 0;
     } frontier;
+    // scan segmentation (gndt_segment.hpp): the call's cell table (16 B a slot, the smallest power of two >= 2 n slots), per point its
+    // cell's slot, then root (4 B), its parent in the union-find (4 B), its root's cells and points, then place (8 B) and its class
+    // (1 B), and four counts per tile of points; grown on demand
+    struct Segment {
+        void* scratch = nullptr;  uint64_t bytes = 0;
+    } segment;
     // clearance field (gndt_clearance.hpp): per row the steps table of its four sides (32 B), two key arrays for the rounds' ping-pong
     // (16 B) and its tall-column bits (1 B), and one flag word per round; grown on demand
     struct Clearance {
@@ -680,6 +687,8 @@ void free_merge(gndt_handle* h);
 void free_plan(gndt_handle* h);
 // ---- gndt_api_frontier.hip ----
 void free_frontier(gndt_handle* h);
+// ---- gndt_api_segment.hip ----
+void free_segment(gndt_handle* h);
 // ---- gndt_api_clearance.hip ----
 void free_clearance(gndt_handle* h);
 // ---- gndt_api_walk.hip ----

@@ -11,7 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, ShortcutParams, Stats, WalkInfo, WalkParams
+from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, SegmentParams, ShortcutParams, Stats, WalkInfo, WalkParams
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
@@ -1370,6 +1370,112 @@ class TwoDmap:
         if want:
             out.update(d2=d2, row=row)
         return out
+
+    # ---- scan segmentation (gndt_segment_scan*: the points of a scan the map does not explain, clustered) ----
+    SEG_UNKEYED, SEG_EXPLAINED, SEG_OFF_SURFACE, SEG_UNMAPPED = 0, 1, 2, 3
+    SEG_CLASSES = {"off_surface": 1 << 2, "unmapped": 1 << 3}
+    SEG_DTYPE = np.dtype([("label", np.uint32), ("cells", np.uint32), ("off_surface", np.uint32), ("unmapped", np.uint32),
+                          ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
+                          ("sz_min", np.int32), ("sz_max", np.int32), ("sum_x", np.int64), ("sum_y", np.int64), ("sum_z", np.int64),
+                          ("z_lo", np.float32), ("z_hi", np.float32)])
+
+    def segment_scan(self, points, pose=None, neighbourhood=7, novel_d2=0.0, classes=None, min_points=1, connectivity=26,
+                     min_cluster_points=1, min_cluster_cells=1, labels=False, max_clusters=None, stream=None, min_count=0, cov_rel=0.0,
+                     cov_floor=0.0):
+        """What in the scan `points` ([N,3] or [N,4] float32) is not in the map, as clusters (include/gndt.h "scan segmentation" defines
+        every word).  pose: one [3,4] / [4,4] matrix, map <- scan (None: the identity).  A point is explained when its least
+        Mahalanobis d2 against the node it falls in (neighbourhood 7: and its six face neighbours) is at most novel_d2 (0 = 11.345),
+        off_surface when candidates count but none is that near, unmapped when none counts; classes: which of "off_surface" /
+        "unmapped" (or the bit mask; None = both) are novel.  Cells of the map's grid with at least min_points novel points that touch
+        (connectivity 26 or 6) form a cluster.  Returns a dict with one [K] array per field of gndt_scan_cluster (label, cells,
+        off_surface, unmapped, sx_min .. sz_max, sum_x, sum_y, sum_z, z_lo, z_hi) for the clusters of at least min_cluster_points
+        points and min_cluster_cells cells in ascending label, `counts` ([4]: those clusters, novel points, novel cells, clusters of
+        any size) and, with labels=True, `point_class` (uint8 [N]) and `point_label` (int32 [N]: the label of the point's cluster,
+        -1 for none).  max_clusters=None sizes the list from a count-only first call (which waits for it on `stream`); a number is
+        the list's capacity — counts[0] may exceed it.  A torch CUDA tensor is segmented on the device (torch tensors, enqueued on
+        `stream`, default torch's current stream, not awaited: the arrays then have max_clusters entries, filled from the front); a
+        host array through gndt_segment_scan (numpy, cut to min(counts[0], max_clusters) entries)."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if classes is None:
+            mask = 0
+        elif isinstance(classes, int):
+            mask = classes
+        else:
+            mask = 0
+            for c in ([classes] if isinstance(classes, str) else classes):
+                mask |= self.SEG_CLASSES[c]
+        prm = SegmentParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(novel_d2), int(mask), int(min_points),
+                            int(connectivity), int(min_cluster_points), int(min_cluster_cells))
+        T = self._as_poses(pose)[0] if pose is not None else None
+        ptr, n, stride, on_dev, keep = self._as_input(points)
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                Td = torch.from_numpy(T).to(keep.device) if T is not None else None
+                counts = torch.zeros(4, dtype=torch.int32, device=keep.device)
+                cls = torch.empty(n, dtype=torch.uint8, device=keep.device) if labels else None
+                lab = torch.empty(n, dtype=torch.int32, device=keep.device) if labels else None
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            call = lambda recs, cap, c, l: self._check(self._L.gndt_segment_scan_device(
+                self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), C.byref(prm), p(c), p(l), p(recs) if cap else C.c_void_p(0), cap,
+                p(counts), _stream_ptr(stream)))
+            if max_clusters is None:
+                call(None, 0, None, None)
+                with _torch_stream_ctx(stream):         # (read on the stream the count was enqueued on: the copy waits for it)
+                    max_clusters = int(counts[0].item())
+            with _torch_stream_ctx(stream):
+                recs = torch.zeros((int(max_clusters), 18), dtype=torch.int32, device=keep.device)
+            call(recs, recs.shape[0], cls, lab)
+            wide = recs.view(torch.int64) if recs.shape[0] else recs.new_zeros((0, 9), dtype=torch.int64)
+            out = {"label": recs[:, 0], "cells": recs[:, 1], "off_surface": recs[:, 2], "unmapped": recs[:, 3],
+                   "sx_min": recs[:, 4], "sx_max": recs[:, 5], "sy_min": recs[:, 6], "sy_max": recs[:, 7], "sz_min": recs[:, 8],
+                   "sz_max": recs[:, 9], "sum_x": wide[:, 5], "sum_y": wide[:, 6], "sum_z": wide[:, 7],
+                   "z_lo": recs[:, 16].view(torch.float32), "z_hi": recs[:, 17].view(torch.float32)}
+        else:
+            counts = np.zeros(4, np.uint32)
+            cls = np.empty(n, np.uint8) if labels else None
+            lab = np.empty(n, np.int32) if labels else None
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            call = lambda recs, cap, c, l: self._check(self._L.gndt_segment_scan(
+                self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), C.byref(prm), p(c), p(l), p(recs) if cap else C.c_void_p(0), cap,
+                p(counts)))
+            if max_clusters is None:
+                call(None, 0, None, None)
+                max_clusters = int(counts[0])
+            recs = np.zeros(int(max_clusters), self.SEG_DTYPE)
+            call(recs, len(recs), cls, lab)
+            recs = recs[:min(int(counts[0]), len(recs))]
+            out = {k: recs[k] for k in self.SEG_DTYPE.names}
+        out["counts"] = counts
+        if labels:
+            out.update(point_class=cls, point_label=lab)
+        return out
+
+    def cluster_boxes(self, seg):
+        """World-frame boxes and centroids of the clusters of segment_scan(): (boxes [K, 2, 3] float32, the min and the max corner of
+        the cluster's cells, and centroids [K, 3] float32, sum / points / 1024).  A cell of signed index s spans origin + lin(s) * len
+        to origin + (lin(s) + 1) * len with lin(s) = s - 1 for s > 0, s otherwise, and len the grid's length in x and y, the level's
+        height in z.  Entries behind counts[0] (a list with room to spare) are NaN.  Torch in, torch out; numpy in, numpy out."""
+        on_dev = not isinstance(seg["label"], np.ndarray)
+        xp = np
+        if on_dev:
+            import torch as xp
+        f64 = (lambda v: v.double()) if on_dev else (lambda v: v.astype(np.float64))
+        lin = lambda v: f64(v) - f64(v > 0)
+        o, steps = self.cloudFirst, (self.gridLen, self.gridLen, self.zLen)
+        lo = xp.stack([float(o[a]) + lin(seg[k]) * float(steps[a]) for a, k in enumerate(("sx_min", "sy_min", "sz_min"))], 1)
+        hi = xp.stack([float(o[a]) + (lin(seg[k]) + 1.0) * float(steps[a]) for a, k in enumerate(("sx_max", "sy_max", "sz_max"))], 1)
+        pts = f64(seg["off_surface"]) + f64(seg["unmapped"])
+        pts = pts.clamp(min=1.0) if on_dev else np.maximum(pts, 1.0)
+        cen = xp.stack([f64(seg[k]) / pts / 1024.0 for k in ("sum_x", "sum_y", "sum_z")], 1)
+        boxes = xp.stack([lo, hi], 1)
+        K = int(seg["label"].shape[0])
+        found = seg["counts"][0]
+        behind = (xp.arange(K, device=seg["label"].device) >= found) if on_dev else (np.arange(K) >= int(found))
+        boxes[behind] = float("nan")
+        cen[behind] = float("nan")
+        return (boxes.float(), cen.float()) if on_dev else (boxes.astype(np.float32), cen.astype(np.float32))
 
     # ---- scan score derivatives (gndt_score_derivs*) and the Newton registration driven from them (registration.py) ----
     _H_INDEX = None

@@ -1047,6 +1047,77 @@ int gndt_score_poses_device(gndt_handle* h, const void* xyz_dev, size_t n, size_
 int gndt_score_poses(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* poses_host, uint32_t K,
                      const gndt_score_params* params, gndt_pose_score* out_host, float* point_d2_host, uint32_t* point_row_host);
 
+/* ---- scan segmentation: the points of a scan that the map does not explain, clustered into objects ---------------------------------
+ * What a robot asks of every frame next to "how well does it fit" (scan scoring): what in this scan is NOT in the map, and where are
+ * those things — a person, a parked car, a pallet that was not there when the map was made.  The answer is a list of clusters (boxes for
+ * gndt_walk_paths / gndt_footprint_poses obstacles), a label per point (the points not to gndt_update the map with) and four counts (a
+ * localisation health signal).  Everything after the classification is integer arithmetic: the answer is exact and does not depend on
+ * the order threads work in.  lin(s) = s > 0 ? s - 1 : s, as in "frontier extraction": signed indices skip 0 on all three axes.
+ * A DEFINITION (tests restate it in numpy).  For point i = (x, y, z) of n (fp32, stride 12 or 16):
+ *   1. transform and key: steps 1 and 2 of "scan scoring" — q = fl32(T p) for the one pose `pose` ([12] doubles; NULL = the identity,
+ *      q = p), then q's GNDT_QUERY_NODE key (sx, sy, sz).  A point without a key has class GNDT_SEG_UNKEYED.
+ *   2. class: candidates and terms are steps 3 and 4 of "scan scoring" with this call's neighbourhood, min_count, cov_rel, cov_floor
+ *      (the same defaults) and max_d2 = 0.  d2_i = the least d2 of the point's counting candidates, rounded to fp32 — the very number
+ *      gndt_score_poses* reports per point (+inf: no candidate counts).
+ *        GNDT_SEG_EXPLAINED    d2_i <= novel_d2           (novel_d2 0 = 11.345f, the 0.99 quantile of chi^2 with 3 degrees of freedom)
+ *        GNDT_SEG_OFF_SURFACE  candidates count, but d2_i > novel_d2
+ *        GNDT_SEG_UNMAPPED     no candidate counts
+ *      A point is NOVEL when `classes` (a mask of 1u << class; 0 = OFF_SURFACE | UNMAPPED) holds its class.
+ *   3. cell: a novel point's cell is its key in the map's grid.  A NOVEL CELL is a cell with at least min_points novel points (0 = 1);
+ *      its id is the smallest index of its novel points.
+ *   4. link: two different novel cells a, b are linked under connectivity 26 (0 = 26) when |lin(s_a) - lin(s_b)| <= 1 on all three
+ *      axes, under 6 when the three differences add up to 1.  An index beyond the codec's range (|sx|, |sy| > 65535, |sz| >= 2^21) does
+ *      not exist.
+ *   5. cluster: a connected component of the links; its label is the smallest id of its cells: the smallest index of its points.
+ *   6. record (gndt_scan_cluster): label; cells; off_surface / unmapped, the cluster's points by class (points = their sum: the novel
+ *      points of its cells); the bounds of its cells' signed indices; sum_x / _y / _z, each the sum over its points of
+ *      llrint((double)q * 1024.0) (round to nearest even; integer, so exact in any order: centroid = sum / points / 1024); z_lo / z_hi,
+ *      the least and greatest q_z of its points (compared through the order-preserving integer image of the float: -0 below +0).
+ * Outputs: clusters[] holds the clusters with at least min_cluster_points points and min_cluster_cells cells (0 = 1 for both) in
+ * ascending label, the first cluster_cap of them (nothing is written behind those); counts[0] is how many there are — it may exceed
+ * cluster_cap (cluster_cap 0 with clusters NULL only counts) — counts[1] the novel points, counts[2] the novel cells, counts[3] the
+ * clusters of any size.  point_class[i] (optional) is the class of step 2; point_label[i] (optional) the label of the point's cluster,
+ * GNDT_NO_ROW for a point that is not novel or whose cell has fewer than min_points; the cluster-size filters do not filter labels.
+ * Order and lifetime are scan scoring's and the frontiers': the call first finishes what gndt_sync finishes, builds or reuses the map's
+ * column index and enqueues its kernels on `hip_stream` (NULL = the handle's stream), not awaited; gndt_segment_scan is synchronous.  The
+ * map is not modified.  Work memory belongs to the handle and grows; its size is a function of n alone, so nothing waits for the host:
+ * a table of the smallest power of two >= max(2 n, 1024) slots of 16 bytes for the cells (n cells in n points stay at or below half
+ * load) and 17 bytes a point, 81 bytes a point at the most.  n == 0 writes four zero counts.  A sharded map answers from the rows this
+ * rank holds.  There is no CPU path.
+ * GNDT_ERR_INVALID: a null handle, params or counts, null points with n > 0, n >= 2^32, a stride other than 12 / 16, an unknown
+ * neighbourhood or connectivity, min_count of 1 or 2 or below the handle's min_points, a negative or non-finite cov_rel, cov_floor or
+ * novel_d2, a `classes` bit other than OFF_SURFACE's and UNMAPPED's, a non-zero reserved word, clusters NULL with cluster_cap > 0 or the
+ * reverse, a device pointer not aligned as its type is, no finished build, a stream under hipGraph capture (the call is not recorded).
+ * GNDT_ERR_CAPACITY: n > 2^30 (the cell table would pass 2^31 slots). */
+enum { GNDT_SEG_UNKEYED = 0, GNDT_SEG_EXPLAINED = 1, GNDT_SEG_OFF_SURFACE = 2, GNDT_SEG_UNMAPPED = 3 };
+typedef struct gndt_segment_params {
+    int32_t  neighbourhood;        /* GNDT_SCORE_DIRECT1 / GNDT_SCORE_DIRECT7                              */
+    int32_t  min_count;            /* 0 = max(min_points of the handle, 3)                                 */
+    float    cov_rel;              /* 0 = 0.01                                                             */
+    float    cov_floor;            /* 0 = 1e-6 (m^2)                                                       */
+    float    novel_d2;             /* 0 = 11.345                                                           */
+    uint32_t classes;              /* mask of 1u << class; 0 = OFF_SURFACE | UNMAPPED                      */
+    uint32_t min_points;           /* novel points that make a cell novel; 0 = 1                           */
+    uint32_t connectivity;         /* 26 or 6; 0 = 26                                                      */
+    uint32_t min_cluster_points;   /* clusters with fewer points are left out of the list; 0 = 1           */
+    uint32_t min_cluster_cells;    /* ... or with fewer cells; 0 = 1                                       */
+    uint32_t reserved[2];          /* 0 */
+} gndt_segment_params;             /* 48 bytes */
+typedef struct gndt_scan_cluster { /* 72 bytes */
+    uint32_t label, cells, off_surface, unmapped;
+    int32_t  sx_min, sx_max, sy_min, sy_max, sz_min, sz_max;
+    int64_t  sum_x, sum_y, sum_z;
+    float    z_lo, z_hi;
+} gndt_scan_cluster;
+/* Device points, pose ([12] doubles or NULL), per-point outputs ([n] each, either may be NULL), clusters ([cluster_cap]), counts ([4]). */
+int gndt_segment_scan_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* pose_dev,
+                             const gndt_segment_params* params, uint8_t* point_class_dev, uint32_t* point_label_dev,
+                             gndt_scan_cluster* clusters_dev, uint32_t cluster_cap, uint32_t* counts_dev /* [4] */, void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; synchronous. */
+int gndt_segment_scan(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_bytes, const double* pose_host,
+                      const gndt_segment_params* params, uint8_t* point_class_host, uint32_t* point_label_host,
+                      gndt_scan_cluster* clusters_host, uint32_t cluster_cap, uint32_t* counts_host);
+
 /* ---- scan score derivatives: the score of a pose with its gradient and Hessian, for K poses ------------------------------------
  * What a registration step needs of "scan scoring": score, gradient g (6) and full Hessian H (6 x 6, not the Gauss-Newton part only)
  * of the score with respect to a pose perturbation.  No optimiser here either (grid_ndt_amd/registration.py drives one from Python).
