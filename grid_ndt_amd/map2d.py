@@ -520,6 +520,7 @@ class TwoDmap:
     DEBUG_BLOCKED_MIN_POINTS = 10   # points from which a build may take blocked buckets: 65 536 .. 1 048 576 (the default; tests lower it)
     DEBUG_COLUMN_DEST = 11          # blocked builds with the two-kernel tail: 1 (the default) orders by the column table, 0 by the staged nodes
     DEBUG_PLACE_EMIT_WORDS = 12     # bitmap words up to which ordering and emit are one kernel: 0 .. 2^24 (16 384 by default; 0: always two)
+    DEBUG_OBSTACLE_TALLY = 13       # 1: the obstacle field's marking pass keeps the tallies of gndt_debug_obstacle_marks (0 by default)
 
     @staticmethod
     def set_debug_option(option, value):
@@ -906,6 +907,100 @@ class TwoDmap:
         vec = mean[near.long().clamp(min=0)] - mean
         vec[none] = float("nan")
         return vec
+
+    # ---- obstacle field (gndt_obstacle_field*: hops to the slopes a list of boxes stands on, for walk_paths / shortcut_routes) ----
+    def obstacle_field(self, boxes, robot=None, inflate=0, max_hops=8, levels_above=None, levels_below=0, base=None, max_columns=0,
+                       obstacle=True, stream=None, host=False):
+        """How far every slope is from the nearest slope a transient obstacle stands on (include/gndt.h "obstacle field" defines every
+        word).  boxes: [B, 6] int32 signed cell indices (sx_min, sx_max, sy_min, sy_max, sz_min, sz_max; index_boxes() makes them from
+        world boxes), numpy or torch — or the dict segment_scan() returned for a device scan: its records and counts[0] are then read
+        where they lie, nothing comes back to the host in between.  A box covers the slopes of the columns within `inflate` columns
+        of it whose level lies within levels_above levels under / levels_below over the box (levels_above=None: ceil(2 radius /
+        zLen), the robot's body); steps are clearance()'s for `robot`.  base: a clearance()'s `hops` (or its dict) to minimise with.
+        max_columns: the budget of the boxes' windows (0 = 2^24), boxes beyond it are dropped and counted.  Returns a dict with, per
+        row of export(), `hops` (int32, -1 = CLEARANCE_BEYOND; what walk_paths(hops=...) takes) and, with obstacle=True, `obstacle`
+        (int32: the least box index that many steps away, -1 = none; the base plays no part), and `counts` ([8]: covered slopes,
+        slopes with finite obstacle hops, the largest of those, boxes, boxes covering a slope, slopes in reach, dropped boxes, 0).
+        Torch tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited, for torch boxes
+        or a segment_scan() dict; numpy arrays through gndt_obstacle_field for numpy boxes or host=True."""
+        from ._lib import ObstacleParams
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+        rb = None
+        if robot is not None:
+            d.update(robot)
+            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        if levels_above is None:
+            levels_above = int(np.ceil(2.0 * float(d["radius"]) / self.zLen))
+        prm = ObstacleParams(int(inflate), int(max_hops), int(levels_above), int(levels_below), int(max_columns))
+        if isinstance(base, dict):
+            base = base["hops"]
+        n = int(self.sync()[0])
+        room = max(n, 1)
+        if base is not None and int(base.shape[0]) != n:
+            raise ValueError(f"base has {int(base.shape[0])} entries, the map {n} rows: a clearance field of another map")
+        to_np = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
+        count_dev = None
+        if isinstance(boxes, dict):                        # segment_scan()'s answer
+            if isinstance(boxes["label"], np.ndarray) or host:
+                six = np.stack([to_np(boxes[k]) for k in ("sx_min", "sx_max", "sy_min", "sy_max", "sz_min", "sz_max")], 1)
+                boxes = six[:min(int(to_np(boxes["counts"])[0]), len(six))]
+            else:                                          # on the device: the records where they lie, cut by counts[0] there
+                boxes, count_dev = boxes["sx_min"], boxes["counts"]
+        on_dev = hasattr(boxes, "is_cuda") and boxes.is_cuda and not host
+        if count_dev is not None:
+            keep, nb, stride = boxes, int(boxes.shape[0]), 4 * int(boxes.stride(0)) if boxes.shape[0] else 72
+        elif on_dev:
+            import torch
+            keep = boxes.to(torch.int32).contiguous().reshape(-1, 6)
+            nb, stride = int(keep.shape[0]), 24
+        else:
+            keep = np.ascontiguousarray(to_np(boxes), dtype=np.int32).reshape(-1, 6)
+            nb, stride = int(keep.shape[0]), 24
+        out = {}
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                out["hops"] = torch.empty(room, dtype=torch.int32, device=keep.device)
+                if obstacle:
+                    out["obstacle"] = torch.empty(room, dtype=torch.int32, device=keep.device)
+                out["counts"] = torch.zeros(8, dtype=torch.int32, device=keep.device)
+                bs = None if base is None else torch.as_tensor(base.view(np.int32) if isinstance(base, np.ndarray) else base, device=keep.device).contiguous()
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_obstacle_field_device(self._h, rb, p(keep), nb, stride, p(count_dev), C.byref(prm), p(bs), p(out["hops"]),
+                                                           p(out.get("obstacle")), p(out["counts"]), _stream_ptr(stream)))
+        else:
+            out["hops"] = np.empty(room, np.int32)
+            if obstacle:
+                out["obstacle"] = np.empty(room, np.int32)
+            out["counts"] = np.zeros(8, np.int32)
+            bs = None if base is None else np.ascontiguousarray(to_np(base)).view(np.uint32)
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_obstacle_field(self._h, rb, p(keep), nb, stride, C.byref(prm), p(bs), p(out["hops"]), p(out.get("obstacle")),
+                                                    p(out["counts"])))
+        for k in ("hops", "obstacle"):
+            if k in out:
+                out[k] = out[k][:n]
+        return out
+
+    def index_boxes(self, lo, hi):
+        """World boxes (lo, hi: [B, 3] corners, lo <= hi) -> [B, 6] int32 index boxes (sx_min, sx_max, sy_min, sy_max, sz_min, sz_max)
+        for obstacle_field(), each corner keyed as the map keys a point (transMortonXYZ's arithmetic).  A corner without a key (not
+        finite, or beyond the key range) gives a void box (1, 0, 1, 0, 1, 0).  Host arithmetic; numpy out."""
+        lo = np.asarray(lo.cpu() if hasattr(lo, "cpu") else lo, np.float32).reshape(-1, 3)
+        hi = np.asarray(hi.cpu() if hasattr(hi, "cpu") else hi, np.float32).reshape(-1, 3)
+        assert lo.shape == hi.shape
+        out = np.empty((len(lo), 6), np.int32)
+        for b in range(len(lo)):
+            ka, kb = (trans_morton_xyz(self.cloudFirst, self.gridLen, self.zLen, c) if np.isfinite(c).all() else (1,) for c in (lo[b], hi[b]))
+            if ka[0] or kb[0]:
+                out[b] = (1, 0, 1, 0, 1, 0)
+                continue
+            # the key's quadrant letter carries the signs of the two magnitudes: A (+,+)  B (+,-)  C (-,+)  D (-,-)
+            (ax, ay, az), (bx, by, bz) = ((k[2] if k[1][0] in "AB" else -k[2], k[3] if k[1][0] in "AC" else -k[3], k[4]) for k in (ka, kb))
+            out[b] = (ax, bx, ay, by, az, bz)
+        return out
 
     # ---- path walks (gndt_walk_paths*: candidate polylines driven over the map's slopes under the flood's gates) ----
     WALK_STATUS = {0: "done", 1: "no_start", 2: "blocked", 3: "left_map", 4: "overhead", 5: "too_close", 6: "limit"}

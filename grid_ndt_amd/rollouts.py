@@ -1,7 +1,9 @@
 """Candidate trajectories for TwoDmap.walk_paths and the choice among the walked ones: the two ends of a local planner's loop.
 
+    seg = m.segment_scan(frame, max_clusters=64)             # what in this frame is not in the map: a pallet, a person, a cart
+    field = m.obstacle_field(seg, base=clearance)            # hops to them for every slope, minimised with the map's own barriers
     paths = rollouts.arcs(pose, v, omegas, dt, T)            # a DWA fan from the robot's pose
-    info = m.walk_paths(paths)                               # driven over the map on the device
+    info = m.walk_paths(paths, hops=field, min_hops=2)       # driven over the map on the device, stopped where a path comes too close
     best = rollouts.choose(info, h[info["end_row"]])         # h: the cost map of the last computeCost, per row
     stance = m.footprints_along(paths[info["status"] == 0], 0.3, 0.2)   # for a vehicle: the footprint along the arcs that survive
 

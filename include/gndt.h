@@ -1118,6 +1118,66 @@ int gndt_segment_scan(gndt_handle* h, const void* xyz_host, size_t n, size_t str
                       const gndt_segment_params* params, uint8_t* point_class_host, uint32_t* point_label_host,
                       gndt_scan_cluster* clusters_host, uint32_t cluster_cap, uint32_t* counts_host);
 
+/* ---- obstacle field: hops to transient obstacles for every slope ----------------------------------------------------------------
+ * What gndt_walk_paths* and gndt_shortcut_routes* take as `hops` when the barrier is not in the map: a list of boxes of signed cell
+ * indices — the clusters gndt_segment_scan* has just found, a keep-out zone, a virtual wall, another robot's announced footprint —
+ * turned into "0 on the slopes a box stands on, 1, 2, ... on the slopes that many steps away", optionally already minimised with a
+ * gndt_clearance* field.  The map is not changed: next frame the pallet has moved on and so has the field.  This is a DEFINITION:
+ * only the flood's three gates are floating point (the clearance field's steps), everything else is integer arithmetic, so the answer
+ * is exact and does not depend on the order threads work in.  lin(s) = s > 0 ? s - 1 : s; all sums are taken in 64 bits.
+ *   1. boxes      box b is six int32 sx_min, sx_max, sy_min, sy_max, sz_min, sz_max read at boxes + b * box_stride_bytes (a multiple
+ *                 of 4, at least 24; the pointer 4-aligned): &clusters[0].sx_min with stride sizeof(gndt_scan_cluster) reads
+ *                 segmentation's records where they lie.  B = n_boxes, with n_boxes_dev min(*n_boxes_dev, n_boxes) read on the device
+ *                 (segmentation's counts[0] may exceed its list's capacity).  A box with min > max on any axis is VOID.
+ *   2. window     K = inflate + max_hops.  On x the window of a box that is not void is the set of indices that exist (non-zero,
+ *                 |s| <= 65535) with lin in [lin(sx_min) - K, lin(sx_max) + K]; the same on y; w_b is the product of the two counts
+ *                 (it may be 0) and W_b the inclusive prefix sum of w over the boxes that are not void, in index order.  Box b is
+ *                 ADMITTED when it is not void and W_b <= max_columns; every other box that is not void is DROPPED: it covers
+ *                 nothing and is counted — the caller reads the count and splits the box or raises the budget.
+ *   3. covered    a row q with GNDT_FLAG_SLOPE is covered by an admitted box b when lin(sx_min) - inflate <= lin(sx_q) <=
+ *                 lin(sx_max) + inflate, the same on y, lin(sz_min) <= lin(sz_q) + levels_above and lin(sz_max) >= lin(sz_q) -
+ *                 levels_below (the robot's body in levels: an obstacle on a bridge does not block the ground under it).
+ *   4. in reach   a slope whose column lies in an admitted box's window (z plays no part).
+ *   5. field      steps are the clearance field's (a directed graph).  hops(q) is the length of the shortest walk from q along steps
+ *                 to a covered slope, 0 on a covered slope, GNDT_CLEARANCE_BEYOND beyond max_hops (0 = 8; above 1024 is refused) and
+ *                 for a row without a slope.  obstacle(q) is the smallest box index among the boxes covering the covered slopes
+ *                 exactly hops(q) steps from q, GNDT_NO_ROW where hops is BEYOND: the clearance key hops << 32 | index under an
+ *                 unsigned minimum.  A walk of at most max_hops steps to a slope covered by b never leaves b's window (a step moves
+ *                 one column along one axis, over the missing index 0 too), so the search visits the rows in reach only.
+ *   6. outputs    hops[q] = min(base_hops[q], hops(q)) with a base (base_hops_dev == hops_dev is allowed), obstacle[q] ignores the
+ *                 base; both have num_nodes entries, every entry is written; either may be NULL, not both.  counts[8]: the covered
+ *                 slopes, the slopes with finite obstacle hops, the largest finite obstacle hops, B, the admitted boxes that cover at
+ *                 least one slope, the slopes in reach, the dropped boxes, 0.
+ * B == 0 or a map without rows writes the base (or BEYOND / NO_ROW) and counts that are zero except counts[3].  `robot` NULL = the
+ * flood's defaults.  Order and lifetime are the clearance call's: the call first finishes what gndt_sync finishes, builds or reuses the
+ * map's column index and enqueues its kernels on `hip_stream` (NULL = the handle's stream), not awaited — B, the prefix sums and the
+ * list of rows in reach stay on the device, one launch per hop, of which those behind the last hop that changed anything return at
+ * once.  Only the fill of the two outputs passes over the map; the marking pass takes one thread per column of the admitted windows
+ * (at most max_columns: 0 = 2^24, above 2^28 is refused), the steps and the hops the rows of the columns in reach.
+ * gndt_obstacle_field is synchronous.  Neither the map nor the cost map is modified and no cost map is needed.  Work memory belongs to
+ * the handle and grows: room for 53 bytes per row of a column in reach, reserved for every row of the map (a window may hold them
+ * all); 16 bytes a map row of marks that are stamped per call, so never cleared; 12 bytes a box.  There is no CPU path.  A sharded map
+ * answers from the rows this rank holds.
+ * GNDT_ERR_INVALID: a null handle, params, boxes (with n_boxes > 0) or counts, hops and obstacle both NULL, a stride below 24 or not a
+ * multiple of 4, boxes or a device pointer not aligned to 4 bytes, n_boxes > 2^20, inflate > 1024, max_hops > 1024, max_columns >
+ * 2^28, a non-zero reserved word, no finished build, a stream under hipGraph capture (the call is not recorded). */
+typedef struct gndt_obstacle_params {
+    uint32_t inflate;        /* columns added round a box on x and y (Chebyshev, in lin space); above 1024 is refused */
+    uint32_t max_hops;       /* 0 = 8; above 1024 is refused */
+    uint32_t levels_above;   /* the robot's body: levels above a slope's own that an obstacle blocks it from */
+    uint32_t levels_below;   /* ... and below */
+    uint64_t max_columns;    /* budget for the windows' columns of one call; 0 = 2^24; above 2^28 is refused */
+    uint32_t reserved[2];    /* 0 */
+} gndt_obstacle_params;      /* 32 bytes */
+/* Device boxes, n_boxes_dev (one uint32 or NULL), base_hops_dev ([num_nodes] or NULL), hops_dev, obstacle_dev ([num_nodes], either or NULL), counts_dev ([8]). */
+int gndt_obstacle_field_device(gndt_handle* h, const gndt_robot* robot, const void* boxes_dev, uint32_t n_boxes, size_t box_stride_bytes,
+                               const uint32_t* n_boxes_dev, const gndt_obstacle_params* params, const uint32_t* base_hops_dev,
+                               uint32_t* hops_dev, uint32_t* obstacle_dev, uint32_t* counts_dev /* [8] */, void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; synchronous. */
+int gndt_obstacle_field(gndt_handle* h, const gndt_robot* robot, const void* boxes_host, uint32_t n_boxes, size_t box_stride_bytes,
+                        const gndt_obstacle_params* params, const uint32_t* base_hops_host, uint32_t* hops_host, uint32_t* obstacle_host,
+                        uint32_t* counts_host);
+
 /* ---- scan score derivatives: the score of a pose with its gradient and Hessian, for K poses ------------------------------------
  * What a registration step needs of "scan scoring": score, gradient g (6) and full Hessian H (6 x 6, not the Gauss-Newton part only)
  * of the score with respect to a pose perturbation.  No optimiser here either (grid_ndt_amd/registration.py drives one from Python).
@@ -1449,6 +1509,8 @@ int gndt_debug_enable_stamps(int on);
  *                                 (3.40e38 as a float) and is none of the library's sentinels (tests run both)      default 0xA5
  *   GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP value == 0: gndt_clearance* launch every hop on its own, the one-workgroup kernel that holds a
  *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1
+ *   GNDT_DEBUG_OBSTACLE_TALLY     value != 0: the marking pass of gndt_obstacle_field* keeps the tallies gndt_debug_obstacle_marks
+ *                                 reads (a few atomics a wavefront)                                                    default 0
  *   GNDT_DEBUG_WALK_STEP_TABLE    value == 1: gndt_walk_paths* first make a per-side steps table of the whole map (the clearance
  *                                 field's first pass) and read every step of every walk from it; 0: a walk finds its steps itself,
  *                                 gates included (tests run the walks both ways); 2: the table for a map of up to 2048 rows per
@@ -1474,6 +1536,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_BLOCKED_MIN_POINTS 10
 #define GNDT_DEBUG_COLUMN_DEST 11
 #define GNDT_DEBUG_PLACE_EMIT_WORDS 12
+#define GNDT_DEBUG_OBSTACLE_TALLY 13
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
@@ -1493,6 +1556,12 @@ int gndt_debug_second_pass_buckets(gndt_handle* h, uint64_t* buckets);
  * and the level padding included), out[4..6] = log2 of a block's extent in columns along x, columns along y and levels (they sum to 9),
  * out[7..8] = blocks along x and y, out[9] = buckets (out[7] * out[8]).  out[1..9] mean something only while out[0] == 1. */
 int gndt_debug_block_layout(gndt_handle* h, int32_t out[10]);
+/* What the marking pass of the handle's last gndt_obstacle_field* call did (tools/measure_obstacle.py); waits for the handle's last
+ * stream.  out[0] = columns of the admitted windows (one thread each), out[1] = rows of the worklist (every row of a column in reach),
+ * out[2] = index probes that found a column, out[3] = columns put on the worklist (one atomic pair each), out[4] = 64-bit minima sent for
+ * covered slopes (a thread that reads a cover word already at or below its own sends none).  out[2..4] are kept only while
+ * GNDT_DEBUG_OBSTACLE_TALLY is set.  Zeros before the first call. */
+int gndt_debug_obstacle_marks(gndt_handle* h, uint64_t out[5]);
 /* Tests of the sharded builds: the next allocation at `site` on this handle fails once, as if the device were out of memory —
  * 1: the receive buffer of gndt_build_owned_device's exchange, 2: its column-pair buffers, 3: the buffers of
  * gndt_gather_owned_map_device, 4: the fixed-size message buffers of a communicator's first owned build (0: none).  Every rank
