@@ -27,8 +27,8 @@ def lib_path(variant=None):
 
 LIB_PATH = lib_path(VARIANT)   # what lib() loads in this process
 SOURCES = ["gndt_api_core.hip", "gndt_api_table.hip", "gndt_api_build.hip", "gndt_api_dist.hip", "gndt_api_cost.hip", "gndt_api_query.hip",
-           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
-HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", os.path.join(_ROOT, "include", "gndt.h")]
+           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_route_field.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
+HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_route_field.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", os.path.join(_ROOT, "include", "gndt.h")]
 
 GNDT_OK = 0
 ERR_NAMES = {0: "OK", 1: "INVALID", 2: "NO_DEVICE", 3: "HIP", 4: "KEY_RANGE", 5: "CAPACITY", 6: "NOMEM", 7: "PEER"}
@@ -132,6 +132,15 @@ class ClearanceParams(C.Structure):
 class ObstacleParams(C.Structure):
     _fields_ = [("inflate", C.c_uint32), ("max_hops", C.c_uint32), ("levels_above", C.c_uint32), ("levels_below", C.c_uint32),
                 ("max_columns", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
+class RouteFieldParams(C.Structure):
+    _fields_ = [("checks", C.c_uint32), ("min_hops", C.c_uint32), ("soft_hops", C.c_uint32), ("soft_weight", C.c_float),
+                ("max_cost", C.c_float), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class DescendParams(C.Structure):
+    _fields_ = [("start_mode", C.c_int32), ("max_steps", C.c_uint32), ("reserved", C.c_uint32 * 6)]
 
 
 class WalkParams(C.Structure):
@@ -367,6 +376,10 @@ def lib():
     L.gndt_clearance.argtypes = [H, C.POINTER(Robot), C.POINTER(ClearanceParams), vp, vp, vp, vp]
     L.gndt_obstacle_field_device.argtypes = [H, C.POINTER(Robot), vp, C.c_uint32, sz, vp, C.POINTER(ObstacleParams), vp, vp, vp, vp, vp]
     L.gndt_obstacle_field.argtypes = [H, C.POINTER(Robot), vp, C.c_uint32, sz, C.POINTER(ObstacleParams), vp, vp, vp, vp]
+    L.gndt_route_field_device.argtypes = [H, C.POINTER(Robot), C.POINTER(RouteFieldParams), vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    L.gndt_route_field.argtypes = [H, C.POINTER(Robot), C.POINTER(RouteFieldParams), vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.gndt_descend_routes_device.argtypes = [H, vp, sz, sz, C.POINTER(DescendParams), vp, vp, vp, C.c_uint32, vp, vp]
+    L.gndt_descend_routes.argtypes = [H, vp, sz, sz, C.POINTER(DescendParams), vp, vp, vp, C.c_uint32, vp]
     L.gndt_walk_paths_device.argtypes = [H, vp, sz, sz, sz, C.POINTER(Robot), C.POINTER(WalkParams), vp, vp, C.c_uint32, vp, vp]
     L.gndt_walk_paths.argtypes = [H, vp, sz, sz, sz, C.POINTER(Robot), C.POINTER(WalkParams), vp, vp, C.c_uint32, vp]
     L.gndt_shortcut_routes_device.argtypes = [H, vp, sz, C.c_uint32, vp, sz, C.POINTER(Robot), C.POINTER(ShortcutParams), vp, vp, C.c_uint32, vp,
@@ -452,7 +465,7 @@ def lib():
                  "gndt_export", "gndt_stats_export_device", "gndt_stats_merge_device", "gndt_trans_morton_xyz",
                  "gndt_compute_cost", "gndt_cost_export_device", "gndt_cost_export", "gndt_query_device", "gndt_query",
                  "gndt_crop_device", "gndt_crop", "gndt_crop_box_from_world", "gndt_raster_shape", "gndt_raster_device", "gndt_raster", "gndt_clear_rays_device", "gndt_clear_rays",
-                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_segment_scan_device", "gndt_segment_scan", "gndt_clearance_device", "gndt_clearance", "gndt_obstacle_field_device", "gndt_obstacle_field", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
+                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_segment_scan_device", "gndt_segment_scan", "gndt_clearance_device", "gndt_clearance", "gndt_obstacle_field_device", "gndt_obstacle_field", "gndt_route_field_device", "gndt_route_field", "gndt_descend_routes_device", "gndt_descend_routes", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
                  "gndt_shard_stats_device", "gndt_finalize_stats_device",
                  "gndt_pcd_read", "gndt_pack_points_device", "gndt_build_cloud", "gndt_get_origin",
                  "gndt_count_morton", "gndt_morton_to_xy", "gndt_device_info", "gndt_set_profiling", "gndt_get_phase_times"):

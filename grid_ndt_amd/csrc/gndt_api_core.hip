@@ -28,6 +28,7 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_COST_ONE_WORKGROUP: t.cost_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP: t.clearance_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_OBSTACLE_TALLY: t.obstacle_tally = value != 0.0; return GNDT_OK;
+        case GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP: t.route_field_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_WALK_STEP_TABLE: if (!(value == 0.0 || value == 1.0 || value == 2.0)) return GNDT_ERR_INVALID; t.walk_step_table = (int)value; return GNDT_OK;
         case GNDT_DEBUG_QUERY_ILP: if (!(value == 1.0 || value == 2.0 || value == 4.0)) return GNDT_ERR_INVALID; t.query_ilp = (int)value; return GNDT_OK;
         case GNDT_DEBUG_CLEAR_EXTENT: if (!(value == 0.0 || value == 1.0)) return GNDT_ERR_INVALID; t.clear_extent = value != 0.0; return GNDT_OK;
@@ -383,6 +384,7 @@ void gndt_destroy(gndt_handle* h) {
     free_clearance(h);
     free_walk(h);
     free_obstacle(h);
+    free_route_field(h);
     for (const RowArray& a : row_arrays(h->out))
         if (*a.p) (void)hipFree(*a.p);
     void* ptrs[] = {h->st_key, h->st_sums, h->st_count, h->st_first, h->stage, h->d_cnt, h->packed, h->d_nvalid, h->index.buf, h->io};

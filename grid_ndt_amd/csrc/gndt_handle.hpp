@@ -14,6 +14,7 @@
 //   gndt_api_frontier.hip  frontier extraction: the slopes where the map ends, clustered
 //   gndt_api_segment.hip   scan segmentation: the points of a scan the map does not explain, clustered
 //   gndt_api_clearance.hip  clearance field: per slope the steps to the nearest barrier, and where it is
+//   gndt_api_route_field.hip route field: per slope the least cost to a set of goals and the step to take, routes by descent
 //   gndt_api_obstacle.hip   obstacle field: per slope the steps to the nearest slope a box of the caller's list stands on
 //   gndt_api_walk.hip       path walks: candidate polylines driven over the map's slopes under the flood's gates
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
@@ -285,6 +286,12 @@ struct gndt_handle {
         void* marks = nullptr;  uint64_t marks_bytes = 0, marks_rows = 0;  uint32_t stamp = 0;
         void* scratch = nullptr;  uint64_t bytes = 0;
     } obstacle;
+    // route field (gndt_route_field.hpp): per row the first step of its four sides with its cost (32 B), the rest of their steps (32 B),
+    // the key the sweeps relax in place (8 B), the weight of entering it (4 B) and its "more" bits (1 B), and one flag word per sweep;
+    // grown on demand
+    struct RouteField {
+        void* scratch = nullptr;  uint64_t bytes = 0;
+    } route_field;
     // path walks (gndt_walk.hpp), the table variant only: per row the steps table of its four sides (32 B) and what else
     // k_clearance_steps writes (a round-0 key, 8 B, and the tall-column bits, 1 B); made again by every call that takes it
     struct Walk {
@@ -437,6 +444,7 @@ struct Tuning {
     int plan_lds_entries = 1024; // GNDT_DEBUG_PLAN_LDS_ENTRIES    entries of a planning query's open queue kept in LDS (64 .. 1024; the rest spills)
     bool clearance_one_workgroup = true;   // GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP   0: every round of the clearance field its own launch
     bool obstacle_tally = false;           // GNDT_DEBUG_OBSTACLE_TALLY            1: the obstacle field's marking pass keeps the tallies gndt_debug_obstacle_marks reads
+    bool route_field_one_workgroup = true; // GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 0: every sweep of the route field its own launch
     int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE           gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
@@ -705,5 +713,7 @@ void free_clearance(gndt_handle* h);
 void free_walk(gndt_handle* h);
 // ---- gndt_api_obstacle.hip ----
 void free_obstacle(gndt_handle* h);
+// ---- gndt_api_route_field.hip ----
+void free_route_field(gndt_handle* h);
 
 }  // namespace gndt_host

@@ -520,6 +520,7 @@ class TwoDmap:
     DEBUG_BLOCKED_MIN_POINTS = 10   # points from which a build may take blocked buckets: 65 536 .. 1 048 576 (the default; tests lower it)
     DEBUG_COLUMN_DEST = 11          # blocked builds with the two-kernel tail: 1 (the default) orders by the column table, 0 by the staged nodes
     DEBUG_PLACE_EMIT_WORDS = 12     # bitmap words up to which ordering and emit are one kernel: 0 .. 2^24 (16 384 by default; 0: always two)
+    DEBUG_ROUTE_FIELD_ONE_WORKGROUP = 14   # 0: every sweep of the route field its own launch (1 by default)
     DEBUG_OBSTACLE_TALLY = 13       # 1: the obstacle field's marking pass keeps the tallies of gndt_debug_obstacle_marks (0 by default)
 
     @staticmethod
@@ -1073,6 +1074,135 @@ class TwoDmap:
         if row_cap:
             out["rows"] = out_rows
         return out
+
+    # ---- route field (gndt_route_field* / gndt_descend_routes*: cost-to-go to a set of goals that keeps clear of obstacles) ----
+    def _robot_ref(self, robot):
+        if robot is None:
+            return None
+        d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
+        d.update(robot)
+        return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+
+    def route_field(self, goals, goal_costs=None, robot=None, hops=None, min_hops=0, soft_hops=0, soft_weight=0.0, overhead=False, max_cost=0.0,
+                    max_rounds=0, next=True, stream=None, host=False):
+        """For every slope the least cost to reach any of `goals` along the steps a robot can take, and the slope to step to next
+        (include/gndt.h "route field" defines every word).  goals: [G] rows of export() or [G, 3] points (looked up with query mode
+        "nearest_slope"; a point without a slope is an ignored goal); goal_costs: [G] float32 or None = zeros.  hops (what clearance()
+        or obstacle_field() returned, or its "hops") with min_hops forbids entering a slope nearer than that to a barrier, with
+        soft_hops / soft_weight makes slopes inside that zone cost 1 + soft_weight * (soft_hops - hops) times as much to enter;
+        overhead=True forbids slopes under a surface too low for `robot`.  max_cost > 0 cuts the field there; max_rounds bounds the
+        sweeps (0 = 1024) — on a map of more than 20 448 rows every one of them is a launch of about 3 us whether it still has work or
+        not, so a caller who knows how deep the map is says so.  Returns a dict: `cost` (float32 per row of export(), FLT_MAX where no route exists), `next` (int32, -1 =
+        NO_ROW; only with next=True), `counts` ([8]: accepted goals, ignored goals, slopes with a finite cost, the bits of the largest,
+        converged, sweeps that changed something, 0, 0) and `converged` (counts[4], a view: reading it waits for the stream).  Torch
+        tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited; or numpy arrays through
+        gndt_route_field with host=True."""
+        from ._lib import RouteFieldParams
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if isinstance(hops, dict):
+            hops = hops["hops"]
+        n = int(self.sync()[0])
+        if hops is not None and int(hops.shape[0]) != n:
+            raise ValueError(f"hops has {int(hops.shape[0])} entries, the map {n} rows: a field of another map")
+        prm = RouteFieldParams(1 if overhead else 0, int(min_hops), int(soft_hops), float(soft_weight), float(max_cost), int(max_rounds))
+        rb = self._robot_ref(robot)
+        room = max(n, 1)           # (an empty map still names its outputs: a NULL one means "not asked for")
+        if len(goals.shape) == 2:  # points -> rows
+            if goals.shape[1] not in (3, 4):
+                raise ValueError("goals must be [G] rows or [G, 3] points")
+            if host and hasattr(goals, "detach"):
+                goals = goals.detach().cpu().numpy()
+            if not host and isinstance(goals, np.ndarray):
+                import torch
+                goals = torch.as_tensor(np.ascontiguousarray(goals, np.float32), device=f"cuda:{self.device}")
+            goals = self.query(goals, "nearest_slope", stream=stream)
+        G = int(goals.shape[0])
+        if goal_costs is not None and int(goal_costs.shape[0]) != G:
+            raise ValueError("goal_costs must have one entry per goal")
+        if host:
+            as_np = lambda a, dt: None if a is None else np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).astype(dt, copy=False)
+            g = as_np(goals, np.int64).astype(np.uint32)
+            gc, hp = as_np(goal_costs, np.float32), as_np(hops, np.int64)
+            hp = None if hp is None else hp.astype(np.uint32)
+            out = {"cost": np.empty(room, np.float32), "counts": np.zeros(8, np.int32)}
+            if next:
+                out["next"] = np.empty(room, np.int32)
+            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_route_field(self._h, rb, C.byref(prm), ptr(g), G, ptr(gc), ptr(hp), ptr(out["cost"]), ptr(out.get("next")),
+                                                 ptr(out["counts"])))
+        else:
+            import torch
+            dev = f"cuda:{self.device}"
+            with _torch_stream_ctx(stream):
+                to_dev = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a).view(np.int32) if isinstance(a, np.ndarray) and
+                                                                           a.dtype == np.uint32 else a, device=dev).to(dt).contiguous()
+                g, gc, hp = to_dev(goals, torch.int32), to_dev(goal_costs, torch.float32), to_dev(hops, torch.int32)
+                out = {"cost": torch.empty(room, dtype=torch.float32, device=dev), "counts": torch.zeros(8, dtype=torch.int32, device=dev)}
+                if next:
+                    out["next"] = torch.empty(room, dtype=torch.int32, device=dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_route_field_device(self._h, rb, C.byref(prm), ptr(g), G, ptr(gc), ptr(hp), ptr(out["cost"]), ptr(out.get("next")),
+                                                        ptr(out["counts"]), _stream_ptr(stream)))
+        for k in ("cost", "next"):
+            if k in out:
+                out[k] = out[k][:n]
+        out["converged"] = out["counts"][4]
+        return out
+
+    def descend_routes(self, starts, field, start_mode="nearest_slope", route_cap=None, max_steps=0, stream=None, host=False):
+        """Routes from `starts` ([K,3] or [K,4] float32) down a route_field() of this map as it is now, by following its `next`
+        (include/gndt.h "route field").  Returns (rows, info) in plan_routes' layout, which shortcut_routes and route_waypoints take
+        as they are: rows [K, route_cap] int32, start first and goal last, -1 behind; info a dict of [K] arrays status
+        (ROUTE_STATUS), length, start_row, expansions (the steps followed), queue_peak (0), cost and h_start (the field's cost at the
+        start).  route_cap None: the map's slope count or 1024, whichever is less.  torch CUDA starts are answered on the device
+        (enqueued on `stream`, not awaited); host=True or a host array goes through gndt_descend_routes (numpy)."""
+        from ._lib import DescendParams
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        if "next" not in field:
+            raise ValueError("descend_routes needs a field with `next` (route_field(next=True))")
+        ptr, K, stride, on_dev, keep = self._as_input(starts)
+        n, _, slopes = (int(v) for v in self.sync())
+        if route_cap is None:
+            route_cap = max(min(slopes, 1024), 1)
+        route_cap = int(route_cap)
+        cost, nxt = field["cost"], field["next"]
+        if int(cost.shape[0]) != n or int(nxt.shape[0]) != n:
+            raise ValueError(f"the field has {int(cost.shape[0])} entries, the map {n} rows: a field of another map")
+        prm = DescendParams(self.WALK_START_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), int(max_steps))
+        if on_dev and host:
+            ptr, K, stride, on_dev, keep = self._as_input(keep.detach().cpu().numpy())
+        if on_dev:
+            import torch
+            with _torch_stream_ctx(stream):
+                c = torch.as_tensor(cost, device=keep.device).to(torch.float32).contiguous()
+                x = torch.as_tensor(nxt, device=keep.device).to(torch.int32).contiguous()
+                rows = torch.empty((K, route_cap), dtype=torch.int32, device=keep.device)
+                raw = torch.empty((max(K, 1), 8), dtype=torch.int32, device=keep.device)[:K]
+                if n == 0:         # (an empty map still names its field)
+                    c, x = torch.zeros(1, dtype=torch.float32, device=keep.device), torch.zeros(1, dtype=torch.int32, device=keep.device)
+            self._check(self._L.gndt_descend_routes_device(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
+                                                           C.c_void_p(c.data_ptr()), C.c_void_p(x.data_ptr()),
+                                                           C.c_void_p(rows.data_ptr() if K and route_cap else 0), route_cap if K else 0,
+                                                           C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
+            info = {"status": raw[:, 0], "length": raw[:, 1], "start_row": raw[:, 2], "expansions": raw[:, 3], "queue_peak": raw[:, 4],
+                    "cost": raw[:, 5].view(torch.float32), "h_start": raw[:, 6].view(torch.float32)}
+            return rows, info
+        as_np = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).astype(dt, copy=False)
+        c, x = as_np(cost, np.float32), as_np(nxt, np.int32)
+        if n == 0:                 # (an empty map still names its field)
+            c, x = np.zeros(1, np.float32), np.zeros(1, np.int32)
+        rows = np.empty((K, route_cap), np.int32)
+        raw = np.zeros(max(K, 1), self.ROUTE_INFO_DTYPE)
+        self._check(self._L.gndt_descend_routes(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
+                                                C.c_void_p(c.ctypes.data), C.c_void_p(x.ctypes.data),
+                                                C.c_void_p(rows.ctypes.data if K and route_cap else 0), route_cap if K else 0,
+                                                C.c_void_p(raw.ctypes.data)))
+        raw = raw[:K]
+        info = {k: raw[k] for k in ("status", "length", "expansions", "queue_peak", "cost", "h_start")}
+        info["start_row"] = raw["start_row"].view(np.int32)
+        return rows, info
 
     # ---- route shortcutting (gndt_shortcut_routes*: slope-to-slope routes string-pulled into any-angle waypoints) ----
     SHORTCUT_STATUS = {0: "ok", 1: "empty", 2: "bad_route", 3: "limit"}

@@ -1178,7 +1178,107 @@ int gndt_obstacle_field(gndt_handle* h, const gndt_robot* robot, const void* box
                         const gndt_obstacle_params* params, const uint32_t* base_hops_host, uint32_t* hops_host, uint32_t* obstacle_host,
                         uint32_t* counts_host);
 
-/* ---- scan score derivatives: the score of a pose with its gradient and Hessian, for K poses ------------------------------------
+/* ---- route field: cost-to-go to a set of goals for every slope, keeping clear of obstacles, and the routes it gives ----------------
+ * A navigation function.  What the flood's h is not: the LEAST cost to reach ANY of G goals along the steps a robot can take, never
+ * entering a slope the caller's `hops` field (a gndt_clearance* or gndt_obstacle_field* output) forbids, with the slope to step to
+ * next.  One field serves every start, any number of robots and every re-plan until the map or the obstacles change: cost[row] is a
+ * rollout's h_end, and following `next` from a start is a route in the layout gndt_plan_routes* writes and gndt_shortcut_routes*
+ * takes.  Every definition is fp32 arithmetic in a stated order under an unsigned minimum: the answer is exact and does not depend on
+ * the order threads work in.
+ *   graph         the clearance field's: the steps of slope q through side k are the rows t of that neighbour column that have
+ *                 GNDT_FLAG_SLOPE and pass the flood's gates seen from q.  Directed.  `robot` NULL = the flood's defaults.
+ *   entering      a step q -> t may be taken only if t may be entered.  A row t may NOT be entered when hops_dev != NULL and
+ *                 hops_dev[t] < min_hops (the caller vouches for hops_dev exactly as for the walks: num_nodes entries OF THIS MAP AS IT
+ *                 IS NOW), or when GNDT_WALK_CHECK_OVERHEAD is set in `checks` and the clearance field's OVERHEAD predicate holds for t.
+ *                 A slope that may not be entered still gets a field value from its own steps: a robot that finds itself inside the
+ *                 inflated zone is shown the way out, but no route passes through it.
+ *   step cost     c(q, t) = fl(TravelCost(mean q, mean t) * w(t)), fp32, never contracted; TravelCost is the flood's (fp32 differences,
+ *                 squares and root in fp64, rounded once).  w(t) = 1 without hops or when hops[t] >= soft_hops (soft_hops 0: no
+ *                 penalty), else fl(1.0f + fl(soft_weight * (float)(soft_hops - hops[t]))).  soft_weight must be finite and >= 0.
+ *   goals         G rows (uint32) with optional goal_cost[G] (fp32; NULL = zeros; -0 counts as 0).  A goal is IGNORED, and counted,
+ *                 when its row is out of range, has no slope or may not be entered, or when its cost is not finite or is negative.
+ *                 The same row given twice keeps its least cost; every accepted entry counts.
+ *   field         cost(q) is the least, over walks q -> ... -> g along steps that end on an accepted goal, of the value accumulated
+ *                 from the goal backwards: v(g) = goal_cost(g), v(p) = fl(c(p, next) + v(next)).  It is the fixed point, reached from
+ *                 above, of
+ *                     key(q) = min(seed(q), min over steps t of q that may be entered of bits(fl(c(q, t) + cost(t))) << 32 | t)
+ *                 under an unsigned 64-bit minimum, seed = bits(goal_cost) << 32 | GNDT_NO_ROW on an accepted goal and all ones
+ *                 elsewhere.  next(q) is the low word: the smallest row among the steps that give the least cost, GNDT_NO_ROW on a
+ *                 goal that nothing improves.  fl(a + c) is monotone in a, so every relaxation order reaches the same fixed point.  A
+ *                 candidate whose sum is not below FLT_MAX is discarded, and with max_cost > 0 one above max_cost (a seed is no
+ *                 candidate).  cost is FLT_MAX and next GNDT_NO_ROW where there is no walk and on rows without a slope.
+ *   sweeps        a sweep relaxes every slope at least once; one that changes nothing proves the fixed point, and the launches behind
+ *                 it return at once, as the clearance rounds do.  max_rounds bounds the sweeps of a call (0 = 1024; above 4096 is
+ *                 refused: it bounds the launches of a call, and the device is shared).  If the deepest least-cost walk has L steps,
+ *                 L + 1 sweeps always suffice.
+ *   counts[8]     0 accepted goals, 1 ignored goals, 2 slopes with a finite cost, 3 the bits of the largest finite cost, 4 converged
+ *                 (1 or 0), 5 the sweeps that changed something (diagnostic: not part of the definition), 6 and 7 zero.
+ *   not converged counts[4] == 0: the outputs are still usable, and this is all that is promised: every finite cost is >= the fixed
+ *                 point's; following `next` from any row with a finite cost reaches an accepted goal without repeating a row; the
+ *                 cost recomputed along that chain from the goal backwards is <= the stored one.
+ * cost and next have num_nodes entries and every entry is written; either may be NULL, not both.  Order, lifetime and refusals are the
+ * clearance call's: the call first finishes what gndt_sync finishes, builds or reuses the map's column index and enqueues its kernels
+ * on `hip_stream` (NULL = the handle's stream), not awaited — one launch per sweep, the keys relaxed in place; a map of up to 20 448
+ * rows takes every sweep in one launch of one workgroup, its keys in LDS (GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP).  gndt_route_field is
+ * synchronous, through the handle's scratch.  G == 0 or a map without rows writes FLT_MAX / GNDT_NO_ROW and counts that are zero but for
+ * counts[4] = 1.  The map, h and state are not modified and no cost map is needed.  Work memory (77 bytes a row: per side the first
+ * step with its cost and the rest of its steps, the key, the weight, one byte) belongs to the handle and grows with the map.  There
+ * is no CPU path.  A sharded map answers from the rows this rank holds.
+ * GNDT_ERR_INVALID: a null handle, params or counts, cost and next both NULL, null goals with G > 0, G > 2^20, an unknown check bit,
+ * soft_weight or max_cost not finite or negative, max_rounds > 4096, a non-zero reserved word, a device pointer not aligned to 4
+ * bytes, no finished build, a stream under hipGraph capture (the call is not recorded). */
+typedef struct gndt_route_field_params {
+    uint32_t checks;         /* GNDT_WALK_CHECK_* bits */
+    uint32_t min_hops;       /* with hops: a slope with fewer hops may not be entered (0: every slope may) */
+    uint32_t soft_hops;      /* with hops: a slope with fewer hops costs more to enter (0: none does) */
+    float soft_weight;       /* ... by this much per hop it lacks; finite, >= 0 */
+    float max_cost;          /* > 0: candidates above it are discarded; 0: none is */
+    uint32_t max_rounds;     /* 0 = 1024; above 4096 is refused */
+    uint32_t reserved[2];    /* 0 */
+} gndt_route_field_params;   /* 32 bytes; zeros = defaults */
+/* Device memory in and out: goals_dev [G] (uint32), goal_cost_dev [G] (fp32) or NULL, hops_dev [num_nodes] or NULL, cost_dev (fp32)
+ * and next_dev (uint32) [num_nodes], either or NULL; counts_dev [8]. */
+int gndt_route_field_device(gndt_handle* h, const gndt_robot* robot, const gndt_route_field_params* params, const uint32_t* goals_dev,
+                            uint32_t G, const float* goal_cost_dev, const uint32_t* hops_dev, float* cost_dev, uint32_t* next_dev,
+                            uint32_t* counts_dev /* [8] */, void* hip_stream);
+/* The same with host memory, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_route_field(gndt_handle* h, const gndt_robot* robot, const gndt_route_field_params* params, const uint32_t* goals_host, uint32_t G,
+                     const float* goal_cost_host, const uint32_t* hops_host, float* cost_host, uint32_t* next_host, uint32_t* counts_host);
+
+/* gndt_descend_routes*: K starts become routes by following `next` of a route field of this map as it is now (cost and next, both
+ * num_nodes entries: the caller vouches for that as for hops), in the layout gndt_plan_routes* writes: route_rows[k * route_cap ..]
+ * start first, goal last, GNDT_NO_ROW behind (a route longer than route_cap writes its first route_cap rows and the caller sees length
+ * > route_cap; route_rows may be NULL with route_cap 0), one gndt_route_info per start.  Starts are floats x, y, z at stride 12 or
+ * 16; start_mode is the walks' (0 = GNDT_WALK_START_NEAREST_SLOPE).  status:
+ *   GNDT_ROUTE_NO_START  the lookup finds no slope (length 0, start_row GNDT_NO_ROW, cost and h_start FLT_MAX);
+ *   GNDT_ROUTE_NO_ROUTE  cost[start_row] is FLT_MAX (length 0);
+ *   GNDT_ROUTE_LIMIT     the chain needs more than max_steps steps (0 = 65536; above 2^20 is refused: it bounds a lane's loop, and the
+ *                        device is shared), or meets a `next` entry that is neither GNDT_NO_ROW nor < num_nodes: no route (length 0,
+ *                        every entry GNDT_NO_ROW, cost FLT_MAX); a chain of exactly max_steps steps is FOUND;
+ *   GNDT_ROUTE_FOUND     otherwise: length counts start and goal, cost = h_start = cost[start_row].
+ * expansions is the steps followed, queue_peak 0.  The kernel reads nothing outside num_nodes entries of the two arrays.  The guard also
+ * covers the one pathology of fp32: a step cost below half an ulp of the cost-to-go is absorbed, fl(c + a) == a, and the smallest-row
+ * tie-break can then point two slopes at each other.  That needs two means a fraction of a millimetre apart in neighbouring cells at
+ * costs of metres; such a chain ends with GNDT_ROUTE_LIMIT instead of spinning.
+ * One lane a start; enqueued on `hip_stream` after what gndt_sync finishes and the column index, not awaited; info_dev must be aligned
+ * to 16 bytes (two 16-byte stores a record).  gndt_descend_routes is synchronous and takes host memory of any alignment.  K == 0
+ * returns GNDT_OK and launches nothing.  There is no CPU path.
+ * GNDT_ERR_INVALID: a null handle, params, cost, next or info, null starts with K > 0, K >= 2^31, a stride other than 12 or 16, an
+ * unknown start_mode, max_steps > 2^20, a non-zero reserved word, route_rows NULL with route_cap != 0 or the reverse, info_dev not
+ * aligned to 16 bytes or another device pointer not to 4, no finished build, a stream under hipGraph capture. */
+typedef struct gndt_descend_params {
+    int32_t start_mode;      /* 0 = GNDT_WALK_START_NEAREST_SLOPE, or GNDT_WALK_START_NODE */
+    uint32_t max_steps;      /* 0 = 65536 */
+    uint32_t reserved[6];    /* 0 */
+} gndt_descend_params;       /* 32 bytes; zeros = defaults */
+int gndt_descend_routes_device(gndt_handle* h, const void* starts_dev, size_t K, size_t stride_bytes, const gndt_descend_params* params,
+                               const float* cost_dev, const uint32_t* next_dev, uint32_t* route_rows_dev, uint32_t route_cap,
+                               gndt_route_info* info_dev, void* hip_stream);
+int gndt_descend_routes(gndt_handle* h, const void* starts_host, size_t K, size_t stride_bytes, const gndt_descend_params* params,
+                        const float* cost_host, const uint32_t* next_host, uint32_t* route_rows_host, uint32_t route_cap,
+                        gndt_route_info* info_host);
+
+/* ---- scan score derivatives:the score of a pose with its gradient and Hessian, for K poses ------------------------------------
  * What a registration step needs of "scan scoring": score, gradient g (6) and full Hessian H (6 x 6, not the Gauss-Newton part only)
  * of the score with respect to a pose perturbation.  No optimiser here either (grid_ndt_amd/registration.py drives one from Python).
  * Steps 1 to 4 of "scan scoring" hold unchanged — the transform q = fl32(T p), the key, the candidates, min_count, cov_rel, cov_floor,
@@ -1523,7 +1623,9 @@ int gndt_debug_enable_stamps(int on);
  *                                 table; same map either way (tests build both and compare)                          default 1
  *   GNDT_DEBUG_PLACE_EMIT_WORDS   PARTITION builds of clouds with up to this many column-order bitmap words (32 points each) order and
  *                                 emit in ONE kernel, larger ones in two; an integer in 0 .. 2^24, 0 = always two kernels (tests send
- *                                 small clouds through the two kernels of a production-size build)                   default 16 384 */
+ *                                 small clouds through the two kernels of a production-size build)                   default 16 384
+ *   GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP value == 0: gndt_route_field* launch every sweep on its own, the one-workgroup kernel that holds a
+ *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1537,6 +1639,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_COLUMN_DEST 11
 #define GNDT_DEBUG_PLACE_EMIT_WORDS 12
 #define GNDT_DEBUG_OBSTACLE_TALLY 13
+#define GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 14
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
