@@ -145,22 +145,18 @@ int gndt_cast_rays(gndt_handle* h, const void* origins_host, size_t origin_strid
     zero_stats(stats);
     if (n == 0) return GNDT_OK;
     if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
-    const uint64_t o_bytes = origin_stride_bytes ? (uint64_t)n * origin_stride_bytes : 12, e_bytes = (uint64_t)n * end_stride_bytes,
-                   out_bytes = (uint64_t)n * 4;
-    const uint64_t bytes[5] = {o_bytes, e_bytes, out_host->row ? out_bytes : 0, out_host->range ? out_bytes : 0, out_host->d2 ? out_bytes : 0};
-    void* dev[5];
-    if ((rc = stage_pieces(h, bytes, dev, 5))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], origins_host, o_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dev[1], ends_host, e_bytes, hipMemcpyHostToDevice, s));
-    const CastOut o{static_cast<uint32_t*>(dev[2]), static_cast<float*>(dev[3]), static_cast<float*>(dev[4])};
-    if ((rc = cast_launch(h, static_cast<const float*>(dev[0]), (uint32_t)(origin_stride_bytes / 4), static_cast<const float*>(dev[1]),
-                          (uint32_t)(end_stride_bytes / 4), n, params, R, o, stats != nullptr, s)))
+    IoPiece io[5] = {io_in(origins_host, origin_stride_bytes ? (uint64_t)n * origin_stride_bytes : 12),
+                     io_in(ends_host, (uint64_t)n * end_stride_bytes),
+                     io_out(out_host->row, (uint64_t)n * 4),
+                     io_out(out_host->range, (uint64_t)n * 4),
+                     io_out(out_host->d2, (uint64_t)n * 4)};
+    if ((rc = stage_in(h, io, s))) return rc;
+    const CastOut o{io[2].as<uint32_t>(), io[3].as<float>(), io[4].as<float>()};
+    if ((rc = cast_launch(h, io[0].as<const float>(), (uint32_t)(origin_stride_bytes / 4), io[1].as<const float>(), (uint32_t)(end_stride_bytes / 4), n,
+                          params, R, o, stats != nullptr, s)))
         return rc;
-    void* const host[3] = {out_host->row, out_host->range, out_host->d2};
-    for (int k = 0; k < 3; ++k)
-        if (host[k]) HIP_TRY(h, hipMemcpyAsync(host[k], dev[2 + k], out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    cast_stats_out(h, stats);
+    if ((rc = stage_out(h, io, s))) return rc;
+    cast_stats_out(h, stats);                          // (from their pinned mirror)
     return GNDT_OK;
 }
 

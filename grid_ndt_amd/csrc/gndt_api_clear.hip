@@ -182,13 +182,12 @@ int gndt_clear_rays(gndt_handle* h, const float origin_xyz[3], const void* xyz_h
     const uint64_t rows = h->res_nodes;
     if ((rc = clear_buffers(h, rows))) return rc;
     auto& c = h->clear;
-    const uint64_t in_bytes = (uint64_t)n * stride_bytes;
-    void* in = nullptr;
-    if ((rc = stage_pieces(h, &in_bytes, &in, 1))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(in, xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    if ((rc = clear_launch(h, origin_xyz, static_cast<const float*>(in), n, (uint32_t)(stride_bytes / 4), p, c.passes, s))) return rc;
+    IoPiece io[1] = {io_in(xyz_host, (uint64_t)n * stride_bytes)};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = clear_launch(h, origin_xyz, io[0].as<const float>(), n, (uint32_t)(stride_bytes / 4), p, c.passes, s))) return rc;
+    // (the passes come from the handle's own array, the stats from their pinned mirror: neither is staged)
     if (passes_out_host && rows) HIP_TRY(h, hipMemcpyAsync(passes_out_host, c.passes, rows * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = stage_out(h, io, s))) return rc;
     if (!count_only && (rc = clear_finish(h, s))) return rc;
     clear_stats_out(h, stats);
     if (!count_only) return gndt_sync(h, nullptr, nullptr, nullptr);

@@ -122,18 +122,44 @@ int refuse_capture(gndt_handle* h, hipStream_t s, const char* msg) {
 }
 
 // Safe to share: gndt_query, gndt_raster and gndt_clear_rays run on own_stream and synchronise before they return
-int stage_pieces(gndt_handle* h, const uint64_t* bytes, void** piece, int count) {
+int stage_pieces(gndt_handle* h, IoPiece* pieces, int count) {
     auto aligned = [](uint64_t b) { return (b + 255) & ~uint64_t(255); };
     uint64_t total = 0;
-    for (int k = 0; k < count; ++k) total += aligned(bytes[k]);
+    for (int k = 0; k < count; ++k) total += aligned(pieces[k].bytes);
     const int rc = grow_scratch(h, h->io, h->io_cap, total);
     if (rc) return rc;
     char* p = static_cast<char*>(h->io);
     for (int k = 0; k < count; ++k) {
-        piece[k] = bytes[k] ? p : nullptr;
-        p += aligned(bytes[k]);
+        pieces[k].dev = pieces[k].bytes ? p : nullptr;
+        p += aligned(pieces[k].bytes);
     }
     return GNDT_OK;
+}
+
+int stage_in(gndt_handle* h, IoPiece* pieces, int count, hipStream_t s) {
+    const int rc = stage_pieces(h, pieces, count);
+    if (rc) return rc;
+    for (const IoPiece* p = pieces; p != pieces + count; ++p)
+        if (p->in && p->bytes) HIP_TRY(h, hipMemcpyAsync(p->dev, p->in, p->bytes, hipMemcpyHostToDevice, s));
+    return GNDT_OK;
+}
+
+int stage_out(gndt_handle* h, const IoPiece* pieces, int count, hipStream_t s) {
+    for (int k = 0; k < count; ++k)
+        if (pieces[k].out && pieces[k].bytes) HIP_TRY(h, hipMemcpyAsync(pieces[k].out, pieces[k].dev, pieces[k].bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return GNDT_OK;
+}
+
+bool lds_granted(const gndt_handle* h, const void* kernel, uint32_t bytes, LdsGrant& grant) {
+    if (h->device < 0 || h->device >= 64) return false;
+    int st = grant.state[h->device].load(std::memory_order_acquire);
+    if (st == 0) {
+        st = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 1 : 2;
+        if (st == 2) (void)hipGetLastError();
+        grant.state[h->device].store(st, std::memory_order_release);
+    }
+    return st == 1;
 }
 
 void free_part(gndt_handle* h) {
@@ -378,13 +404,8 @@ void gndt_destroy(gndt_handle* h) {
     free_score(h);
     free_cast(h);
     free_merge(h);
-    free_plan(h);
-    free_frontier(h);
-    free_segment(h);
-    free_clearance(h);
-    free_walk(h);
     free_obstacle(h);
-    free_route_field(h);
+    for (gndt_handle::Scratch* a : {&h->plan.scratch, &h->frontier, &h->segment, &h->clearance, &h->walk, &h->route_field}) free_scratch(*a);
     for (const RowArray& a : row_arrays(h->out))
         if (*a.p) (void)hipFree(*a.p);
     void* ptrs[] = {h->st_key, h->st_sums, h->st_count, h->st_first, h->stage, h->d_cnt, h->packed, h->d_nvalid, h->index.buf, h->io};

@@ -65,9 +65,7 @@ int footprint_enqueue(gndt_handle* h, const Robot& R, const FootRule& F, const v
                       uint32_t row_cap, FootInfo* info, hipStream_t s) {
     int rc = use_stream(h, s);
     if (rc) return rc;
-    const uint64_t n = h->res_nodes;
-    if (n >= 0xFFFFFFFFull) { h->err = "gndt_footprint_poses: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_footprint_poses")) || (rc = column_index(h, s))) return rc;
     const ScoreView S{query_view(h), h->out.count, h->out.cov};
     // one pose a wavefront: at most kFootMaxBlocks workgroups of kFootWaves (16 wavefronts on each of the 256 CUs), grid-stride beyond
     const dim3 grid(grid_for(K, kFootWaves, kFootMaxBlocks)), block(kFootThreads);
@@ -91,7 +89,7 @@ int gndt_footprint_poses_device(gndt_handle* h, const void* poses_dev, size_t K,
     if (rc) return rc;
     FootRule F;
     if ((rc = footprint_args(h, poses_dev, K, stride_bytes, robot, params, rows_dev, row_cap, info_dev, F))) return rc;
-    if ((reinterpret_cast<uintptr_t>(info_dev) & 15u) || (reinterpret_cast<uintptr_t>(rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(poses_dev) & 3u)) {
+    if (misaligned(15u, {info_dev}) || misaligned(3u, {rows_dev, poses_dev})) {
         h->err = "gndt_footprint_poses_device: info_dev must be 16-byte aligned (it is written 16 bytes at a time), poses and rows 4-byte";
         return GNDT_ERR_INVALID;
     }
@@ -111,17 +109,12 @@ int gndt_footprint_poses(gndt_handle* h, const void* poses_host, size_t K, size_
     if ((rc = query_sync(h, false, s, kFootCapture))) return rc;
     if (K == 0) return GNDT_OK;
     // (the last pose's record ends after its five floats: a caller's array need not be padded to the stride)
-    const uint64_t bytes[3] = {(uint64_t)(K - 1) * stride_bytes + 20, (uint64_t)K * row_cap * 4, (uint64_t)K * sizeof(FootInfo)};
-    void* dev[3];
-    if ((rc = stage_pieces(h, bytes, dev, 3))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], poses_host, bytes[0], hipMemcpyHostToDevice, s));
-    if ((rc = footprint_enqueue(h, robot_of(robot), F, dev[0], K, stride_bytes, static_cast<uint32_t*>(dev[1]), row_cap,
-                                static_cast<FootInfo*>(dev[2]), s)))
-        return rc;
-    if (bytes[1]) HIP_TRY(h, hipMemcpyAsync(rows_host, dev[1], bytes[1], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(info_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    IoPiece io[3] = {io_in(poses_host, (uint64_t)(K - 1) * stride_bytes + 20),
+                     io_out(rows_host, (uint64_t)K * row_cap * 4),
+                     io_out(info_host, (uint64_t)K * sizeof(FootInfo))};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = footprint_enqueue(h, robot_of(robot), F, io[0].dev, K, stride_bytes, io[1].as<uint32_t>(), row_cap, io[2].as<FootInfo>(), s))) return rc;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

@@ -17,12 +17,9 @@ static_assert(GNDT_FRONTIER_REACHED == kFrontierReached && GNDT_FRONTIER_SLOPES 
 
 namespace gndt_host {
 
-void free_frontier(gndt_handle* h) {
-    if (h->frontier.scratch) (void)hipFree(h->frontier.scratch);
-    h->frontier = gndt_handle::Frontier{};
-}
-
 namespace {
+
+constexpr const char* kFrontierCapture = "gndt_frontiers: a frontier call is not recorded into a hipGraph";
 
 // Arguments (every GNDT_ERR_INVALID of include/gndt.h but the handle's state) -> the rule the kernels apply
 int frontier_args(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* p, const gndt_frontier* clusters, uint32_t cluster_cap,
@@ -50,40 +47,33 @@ int frontier_args(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_
     return GNDT_OK;
 }
 
-// Arguments checked: the queries' steps (capture, finished map, cost map under REACHED, gndt_sync), the stream and the column index,
-// then the passes of gndt_frontier.hpp.  Nothing is awaited.
+// The handle's state (query_sync has run, with the cost map under REACHED): the stream and the column index, then the passes of
+// gndt_frontier.hpp.  Nothing is awaited.
 int frontier_enqueue(gndt_handle* h, const FrontierRule& F, uint32_t min_size, uint32_t* label, FrontierRecord* clusters, uint32_t cluster_cap,
                      uint32_t* counts, hipStream_t s) {
-    int rc = query_sync(h, F.candidates == kFrontierReached, s, "gndt_frontiers: a frontier call is not recorded into a hipGraph");
+    int rc = use_stream(h, s);
     if (rc) return rc;
-    if ((rc = use_stream(h, s))) return rc;
     const uint64_t rows = h->res_nodes;
     if (rows == 0) {                                   // nothing that indexes rows
         HIP_TRY(h, hipMemsetAsync(counts, 0, 4 * sizeof(uint32_t), s));
         return GNDT_OK;
     }
-    if (rows >= 0xFFFFFFFFull) { h->err = "gndt_frontiers: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_frontiers")) || (rc = column_index(h, s))) return rc;
     const uint32_t n = (uint32_t)rows;
     const uint32_t tiles = (n + kCropTile - 1) / kCropTile;
-    // parent [n] | size, then place [n] | tile counts [3 tiles] | open sides [n] (bytes)
-    auto& fr = h->frontier;
-    if ((rc = grow_scratch(h, fr.scratch, fr.bytes, (uint64_t)n * 9 + (uint64_t)tiles * 12 + 16))) return rc;
-    uint32_t* parent = static_cast<uint32_t*>(fr.scratch);
-    uint32_t* size_at = parent + n;
-    uint32_t* tile_cnt = size_at + n;
-    uint8_t* open = reinterpret_cast<uint8_t*>(tile_cnt + 3 * (uint64_t)tiles);
+    FrontierScratch S;
+    if ((rc = carve_scratch(h, h->frontier, S, n, tiles))) return rc;
     const QueryView Q = query_view(h);
     // the row passes: at most 2048 workgroups of 256 threads (what the chip holds at once), grid-stride beyond: the raster's launch
     const dim3 grid(grid_for(n, 256, 2048)), block(256);
-    hipLaunchKernelGGL(k_frontier_mark, grid, block, 0, s, Q, F, n, parent, open, size_at);
-    hipLaunchKernelGGL(k_frontier_link, grid, block, 0, s, Q, F, n, parent);
-    hipLaunchKernelGGL(k_frontier_flatten, grid, block, 0, s, n, parent, size_at, label);
-    hipLaunchKernelGGL(k_frontier_count, dim3(tiles), dim3(kCropT), 0, s, parent, size_at, n, min_size, tile_cnt);
-    hipLaunchKernelGGL(k_frontier_scan, dim3(1), dim3(kCropScanT), 0, s, tile_cnt, tiles, counts);
+    hipLaunchKernelGGL(k_frontier_mark, grid, block, 0, s, Q, F, n, S.parent, S.open, S.size_at);
+    hipLaunchKernelGGL(k_frontier_link, grid, block, 0, s, Q, F, n, S.parent);
+    hipLaunchKernelGGL(k_frontier_flatten, grid, block, 0, s, n, S.parent, S.size_at, label);
+    hipLaunchKernelGGL(k_frontier_count, dim3(tiles), dim3(kCropT), 0, s, S.parent, S.size_at, n, min_size, S.tile_cnt);
+    hipLaunchKernelGGL(k_frontier_scan, dim3(1), dim3(kCropScanT), 0, s, S.tile_cnt, tiles, counts);
     if (cluster_cap) {                                 // (a count-only call stops here)
-        hipLaunchKernelGGL(k_frontier_rank, dim3(tiles), dim3(kCropT), 0, s, parent, size_at, n, min_size, tile_cnt, clusters, cluster_cap);
-        hipLaunchKernelGGL(k_frontier_reduce, grid, block, 0, s, Q, F, n, parent, size_at, open, clusters);
+        hipLaunchKernelGGL(k_frontier_rank, dim3(tiles), dim3(kCropT), 0, s, S.parent, S.size_at, n, min_size, S.tile_cnt, clusters, cluster_cap);
+        hipLaunchKernelGGL(k_frontier_reduce, grid, block, 0, s, Q, F, n, S.parent, S.size_at, S.open, clusters);
     }
     HIP_TRY(h, hipGetLastError());
     return GNDT_OK;
@@ -102,12 +92,13 @@ int gndt_frontiers_device(gndt_handle* h, const gndt_crop_box* box, const gndt_f
     FrontierRule F;
     uint32_t min_size = 1;
     if ((rc = frontier_args(h, box, params, clusters_dev, cluster_cap, counts_dev, F, min_size))) return rc;
-    if ((reinterpret_cast<uintptr_t>(clusters_dev) & 7u) || (reinterpret_cast<uintptr_t>(counts_dev) & 3u) || (reinterpret_cast<uintptr_t>(label_dev) & 3u)) {
+    if (misaligned(7u, {clusters_dev}) || misaligned(3u, {counts_dev, label_dev})) {
         h->err = "gndt_frontiers_device: clusters_dev must be aligned as gndt_frontier is (8 bytes), counts_dev and label_dev to 4";
         return GNDT_ERR_INVALID;
     }
-    return frontier_enqueue(h, F, min_size, label_dev, reinterpret_cast<FrontierRecord*>(clusters_dev), cluster_cap, counts_dev,
-                            stream_of(h, hip_stream));
+    const hipStream_t s = stream_of(h, hip_stream);
+    if ((rc = query_sync(h, F.candidates == kFrontierReached, s, kFrontierCapture))) return rc;
+    return frontier_enqueue(h, F, min_size, label_dev, reinterpret_cast<FrontierRecord*>(clusters_dev), cluster_cap, counts_dev, s);
 }
 
 int gndt_frontiers(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* params, uint32_t* label_host,
@@ -118,21 +109,18 @@ int gndt_frontiers(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier
     uint32_t min_size = 1;
     if ((rc = frontier_args(h, box, params, clusters_host, cluster_cap, counts_host, F, min_size))) return rc;
     const hipStream_t s = h->own_stream;
-    // the steps that fix the row count first (staging is sized by it): what frontier_enqueue does again, then as no-ops
-    if ((rc = query_sync(h, F.candidates == kFrontierReached, s, "gndt_frontiers: a frontier call is not recorded into a hipGraph"))) return rc;
+    // the steps that fix the row count first (staging is sized by it)
+    if ((rc = query_sync(h, F.candidates == kFrontierReached, s, kFrontierCapture))) return rc;
     const uint64_t rows = h->res_nodes;
-    const uint64_t bytes[3] = {label_host ? rows * 4 : 0, (uint64_t)cluster_cap * sizeof(gndt_frontier), 4 * sizeof(uint32_t)};
-    void* dev[3];
-    if ((rc = stage_pieces(h, bytes, dev, 3))) return rc;
-    if ((rc = frontier_enqueue(h, F, min_size, static_cast<uint32_t*>(dev[0]), static_cast<FrontierRecord*>(dev[1]), cluster_cap,
-                               static_cast<uint32_t*>(dev[2]), s)))
-        return rc;
-    HIP_TRY(h, hipMemcpyAsync(counts_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));
-    if (bytes[0]) HIP_TRY(h, hipMemcpyAsync(label_host, dev[0], bytes[0], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    IoPiece io[3] = {io_out(counts_host, 4 * sizeof(uint32_t)),     // (first of the outputs: the counts come back before the rest)
+                     io_out(label_host, rows * 4),
+                     {nullptr, nullptr, (uint64_t)cluster_cap * sizeof(gndt_frontier)}};     // the clusters: copied below
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = frontier_enqueue(h, F, min_size, io[1].as<uint32_t>(), io[2].as<FrontierRecord>(), cluster_cap, io[0].as<uint32_t>(), s))) return rc;
+    if ((rc = stage_out(h, io, s))) return rc;
     // only the records the call wrote: what lies beyond them in the caller's array stays as it is
     const uint64_t written = std::min<uint64_t>(counts_host[0], cluster_cap);
-    if (written) HIP_TRY(h, hipMemcpy(clusters_host, dev[1], written * sizeof(gndt_frontier), hipMemcpyDeviceToHost));
+    if (written) HIP_TRY(h, hipMemcpy(clusters_host, io[2].dev, written * sizeof(gndt_frontier), hipMemcpyDeviceToHost));
     return GNDT_OK;
 }
 

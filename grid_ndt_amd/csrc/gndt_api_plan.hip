@@ -14,11 +14,6 @@ static_assert(GNDT_ROUTE_FOUND == kRouteFound && GNDT_ROUTE_NO_START == kRouteNo
 
 namespace gndt_host {
 
-void free_plan(gndt_handle* h) {
-    if (h->plan.scratch) (void)hipFree(h->plan.scratch);
-    h->plan = gndt_handle::Plan{};
-}
-
 namespace {
 
 constexpr uint64_t kPlanDefaultScratch = 256ull << 20;
@@ -86,8 +81,8 @@ int plan_launch(gndt_handle* h, const float* starts, uint32_t sf, uint64_t K, co
     const uint64_t want = per_launch * slot_bytes;
     // Stamps (gndt_plan.hpp PlanRowState) stand for "cleared": the area is zeroed when it is new, when a slot's layout changes (another
     // map size moves the words a stamp is read from) and when the stamps run out.
-    const bool fresh = want > pl.bytes || pl.slot_bytes != slot_bytes || pl.rows != rows;
-    int rc = grow_scratch(h, pl.scratch, pl.bytes, want);
+    const bool fresh = want > pl.scratch.bytes || pl.slot_bytes != slot_bytes || pl.rows != rows;
+    int rc = grow_scratch(h, pl.scratch.p, pl.scratch.bytes, want);
     if (rc) return rc;
     const uint32_t max_exp = p->max_expansions ? p->max_expansions : plan_default_expansions(h->res_slopes);
     const PlanView P = plan_view(h);
@@ -95,16 +90,16 @@ int plan_launch(gndt_handle* h, const float* starts, uint32_t sf, uint64_t K, co
     for (uint64_t first = 0; first < K; first += per_launch) {
         const uint64_t count = std::min<uint64_t>(per_launch, K - first);
         if ((fresh && first == 0) || pl.stamp >= 0x7FFFFFFEu) {
-            HIP_TRY(h, hipMemsetAsync(pl.scratch, 0, pl.bytes, s));
+            HIP_TRY(h, hipMemsetAsync(pl.scratch.p, 0, pl.scratch.bytes, s));
             pl.stamp = 0; pl.slot_bytes = slot_bytes; pl.rows = rows;
         }
         const uint32_t stamp = ++pl.stamp;
         if (p->start_mode == GNDT_QUERY_NODE)
-            hipLaunchKernelGGL((k_plan<kQueryNode>), dim3((uint32_t)count), dim3(64), 0, s, P, Q, starts, sf, first, static_cast<char*>(pl.scratch),
+            hipLaunchKernelGGL((k_plan<kQueryNode>), dim3((uint32_t)count), dim3(64), 0, s, P, Q, starts, sf, first, static_cast<char*>(pl.scratch.p),
                                slot_bytes, cap0, cap1, stamp, max_exp, route, route_cap, info);
         else
             hipLaunchKernelGGL((k_plan<kQueryNearestSlope>), dim3((uint32_t)count), dim3(64), 0, s, P, Q, starts, sf, first,
-                               static_cast<char*>(pl.scratch), slot_bytes, cap0, cap1, stamp, max_exp, route, route_cap, info);
+                               static_cast<char*>(pl.scratch.p), slot_bytes, cap0, cap1, stamp, max_exp, route, route_cap, info);
     }
     HIP_TRY(h, hipGetLastError());
 #if defined(GNDT_PLAN_STAMPS)
@@ -138,7 +133,7 @@ int gndt_plan_routes_device(gndt_handle* h, const void* starts_dev, size_t K, si
     if ((rc = plan_sync(h, s))) return rc;
     if (K == 0) return GNDT_OK;
     if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
-    if ((reinterpret_cast<uintptr_t>(info_dev) & 15u) || (reinterpret_cast<uintptr_t>(route_rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(starts_dev) & 3u)) {
+    if (misaligned(15u, {info_dev}) || misaligned(3u, {route_rows_dev, starts_dev})) {
         h->err = "gndt_plan_routes_device: info_dev must be 16-byte aligned (it is written 16 bytes at a time), starts and route_rows 4-byte";
         return GNDT_ERR_INVALID;
     }
@@ -155,17 +150,13 @@ int gndt_plan_routes(gndt_handle* h, const void* starts_host, size_t K, size_t s
     if ((rc = plan_sync(h, s))) return rc;
     if (K == 0) return GNDT_OK;
     if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
-    const uint64_t bytes[3] = {(uint64_t)K * stride_bytes, (uint64_t)K * route_cap * 4, (uint64_t)K * sizeof(RouteInfo)};
-    void* dev[3];
-    if ((rc = stage_pieces(h, bytes, dev, 3))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], starts_host, bytes[0], hipMemcpyHostToDevice, s));
-    if ((rc = plan_launch(h, static_cast<const float*>(dev[0]), (uint32_t)(stride_bytes / 4), K, params, static_cast<uint32_t*>(dev[1]), route_cap,
-                          static_cast<RouteInfo*>(dev[2]), s)))
+    IoPiece io[3] = {io_in(starts_host, (uint64_t)K * stride_bytes),
+                     io_out(route_rows_host, (uint64_t)K * route_cap * 4),
+                     io_out(info_host, (uint64_t)K * sizeof(RouteInfo))};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = plan_launch(h, io[0].as<const float>(), (uint32_t)(stride_bytes / 4), K, params, io[1].as<uint32_t>(), route_cap, io[2].as<RouteInfo>(), s)))
         return rc;
-    if (bytes[1]) HIP_TRY(h, hipMemcpyAsync(route_rows_host, dev[1], bytes[1], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(info_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

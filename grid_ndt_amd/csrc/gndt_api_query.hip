@@ -104,18 +104,13 @@ int gndt_query(gndt_handle* h, const void* xyz_host, size_t n, size_t stride_byt
     const hipStream_t s = h->own_stream;
     rc = query_prepare(h, xyz_host, n, stride_bytes, mode, row_out, h_out || state_out, s);
     if (rc || n == 0) return rc;
-    const uint64_t in_bytes = (uint64_t)n * stride_bytes, out_bytes = (uint64_t)n * 4;
-    const uint64_t bytes[4] = {in_bytes, out_bytes, h_out ? out_bytes : 0, state_out ? out_bytes : 0};
-    void* dev[4];
-    if ((rc = stage_pieces(h, bytes, dev, 4))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    rc = query_run(h, dev[0], n, stride_bytes, mode, static_cast<uint32_t*>(dev[1]), static_cast<float*>(dev[2]), static_cast<uint32_t*>(dev[3]), s);
-    if (rc) return rc;
-    void* const host[4] = {nullptr, row_out, h_out, state_out};
-    for (int k = 1; k < 4; ++k)
-        if (host[k]) HIP_TRY(h, hipMemcpyAsync(host[k], dev[k], out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    IoPiece io[4] = {io_in(xyz_host, (uint64_t)n * stride_bytes),
+                     io_out(row_out, (uint64_t)n * 4),
+                     io_out(h_out, (uint64_t)n * 4),
+                     io_out(state_out, (uint64_t)n * 4)};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = query_run(h, io[0].dev, n, stride_bytes, mode, io[1].as<uint32_t>(), io[2].as<float>(), io[3].as<uint32_t>(), s))) return rc;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

@@ -101,18 +101,12 @@ int gndt_raster(gndt_handle* h, const gndt_crop_box* box, int32_t mode, float z_
     const hipStream_t s = h->own_stream;
     // the requested layers in the handle's staging
     const uint64_t n = (uint64_t)width * height;
-    void* const host[6] = {out_host->row, out_host->z, out_host->rough, out_host->nodes, out_host->h, out_host->state};
-    uint64_t bytes[6];
-    for (int k = 0; k < 6; ++k) bytes[k] = host[k] ? n * 4 : 0;
-    void* dev[6];
-    if ((rc = stage_pieces(h, bytes, dev, 6))) return rc;
-    const gndt_raster_layers L{static_cast<uint32_t*>(dev[0]), static_cast<float*>(dev[1]), static_cast<float*>(dev[2]),
-                               static_cast<uint32_t*>(dev[3]), static_cast<float*>(dev[4]), static_cast<uint32_t*>(dev[5])};
+    IoPiece io[6] = {io_out(out_host->row, n * 4), io_out(out_host->z, n * 4),     io_out(out_host->rough, n * 4),
+                     io_out(out_host->nodes, n * 4), io_out(out_host->h, n * 4), io_out(out_host->state, n * 4)};
+    if ((rc = stage_in(h, io, s))) return rc;
+    const gndt_raster_layers L{io[0].as<uint32_t>(), io[1].as<float>(), io[2].as<float>(), io[3].as<uint32_t>(), io[4].as<float>(), io[5].as<uint32_t>()};
     if ((rc = raster_enqueue(h, *box, mode, z_ref, width, height, L, s))) return rc;
-    for (int k = 0; k < 6; ++k)
-        if (host[k]) HIP_TRY(h, hipMemcpyAsync(host[k], dev[k], n * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

@@ -5,8 +5,6 @@
 // changed by the one before returns at once.  The steps tables, the weights and the keys live in a scratch area of the handle.
 #include <math.h>
 
-#include <atomic>
-
 #include "gndt_handle.hpp"
 #include "gndt_route_field.hpp"
 
@@ -22,11 +20,6 @@ static_assert(sizeof(RouteFirst) == 8 && sizeof(ClearanceStep) == 8, "a side of 
 static_assert(kRouteLdsRows * 8u + kRouteLdsTail <= 160u * 1024u && kRouteWgSlots <= 32u, "k_route_wg's keys fit the CU's LDS, its slots a word");
 
 namespace gndt_host {
-
-void free_route_field(gndt_handle* h) {
-    if (h->route_field.scratch) (void)hipFree(h->route_field.scratch);
-    h->route_field = gndt_handle::RouteField{};
-}
 
 namespace {
 
@@ -51,20 +44,6 @@ int route_args(gndt_handle* h, const gndt_route_field_params* p, const uint32_t*
     return GNDT_OK;
 }
 
-// ~160 KiB of dynamic LDS have to be asked for once per device (clearance_lds_granted's rule)
-bool route_lds_granted(const gndt_handle* h) {
-    static std::atomic<int> state[64];                 // per device: 0 not asked yet, 1 granted, 2 refused
-    if (h->device < 0 || h->device >= 64) return false;
-    int st = state[h->device].load(std::memory_order_acquire);
-    if (st == 0) {
-        st = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_route_wg), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(kRouteLdsRows * 8u + kRouteLdsTail)) == hipSuccess ? 1 : 2;
-        if (st == 2) (void)hipGetLastError();
-        state[h->device].store(st, std::memory_order_release);
-    }
-    return st == 1;
-}
-
 // The handle's state (query_sync has run): the stream, the column index, then the passes of gndt_route_field.hpp.  Nothing is awaited.
 int route_enqueue(gndt_handle* h, const Robot& R, const RouteRule& F, const uint32_t* goals, uint32_t G, const float* goal_cost, const uint32_t* hops,
                   float* cost, uint32_t* next, uint32_t* counts, hipStream_t s) {
@@ -76,35 +55,26 @@ int route_enqueue(gndt_handle* h, const Robot& R, const RouteRule& F, const uint
         HIP_TRY(h, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(counts + 4), 1, 1, s));
         return GNDT_OK;
     }
-    if (rows >= 0xFFFFFFFFull) { h->err = "gndt_route_field: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_route_field")) || (rc = column_index(h, s))) return rc;
     const uint32_t n = (uint32_t)rows;
-    // first steps [4 n] (8 B) | rest of the steps [4 n] (8 B) | keys [n] (8 B) | the sweeps' flags [kRouteMaxRounds + 1, padded] |
-    // weights [n] (4 B) | "more" bits [n] (bytes): 77 B a row
-    constexpr uint64_t kFlagWords = kRouteMaxRounds + 8u;
-    auto& rf = h->route_field;
-    if ((rc = grow_scratch(h, rf.scratch, rf.bytes, (uint64_t)n * 77 + kFlagWords * 4))) return rc;
-    RouteFirst* first = static_cast<RouteFirst*>(rf.scratch);
-    ClearanceStep* rest = reinterpret_cast<ClearanceStep*>(first + 4 * (uint64_t)n);
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(rest + 4 * (uint64_t)n);
-    uint32_t* flags = reinterpret_cast<uint32_t*>(key + n);
-    float* w = reinterpret_cast<float*>(flags + kFlagWords);
-    uint8_t* more = reinterpret_cast<uint8_t*>(w + n);
+    RouteScratch S;
+    if ((rc = carve_scratch(h, h->route_field, S, n))) return rc;
     const CostView V = query_view(h).V;
-    const bool wg = tuning().route_field_one_workgroup && n <= kRouteLdsRows && route_lds_granted(h);
-    HIP_TRY(h, hipMemsetAsync(flags, 0, ((uint64_t)F.max_rounds + 1) * sizeof(uint32_t), s));
+    static LdsGrant grant;                             // k_route_wg's ~160 KiB
+    const bool wg = tuning().route_field_one_workgroup && n <= kRouteLdsRows && lds_granted(h, (const void*)&k_route_wg, kRouteLdsRows * 8u + kRouteLdsTail, grant);
+    HIP_TRY(h, hipMemsetAsync(S.flags, 0, ((uint64_t)F.max_rounds + 1) * sizeof(uint32_t), s));
     // the row passes: at most 2048 workgroups of 256 threads (what the chip holds at once), grid-stride beyond
     const dim3 grid4(grid_for(4 * (uint64_t)n, 256, 2048)), grid1(grid_for(n, 256, 2048)), block(256);
-    hipLaunchKernelGGL(k_route_enter, grid1, block, 0, s, V, R, F, n, hops, w, key);
-    if (G) hipLaunchKernelGGL(k_route_goals, dim3(grid_for(G, 256, 2048)), block, 0, s, n, w, goals, goal_cost, G, key, counts);
-    hipLaunchKernelGGL(k_route_steps, grid4, block, 0, s, V, R, n, w, first, rest, more, flags);
+    hipLaunchKernelGGL(k_route_enter, grid1, block, 0, s, V, R, F, n, hops, S.w, S.key);
+    if (G) hipLaunchKernelGGL(k_route_goals, dim3(grid_for(G, 256, 2048)), block, 0, s, n, S.w, goals, goal_cost, G, S.key, counts);
+    hipLaunchKernelGGL(k_route_steps, grid4, block, 0, s, V, R, n, S.w, S.first, S.rest, S.more, S.flags);
     if (wg) {
-        hipLaunchKernelGGL(k_route_wg, dim3(1), dim3(kRouteWgThreads), (size_t)n * 8 + kRouteLdsTail, s, V, R, F.max_cost, n, F.max_rounds, first, rest,
-                           more, w, key, cost, next, counts);
+        hipLaunchKernelGGL(k_route_wg, dim3(1), dim3(kRouteWgThreads), (size_t)n * 8 + kRouteLdsTail, s, V, R, F.max_cost, n, F.max_rounds, S.first, S.rest,
+                           S.more, S.w, S.key, cost, next, counts);
     } else {
         for (uint32_t round = 1; round <= F.max_rounds; ++round)
-            hipLaunchKernelGGL(k_route_sweep, grid4, block, 0, s, V, R, F.max_cost, n, round, first, rest, more, w, key, flags);
-        hipLaunchKernelGGL(k_route_finish, dim3(grid_for(n, 256, kRouteFinishBlocks)), block, 0, s, key, n, F.max_rounds, flags, cost, next, counts);
+            hipLaunchKernelGGL(k_route_sweep, grid4, block, 0, s, V, R, F.max_cost, n, round, S.first, S.rest, S.more, S.w, S.key, S.flags);
+        hipLaunchKernelGGL(k_route_finish, dim3(grid_for(n, 256, kRouteFinishBlocks)), block, 0, s, S.key, n, F.max_rounds, S.flags, cost, next, counts);
     }
     HIP_TRY(h, hipGetLastError());
     return GNDT_OK;
@@ -135,8 +105,7 @@ int descend_enqueue(gndt_handle* h, const DescendRule& F, const float* starts, u
     int rc = use_stream(h, s);
     if (rc) return rc;
     const uint64_t n = h->res_nodes;
-    if (n >= 0xFFFFFFFFull) { h->err = "gndt_descend_routes: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_descend_routes")) || (rc = column_index(h, s))) return rc;
     // one wavefront a workgroup; at most 8192 of them (k_walk_paths' grid), grid-stride beyond
     hipLaunchKernelGGL(k_route_descend, dim3(grid_for(K, kRouteDescendThreads, 8192)), dim3(kRouteDescendThreads), 0, s, query_view(h), F, (uint32_t)n, cost,
                        next, starts, sf, K, rows, route_cap, info);
@@ -157,8 +126,7 @@ int gndt_route_field_device(gndt_handle* h, const gndt_robot* robot, const gndt_
     if (rc) return rc;
     RouteRule F;
     if ((rc = route_args(h, params, goals_dev, G, cost_dev, next_dev, counts_dev, F))) return rc;
-    if ((reinterpret_cast<uintptr_t>(goals_dev) & 3u) || (reinterpret_cast<uintptr_t>(goal_cost_dev) & 3u) || (reinterpret_cast<uintptr_t>(hops_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(cost_dev) & 3u) || (reinterpret_cast<uintptr_t>(next_dev) & 3u) || (reinterpret_cast<uintptr_t>(counts_dev) & 3u)) {
+    if (misaligned(3u, {goals_dev, goal_cost_dev, hops_dev, cost_dev, next_dev, counts_dev})) {
         h->err = "gndt_route_field_device: goals_dev, goal_cost_dev, hops_dev, cost_dev, next_dev and counts_dev must be aligned to 4 bytes";
         return GNDT_ERR_INVALID;
     }
@@ -177,23 +145,18 @@ int gndt_route_field(gndt_handle* h, const gndt_robot* robot, const gndt_route_f
     // the steps that fix the row count first (staging is sized by it)
     if ((rc = query_sync(h, false, s, kRouteCapture))) return rc;
     const uint64_t rows = h->res_nodes;
-    const uint64_t bytes[6] = {(uint64_t)G * 4, goal_cost_host ? (uint64_t)G * 4 : 0, hops_host ? rows * 4 : 0, cost_host ? rows * 4 : 0,
-                               next_host ? rows * 4 : 0, 8 * sizeof(uint32_t)};
-    void* dev[6];
-    if ((rc = stage_pieces(h, bytes, dev, 6))) return rc;
-    const void* in[3] = {goals_host, goal_cost_host, hops_host};
-    for (int k = 0; k < 3; ++k)
-        if (bytes[k]) HIP_TRY(h, hipMemcpyAsync(dev[k], in[k], bytes[k], hipMemcpyHostToDevice, s));
+    IoPiece io[6] = {io_in(goals_host, (uint64_t)G * 4),
+                     io_in(goal_cost_host, (uint64_t)G * 4),
+                     io_in(hops_host, rows * 4),
+                     io_out(cost_host, rows * 4),
+                     io_out(next_host, rows * 4),
+                     io_out(counts_host, 8 * sizeof(uint32_t))};
+    if ((rc = stage_in(h, io, s))) return rc;
     // (a map without rows: hops has no entry and no row is read; the outputs have none either, and route_args has seen the caller's)
-    if ((rc = route_enqueue(h, robot_of(robot), F, static_cast<const uint32_t*>(dev[0]), G, static_cast<const float*>(dev[1]),
-                            static_cast<const uint32_t*>(dev[2]), static_cast<float*>(dev[3]), static_cast<uint32_t*>(dev[4]),
-                            static_cast<uint32_t*>(dev[5]), s)))
+    if ((rc = route_enqueue(h, robot_of(robot), F, io[0].as<const uint32_t>(), G, io[1].as<const float>(), io[2].as<const uint32_t>(),
+                            io[3].as<float>(), io[4].as<uint32_t>(), io[5].as<uint32_t>(), s)))
         return rc;
-    void* out[3] = {cost_host, next_host, counts_host};
-    for (int k = 0; k < 3; ++k)
-        if (bytes[3 + k]) HIP_TRY(h, hipMemcpyAsync(out[k], dev[3 + k], bytes[3 + k], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    return stage_out(h, io, s);
 }
 
 int gndt_descend_routes_device(gndt_handle* h, const void* starts_dev, size_t K, size_t stride_bytes, const gndt_descend_params* params,
@@ -203,8 +166,7 @@ int gndt_descend_routes_device(gndt_handle* h, const void* starts_dev, size_t K,
     if (rc) return rc;
     DescendRule F;
     if ((rc = descend_args(h, starts_dev, K, stride_bytes, params, cost_dev, next_dev, route_rows_dev, route_cap, info_dev, F))) return rc;
-    if ((reinterpret_cast<uintptr_t>(info_dev) & 15u) || (reinterpret_cast<uintptr_t>(route_rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(starts_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(cost_dev) & 3u) || (reinterpret_cast<uintptr_t>(next_dev) & 3u)) {
+    if (misaligned(15u, {info_dev}) || misaligned(3u, {route_rows_dev, starts_dev, cost_dev, next_dev})) {
         h->err = "gndt_descend_routes_device: info_dev must be 16-byte aligned (it is written 16 bytes at a time), starts, cost, next and route_rows 4-byte";
         return GNDT_ERR_INVALID;
     }
@@ -225,19 +187,16 @@ int gndt_descend_routes(gndt_handle* h, const void* starts_host, size_t K, size_
     if ((rc = query_sync(h, false, s, kDescendCapture))) return rc;
     if (K == 0) return GNDT_OK;
     const uint64_t rows = h->res_nodes;
-    const uint64_t bytes[5] = {(uint64_t)K * stride_bytes, rows * 4, rows * 4, (uint64_t)K * route_cap * 4, (uint64_t)K * sizeof(RouteInfo)};
-    void* dev[5];
-    if ((rc = stage_pieces(h, bytes, dev, 5))) return rc;
-    const void* in[3] = {starts_host, cost_host, next_host};
-    for (int k = 0; k < 3; ++k)
-        if (bytes[k]) HIP_TRY(h, hipMemcpyAsync(dev[k], in[k], bytes[k], hipMemcpyHostToDevice, s));
-    if ((rc = descend_enqueue(h, F, static_cast<const float*>(dev[0]), (uint32_t)(stride_bytes / 4), K, static_cast<const float*>(dev[1]),
-                              static_cast<const uint32_t*>(dev[2]), static_cast<uint32_t*>(dev[3]), route_cap, static_cast<RouteInfo*>(dev[4]), s)))
+    IoPiece io[5] = {io_in(starts_host, (uint64_t)K * stride_bytes),
+                     io_in(cost_host, rows * 4),
+                     io_in(next_host, rows * 4),
+                     io_out(route_rows_host, (uint64_t)K * route_cap * 4),
+                     io_out(info_host, (uint64_t)K * sizeof(RouteInfo))};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = descend_enqueue(h, F, io[0].as<const float>(), (uint32_t)(stride_bytes / 4), K, io[1].as<const float>(), io[2].as<const uint32_t>(),
+                              io[3].as<uint32_t>(), route_cap, io[4].as<RouteInfo>(), s)))
         return rc;
-    if (bytes[3]) HIP_TRY(h, hipMemcpyAsync(route_rows_host, dev[3], bytes[3], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(info_host, dev[4], bytes[4], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

@@ -184,21 +184,16 @@ int gndt_score_poses(gndt_handle* h, const void* xyz_host, size_t n, size_t stri
         return GNDT_OK;
     }
     if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
-    const uint64_t in_bytes = (uint64_t)n * stride_bytes, pose_bytes = (uint64_t)K * 12 * sizeof(double),
-                   out_bytes = (uint64_t)K * sizeof(gndt_pose_score), pt_bytes = (uint64_t)n * 4;
-    const uint64_t bytes[5] = {in_bytes, pose_bytes, out_bytes, point_d2_host ? pt_bytes : 0, point_row_host ? pt_bytes : 0};
-    void* dev[5];
-    if ((rc = stage_pieces(h, bytes, dev, 5))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dev[1], poses_host, pose_bytes, hipMemcpyHostToDevice, s));
-    rc = score_run(h, dev[0], n, stride_bytes, static_cast<const double*>(dev[1]), K, params->neighbourhood, R, params->point_pose,
-                   static_cast<gndt_pose_score*>(dev[2]), static_cast<float*>(dev[3]), static_cast<uint32_t*>(dev[4]), s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(out_host, dev[2], out_bytes, hipMemcpyDeviceToHost, s));
-    if (point_d2_host) HIP_TRY(h, hipMemcpyAsync(point_d2_host, dev[3], pt_bytes, hipMemcpyDeviceToHost, s));
-    if (point_row_host) HIP_TRY(h, hipMemcpyAsync(point_row_host, dev[4], pt_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    IoPiece io[5] = {io_in(xyz_host, (uint64_t)n * stride_bytes),
+                     io_in(poses_host, (uint64_t)K * 12 * sizeof(double)),
+                     io_out(out_host, (uint64_t)K * sizeof(gndt_pose_score)),
+                     io_out(point_d2_host, (uint64_t)n * 4),
+                     io_out(point_row_host, (uint64_t)n * 4)};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = score_run(h, io[0].dev, n, stride_bytes, io[1].as<const double>(), K, params->neighbourhood, R, params->point_pose,
+                        io[2].as<gndt_pose_score>(), io[3].as<float>(), io[4].as<uint32_t>(), s)))
+        return rc;
+    return stage_out(h, io, s);
 }
 
 int gndt_score_derivs_device(gndt_handle* h, const void* xyz_dev, size_t n, size_t stride_bytes, const double* poses_dev, uint32_t K,
@@ -231,19 +226,13 @@ int gndt_score_derivs(gndt_handle* h, const void* xyz_host, size_t n, size_t str
         return GNDT_OK;
     }
     if ((rc = use_stream(h, s)) || (rc = column_index(h, s))) return rc;
-    const uint64_t in_bytes = (uint64_t)n * stride_bytes, pose_bytes = (uint64_t)K * 12 * sizeof(double),
-                   out_bytes = (uint64_t)K * sizeof(gndt_pose_derivs);
-    const uint64_t bytes[3] = {in_bytes, pose_bytes, out_bytes};
-    void* dev[3];
-    if ((rc = stage_pieces(h, bytes, dev, 3))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dev[1], poses_host, pose_bytes, hipMemcpyHostToDevice, s));
-    rc = score_derivs_run(h, dev[0], n, stride_bytes, static_cast<const double*>(dev[1]), K, params->neighbourhood, R,
-                          static_cast<gndt_pose_derivs*>(dev[2]), s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpyAsync(out_host, dev[2], out_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    IoPiece io[3] = {io_in(xyz_host, (uint64_t)n * stride_bytes),
+                     io_in(poses_host, (uint64_t)K * 12 * sizeof(double)),
+                     io_out(out_host, (uint64_t)K * sizeof(gndt_pose_derivs))};
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = score_derivs_run(h, io[0].dev, n, stride_bytes, io[1].as<const double>(), K, params->neighbourhood, R, io[2].as<gndt_pose_derivs>(), s)))
+        return rc;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

@@ -20,11 +20,6 @@ static_assert(GNDT_SEG_UNKEYED == kSegUnkeyed && GNDT_SEG_EXPLAINED == kSegExpla
 
 namespace gndt_host {
 
-void free_segment(gndt_handle* h) {
-    if (h->segment.scratch) (void)hipFree(h->segment.scratch);
-    h->segment = gndt_handle::Segment{};
-}
-
 namespace {
 
 constexpr uint64_t kSegMaxPoints = 1ull << 30;       // 2 n slots stay within 2^31
@@ -90,24 +85,12 @@ int segment_enqueue(gndt_handle* h, const void* xyz_dev, size_t n64, size_t stri
     const uint32_t n = (uint32_t)n64;
     const uint64_t slots = seg_table_slots(n);
     const uint32_t tiles = (n + kCropTile - 1) / kCropTile;
-    // keys [slots] (8 B) | first [slots] | count [slots] | slot, then root [n] | parent [n] | cells_at [n] | points_at [n] |
-    // tile counts [4 tiles] | class [n] (bytes)
-    auto& sg = h->segment;
-    if ((rc = grow_scratch(h, sg.scratch, sg.bytes, slots * 16 + (uint64_t)n * 17 + (uint64_t)tiles * 16 + 16))) return rc;
-    SegTable T;
-    T.key = static_cast<uint64_t*>(sg.scratch);
-    T.first = reinterpret_cast<uint32_t*>(T.key + slots);
-    T.count = T.first + slots;
-    T.mask = (uint32_t)(slots - 1);
-    uint32_t* slot_root = T.count + slots;
-    uint32_t* parent = slot_root + n;
-    uint32_t* cells_at = parent + n;
-    uint32_t* points_at = cells_at + n;
-    uint32_t* tile_cnt = points_at + n;
-    uint8_t* cls_of = reinterpret_cast<uint8_t*>(tile_cnt + 4 * (uint64_t)tiles);
-    HIP_TRY(h, hipMemsetAsync(T.key, 0xFF, slots * 12, s));             // kEmptyKey, and the identity of the minimum
+    SegmentScratch A;
+    if ((rc = carve_scratch(h, h->segment, A, n, slots, tiles))) return rc;
+    const SegTable T = A.T;
+    HIP_TRY(h, hipMemsetAsync(T.key, 0xFF, slots * 12, s));             // key | first: kEmptyKey, and the identity of the minimum
     HIP_TRY(h, hipMemsetAsync(T.count, 0, slots * 4, s));
-    HIP_TRY(h, hipMemsetAsync(cells_at, 0, (uint64_t)n * 8, s));       // (and points_at)
+    HIP_TRY(h, hipMemsetAsync(A.cells_at, 0, (uint64_t)n * 8, s));       // A.cells_at | A.points_at
     ScoreView S{};
     S.Q = query_view(h);
     S.count = h->out.count;
@@ -117,17 +100,17 @@ int segment_enqueue(gndt_handle* h, const void* xyz_dev, size_t n64, size_t stri
     // the point passes: at most 2048 workgroups of 256 threads (what the chip holds at once), grid-stride beyond
     const dim3 grid(grid_for(n, 256, 2048)), block(256);
     if (nbh == GNDT_SCORE_DIRECT1)
-        hipLaunchKernelGGL((k_seg_classify<kScoreDirect1>), grid, block, 0, s, S, P, R, xyz, sf, n, pose, T, slot_root, cls_of, point_class);
+        hipLaunchKernelGGL((k_seg_classify<kScoreDirect1>), grid, block, 0, s, S, P, R, xyz, sf, n, pose, T, A.slot_root, A.cls_of, point_class);
     else
-        hipLaunchKernelGGL((k_seg_classify<kScoreDirect7>), grid, block, 0, s, S, P, R, xyz, sf, n, pose, T, slot_root, cls_of, point_class);
-    hipLaunchKernelGGL(k_seg_cells, grid, block, 0, s, T, R, n, slot_root, parent);
-    hipLaunchKernelGGL(k_seg_link, grid, block, 0, s, T, R, n, slot_root, parent);
-    hipLaunchKernelGGL(k_seg_flatten, grid, block, 0, s, T, R, n, parent, slot_root, cells_at, points_at, point_label);
-    hipLaunchKernelGGL(k_seg_count, dim3(tiles), dim3(kCropT), 0, s, R, parent, cls_of, cells_at, points_at, n, tile_cnt);
-    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kCropScanT), 0, s, tile_cnt, tiles, counts);
+        hipLaunchKernelGGL((k_seg_classify<kScoreDirect7>), grid, block, 0, s, S, P, R, xyz, sf, n, pose, T, A.slot_root, A.cls_of, point_class);
+    hipLaunchKernelGGL(k_seg_cells, grid, block, 0, s, T, R, n, A.slot_root, A.parent);
+    hipLaunchKernelGGL(k_seg_link, grid, block, 0, s, T, R, n, A.slot_root, A.parent);
+    hipLaunchKernelGGL(k_seg_flatten, grid, block, 0, s, T, R, n, A.parent, A.slot_root, A.cells_at, A.points_at, point_label);
+    hipLaunchKernelGGL(k_seg_count, dim3(tiles), dim3(kCropT), 0, s, R, A.parent, A.cls_of, A.cells_at, A.points_at, n, A.tile_cnt);
+    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(kCropScanT), 0, s, A.tile_cnt, tiles, counts);
     if (cluster_cap) {                                 // (a count-only call stops here)
-        hipLaunchKernelGGL(k_seg_rank, dim3(tiles), dim3(kCropT), 0, s, R, parent, cls_of, cells_at, points_at, n, tile_cnt, clusters, cluster_cap);
-        hipLaunchKernelGGL(k_seg_reduce, grid, block, 0, s, S.Q, xyz, sf, n, pose, slot_root, points_at, cls_of, clusters);
+        hipLaunchKernelGGL(k_seg_rank, dim3(tiles), dim3(kCropT), 0, s, R, A.parent, A.cls_of, A.cells_at, A.points_at, n, A.tile_cnt, clusters, cluster_cap);
+        hipLaunchKernelGGL(k_seg_reduce, grid, block, 0, s, S.Q, xyz, sf, n, pose, A.slot_root, A.points_at, A.cls_of, clusters);
         hipLaunchKernelGGL(k_seg_finish, dim3(grid_for(cluster_cap, 256, 256)), block, 0, s, clusters, cluster_cap, counts);
     }
     HIP_TRY(h, hipGetLastError());
@@ -148,9 +131,7 @@ int gndt_segment_scan_device(gndt_handle* h, const void* xyz_dev, size_t n, size
     ScoreParams P{};
     SegRule R{};
     if ((rc = segment_args(h, xyz_dev, n, stride_bytes, params, clusters_dev, cluster_cap, counts_dev, P, R))) return rc;
-    if ((reinterpret_cast<uintptr_t>(clusters_dev) & 7u) || (reinterpret_cast<uintptr_t>(counts_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(point_label_dev) & 3u) || (reinterpret_cast<uintptr_t>(pose_dev) & 7u) ||
-        (reinterpret_cast<uintptr_t>(xyz_dev) & 3u)) {
+    if (misaligned(7u, {clusters_dev, pose_dev}) || misaligned(3u, {counts_dev, point_label_dev, xyz_dev})) {
         h->err = "gndt_segment_scan_device: clusters_dev and pose_dev must be aligned to 8 bytes, counts_dev, point_label_dev and xyz_dev to 4";
         return GNDT_ERR_INVALID;
     }
@@ -171,24 +152,20 @@ int gndt_segment_scan(gndt_handle* h, const void* xyz_host, size_t n, size_t str
     const hipStream_t s = h->own_stream;
     if ((rc = segment_sync(h, s)) || (rc = use_stream(h, s))) return rc;
     if (n > kSegMaxPoints) { h->err = "gndt_segment_scan: more than 2^30 points in one call (the cell table would pass 2^31 slots)"; return GNDT_ERR_CAPACITY; }
-    const uint64_t in_bytes = (uint64_t)n * stride_bytes;
-    const uint64_t bytes[6] = {in_bytes, pose_host ? 12 * sizeof(double) : 0, point_class_host ? (uint64_t)n : 0,
-                               point_label_host ? (uint64_t)n * 4 : 0, (uint64_t)cluster_cap * sizeof(gndt_scan_cluster), 4 * sizeof(uint32_t)};
-    void* dev[6];
-    if ((rc = stage_pieces(h, bytes, dev, 6))) return rc;
-    if (in_bytes) HIP_TRY(h, hipMemcpyAsync(dev[0], xyz_host, in_bytes, hipMemcpyHostToDevice, s));
-    if (pose_host) HIP_TRY(h, hipMemcpyAsync(dev[1], pose_host, bytes[1], hipMemcpyHostToDevice, s));
-    if ((rc = segment_enqueue(h, dev[0], n, stride_bytes, static_cast<const double*>(dev[1]), params->neighbourhood, P, R,
-                              static_cast<uint8_t*>(dev[2]), static_cast<uint32_t*>(dev[3]), static_cast<SegRecord*>(dev[4]), cluster_cap,
-                              static_cast<uint32_t*>(dev[5]), s)))
+    IoPiece io[6] = {io_in(xyz_host, (uint64_t)n * stride_bytes),
+                     io_in(pose_host, 12 * sizeof(double)),
+                     io_out(counts_host, 4 * sizeof(uint32_t)),     // (first of the outputs: the counts come back before the rest)
+                     io_out(point_class_host, (uint64_t)n),
+                     io_out(point_label_host, (uint64_t)n * 4),
+                     {nullptr, nullptr, (uint64_t)cluster_cap * sizeof(gndt_scan_cluster)}};     // the clusters: copied below
+    if ((rc = stage_in(h, io, s))) return rc;
+    if ((rc = segment_enqueue(h, io[0].dev, n, stride_bytes, io[1].as<const double>(), params->neighbourhood, P, R, io[3].as<uint8_t>(),
+                              io[4].as<uint32_t>(), io[5].as<SegRecord>(), cluster_cap, io[2].as<uint32_t>(), s)))
         return rc;
-    HIP_TRY(h, hipMemcpyAsync(counts_host, dev[5], bytes[5], hipMemcpyDeviceToHost, s));
-    if (bytes[2]) HIP_TRY(h, hipMemcpyAsync(point_class_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));
-    if (bytes[3]) HIP_TRY(h, hipMemcpyAsync(point_label_host, dev[3], bytes[3], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
+    if ((rc = stage_out(h, io, s))) return rc;
     // only the records the call wrote: what lies beyond them in the caller's array stays as it is
     const uint64_t written = std::min<uint64_t>(counts_host[0], cluster_cap);
-    if (written) HIP_TRY(h, hipMemcpy(clusters_host, dev[4], written * sizeof(gndt_scan_cluster), hipMemcpyDeviceToHost));
+    if (written) HIP_TRY(h, hipMemcpy(clusters_host, io[5].dev, written * sizeof(gndt_scan_cluster), hipMemcpyDeviceToHost));
     return GNDT_OK;
 }
 

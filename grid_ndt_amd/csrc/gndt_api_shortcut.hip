@@ -49,8 +49,7 @@ int shortcut_enqueue(gndt_handle* h, const Robot& R, const ShortcutRule& F, cons
     int rc = use_stream(h, s);
     if (rc) return rc;
     const uint64_t n = h->res_nodes;
-    if (n >= 0xFFFFFFFFull) { h->err = "gndt_shortcut_routes: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_shortcut_routes")) || (rc = column_index(h, s))) return rc;
     const QueryView Q = query_view(h);
     // one route a wavefront: at most kShortcutMaxBlocks workgroups of kShortcutWaves (16 wavefronts on each of the 256 CUs), grid-stride beyond
     const dim3 grid(grid_for(K, kShortcutWaves, kShortcutMaxBlocks)), block(kShortcutThreads);
@@ -78,9 +77,7 @@ int gndt_shortcut_routes_device(gndt_handle* h, const uint32_t* route_rows_dev, 
     if ((rc = shortcut_args(h, route_rows_dev, K, route_cap, lengths_dev, length_stride_bytes, params, waypoint_rows_dev, path_rows_dev, path_cap,
                             info_dev, F)))
         return rc;
-    if ((reinterpret_cast<uintptr_t>(info_dev) & 15u) || (reinterpret_cast<uintptr_t>(route_rows_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(lengths_dev) & 3u) || (reinterpret_cast<uintptr_t>(hops_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(waypoint_rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(path_rows_dev) & 3u)) {
+    if (misaligned(15u, {info_dev}) || misaligned(3u, {route_rows_dev, lengths_dev, hops_dev, waypoint_rows_dev, path_rows_dev})) {
         h->err = "gndt_shortcut_routes_device: info_dev must be 16-byte aligned (it is written 16 bytes at a time), the other pointers 4-byte";
         return GNDT_ERR_INVALID;
     }
@@ -106,23 +103,18 @@ int gndt_shortcut_routes(gndt_handle* h, const uint32_t* route_rows_host, size_t
     if (K == 0) return GNDT_OK;
     std::vector<uint32_t> lengths(K);                    // the lengths out of their records, whatever their alignment
     for (size_t k = 0; k < K; ++k) memcpy(&lengths[k], static_cast<const char*>(lengths_host) + k * length_stride_bytes, 4);
-    const uint64_t bytes[6] = {(uint64_t)K * route_cap * 4, (uint64_t)K * 4, hops_host ? h->res_nodes * 4 : 0, (uint64_t)K * waypoint_cap * 4,
-                               (uint64_t)K * path_cap * 4, (uint64_t)K * sizeof(ShortcutInfo)};
-    void* dev[6];
-    if ((rc = stage_pieces(h, bytes, dev, 6))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], route_rows_host, bytes[0], hipMemcpyHostToDevice, s));
-    HIP_TRY(h, hipMemcpyAsync(dev[1], lengths.data(), bytes[1], hipMemcpyHostToDevice, s));
-    if (bytes[2]) HIP_TRY(h, hipMemcpyAsync(dev[2], hops_host, bytes[2], hipMemcpyHostToDevice, s));
+    IoPiece io[6] = {io_in(route_rows_host, (uint64_t)K * route_cap * 4),
+                     io_in(lengths.data(), (uint64_t)K * 4),
+                     io_in(hops_host, h->res_nodes * 4),
+                     io_out(waypoint_rows_host, (uint64_t)K * waypoint_cap * 4),
+                     io_out(path_rows_host, (uint64_t)K * path_cap * 4),
+                     io_out(info_host, (uint64_t)K * sizeof(ShortcutInfo))};
+    if ((rc = stage_in(h, io, s))) return rc;
     // (a map without rows: hops has no entry and every route is a BAD_ROUTE)
-    if ((rc = shortcut_enqueue(h, robot_of(robot), F, static_cast<const uint32_t*>(dev[0]), K, route_cap, dev[1], 4,
-                               static_cast<const uint32_t*>(dev[2]), static_cast<uint32_t*>(dev[3]), waypoint_cap, static_cast<uint32_t*>(dev[4]),
-                               path_cap, static_cast<ShortcutInfo*>(dev[5]), s)))
+    if ((rc = shortcut_enqueue(h, robot_of(robot), F, io[0].as<const uint32_t>(), K, route_cap, io[1].dev, 4, io[2].as<const uint32_t>(),
+                               io[3].as<uint32_t>(), waypoint_cap, io[4].as<uint32_t>(), path_cap, io[5].as<ShortcutInfo>(), s)))
         return rc;
-    if (bytes[3]) HIP_TRY(h, hipMemcpyAsync(waypoint_rows_host, dev[3], bytes[3], hipMemcpyDeviceToHost, s));
-    if (bytes[4]) HIP_TRY(h, hipMemcpyAsync(path_rows_host, dev[4], bytes[4], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(info_host, dev[5], bytes[5], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));                 // (`lengths` lives until here)
-    return GNDT_OK;
+    return stage_out(h, io, s);                          // (awaits the stream: `lengths` lives until here)
 }
 
 }  // extern "C"

@@ -16,11 +16,6 @@ static_assert(GNDT_WALK_DONE == kWalkDone && GNDT_WALK_NO_START == kWalkNoStart 
 
 namespace gndt_host {
 
-void free_walk(gndt_handle* h) {
-    if (h->walk.scratch) (void)hipFree(h->walk.scratch);
-    h->walk = gndt_handle::Walk{};
-}
-
 namespace {
 
 // Arguments (every GNDT_ERR_INVALID of include/gndt.h but the handle's state) -> the rule the kernel applies
@@ -55,8 +50,7 @@ int walk_enqueue(gndt_handle* h, const Robot& R, const WalkRule& F, const float*
     int rc = use_stream(h, s);
     if (rc) return rc;
     const uint64_t n = h->res_nodes;
-    if (n >= 0xFFFFFFFFull) { h->err = "gndt_walk_paths: row numbers do not fit 32 bits"; return GNDT_ERR_CAPACITY; }
-    if ((rc = column_index(h, s))) return rc;
+    if ((rc = rows_fit_32(h, "gndt_walk_paths")) || (rc = column_index(h, s))) return rc;
     const QueryView Q = query_view(h);
     // one wavefront a workgroup; at most 8192 of them (32 on each of the 256 CUs: what the chip holds at once), grid-stride beyond
     const dim3 grid(grid_for(K, kWalkThreads, 8192)), block(kWalkThreads);
@@ -65,16 +59,11 @@ int walk_enqueue(gndt_handle* h, const Robot& R, const WalkRule& F, const float*
     const int mode = tuning().walk_step_table;
     const bool table = n != 0 && (mode == 1 || (mode == 2 && n <= (uint64_t)kWalkTableRowsPerWaypoint * T));
     if (table) {
-        // steps [4 n] (8 B) | k_clearance_steps' round-0 keys [n] (8 B, not read) | its flag word, padded | tall columns [n] (bytes)
-        auto& wk = h->walk;
-        if ((rc = grow_scratch(h, wk.scratch, wk.bytes, n * 41 + 8))) return rc;
-        ClearanceStep* step = static_cast<ClearanceStep*>(wk.scratch);
-        unsigned long long* key0 = reinterpret_cast<unsigned long long*>(step + 4 * n);
-        uint32_t* flag = reinterpret_cast<uint32_t*>(key0 + n);
-        uint8_t* tall = reinterpret_cast<uint8_t*>(flag + 2);
+        WalkScratch S;
+        if ((rc = carve_scratch(h, h->walk, S, n))) return rc;
         hipLaunchKernelGGL(k_clearance_steps, dim3(grid_for(4 * n, 256, 2048)), dim3(256), 0, s, Q.V, R, ClearanceRule{kClrBlocked, 1u}, (uint32_t)n,
-                           step, tall, key0, static_cast<uint8_t*>(nullptr), flag);
-        hipLaunchKernelGGL(k_walk_paths<true>, grid, block, 0, s, Q, R, F, WalkTable{step, tall}, hops, paths, sf, K, T, rows, row_cap, info);
+                           S.step, S.tall, S.key0, static_cast<uint8_t*>(nullptr), S.flag);
+        hipLaunchKernelGGL(k_walk_paths<true>, grid, block, 0, s, Q, R, F, WalkTable{S.step, S.tall}, hops, paths, sf, K, T, rows, row_cap, info);
     } else {
         hipLaunchKernelGGL(k_walk_paths<false>, grid, block, 0, s, Q, R, F, WalkTable{nullptr, nullptr}, hops, paths, sf, K, T, rows, row_cap, info);
     }
@@ -97,8 +86,7 @@ int gndt_walk_paths_device(gndt_handle* h, const void* paths_dev, size_t K, size
     if (rc) return rc;
     WalkRule F;
     if ((rc = walk_args(h, paths_dev, K, T, stride_bytes, params, rows_dev, row_cap, info_dev, F))) return rc;
-    if ((reinterpret_cast<uintptr_t>(info_dev) & 15u) || (reinterpret_cast<uintptr_t>(rows_dev) & 3u) || (reinterpret_cast<uintptr_t>(paths_dev) & 3u) ||
-        (reinterpret_cast<uintptr_t>(hops_dev) & 3u)) {
+    if (misaligned(15u, {info_dev}) || misaligned(3u, {rows_dev, paths_dev, hops_dev})) {
         h->err = "gndt_walk_paths_device: info_dev must be 16-byte aligned (it is written 16 bytes at a time), paths, hops and rows 4-byte";
         return GNDT_ERR_INVALID;
     }
@@ -118,19 +106,16 @@ int gndt_walk_paths(gndt_handle* h, const void* paths_host, size_t K, size_t T, 
     const hipStream_t s = h->own_stream;
     if ((rc = query_sync(h, false, s, kWalkCapture))) return rc;
     if (K == 0 || T == 0) return GNDT_OK;
-    const uint64_t bytes[4] = {(uint64_t)K * T * stride_bytes, hops_host ? h->res_nodes * 4 : 0, (uint64_t)K * row_cap * 4, (uint64_t)K * sizeof(WalkInfo)};
-    void* dev[4];
-    if ((rc = stage_pieces(h, bytes, dev, 4))) return rc;
-    HIP_TRY(h, hipMemcpyAsync(dev[0], paths_host, bytes[0], hipMemcpyHostToDevice, s));
-    if (bytes[1]) HIP_TRY(h, hipMemcpyAsync(dev[1], hops_host, bytes[1], hipMemcpyHostToDevice, s));
+    IoPiece io[4] = {io_in(paths_host, (uint64_t)K * T * stride_bytes),
+                     io_in(hops_host, h->res_nodes * 4),
+                     io_out(rows_host, (uint64_t)K * row_cap * 4),
+                     io_out(info_host, (uint64_t)K * sizeof(WalkInfo))};
+    if ((rc = stage_in(h, io, s))) return rc;
     // (a map without rows: hops has no entry and no slope is stood on)
-    if ((rc = walk_enqueue(h, robot_of(robot), F, static_cast<const float*>(dev[0]), (uint32_t)(stride_bytes / 4), K, (uint32_t)T,
-                           static_cast<const uint32_t*>(dev[1]), static_cast<uint32_t*>(dev[2]), row_cap, static_cast<WalkInfo*>(dev[3]), s)))
+    if ((rc = walk_enqueue(h, robot_of(robot), F, io[0].as<const float>(), (uint32_t)(stride_bytes / 4), K, (uint32_t)T, io[1].as<const uint32_t>(),
+                           io[2].as<uint32_t>(), row_cap, io[3].as<WalkInfo>(), s)))
         return rc;
-    if (bytes[2]) HIP_TRY(h, hipMemcpyAsync(rows_host, dev[2], bytes[2], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(info_host, dev[3], bytes[3], hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return GNDT_OK;
+    return stage_out(h, io, s);
 }
 
 }  // extern "C"

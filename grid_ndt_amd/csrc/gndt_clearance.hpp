@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "gndt_query.hpp"
+#include "gndt_scratch.hpp"
 
 namespace gndt {
 
@@ -168,6 +169,19 @@ GNDT_HD void clearance_fold(uint32_t* counts, const ClearanceTally& t) {
     if (t.finite) Ops::add_u32(counts + 1, t.finite);
     if (t.max_hops) Ops::max_u32(counts + 2, t.max_hops);
 }
+
+// A call's scratch for a map of n rows (gndt_api_clearance.hip; the obstacle field's flags have the same room)
+constexpr uint64_t kClrFlagWords = kClrMaxHops + 8u;   // one word a round, kClrMaxHops + 1 of them, padded
+struct ClearanceScratch {
+    ClearanceStep* step;             // [4 n] the steps table, a side a record
+    unsigned long long* key[2];      // [n] each: the rounds' ping-pong
+    uint32_t* flags;                 // [kClrFlagWords]
+    uint8_t* tall;                   // [n] the tall-column bits
+    ClearanceScratch() = default;
+    ClearanceScratch(Carver& c, uint64_t n)
+        : step(c.take<ClearanceStep>(4 * n)), key{c.take<unsigned long long>(n), c.take<unsigned long long>(n)},
+          flags(c.take<uint32_t>(kClrFlagWords)), tall(c.take<uint8_t>(n)) {}
+};
 
 }  // namespace gndt
 

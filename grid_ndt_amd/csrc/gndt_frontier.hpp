@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "gndt_query.hpp"
+#include "gndt_scratch.hpp"
 
 namespace gndt {
 
@@ -199,6 +200,19 @@ GNDT_HD void frontier_fold(FrontierRecord* r, const FrontierSum& s) {
     Ops::min_i32(&r->sy_min, s.sy_min); Ops::max_i32(&r->sy_max, s.sy_max);
     Ops::min_u64(&r->best, s.best);
 }
+
+// A call's scratch for a map of n rows in `tiles` tiles of the ordered compaction (gndt_api_frontier.hip)
+struct FrontierScratch {
+    uint32_t* parent;                // [n] the union-find
+    uint32_t* size_at;               // [n] a root's member count, then its place in the list
+    uint32_t* tile_cnt;              // [3 tiles]
+    uint8_t* open;                   // [n] the open sides
+    uint8_t* slack;                  // [16]
+    FrontierScratch() = default;
+    FrontierScratch(Carver& c, uint64_t n, uint64_t tiles)
+        : parent(c.take<uint32_t>(n)), size_at(c.take<uint32_t>(n)), tile_cnt(c.take<uint32_t>(3 * tiles)), open(c.take<uint8_t>(n)),
+          slack(c.take<uint8_t>(16)) {}
+};
 
 }  // namespace gndt
 

@@ -20,10 +20,13 @@
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
 //   gndt_api_io.hip     input side (record unpack + NaN strip, gndt_build_cloud)
+// The consumers' per-call scratch areas are carved by gndt_scratch.hpp's Carver from the layout structs next to their kernels
+// (carve_scratch below); their host-pointer entry points stage their arrays through stage_in / stage_out.
 // There is NO CPU fallback: without a HIP device every compute entry point fails with GNDT_ERR_NO_DEVICE.
 #pragma once
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +49,6 @@ namespace gndt { struct QueryView; }   // gndt_query.hpp
 // 0x7F for the floating-point reads (3.40e38 as a float, 1.38e306 as a double, 2 139 062 143 as an int; none of the library's
 // sentinels).  gndt_debug_poisoned_bytes counts what has been filled.  tests/test_gpu_poisoned.py runs the consumers' tests under both.
 #ifdef GNDT_POISON
-#include <atomic>
 namespace gndt_host {
 inline std::atomic<int> g_poison_byte{0xA5};
 inline std::atomic<unsigned long long> g_poisoned_device{0}, g_poisoned_host{0};
@@ -67,6 +69,7 @@ inline hipError_t poison_host_malloc(void** p, size_t bytes) {
 #include "gndt_kernels.hpp"
 #include "gndt_partition.hpp"
 #include "gndt_cost.hpp"
+#include "gndt_scratch.hpp"
 
 using namespace gndt;   // host translation units of libgndt only: nothing else includes this header
 
@@ -97,6 +100,9 @@ struct gndt_handle {
                                        //   before that writes through the old pointers when replayed — noticed and reported (Pending::captured_gen)
     bool capturing = false;            // the stream of the call in progress is under hipGraph capture (use_stream): nothing may allocate,
                                        //   free or wait — such a call would not only fail, it INVALIDATES the capture (GNDT_NO_CAPTURE)
+
+    // A device area that a consumer owns, grows on demand (grow_scratch) and never records into a graph; freed by free_scratch
+    struct Scratch { void* p = nullptr;  uint64_t bytes = 0; };
 
     // node table
     uint32_t cap = 0;  // slots, power of two
@@ -230,7 +236,7 @@ struct gndt_handle {
         uint64_t* key = nullptr;  uint32_t* val = nullptr;  uint32_t mask = 0;
         uint64_t serial = 0;            // result_serial the index was built for (0 = none)
     } index;
-    // device staging of the host-pointer consumers (gndt_query, gndt_raster, gndt_clear_rays: stage_pieces), grown on demand
+    // device staging of the host-pointer consumers (gndt_query, gndt_raster, gndt_clear_rays, ...: stage_in), grown on demand
     void* io = nullptr;  uint64_t io_cap = 0;     // bytes
     // region crop (gndt_crop.hpp): the second set of result arrays the kept rows are compacted into (then swapped with out / row_ncol:
     // same capacities), and the per-tile counts of the scan
@@ -259,44 +265,34 @@ struct gndt_handle {
     // launch's (a row's state counts only with the launch's stamp, so nothing is cleared between launches); slot_bytes / rows: the
     // layout the stamps in the area belong to
     struct Plan {
-        void* scratch = nullptr;  uint64_t bytes = 0;
+        Scratch scratch;
         uint32_t stamp = 0;  uint64_t slot_bytes = 0, rows = 0;
     } plan;
     // frontier extraction (gndt_frontier.hpp): per row its parent in the union-find (4 B), its root's member count, then place in the
     // list (4 B) and its open sides (1 B), and three counts per tile of rows; grown on demand
-    struct Frontier {
-        void* scratch = nullptr;  uint64_t bytes = 0;
-    } frontier;
+    Scratch frontier;
     // scan segmentation (gndt_segment.hpp): the call's cell table (16 B a slot, the smallest power of two >= 2 n slots), per point its
     // cell's slot, then root (4 B), its parent in the union-find (4 B), its root's cells and points, then place (8 B) and its class
     // (1 B), and four counts per tile of points; grown on demand
-    struct Segment {
-        void* scratch = nullptr;  uint64_t bytes = 0;
-    } segment;
+    Scratch segment;
     // clearance field (gndt_clearance.hpp): per row the steps table of its four sides (32 B), two key arrays for the rounds' ping-pong
     // (16 B) and its tall-column bits (1 B), and one flag word per round; grown on demand
-    struct Clearance {
-        void* scratch = nullptr;  uint64_t bytes = 0;
-    } clearance;
+    Scratch clearance;
     // obstacle field (gndt_obstacle.hpp).  marks: per map row a column stamp and its first worklist place (4 B each) and the stamped cover
     // word (8 B), set to "never" when allocated and when the stamp would wrap, never cleared between calls: a call's stamp is marks_stamp
     // after it.  scratch: per row the worklist (4 B), the steps of its four sides (32 B), two key arrays (16 B) and the tall-column bits
     // (1 B), per box its prefix sum (8 B) and its covers-a-slope word (4 B), the header and one flag word per round; grown on demand
     struct Obstacle {
         void* marks = nullptr;  uint64_t marks_bytes = 0, marks_rows = 0;  uint32_t stamp = 0;
-        void* scratch = nullptr;  uint64_t bytes = 0;
+        Scratch scratch;
     } obstacle;
     // route field (gndt_route_field.hpp): per row the first step of its four sides with its cost (32 B), the rest of their steps (32 B),
     // the key the sweeps relax in place (8 B), the weight of entering it (4 B) and its "more" bits (1 B), and one flag word per sweep;
     // grown on demand
-    struct RouteField {
-        void* scratch = nullptr;  uint64_t bytes = 0;
-    } route_field;
+    Scratch route_field;
     // path walks (gndt_walk.hpp), the table variant only: per row the steps table of its four sides (32 B) and what else
     // k_clearance_steps writes (a round-0 key, 8 B, and the tall-column bits, 1 B); made again by every call that takes it
-    struct Walk {
-        void* scratch = nullptr;  uint64_t bytes = 0;
-    } walk;
+    Scratch walk;
     // map merge (gndt_merge.hpp): the call's tallies, device and pinned
     struct Merge {
         unsigned long long* d_stats = nullptr;  unsigned long long* h_stats = nullptr;
@@ -553,6 +549,33 @@ int grow_scratch(gndt_handle* h, T*& p, uint64_t& cap, uint64_t bytes) {
     return GNDT_OK;
 }
 
+inline void free_scratch(gndt_handle::Scratch& a) { if (a.p) (void)hipFree(a.p);  a = gndt_handle::Scratch{}; }
+
+// A consumer's per-call scratch: LAYOUT (a layout struct over gndt_scratch.hpp's Carver) run over a null base for the bytes, the area
+// grown to them, the pieces carved from it.  What is carved is what was counted.
+template <typename LAYOUT, typename... SIZES>
+int carve_scratch(gndt_handle* h, gndt_handle::Scratch& a, LAYOUT& out, SIZES... sizes) {
+    Carver sizer;
+    (void)LAYOUT(sizer, sizes...);
+    const int rc = grow_scratch(h, a.p, a.bytes, sizer.pos);
+    if (rc) return rc;
+    Carver c(a.p);
+    out = LAYOUT(c, sizes...);
+    return GNDT_OK;
+}
+
+// The row numbers of a finished map as the consumers' 32-bit words (kNoRow excepted)
+inline int rows_fit_32(gndt_handle* h, const char* entry) {
+    if (h->res_nodes < 0xFFFFFFFFull) return GNDT_OK;
+    h->err = std::string(entry) + ": row numbers do not fit 32 bits";
+    return GNDT_ERR_CAPACITY;
+}
+
+// one of the pointers has a bit of `mask` set (null is aligned)
+inline bool misaligned(uintptr_t mask, std::initializer_list<const void*> ptrs) {
+    return std::any_of(ptrs.begin(), ptrs.end(), [mask](const void* p) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; });
+}
+
 // A cache of the map (the column index, the clear's level extents, the flood's per-map tables) is current while the map is the one it
 // was made for — never on a handle that has recorded a hipGraph: a replay rewrites the map without the host's serial moving
 inline bool map_current(const gndt_handle* h, uint64_t serial) { return serial && serial == h->result_serial && !h->ever_captured; }
@@ -633,8 +656,27 @@ int check_ready(gndt_handle* h);
 int finished_map(gndt_handle* h, const char* no_map_err, bool key_range_ok);
 int refuse_capture(gndt_handle* h, hipStream_t s, const char* msg);   // GNDT_ERR_INVALID with msg when s is under hipGraph capture
 int alloc_rows(gndt_handle* h, OutView& v, uint64_t rows);            // the ten result-row arrays, `rows` rows each
-// the host-pointer consumers' staging (h->io): `count` pieces of bytes[k], 256-byte aligned (null where bytes[k] is 0)
-int stage_pieces(gndt_handle* h, const uint64_t* bytes, void** piece, int count);
+// One array of a host-pointer entry point: `bytes` of staging at dev (stage_in sets it), filled from `in` before the kernels and copied
+// to `out` behind them (either may be null: an output, an input, or room that the entry point copies from itself)
+struct IoPiece {
+    const void* in;  void* out;  uint64_t bytes;
+    void* dev = nullptr;
+    template <typename T> T* as() const { return static_cast<T*>(dev); }
+};
+// an input / an output of the caller's; null: not passed, so no room and a null kernel argument
+inline IoPiece io_in(const void* host, uint64_t bytes) { return IoPiece{host, nullptr, host ? bytes : 0}; }
+inline IoPiece io_out(void* host, uint64_t bytes) { return IoPiece{nullptr, host, host ? bytes : 0}; }
+// the host-pointer consumers' staging (h->io): every piece's dev, 256-byte aligned (null where its bytes are 0)
+int stage_pieces(gndt_handle* h, IoPiece* pieces, int count);
+int stage_in(gndt_handle* h, IoPiece* pieces, int count, hipStream_t s);          // staged; every piece with `in` and bytes copied in, in order
+int stage_out(gndt_handle* h, const IoPiece* pieces, int count, hipStream_t s);   // every piece with `out` and bytes copied out, in order; the stream awaited
+template <int N> int stage_in(gndt_handle* h, IoPiece (&pieces)[N], hipStream_t s) { return stage_in(h, pieces, N, s); }
+template <int N> int stage_out(gndt_handle* h, const IoPiece (&pieces)[N], hipStream_t s) { return stage_out(h, pieces, N, s); }
+// More dynamic LDS than the default has to be asked for once per device (the attribute belongs to the function ON the current device,
+// which check_ready has made the handle's).  `grant` is the asking kernel's own (static storage).  A refusal clears the sticky error
+// and is final: the caller launches per round from then on.  Devices outside 0-63 are never granted.
+struct LdsGrant { std::atomic<int> state[64]; };        // per device: 0 not asked yet, 1 granted, 2 refused
+bool lds_granted(const gndt_handle* h, const void* kernel, uint32_t bytes, LdsGrant& grant);
 int use_stream(gndt_handle* h, hipStream_t s);     // work moves to stream s: it waits for what the handle's last stream still runs
 int ensure_out(gndt_handle* h, uint64_t n);
 int ensure_stats_buffers(gndt_handle* h, uint64_t n);
@@ -701,19 +743,7 @@ void free_score(gndt_handle* h);
 void free_cast(gndt_handle* h);
 // ---- gndt_api_merge.hip ----
 void free_merge(gndt_handle* h);
-// ---- gndt_api_plan.hip ----
-void free_plan(gndt_handle* h);
-// ---- gndt_api_frontier.hip ----
-void free_frontier(gndt_handle* h);
-// ---- gndt_api_segment.hip ----
-void free_segment(gndt_handle* h);
-// ---- gndt_api_clearance.hip ----
-void free_clearance(gndt_handle* h);
-// ---- gndt_api_walk.hip ----
-void free_walk(gndt_handle* h);
 // ---- gndt_api_obstacle.hip ----
-void free_obstacle(gndt_handle* h);
-// ---- gndt_api_route_field.hip ----
-void free_route_field(gndt_handle* h);
+void free_obstacle(gndt_handle* h);        // (the marks beside the scratch)
 
 }  // namespace gndt_host

@@ -189,6 +189,39 @@ GNDT_HD void obstacle_finish_row(const CostView& V, uint32_t row, unsigned long 
     if (obstacle) obstacle[row] = ob;
 }
 
+// the call's words on the device: what the later kernels size their loops by
+struct ObstacleHeader {
+    unsigned long long items;          // columns of the concatenated admitted windows: the largest W within the budget
+    uint32_t B, len;                   // the boxes of the call; the worklist's length (k_obstacle_mark adds to it)
+    unsigned long long probes, claims, cover_atomics;       // the mark pass's tallies (tools/measure_obstacle.py; only with `tally`)
+};
+
+// The stamped marks of `rows` map rows (gndt_api_obstacle.hip obstacle_marks): 16 B a row
+inline void obstacle_carve_marks(Carver& c, uint64_t rows, ObstacleMarks& M) {
+    M.cover = c.take<unsigned long long>(rows);
+    M.cstamp = c.take<uint32_t>(rows);
+    M.slot = c.take<uint32_t>(rows);
+}
+
+// A call's scratch for a map of n rows and a list of n_boxes boxes (gndt_api_obstacle.hip)
+constexpr uint64_t kObsHeaderBytes = 64;
+static_assert(sizeof(ObstacleHeader) <= kObsHeaderBytes && alignof(ObstacleHeader) == alignof(unsigned long long), "the header's room");
+struct ObstacleScratch {
+    ObstacleHeader* hdr;             // kObsHeaderBytes of room
+    unsigned long long* W;           // [n_boxes] the windows' prefix sums
+    unsigned long long* key[2];      // [n] each: the rounds' ping-pong
+    ClearanceStep* step;             // [4 n] the steps table
+    uint32_t* flags;                 // [kClrFlagWords]
+    uint32_t* covers;                // [n_boxes] box b covers a slope
+    uint32_t* list;                  // [n] the worklist
+    uint8_t* tall;                   // [n] the tall-column bits
+    ObstacleScratch() = default;
+    ObstacleScratch(Carver& c, uint64_t n, uint64_t n_boxes)
+        : hdr(reinterpret_cast<ObstacleHeader*>(c.take<unsigned long long>(kObsHeaderBytes / 8))), W(c.take<unsigned long long>(n_boxes)),
+          key{c.take<unsigned long long>(n), c.take<unsigned long long>(n)}, step(c.take<ClearanceStep>(4 * n)),
+          flags(c.take<uint32_t>(kClrFlagWords)), covers(c.take<uint32_t>(n_boxes)), list(c.take<uint32_t>(n)), tall(c.take<uint8_t>(n)) {}
+};
+
 }  // namespace gndt
 
 #if defined(__HIPCC__)
@@ -203,13 +236,6 @@ struct ObstacleDeviceOps : ClearanceDeviceOps {
     static __device__ __forceinline__ uint32_t max_u32_old(uint32_t* p, uint32_t v) { return atomicMax(p, v); }
     static __device__ __forceinline__ uint32_t add_u32_old(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
     static __device__ __forceinline__ void min_u64(unsigned long long* p, unsigned long long v) { atomicMin(p, v); }
-};
-
-// the call's words on the device: what the later kernels size their loops by
-struct ObstacleHeader {
-    unsigned long long items;          // columns of the concatenated admitted windows: the largest W within the budget
-    uint32_t B, len;                   // the boxes of the call; the worklist's length (k_obstacle_mark adds to it)
-    unsigned long long probes, claims, cover_atomics;       // the mark pass's tallies (tools/measure_obstacle.py; only with `tally`)
 };
 
 // One workgroup: tiles of 1024 boxes, an inclusive scan of the windows' columns across the tile with the carry of the tiles before.

@@ -239,6 +239,21 @@ GNDT_HD void route_descend(const QueryView& Q, const DescendRule& P, uint32_t n,
     for (uint32_t i = len; i < route_cap; ++i) rows[i] = kNoRow;
 }
 
+// A call's scratch for a map of n rows (gndt_api_route_field.hip)
+constexpr uint64_t kRouteFlagWords = kRouteMaxRounds + 8u;   // one word a sweep, kRouteMaxRounds + 1 of them, padded
+struct RouteScratch {
+    RouteFirst* first;               // [4 n] the first step of a side with its cost
+    ClearanceStep* rest;             // [4 n] the rest of its steps
+    unsigned long long* key;         // [n] relaxed in place by the sweeps
+    uint32_t* flags;                 // [kRouteFlagWords]
+    float* w;                        // [n] the weight of entering the row
+    uint8_t* more;                   // [n] the "more" bits
+    RouteScratch() = default;
+    RouteScratch(Carver& c, uint64_t n)
+        : first(c.take<RouteFirst>(4 * n)), rest(c.take<ClearanceStep>(4 * n)), key(c.take<unsigned long long>(n)),
+          flags(c.take<uint32_t>(kRouteFlagWords)), w(c.take<float>(n)), more(c.take<uint8_t>(n)) {}
+};
+
 }  // namespace gndt
 
 #if defined(__HIPCC__)

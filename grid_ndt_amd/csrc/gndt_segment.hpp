@@ -237,6 +237,30 @@ GNDT_HD void seg_fold(SegRecord* r, const SegSum& s) {
 // z_lo / z_hi of a finished record: the floats' bits back from their images
 GNDT_HD void seg_record_finish(SegRecord* r) { r->z_lo = seg_z_bits(r->z_lo); r->z_hi = seg_z_bits(r->z_hi); }
 
+// A call's scratch for n points, a cell table of `slots` slots (seg_table_slots) and `tiles` tiles of the ordered compaction
+// (gndt_api_segment.hip).  Two pairs are cleared by one memset each, so each is ONE piece and its second array starts where the first
+// ends: the table's key | first (12 B a slot, all ones) and cells_at | points_at (8 B a point, zero).
+struct SegmentScratch {
+    SegTable T;                      // key [slots] | first [slots], count [slots]
+    uint32_t* slot_root;             // [n] a point's slot, then its root
+    uint32_t* parent;                // [n] the union-find
+    uint32_t *cells_at, *points_at;  // [n] | [n] a root's cells and points, then its place
+    uint32_t* tile_cnt;              // [4 tiles]
+    uint8_t* cls_of;                 // [n] the class
+    uint8_t* slack;                  // [16]
+    SegmentScratch() = default;
+    SegmentScratch(Carver& c, uint64_t n, uint64_t slots, uint64_t tiles) {
+        T.key = c.take<uint64_t>(slots + slots / 2);             // 12 B a slot; slots is a power of two (seg_table_slots)
+        T.first = T.key ? reinterpret_cast<uint32_t*>(T.key + slots) : nullptr;
+        T.count = c.take<uint32_t>(slots);
+        T.mask = (uint32_t)(slots - 1);
+        slot_root = c.take<uint32_t>(n);  parent = c.take<uint32_t>(n);
+        cells_at = c.take<uint32_t>(2 * n);
+        points_at = cells_at ? cells_at + n : nullptr;
+        tile_cnt = c.take<uint32_t>(4 * tiles);  cls_of = c.take<uint8_t>(n);  slack = c.take<uint8_t>(16);
+    }
+};
+
 }  // namespace gndt
 
 #if defined(__HIPCC__)

@@ -176,6 +176,17 @@ GNDT_HD void walk_path(const QueryView& Q, const Robot& R, const WalkRule& P, co
     for (uint32_t i = stood; i < row_cap; ++i) rows[i] = kNoRow;
 }
 
+// The table variant's scratch for a map of n rows (gndt_api_walk.hip): what k_clearance_steps writes
+struct WalkScratch {
+    ClearanceStep* step;             // [4 n] the steps table
+    unsigned long long* key0;        // [n] its round-0 keys (not read)
+    uint32_t* flag;                  // [2] its flag word, padded
+    uint8_t* tall;                   // [n] the tall-column bits
+    WalkScratch() = default;
+    WalkScratch(Carver& c, uint64_t n)
+        : step(c.take<ClearanceStep>(4 * n)), key0(c.take<unsigned long long>(n)), flag(c.take<uint32_t>(2)), tall(c.take<uint8_t>(n)) {}
+};
+
 }  // namespace gndt
 
 #if defined(__HIPCC__)

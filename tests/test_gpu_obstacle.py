@@ -396,6 +396,13 @@ def test_first_builder_of_the_index_and_after_an_update_a_crop_and_a_clear():
     n3, after = fresh("clear")
     assert n1 == n0 + 60 and n2 < n1 and st["cleared"] > 0 and n3 == n2 - st["cleared"]
     assert after["counts"][0] > 0
+    # everything cropped away: both entry points answer alike, the boxes counted, no slope covered, nothing else written
+    m.crop_box((1000, 1010, 1, 2), "keep_inside")
+    assert m.sync()[0] == 0
+    empty = [raw(m, boxes, host=host, max_hops=3, inflate=1) for host in (False, True)]
+    for rc, got in empty:
+        assert rc == 0 and untouched(got) and got["counts"][3] == len(boxes) and not got["counts"][:3].any()
+    assert empty[0][1]["counts"].tobytes() == empty[1][1]["counts"].tobytes()
 
 
 # ---- the chain ------------------------------------------------------------------------------------------------------------------------
