@@ -27,8 +27,8 @@ def lib_path(variant=None):
 
 LIB_PATH = lib_path(VARIANT)   # what lib() loads in this process
 SOURCES = ["gndt_api_core.hip", "gndt_api_table.hip", "gndt_api_build.hip", "gndt_api_dist.hip", "gndt_api_cost.hip", "gndt_api_query.hip",
-           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_route_field.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
-HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_route_field.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", "gndt_scratch.hpp", os.path.join(_ROOT, "include", "gndt.h")]
+           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_view.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_route_field.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
+HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_view.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_route_field.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", "gndt_scratch.hpp", os.path.join(_ROOT, "include", "gndt.h")]
 
 GNDT_OK = 0
 ERR_NAMES = {0: "OK", 1: "INVALID", 2: "NO_DEVICE", 3: "HIP", 4: "KEY_RANGE", 5: "CAPACITY", 6: "NOMEM", 7: "PEER"}
@@ -103,6 +103,15 @@ class CastOut(C.Structure):
 
 class CastStats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("skipped", C.c_uint64), ("hits", C.c_uint64)]
+
+
+class ViewParams(C.Structure):
+    _fields_ = [("max_range", C.c_float), ("min_range", C.c_float), ("min_count", C.c_int32), ("reserved", C.c_uint32 * 5)]
+
+
+class ViewInfo(C.Structure):
+    _fields_ = [("rays", C.c_uint32), ("skipped", C.c_uint32), ("hits", C.c_uint32), ("unknown", C.c_uint32), ("known", C.c_uint32),
+                ("status", C.c_uint32), ("steps", C.c_uint64), ("sum_ux", C.c_int64), ("sum_uy", C.c_int64)]
 
 
 class PlanParams(C.Structure):
@@ -366,6 +375,8 @@ def lib():
     L.gndt_score_maps_derivs_device.argtypes = [H, H, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp]
     L.gndt_cast_rays_device.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(CastParams), C.POINTER(CastOut), C.POINTER(CastStats), vp]
     L.gndt_cast_rays.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(CastParams), C.POINTER(CastOut), C.POINTER(CastStats)]
+    L.gndt_view_gain_device.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(ViewParams), vp, vp, vp, vp]
+    L.gndt_view_gain.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(ViewParams), vp, vp, vp]
     L.gndt_plan_routes_device.argtypes = [H, vp, sz, sz, C.POINTER(PlanParams), vp, C.c_uint32, vp, vp]
     L.gndt_plan_routes.argtypes = [H, vp, sz, sz, C.POINTER(PlanParams), vp, C.c_uint32, vp]
     L.gndt_frontiers_device.argtypes = [H, C.POINTER(CropBox), C.POINTER(FrontierParams), vp, vp, C.c_uint32, vp, vp]
@@ -465,7 +476,7 @@ def lib():
                  "gndt_export", "gndt_stats_export_device", "gndt_stats_merge_device", "gndt_trans_morton_xyz",
                  "gndt_compute_cost", "gndt_cost_export_device", "gndt_cost_export", "gndt_query_device", "gndt_query",
                  "gndt_crop_device", "gndt_crop", "gndt_crop_box_from_world", "gndt_raster_shape", "gndt_raster_device", "gndt_raster", "gndt_clear_rays_device", "gndt_clear_rays",
-                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_segment_scan_device", "gndt_segment_scan", "gndt_clearance_device", "gndt_clearance", "gndt_obstacle_field_device", "gndt_obstacle_field", "gndt_route_field_device", "gndt_route_field", "gndt_descend_routes_device", "gndt_descend_routes", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
+                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_view_gain_device", "gndt_view_gain", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_segment_scan_device", "gndt_segment_scan", "gndt_clearance_device", "gndt_clearance", "gndt_obstacle_field_device", "gndt_obstacle_field", "gndt_route_field_device", "gndt_route_field", "gndt_descend_routes_device", "gndt_descend_routes", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
                  "gndt_shard_stats_device", "gndt_finalize_stats_device",
                  "gndt_pcd_read", "gndt_pack_points_device", "gndt_build_cloud", "gndt_get_origin",
                  "gndt_count_morton", "gndt_morton_to_xy", "gndt_device_info", "gndt_set_profiling", "gndt_get_phase_times"):

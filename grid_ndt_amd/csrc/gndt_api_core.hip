@@ -29,6 +29,9 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP: t.clearance_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_OBSTACLE_TALLY: t.obstacle_tally = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP: t.route_field_one_workgroup = value != 0.0; return GNDT_OK;
+        case GNDT_DEBUG_VIEW_THREADS:
+            if (!(value >= 64.0 && value <= 1024.0) || value != (double)(int)value || ((int)value & 63)) return GNDT_ERR_INVALID;
+            t.view_threads = (int)value; return GNDT_OK;
         case GNDT_DEBUG_WALK_STEP_TABLE: if (!(value == 0.0 || value == 1.0 || value == 2.0)) return GNDT_ERR_INVALID; t.walk_step_table = (int)value; return GNDT_OK;
         case GNDT_DEBUG_QUERY_ILP: if (!(value == 1.0 || value == 2.0 || value == 4.0)) return GNDT_ERR_INVALID; t.query_ilp = (int)value; return GNDT_OK;
         case GNDT_DEBUG_CLEAR_EXTENT: if (!(value == 0.0 || value == 1.0)) return GNDT_ERR_INVALID; t.clear_extent = value != 0.0; return GNDT_OK;

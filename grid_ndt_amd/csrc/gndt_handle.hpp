@@ -16,6 +16,7 @@
 //   gndt_api_clearance.hip  clearance field: per slope the steps to the nearest barrier, and where it is
 //   gndt_api_route_field.hip route field: per slope the least cost to a set of goals and the step to take, routes by descent
 //   gndt_api_obstacle.hip   obstacle field: per slope the steps to the nearest slope a box of the caller's list stands on
+//   gndt_api_view.hip       view gain: per pose the distinct unknown and known columns a fan of rays crosses (the handle owns nothing for it)
 //   gndt_api_walk.hip       path walks: candidate polylines driven over the map's slopes under the flood's gates
 //   gndt_api_coarsen.hip  map pyramids: a coarser map of the same stream from the node table
 //   gndt_api_merge.hip  map merge: one map's node table folded into another's under a rigid transform
@@ -441,7 +442,8 @@ struct Tuning {
     bool clearance_one_workgroup = true;   // GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP   0: every round of the clearance field its own launch
     bool obstacle_tally = false;           // GNDT_DEBUG_OBSTACLE_TALLY            1: the obstacle field's marking pass keeps the tallies gndt_debug_obstacle_marks reads
     bool route_field_one_workgroup = true; // GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 0: every sweep of the route field its own launch
-    int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE           gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
+    int view_threads = 1024;               // GNDT_DEBUG_VIEW_THREADS              threads of a view gain workgroup at most (64 .. 1024, whole waves; same records at every value)
+    int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE          gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's
                                  //   level range (lost its A/B on the S4 frame: walk 1057 against 958 µs)
     uint32_t blocked_min_points = 1u << 20;   // GNDT_DEBUG_BLOCKED_MIN_POINTS   points from which a build may take BLOCKED buckets (65 536 .. 2^20; tests lower it)

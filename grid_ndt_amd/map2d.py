@@ -521,6 +521,7 @@ class TwoDmap:
     DEBUG_COLUMN_DEST = 11          # blocked builds with the two-kernel tail: 1 (the default) orders by the column table, 0 by the staged nodes
     DEBUG_PLACE_EMIT_WORDS = 12     # bitmap words up to which ordering and emit are one kernel: 0 .. 2^24 (16 384 by default; 0: always two)
     DEBUG_ROUTE_FIELD_ONE_WORKGROUP = 14   # 0: every sweep of the route field its own launch (1 by default)
+    DEBUG_VIEW_THREADS = 15                # threads of a view_gain workgroup at most: a multiple of 64 in 64 .. 1024 (1024 by default)
     DEBUG_OBSTACLE_TALLY = 13       # 1: the obstacle field's marking pass keeps the tallies of gndt_debug_obstacle_marks (0 by default)
 
     @staticmethod
@@ -1536,6 +1537,105 @@ class TwoDmap:
             ends = torch.stack([float(T[a, 3]) + float(max_range) * ((float(T[a, 0]) * x + float(T[a, 1]) * y) + float(T[a, 2]) * z)
                                 for a in range(3)], 1).to(torch.float32)
         return self.cast_rays(np.asarray(T[:, 3], np.float32), ends, **kw)
+
+    # ---- view gain (gndt_view_gain*: the unknown columns a sensor would see from each of K poses) ----
+    VIEW_INFO_DTYPE = np.dtype([("rays", np.uint32), ("skipped", np.uint32), ("hits", np.uint32), ("unknown", np.uint32), ("known", np.uint32),
+                                ("status", np.uint32), ("steps", np.uint64), ("sum_ux", np.int64), ("sum_uy", np.int64)])
+
+    def view_gain(self, poses, directions, max_range, min_count=0, min_range=0.0, per_ray=False, stream=None, host=False):
+        """How much a sensor would learn at each of K `poses` ([K, 12], [K, 3, 4], [K, 4, 4] or one matrix, [R | t], map <- sensor): the
+        rays t -> t + max_range * R dir of the fan `directions` ([N, 3|4] float32, sensor frame; rollouts.view_directions) are walked
+        through the map until a node with count >= min_count (0 = 1) at least min_range away stops them, and the DISTINCT columns they
+        cross are counted (include/gndt.h "view gain" defines every word).  Returns a dict of [K] arrays, one per field of
+        gndt_view_info: rays, skipped, hits, unknown (crossed columns that are not in the map: what there is to learn), known, status (1:
+        the pose's origin is not finite or has no key), steps (column visits: the work), sum_ux, sum_uy (sums of the unknown columns'
+        contiguous cell indices: sum / unknown is where the unknown lies); with per_ray=True also `row` and `range` [K, N], cast_rays'
+        for every ray.  max_range / grid_len is limited by the LDS of a workgroup (GndtError beyond; coarsen() the map for longer
+        ranges).  Torch tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited; numpy
+        arrays through gndt_view_gain with host=True."""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+        prm = _lib.ViewParams(float(max_range), float(min_range), int(min_count))
+        fields = self.VIEW_INFO_DTYPE.names
+        def flat(p):
+            """numpy poses -> float64 [K, 12]: also the flat [K, 12] frontier_views returns, and one pose as [12]"""
+            p = p.detach().cpu().numpy() if hasattr(p, "detach") else np.asarray(p, np.float64)
+            if p.ndim in (1, 2) and p.shape[-1] == 12:
+                return np.ascontiguousarray(p, np.float64).reshape(-1, 12)
+            return self._as_poses(p)
+        if host:
+            T = flat(poses)
+            d = directions.detach().cpu().numpy() if hasattr(directions, "detach") else directions
+            d = np.ascontiguousarray(d, np.float32)
+            if d.ndim != 2 or d.shape[1] not in (3, 4):
+                raise ValueError("directions must be [N, 3] or [N, 4]")
+            K, n = T.shape[0], d.shape[0]
+            raw = np.zeros(K, self.VIEW_INFO_DTYPE)
+            row = np.full((K, n), -1, np.int32) if per_ray else None
+            rng = np.full((K, n), np.nan, np.float32) if per_ray else None
+            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
+            self._check(self._L.gndt_view_gain(self._h, p(T), K, p(d), n, 4 * d.shape[1], C.byref(prm), p(raw), p(row), p(rng)))
+            out = {k: raw[k] for k in fields}
+        else:
+            import torch
+            dev = f"cuda:{self.device}"
+            with _torch_stream_ctx(stream):
+                if isinstance(poses, torch.Tensor) and poses.is_cuda:
+                    T = poses.to(torch.float64)
+                    if T.dim() == 1:
+                        T = T[None]
+                    elif T.dim() == 2 and T.shape[1] != 12:
+                        T = T[None]
+                    if T.dim() == 3:
+                        if T.shape[1] not in (3, 4) or T.shape[2] != 4:
+                            raise ValueError("poses must be [K, 12], [K, 3, 4], [K, 4, 4] or one such matrix")
+                        T = T[:, :3, :].reshape(-1, 12)
+                    T = T.contiguous()
+                else:
+                    T = torch.from_numpy(flat(poses)).to(dev)
+                d = directions if isinstance(directions, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(directions, np.float32))
+                d = d.to(device=dev, dtype=torch.float32).contiguous()
+                if d.dim() != 2 or d.shape[1] not in (3, 4):
+                    raise ValueError("directions must be [N, 3] or [N, 4]")
+                K, n = int(T.shape[0]), int(d.shape[0])
+                raw = torch.zeros((K, 12), dtype=torch.int32, device=dev)
+                row = torch.full((K, n), -1, dtype=torch.int32, device=dev) if per_ray else None
+                rng = torch.full((K, n), float("nan"), dtype=torch.float32, device=dev) if per_ray else None
+            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
+            self._check(self._L.gndt_view_gain_device(self._h, p(T), K, p(d), n, 4 * int(d.shape[1]), C.byref(prm), p(raw), p(row), p(rng),
+                                                      _stream_ptr(stream)))
+            wide = raw.view(torch.int64)             # (views: nothing is enqueued behind the caller's stream)
+            out = {k: raw[:, i] for i, k in enumerate(fields[:6])}
+            out.update(steps=wide[:, 3], sum_ux=wide[:, 4], sum_uy=wide[:, 5])
+        if per_ray:
+            out.update(row=row, range=rng)
+        return out
+
+    def frontier_views(self, fr, yaws=8, height=1.0, which="best"):
+        """Candidate sensor poses for view_gain: per cluster of frontiers() and per yaw j * 2 pi / yaws (about the map's z), the pose
+        whose origin is frontier_points(fr, which) lifted by `height` and whose x axis (view_directions' forward) looks along the yaw.
+        Returns float64 [K * yaws, 12] (pose k * yaws + j; row-major 3 x 4 [R | t]), torch for a torch `fr`, numpy otherwise.  A cluster
+        of size 0 gives NaN poses, which view_gain answers with status 1."""
+        pts = self.frontier_points(fr, which)
+        on_dev = not isinstance(pts, np.ndarray)
+        yaws = int(yaws)
+        a = np.arange(yaws, dtype=np.float64) * (2.0 * np.pi / yaws)
+        R = np.zeros((yaws, 3, 4))
+        R[:, 0, 0], R[:, 0, 1], R[:, 1, 0], R[:, 1, 1], R[:, 2, 2] = np.cos(a), -np.sin(a), np.sin(a), np.cos(a), 1.0
+        if on_dev:
+            import torch
+            Rt = torch.from_numpy(R).to(pts.device)
+            T = Rt[None].repeat(pts.shape[0], 1, 1, 1)
+            t = pts.double()
+            t = torch.stack([t[:, 0], t[:, 1], t[:, 2] + float(height)], 1)
+            T[:, :, :, 3] = t[:, None, :]
+            T[torch.isnan(t).any(1)] = float("nan")
+            return T.reshape(-1, 12)
+        T = np.repeat(R[None], pts.shape[0], axis=0)
+        t = pts.astype(np.float64) + np.array([0.0, 0.0, float(height)])
+        T[:, :, :, 3] = t[:, None, :]
+        T[np.isnan(t).any(1)] = np.nan
+        return T.reshape(-1, 12)
 
     # ---- scan scoring (gndt_score_poses*: the NDT match score of a scan for a batch of poses) ----
     @staticmethod

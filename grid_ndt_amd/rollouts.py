@@ -84,3 +84,21 @@ def headings(paths):
     h = xp.where((live & ~has_next)[..., None], prev, h)
     out = cat([p, h], -1)
     return xp.where(live[..., None], out, xp.full_like(out, float("nan")))
+
+
+def view_directions(h_fov, v_fov, n_h, n_v):
+    """Unit vectors of a sensor's fan for TwoDmap.view_gain / cast_scan: float32 [n_h * n_v, 3] in the sensor frame (x forward, y left,
+    z up), direction iv * n_h + ih = (cos e cos a, cos e sin a, sin e) with the azimuths a spread evenly over the horizontal field of
+    view h_fov and the elevations e over the vertical one v_fov (radians, both centred on the x axis; n = 1 looks along it).  A
+    full turn (h_fov >= 2 pi) leaves out its far end, which is its near end again."""
+    def spread(fov, n):
+        n = int(n)
+        if n <= 1:
+            return np.zeros(max(n, 0))
+        if fov >= 2.0 * np.pi:
+            return -np.pi + np.arange(n) * (2.0 * np.pi / n)
+        return np.linspace(-0.5 * fov, 0.5 * fov, n)
+    a, e = spread(float(h_fov), n_h), spread(float(v_fov), n_v)
+    ce = np.cos(e)[:, None]
+    d = np.stack([ce * np.cos(a)[None, :], ce * np.sin(a)[None, :], np.broadcast_to(np.sin(e)[:, None], (len(e), len(a)))], 2)
+    return np.ascontiguousarray(d.reshape(-1, 3), np.float32)

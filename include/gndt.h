@@ -1385,6 +1385,65 @@ int gndt_cast_rays_device(gndt_handle* h, const void* origins_dev, size_t origin
 int gndt_cast_rays(gndt_handle* h, const void* origins_host, size_t origin_stride_bytes, const void* ends_host, size_t n,
                    size_t end_stride_bytes, const gndt_cast_params* params, const gndt_cast_out* out_host, gndt_cast_stats* stats);
 
+/* ---- view gain: the unknown columns a sensor would see from each of K poses ---------------------------------------------------
+ * What a next-best-view planner divides by the cost of getting there: gndt_frontiers* gives candidate places, gndt_route_field* the cost
+ * to reach them, and this call how much a sensor standing there would learn.  For each of K poses a fan of N rays is walked through
+ * the map, and the DISTINCT columns the rays cross before something stops them are counted, split into columns the map has and columns
+ * it has not.  It cannot be composed from gndt_cast_rays*: a cast says where a ray stopped, not which columns it crossed, and the rays
+ * of a fan cross the same columns many times over near the sensor, so the walk has to mark a set.
+ * "Unknown" is GNDT_FRONTIER_OPEN_COLUMN's rule: the map cannot tell a column nobody has looked at from one that was seen empty, so a
+ * column that is not in the map is unknown.
+ * The answer is a DEFINITION (tests/view_ref.py restates it with sets of columns):
+ *   - inputs: K poses, fp64 [K, 12], row-major 3 x 4 [R | t], map <- sensor (the layout gndt_score_poses* takes); N directions (x, y, z)
+ *     in the sensor frame, fp32 at dir_stride_bytes 12 or 16, shared by all poses; max_range is the struct's float, widened.
+ *   - ray (k, i): origin o = float32(t); end e_a = float32(t_a + max_range * ((R_a0 x + R_a1 y) + R_a2 z)), formed in fp64 in exactly
+ *     this order, no product fused with a sum.  The walk is "ray casting"'s in GNDT_CAST_VOXEL mode with its max_range set to
+ *     max_range, min_count (0 = 1) and min_range as there: the columns of the walk in order, until a column holds a counting candidate
+ *     (the hit) or the cut point's column has been given.  A ray whose origin or end is not finite or has no key is SKIPPED.
+ *   - sets: every column the walk of a ray that is not skipped is given, up to and including the column of its hit, is SEEN by pose k.  A
+ *     seen column that is not in the map is UNKNOWN, every other seen column is KNOWN.
+ *   - the record of pose k (gndt_view_info): rays (not skipped), skipped, hits; unknown and known, the DISTINCT columns of either kind;
+ *     status 0, or 1 when the pose's origin is not finite or has no key (every ray is then skipped); steps, the column visits summed over
+ *     the rays (the call's work); sum_ux and sum_uy, the sums of c(sx) and c(sy) over the distinct unknown columns, c(s) = s > 0 ? s - 1 : s
+ *     the contiguous cell index: sum / unknown is where the unknown lies, the direction to turn the sensor to.
+ *   Everything is integer arithmetic over a set: the record does not depend on the order of the directions or of the threads, and
+ *   directions given several times change only rays, skipped, hits and steps.
+ *   - per ray, optional (row and range, [K, N], each may be NULL): the cast's row and range of that ray, bit for bit what
+ *     gndt_cast_rays* in VOXEL mode gives for the same origins and ends (GNDT_NO_ROW and +inf for a miss, GNDT_NO_ROW and NaN skipped).
+ * Window and limit: with reach = ceil(max_range / grid_len) + 1, every column a ray of pose k can be given lies within `reach` columns of
+ * the origin's column on both axes (the cut point lies within max_range of the origin and the walk stays between the two columns; the
+ * one is for the float32 rounding of the cut point).  The two sets of a pose are two bitmaps of W * W bits, W = 2 reach + 1, held in the
+ * LDS of the one workgroup that walks the pose's rays.  A call whose bitmaps do not fit the LDS a workgroup can be granted (reach 403
+ * on a gfx950 CU's 160 KiB) returns GNDT_ERR_INVALID and names the largest reach it takes: lower max_range or look into a coarser map
+ * (gndt_coarsen_device).  There is no global-memory tier for larger windows.
+ * Order, lifetime and stream rules are the cast's: the call first finishes what gndt_sync finishes, then builds or reuses the map's
+ * column index, then enqueues one kernel on `hip_stream` (NULL = the handle's stream) and waits for nothing.  The map is not modified.
+ * There is no CPU path.  K == 0 or N == 0 returns GNDT_OK, launches nothing and writes nothing.
+ * GNDT_ERR_INVALID: null handle or params, null poses, directions or info with K > 0 and N > 0, K or N >= 2^31, a stride other than
+ * 12 or 16, max_range not finite or not > 0, min_range negative or not finite, a negative min_count, reserved != 0, a window beyond
+ * the limit above, (device entry point) poses_dev or info_dev not aligned to 8 bytes or another pointer not to 4, no finished build, a
+ * stream under hipGraph capture (the call is not recorded). */
+typedef struct gndt_view_params {
+    float max_range;         /* > 0, finite: the length of every ray                              */
+    float min_range;         /* >= 0: candidates nearer than this do not stop a ray               */
+    int32_t min_count;       /* 0 = 1: a node stops a ray from this many points on                */
+    uint32_t reserved[5];    /* 0                                                                 */
+} gndt_view_params;          /* 32 bytes */
+typedef struct gndt_view_info {
+    uint32_t rays, skipped, hits;
+    uint32_t unknown;        /* distinct seen columns that are not in the map                     */
+    uint32_t known;          /* distinct seen columns that are                                    */
+    uint32_t status;         /* 0; 1: the origin is not finite or has no key                      */
+    uint64_t steps;          /* column visits, summed over the rays                               */
+    int64_t sum_ux, sum_uy;  /* sums of the unknown columns' contiguous cell indices              */
+} gndt_view_info;            /* 48 bytes */
+/* Device poses, directions and outputs (info_dev [K]; row_dev, range_dev [K, N] or NULL). */
+int gndt_view_gain_device(gndt_handle* h, const double* poses_dev, size_t K, const void* dirs_dev, size_t n, size_t dir_stride_bytes,
+                          const gndt_view_params* params, gndt_view_info* info_dev, uint32_t* row_dev, float* range_dev, void* hip_stream);
+/* The same with host memory of any alignment, through a device scratch the handle owns and grows; synchronous. */
+int gndt_view_gain(gndt_handle* h, const double* poses_host, size_t K, const void* dirs_host, size_t n, size_t dir_stride_bytes,
+                   const gndt_view_params* params, gndt_view_info* info_host, uint32_t* row_host, float* range_host);
+
 /* ---- map pyramids: a coarser map of the same point stream, from the map alone --------------------------------------------------
  * The scan score has a basin of less than a cell (grid_ndt_amd/registration.py); coarse-to-fine registration needs the same cloud at
  * 2x, 4x ... the cell lengths, and a map grown by gndt_update*, cropped or cleared no longer has its points.  It does not need them:
@@ -1625,7 +1684,9 @@ int gndt_debug_enable_stamps(int on);
  *                                 emit in ONE kernel, larger ones in two; an integer in 0 .. 2^24, 0 = always two kernels (tests send
  *                                 small clouds through the two kernels of a production-size build)                   default 16 384
  *   GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP value == 0: gndt_route_field* launch every sweep on its own, the one-workgroup kernel that holds a
- *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1 */
+ *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1
+ *   GNDT_DEBUG_VIEW_THREADS       threads of a gndt_view_gain* workgroup at most, a multiple of 64 in 64 .. 1024 (a fan of fewer rays
+ *                                 takes fewer); the records do not depend on it (tests run several)                 default 1024 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1640,6 +1701,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_PLACE_EMIT_WORDS 12
 #define GNDT_DEBUG_OBSTACLE_TALLY 13
 #define GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 14
+#define GNDT_DEBUG_VIEW_THREADS 15
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
