@@ -4,8 +4,11 @@ The shared library is built in-tree by `build_native()` (hipcc, gfx950).  There 
 implementation of the path behind it: if the library is missing, loading raises.
 """
 import ctypes as C
+import functools
 import os
 import subprocess
+
+import numpy as np
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -83,11 +86,7 @@ class ScoreParams(C.Structure):
                 ("max_d2", C.c_float), ("point_pose", C.c_uint32)]
 
 
-class PoseScore(C.Structure):
-    _fields_ = [("score", C.c_double), ("d2_sum", C.c_double), ("matched", C.c_uint64), ("terms", C.c_uint64)]
-
-
-class PoseDerivs(C.Structure):
+class PoseDerivs(C.Structure):      # (the per-item records are RECORDS' dtypes below; this one mirror stays for the GPU tier, which reads its size)
     _fields_ = [("score", C.c_double), ("d2_sum", C.c_double), ("matched", C.c_uint64), ("terms", C.c_uint64),
                 ("g", C.c_double * 6), ("H", C.c_double * 21)]
 
@@ -109,18 +108,8 @@ class ViewParams(C.Structure):
     _fields_ = [("max_range", C.c_float), ("min_range", C.c_float), ("min_count", C.c_int32), ("reserved", C.c_uint32 * 5)]
 
 
-class ViewInfo(C.Structure):
-    _fields_ = [("rays", C.c_uint32), ("skipped", C.c_uint32), ("hits", C.c_uint32), ("unknown", C.c_uint32), ("known", C.c_uint32),
-                ("status", C.c_uint32), ("steps", C.c_uint64), ("sum_ux", C.c_int64), ("sum_uy", C.c_int64)]
-
-
 class PlanParams(C.Structure):
     _fields_ = [("start_mode", C.c_int32), ("max_expansions", C.c_uint32), ("scratch_bytes", C.c_uint64), ("reserved", C.c_uint32 * 4)]
-
-
-class RouteInfo(C.Structure):
-    _fields_ = [("status", C.c_int32), ("length", C.c_uint32), ("start_row", C.c_uint32), ("expansions", C.c_uint32),
-                ("queue_peak", C.c_uint32), ("cost", C.c_float), ("h_start", C.c_float), ("reserved", C.c_uint32)]
 
 
 class FrontierParams(C.Structure):
@@ -157,33 +146,14 @@ class WalkParams(C.Structure):
                 ("reserved", C.c_uint32 * 4)]
 
 
-class WalkInfo(C.Structure):
-    _fields_ = [("status", C.c_int32), ("stop_side", C.c_uint32), ("steps", C.c_uint32), ("waypoints", C.c_uint32),
-                ("start_row", C.c_uint32), ("end_row", C.c_uint32), ("length", C.c_float), ("climb", C.c_float),
-                ("rough_max", C.c_float), ("hops_min", C.c_uint32), ("reserved", C.c_uint32 * 2)]
-
-
 class ShortcutParams(C.Structure):
     _fields_ = [("window", C.c_uint32), ("checks", C.c_uint32), ("min_hops", C.c_uint32), ("max_links", C.c_uint32),
                 ("reserved", C.c_uint32 * 4)]
 
 
-class ShortcutInfo(C.Structure):
-    _fields_ = [("status", C.c_int32), ("length_in", C.c_uint32), ("waypoints", C.c_uint32), ("path_slopes", C.c_uint32),
-                ("links_tested", C.c_uint32), ("fallback_links", C.c_uint32), ("cost_in", C.c_float), ("cost_out", C.c_float),
-                ("hops_min", C.c_uint32), ("reserved", C.c_uint32 * 3)]
-
-
 class FootprintParams(C.Structure):
     _fields_ = [("half_length", C.c_float), ("half_width", C.c_float), ("max_dz", C.c_float), ("height", C.c_float),
                 ("min_cells", C.c_uint32), ("min_cover", C.c_float), ("weight", C.c_uint32), ("reserved", C.c_uint32 * 5)]
-
-
-class FootprintInfo(C.Structure):
-    _fields_ = [("status", C.c_int32), ("flags", C.c_uint32), ("centre_row", C.c_uint32), ("cells", C.c_uint16), ("support", C.c_uint16),
-                ("gaps", C.c_uint16), ("unknown", C.c_uint16), ("z", C.c_float), ("normal", C.c_float * 3), ("along", C.c_float),
-                ("across", C.c_float), ("rms", C.c_float), ("step_max", C.c_float), ("bump_max", C.c_float), ("headroom", C.c_float),
-                ("reserved", C.c_uint32)]
 
 
 class MergeParams(C.Structure):
@@ -302,6 +272,217 @@ def build_native(force=False, verbose=False, variant=None):
     return LIB_PATH
 
 
+# ---- the per-item records the library writes, each described ONCE: C typedef -> numpy structured dtype (tests/test_abi_layout_host.py
+# checks size and offsets against include/gndt.h).  A host twin hands out the fields of a zeroed array of the dtype; a device twin the
+# same fields as views of a [K, itemsize / 4] int32 tensor (record_views).  Field dtypes are the ones the host twins return — which is
+# why some are signed where the C field is not (rows come back with GNDT_NO_ROW as -1).
+ROUTE_INFO = np.dtype([("status", np.int32), ("length", np.uint32), ("start_row", np.uint32), ("expansions", np.uint32),
+                       ("queue_peak", np.uint32), ("cost", np.float32), ("h_start", np.float32), ("reserved", np.uint32)])
+WALK_INFO = np.dtype([("status", np.int32), ("stop_side", np.int32), ("steps", np.int32), ("waypoints", np.int32),
+                      ("start_row", np.int32), ("end_row", np.int32), ("length", np.float32), ("climb", np.float32),
+                      ("rough_max", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 2)])
+SHORTCUT_INFO = np.dtype([("status", np.int32), ("length_in", np.int32), ("waypoints", np.int32), ("path_slopes", np.int32),
+                          ("links_tested", np.int32), ("fallback_links", np.int32), ("cost_in", np.float32),
+                          ("cost_out", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 3)])
+FOOTPRINT_INFO = np.dtype([("status", np.int32), ("flags", np.uint32), ("centre_row", np.int32), ("cells", np.uint16),
+                           ("support", np.uint16), ("gaps", np.uint16), ("unknown", np.uint16), ("z", np.float32),
+                           ("normal", np.float32, 3), ("along", np.float32), ("across", np.float32), ("rms", np.float32),
+                           ("step_max", np.float32), ("bump_max", np.float32), ("headroom", np.float32), ("reserved", np.uint32)])
+VIEW_INFO = np.dtype([("rays", np.uint32), ("skipped", np.uint32), ("hits", np.uint32), ("unknown", np.uint32), ("known", np.uint32),
+                      ("status", np.uint32), ("steps", np.uint64), ("sum_ux", np.int64), ("sum_uy", np.int64)])
+POSE_SCORE = np.dtype([("score", np.float64), ("d2_sum", np.float64), ("matched", np.int64), ("terms", np.int64)])
+POSE_DERIVS = np.dtype(POSE_SCORE.descr + [("g", np.float64, 6), ("H", np.float64, 21)])   # H: the upper triangle, row-major
+FRONTIER = np.dtype([("label", np.int32), ("size", np.int32), ("best_row", np.int32), ("best_h", np.float32),
+                     ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
+                     ("sum_px", np.int64), ("sum_py", np.int64), ("sum_pz", np.int64), ("open_sides", np.int32), ("reserved", np.int32)])
+SCAN_CLUSTER = np.dtype([("label", np.uint32), ("cells", np.uint32), ("off_surface", np.uint32), ("unmapped", np.uint32),
+                         ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
+                         ("sz_min", np.int32), ("sz_max", np.int32), ("sum_x", np.int64), ("sum_y", np.int64), ("sum_z", np.int64),
+                         ("z_lo", np.float32), ("z_hi", np.float32)])
+RECORDS = {"gndt_route_info": ROUTE_INFO, "gndt_walk_info": WALK_INFO, "gndt_shortcut_info": SHORTCUT_INFO,
+           "gndt_footprint_info": FOOTPRINT_INFO, "gndt_view_info": VIEW_INFO, "gndt_pose_score": POSE_SCORE,
+           "gndt_pose_derivs": POSE_DERIVS, "gndt_frontier": FRONTIER, "gndt_scan_cluster": SCAN_CLUSTER}
+
+
+@functools.lru_cache(maxsize=None)
+def _record_columns(dtype):
+    """the fields of a record but `reserved`, as record_views needs them: (name, bytes of an element, its index among the elements of
+    that size (8: among the int64 view's), elements of a sub-array or 0, float?, bit shift of a 2-byte field in its word)"""
+    cols = []
+    for name in dtype.names:
+        if name == "reserved":
+            continue
+        field, offset = dtype.fields[name][:2]
+        base, shape = field.subdtype or (field, ())
+        size = base.itemsize
+        assert size in (2, 4, 8) and offset % size == 0 and len(shape) <= 1 and (size > 2 or not shape)
+        cols.append((name, size, offset // max(size, 4), shape[0] if shape else 0, base.kind == "f", 8 * (offset % 4)))
+    return tuple(cols)
+
+
+@functools.lru_cache(maxsize=None)
+def record_fields(dtype):
+    """the names a method hands out: the record's but `reserved`"""
+    return tuple(c[0] for c in _record_columns(dtype))
+
+
+@functools.lru_cache(maxsize=None)
+def record_is_wide(dtype):
+    """every field of the record is 8 bytes (gndt_pose_score, gndt_pose_derivs): its device tensor may be int64 from the start"""
+    return all(size == 8 for _, size, _, _, _, _ in _record_columns(dtype))
+
+
+@functools.lru_cache(maxsize=None)
+def _record_decoder(dtype):
+    """-> f(raw) -> {field: view} of a device tensor of records: the dict display a method would spell out by hand, written from the
+    dtype's offsets once and compiled, so that a call pays no loop over the fields (and no look at torch's module)"""
+    import torch
+    items, sizes = [], set()
+    for name, size, at, count, is_float, shift in _record_columns(dtype):
+        sizes.add((size, is_float))
+        if size == 2:
+            expr = f"(raw[:, {at}] >> {shift}) & 0xFFFF" if shift else f"raw[:, {at}] & 0xFFFF"
+        else:
+            cols = "raw" if size == 4 else ("wide_f" if is_float else "wide")
+            expr = f"{cols}[:, {at}:{at + count}]" if count else f"{cols}[:, {at}]"
+            if size == 4 and is_float:
+                expr += ".view(f32)"
+        items.append(f"{name!r}: {expr}")
+    env = {"f32": torch.float32, "i64": torch.int64, "f64": torch.float64}
+    body = "{" + ", ".join(items) + "}"
+    if (8, False) not in sizes and (8, True) not in sizes:
+        return eval("lambda raw: " + body, env)
+    # (an int64 tensor is its own wide view; a tensor without rows has nothing to view)
+    src = ("def decode(raw):\n"
+           "    wide = raw if raw.dtype == i64 else (raw.view(i64) if len(raw) else raw.new_zeros((0, raw.shape[1] // 2), dtype=i64))\n"
+           + ("    wide_f = wide.view(f64)\n" if (8, True) in sizes else "")
+           + "    return " + body + "\n")
+    exec(src, env)
+    return env["decode"]
+
+
+def record_views(raw, dtype):
+    """A [K, dtype.itemsize / 4] int32 torch tensor of records (or, for a record of 8-byte fields only, the [K, itemsize / 8] int64
+    one) -> {field: view}, every column derived from the dtype's offsets: a 4-byte field is a column (as float32 for a float), an
+    8-byte field a column of the int64 view (of its float64 view for a float), a 2-byte field its word shifted and masked (the one
+    entry that is computed, not a view), a sub-array a column slice.  Integer fields are int32 / int64 whatever their sign in the
+    record: the bits are the library's.  `reserved` is left out."""
+    return _record_decoder(dtype)(raw)
+
+
+def _prototypes():
+    """name -> argtypes of every function of include/gndt.h the binding calls (None: left unset).  restype is c_int but for _RESTYPES."""
+    vp, sz, u64, u32, i32, H, P = C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_int32, C.c_void_p, C.POINTER
+    f32p, i32p, u64p = P(C.c_float), P(i32), P(u64)
+    T = {
+        "gndt_create": [P(Params), P(H)],
+        "gndt_destroy": [H],
+        "gndt_last_error": [H],
+        "gndt_set_origin": [H, f32p],
+        "gndt_get_origin": [H, f32p],
+        "gndt_build": [H, vp, sz, sz],
+        "gndt_update": [H, vp, sz, sz],
+        "gndt_remove": [H, vp, sz, sz],
+        "gndt_reset": [H, vp],
+        "gndt_accumulate_device": [H, vp, sz, sz, u64, vp],
+        "gndt_finalize_device": [H, vp],
+        "gndt_sync": [H, u64p, u64p, u64p],
+        "gndt_export_device": [H, P(Cells)],
+        "gndt_export": [H, P(Cells)],
+        "gndt_export_host": [H, P(Cells)],
+        "gndt_reserve": [H, u64, u64],
+        "gndt_set_deferred_emit": [H, C.c_int],
+        "gndt_stats_export_device": [H, P(Stats), vp],
+        "gndt_stats_merge_device": [H, P(Stats), vp],
+        "gndt_shard_stats_device": [H, vp, sz, sz, u64, P(Stats), vp],
+        "gndt_finalize_stats_device": [H, P(Stats), u64, vp],
+        "gndt_pcd_read": [C.c_char_p, P(Pcd), C.c_char_p],
+        "gndt_pcd_free": [P(Pcd)],
+        "gndt_pack_points_device": [H, vp, sz, P(PointLayout), vp, u64p, vp],
+        "gndt_build_cloud": [H, vp, sz, P(PointLayout)],
+        "gndt_compute_cost": [H, f32p, P(Robot), vp],
+        "gndt_cost_export_device": [H, P(vp), P(vp), P(CostStats)],
+        "gndt_cost_export": [H, vp, vp, P(CostStats)],
+        "gndt_query": [H, vp, sz, sz, i32, vp, vp, vp],
+        "gndt_crop": [H, P(CropBox), i32],
+        "gndt_crop_box_from_world": [f32p, C.c_float, f32p, f32p, P(CropBox)],
+        "gndt_raster_shape": [P(CropBox), P(u32), P(u32)],
+        "gndt_raster": [H, P(CropBox), i32, C.c_float, P(RasterLayers)],
+        "gndt_clear_rays": [H, f32p, vp, sz, sz, P(ClearParams), vp, P(ClearStats)],
+        "gndt_score_poses": [H, vp, sz, sz, vp, u32, P(ScoreParams), vp, vp, vp],
+        "gndt_score_derivs": [H, vp, sz, sz, vp, u32, P(ScoreParams), vp],
+        "gndt_score_maps_device": [H, H, vp, u32, P(ScoreParams), vp, vp, vp, vp],
+        "gndt_score_maps_derivs_device": [H, H, vp, u32, P(ScoreParams), vp, vp],
+        "gndt_cast_rays": [H, vp, sz, vp, sz, sz, P(CastParams), P(CastOut), P(CastStats)],
+        "gndt_view_gain": [H, vp, sz, vp, sz, sz, P(ViewParams), vp, vp, vp],
+        "gndt_plan_routes": [H, vp, sz, sz, P(PlanParams), vp, u32, vp],
+        "gndt_frontiers": [H, P(CropBox), P(FrontierParams), vp, vp, u32, vp],
+        "gndt_segment_scan": [H, vp, sz, sz, vp, P(SegmentParams), vp, vp, vp, u32, vp],
+        "gndt_clearance": [H, P(Robot), P(ClearanceParams), vp, vp, vp, vp],
+        # (the device twin also takes the box count where it lies on the device: not the host's arguments plus a stream)
+        "gndt_obstacle_field": [H, P(Robot), vp, u32, sz, P(ObstacleParams), vp, vp, vp, vp],
+        "gndt_obstacle_field_device": [H, P(Robot), vp, u32, sz, vp, P(ObstacleParams), vp, vp, vp, vp, vp],
+        "gndt_route_field": [H, P(Robot), P(RouteFieldParams), vp, u32, vp, vp, vp, vp, vp],
+        "gndt_descend_routes": [H, vp, sz, sz, P(DescendParams), vp, vp, vp, u32, vp],
+        "gndt_walk_paths": [H, vp, sz, sz, sz, P(Robot), P(WalkParams), vp, vp, u32, vp],
+        "gndt_shortcut_routes": [H, vp, sz, u32, vp, sz, P(Robot), P(ShortcutParams), vp, vp, u32, vp, u32, vp],
+        "gndt_footprint_poses": [H, vp, sz, sz, P(Robot), P(FootprintParams), vp, u32, vp],
+        "gndt_coarsen_device": [H, H, u32, u32, vp],
+        "gndt_merge_map_device": [H, H, vp, P(MergeParams), P(MergeStats), vp],
+        "gndt_trans_morton_xyz": [f32p, C.c_float, C.c_float, f32p, C.c_char_p, i32p, i32p, i32p, C.c_char_p],
+        "gndt_count_morton": [i32, i32, C.c_char_p],
+        "gndt_morton_to_xy": [i32, i32p, i32p],
+        "gndt_pack_key": [i32, i32, i32],
+        "gndt_unpack_key": [u64, i32p, i32p, i32p],
+        "gndt_set_profiling": [H, C.c_int],
+        "gndt_get_phase_times": [H, P(C.c_double)],
+        "gndt_debug_bucket_phases": [H, P(C.c_double), P(u32)],
+        "gndt_debug_retry_count": [H, u64p],
+        "gndt_debug_enable_stamps": [C.c_int],
+        "gndt_warmup": [H, u64],
+        "gndt_debug_set_option": [C.c_int, C.c_double],
+        "gndt_debug_poisoned_bytes": [u64p, u64p],
+        "gndt_debug_set_fp_bits": [C.c_int],
+        "gndt_debug_fp_clashes": [H, u64p],
+        "gndt_debug_second_pass_buckets": [H, u64p],
+        "gndt_debug_block_layout": [H, i32p],
+        "gndt_debug_obstacle_marks": [H, u64p],
+        "gndt_debug_fail_next_alloc": [H, C.c_int],
+        "gndt_comm_unique_id": [C.c_char_p],
+        "gndt_comm_create": [C.c_char_p, i32, i32, i32, P(vp)],
+        "gndt_comm_destroy": [vp],
+        "gndt_comm_create_threads": [i32, i32, P(vp)],
+        "gndt_comm_last_error": None,
+        "gndt_comm_selftest": [H, vp, P(CommSelftest), vp],
+        "gndt_build_global_device": [H, vp, vp, sz, sz, u64, u64, P(ExchangeTimes), vp],
+        "gndt_owner_of_columns": [vp, vp, sz, u32, vp],
+        "gndt_owner_sample_device": [H, vp, sz, sz, P(vp), u64p, vp],
+        "gndt_owner_map_device": [H, vp, u32, vp],
+        "gndt_owner_split_device": [H, vp, sz, sz, u64, u64, u32, P(vp), u64p, u64p, vp],
+        "gndt_build_records_device": [H, vp, sz, u64, vp],
+        "gndt_build_records2_device": [H, vp, sz, vp, sz, u64, vp],
+        "gndt_owned_columns_device": [H, P(vp), u64p, vp],
+        "gndt_owned_global_rows_device": [H, vp, u64, u64, P(vp), u64p, u64p, vp],
+        "gndt_build_owned_device": [H, vp, vp, sz, sz, u64, u64, P(vp), P(OwnedInfo), vp],
+        "gndt_gather_owned_map_device": [H, vp, i32, vp],
+        "gndt_owned_pack_rows_device": [H, P(vp), u64p, vp],
+        "gndt_adopt_rows_device": [H, vp, u64, u64, u64, u64, vp],
+        "gndt_locality_sample": [H, vp, sz, sz, u32, P(C.c_double), vp],
+        "gndt_last_strategy": [H],
+        "gndt_device_info": [i32, C.c_char_p, i32p, u64p],
+    }
+    # the device twins whose arguments are the host twin's with the stream behind them
+    for name in ("gndt_build", "gndt_update", "gndt_remove", "gndt_query", "gndt_crop", "gndt_raster", "gndt_clear_rays", "gndt_score_poses",
+                 "gndt_score_derivs", "gndt_cast_rays", "gndt_view_gain", "gndt_plan_routes", "gndt_frontiers", "gndt_segment_scan",
+                 "gndt_clearance", "gndt_route_field", "gndt_descend_routes", "gndt_walk_paths", "gndt_shortcut_routes",
+                 "gndt_footprint_poses"):
+        T[name + "_device"] = T[name] + [vp]
+    return T
+
+
+_RESTYPES = {"gndt_destroy": None, "gndt_last_error": C.c_char_p, "gndt_comm_last_error": C.c_char_p, "gndt_pcd_free": None,
+             "gndt_pack_key": C.c_uint64, "gndt_unpack_key": None, "gndt_comm_destroy": None}
+
 _lib = None
 
 
@@ -318,168 +499,10 @@ def lib():
     if os.path.exists(rt):
         C.CDLL(rt, mode=C.RTLD_GLOBAL)
     L = C.CDLL(LIB_PATH)
-    vp, sz, u64 = C.c_void_p, C.c_size_t, C.c_uint64
-    H = C.c_void_p
-    L.gndt_create.argtypes = [C.POINTER(Params), C.POINTER(H)]
-    L.gndt_destroy.argtypes = [H]
-    L.gndt_destroy.restype = None
-    L.gndt_last_error.argtypes = [H]
-    L.gndt_last_error.restype = C.c_char_p
-    L.gndt_set_origin.argtypes = [H, C.POINTER(C.c_float)]
-    L.gndt_build.argtypes = [H, vp, sz, sz]
-    L.gndt_build_device.argtypes = [H, vp, sz, sz, vp]
-    L.gndt_update.argtypes = [H, vp, sz, sz]
-    L.gndt_update_device.argtypes = [H, vp, sz, sz, vp]
-    L.gndt_remove.argtypes = [H, vp, sz, sz]
-    L.gndt_remove_device.argtypes = [H, vp, sz, sz, vp]
-    L.gndt_reset.argtypes = [H, vp]
-    L.gndt_accumulate_device.argtypes = [H, vp, sz, sz, u64, vp]
-    L.gndt_finalize_device.argtypes = [H, vp]
-    L.gndt_sync.argtypes = [H, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
-    L.gndt_export_device.argtypes = [H, C.POINTER(Cells)]
-    L.gndt_export.argtypes = [H, C.POINTER(Cells)]
-    L.gndt_export_host.argtypes = [H, C.POINTER(Cells)]
-    L.gndt_reserve.argtypes = [H, u64, u64]
-    L.gndt_set_deferred_emit.argtypes = [H, C.c_int]
-    L.gndt_set_deferred_emit.restype = C.c_int
-    L.gndt_reserve.restype = C.c_int
-    L.gndt_export_host.restype = C.c_int
-    L.gndt_stats_export_device.argtypes = [H, C.POINTER(Stats), vp]
-    L.gndt_stats_merge_device.argtypes = [H, C.POINTER(Stats), vp]
-    L.gndt_shard_stats_device.argtypes = [H, vp, C.c_size_t, C.c_size_t, u64, C.POINTER(Stats), vp]
-    L.gndt_finalize_stats_device.argtypes = [H, C.POINTER(Stats), u64, vp]
-    L.gndt_get_origin.argtypes = [H, C.POINTER(C.c_float)]
-    L.gndt_pcd_read.argtypes = [C.c_char_p, C.POINTER(Pcd), C.c_char_p]
-    L.gndt_pcd_free.argtypes = [C.POINTER(Pcd)]
-    L.gndt_pcd_free.restype = None
-    L.gndt_pack_points_device.argtypes = [H, vp, C.c_size_t, C.POINTER(PointLayout), vp, C.POINTER(u64), vp]
-    L.gndt_build_cloud.argtypes = [H, vp, C.c_size_t, C.POINTER(PointLayout)]
-    L.gndt_compute_cost.argtypes = [H, C.POINTER(C.c_float), C.POINTER(Robot), vp]
-    L.gndt_cost_export_device.argtypes = [H, C.POINTER(vp), C.POINTER(vp), C.POINTER(CostStats)]
-    L.gndt_cost_export.argtypes = [H, vp, vp, C.POINTER(CostStats)]
-    L.gndt_query_device.argtypes = [H, vp, sz, sz, C.c_int32, vp, vp, vp, vp]
-    L.gndt_query.argtypes = [H, vp, sz, sz, C.c_int32, vp, vp, vp]
-    L.gndt_crop_device.argtypes = [H, C.POINTER(CropBox), C.c_int32, vp]
-    L.gndt_crop.argtypes = [H, C.POINTER(CropBox), C.c_int32]
-    L.gndt_crop_box_from_world.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(CropBox)]
-    L.gndt_raster_shape.argtypes = [C.POINTER(CropBox), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    L.gndt_raster_device.argtypes = [H, C.POINTER(CropBox), C.c_int32, C.c_float, C.POINTER(RasterLayers), vp]
-    L.gndt_raster.argtypes = [H, C.POINTER(CropBox), C.c_int32, C.c_float, C.POINTER(RasterLayers)]
-    L.gndt_clear_rays_device.argtypes = [H, C.POINTER(C.c_float), vp, sz, sz, C.POINTER(ClearParams), vp, C.POINTER(ClearStats), vp]
-    L.gndt_clear_rays.argtypes = [H, C.POINTER(C.c_float), vp, sz, sz, C.POINTER(ClearParams), vp, C.POINTER(ClearStats)]
-    L.gndt_score_poses_device.argtypes = [H, vp, sz, sz, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp, vp, vp]
-    L.gndt_score_poses.argtypes = [H, vp, sz, sz, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp, vp]
-    L.gndt_score_derivs_device.argtypes = [H, vp, sz, sz, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp]
-    L.gndt_score_derivs.argtypes = [H, vp, sz, sz, vp, C.c_uint32, C.POINTER(ScoreParams), vp]
-    L.gndt_score_maps_device.argtypes = [H, H, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp, vp, vp]
-    L.gndt_score_maps_derivs_device.argtypes = [H, H, vp, C.c_uint32, C.POINTER(ScoreParams), vp, vp]
-    L.gndt_cast_rays_device.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(CastParams), C.POINTER(CastOut), C.POINTER(CastStats), vp]
-    L.gndt_cast_rays.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(CastParams), C.POINTER(CastOut), C.POINTER(CastStats)]
-    L.gndt_view_gain_device.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(ViewParams), vp, vp, vp, vp]
-    L.gndt_view_gain.argtypes = [H, vp, sz, vp, sz, sz, C.POINTER(ViewParams), vp, vp, vp]
-    L.gndt_plan_routes_device.argtypes = [H, vp, sz, sz, C.POINTER(PlanParams), vp, C.c_uint32, vp, vp]
-    L.gndt_plan_routes.argtypes = [H, vp, sz, sz, C.POINTER(PlanParams), vp, C.c_uint32, vp]
-    L.gndt_frontiers_device.argtypes = [H, C.POINTER(CropBox), C.POINTER(FrontierParams), vp, vp, C.c_uint32, vp, vp]
-    L.gndt_frontiers.argtypes = [H, C.POINTER(CropBox), C.POINTER(FrontierParams), vp, vp, C.c_uint32, vp]
-    L.gndt_segment_scan_device.argtypes = [H, vp, sz, sz, vp, C.POINTER(SegmentParams), vp, vp, vp, C.c_uint32, vp, vp]
-    L.gndt_segment_scan.argtypes = [H, vp, sz, sz, vp, C.POINTER(SegmentParams), vp, vp, vp, C.c_uint32, vp]
-    L.gndt_clearance_device.argtypes = [H, C.POINTER(Robot), C.POINTER(ClearanceParams), vp, vp, vp, vp, vp]
-    L.gndt_clearance.argtypes = [H, C.POINTER(Robot), C.POINTER(ClearanceParams), vp, vp, vp, vp]
-    L.gndt_obstacle_field_device.argtypes = [H, C.POINTER(Robot), vp, C.c_uint32, sz, vp, C.POINTER(ObstacleParams), vp, vp, vp, vp, vp]
-    L.gndt_obstacle_field.argtypes = [H, C.POINTER(Robot), vp, C.c_uint32, sz, C.POINTER(ObstacleParams), vp, vp, vp, vp]
-    L.gndt_route_field_device.argtypes = [H, C.POINTER(Robot), C.POINTER(RouteFieldParams), vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
-    L.gndt_route_field.argtypes = [H, C.POINTER(Robot), C.POINTER(RouteFieldParams), vp, C.c_uint32, vp, vp, vp, vp, vp]
-    L.gndt_descend_routes_device.argtypes = [H, vp, sz, sz, C.POINTER(DescendParams), vp, vp, vp, C.c_uint32, vp, vp]
-    L.gndt_descend_routes.argtypes = [H, vp, sz, sz, C.POINTER(DescendParams), vp, vp, vp, C.c_uint32, vp]
-    L.gndt_walk_paths_device.argtypes = [H, vp, sz, sz, sz, C.POINTER(Robot), C.POINTER(WalkParams), vp, vp, C.c_uint32, vp, vp]
-    L.gndt_walk_paths.argtypes = [H, vp, sz, sz, sz, C.POINTER(Robot), C.POINTER(WalkParams), vp, vp, C.c_uint32, vp]
-    L.gndt_shortcut_routes_device.argtypes = [H, vp, sz, C.c_uint32, vp, sz, C.POINTER(Robot), C.POINTER(ShortcutParams), vp, vp, C.c_uint32, vp,
-                                              C.c_uint32, vp, vp]
-    L.gndt_shortcut_routes.argtypes = [H, vp, sz, C.c_uint32, vp, sz, C.POINTER(Robot), C.POINTER(ShortcutParams), vp, vp, C.c_uint32, vp,
-                                       C.c_uint32, vp]
-    L.gndt_footprint_poses_device.argtypes = [H, vp, sz, sz, C.POINTER(Robot), C.POINTER(FootprintParams), vp, C.c_uint32, vp, vp]
-    L.gndt_footprint_poses.argtypes = [H, vp, sz, sz, C.POINTER(Robot), C.POINTER(FootprintParams), vp, C.c_uint32, vp]
-    L.gndt_coarsen_device.argtypes = [H, H, C.c_uint32, C.c_uint32, vp]
-    L.gndt_merge_map_device.argtypes = [H, H, vp, C.POINTER(MergeParams), C.POINTER(MergeStats), vp]
-    L.gndt_trans_morton_xyz.argtypes = [C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float), C.c_char_p,
-                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p]
-    L.gndt_count_morton.argtypes = [C.c_int32, C.c_int32, C.c_char_p]
-    L.gndt_morton_to_xy.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.gndt_pack_key.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.gndt_pack_key.restype = u64
-    L.gndt_unpack_key.argtypes = [u64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.gndt_unpack_key.restype = None
-    L.gndt_set_profiling.argtypes = [H, C.c_int]
-    L.gndt_get_phase_times.argtypes = [H, C.POINTER(C.c_double)]
-    L.gndt_debug_bucket_phases.argtypes = [H, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
-    L.gndt_debug_bucket_phases.restype = C.c_int
-    L.gndt_debug_retry_count.argtypes = [H, C.POINTER(u64)]
-    L.gndt_debug_retry_count.restype = C.c_int
-    L.gndt_debug_enable_stamps.argtypes = [C.c_int]
-    L.gndt_debug_enable_stamps.restype = C.c_int
-    L.gndt_warmup.argtypes = [C.c_void_p, C.c_uint64]
-    L.gndt_warmup.restype = C.c_int
-    L.gndt_debug_set_option.argtypes = [C.c_int, C.c_double]
-    L.gndt_debug_set_option.restype = C.c_int
-    L.gndt_debug_poisoned_bytes.argtypes = [C.POINTER(u64), C.POINTER(u64)]
-    L.gndt_debug_poisoned_bytes.restype = C.c_int
-    L.gndt_debug_set_fp_bits.argtypes = [C.c_int]
-    L.gndt_debug_set_fp_bits.restype = C.c_int
-    L.gndt_debug_fp_clashes.argtypes = [H, C.POINTER(u64)]
-    L.gndt_debug_fp_clashes.restype = C.c_int
-    L.gndt_debug_second_pass_buckets.argtypes = [H, C.POINTER(u64)]
-    L.gndt_debug_second_pass_buckets.restype = C.c_int
-    L.gndt_debug_block_layout.argtypes = [H, C.POINTER(C.c_int32)]
-    L.gndt_debug_block_layout.restype = C.c_int
-    L.gndt_debug_obstacle_marks.argtypes = [H, C.POINTER(u64)]
-    L.gndt_debug_obstacle_marks.restype = C.c_int
-    L.gndt_debug_fail_next_alloc.argtypes = [H, C.c_int]
-    L.gndt_debug_fail_next_alloc.restype = C.c_int
-    L.gndt_comm_unique_id.argtypes = [C.c_char_p]
-    L.gndt_comm_create.argtypes = [C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.gndt_comm_destroy.argtypes = [vp]
-    L.gndt_comm_create_threads.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp)]
-    L.gndt_comm_create_threads.restype = C.c_int
-    L.gndt_comm_destroy.restype = None
-    L.gndt_comm_last_error.restype = C.c_char_p
-    L.gndt_comm_selftest.argtypes = [H, vp, C.POINTER(CommSelftest), vp]
-    L.gndt_comm_selftest.restype = C.c_int
-    L.gndt_build_global_device.argtypes = [H, vp, vp, C.c_size_t, C.c_size_t, u64, u64, C.POINTER(ExchangeTimes), vp]
-    L.gndt_owner_of_columns.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp]
-    L.gndt_owner_of_columns.restype = C.c_int
-    L.gndt_owner_sample_device.argtypes = [H, vp, C.c_size_t, C.c_size_t, C.POINTER(vp), C.POINTER(u64), vp]
-    L.gndt_owner_map_device.argtypes = [H, vp, C.c_uint32, vp]
-    L.gndt_owner_sample_device.restype = L.gndt_owner_map_device.restype = C.c_int
-    L.gndt_owner_split_device.argtypes = [H, vp, C.c_size_t, C.c_size_t, u64, u64, C.c_uint32, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), vp]
-    L.gndt_build_records_device.argtypes = [H, vp, C.c_size_t, u64, vp]
-    L.gndt_build_records2_device.argtypes = [H, vp, C.c_size_t, vp, C.c_size_t, u64, vp]
-    L.gndt_build_records2_device.restype = C.c_int
-    L.gndt_owned_columns_device.argtypes = [H, C.POINTER(vp), C.POINTER(u64), vp]
-    L.gndt_owned_global_rows_device.argtypes = [H, vp, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64), vp]
-    L.gndt_build_owned_device.argtypes = [H, vp, vp, C.c_size_t, C.c_size_t, u64, u64, C.POINTER(vp), C.POINTER(OwnedInfo), vp]
-    L.gndt_gather_owned_map_device.argtypes = [H, vp, C.c_int32, vp]
-    L.gndt_owned_pack_rows_device.argtypes = [H, C.POINTER(vp), C.POINTER(u64), vp]
-    L.gndt_adopt_rows_device.argtypes = [H, vp, u64, u64, u64, u64, vp]
-    for name in ("gndt_gather_owned_map_device", "gndt_owned_pack_rows_device", "gndt_adopt_rows_device"):
-        getattr(L, name).restype = C.c_int
-    for name in ("gndt_comm_unique_id", "gndt_comm_create", "gndt_build_global_device", "gndt_owner_split_device",
-                 "gndt_build_records_device", "gndt_owned_columns_device", "gndt_owned_global_rows_device", "gndt_build_owned_device"):
-        getattr(L, name).restype = C.c_int
-    L.gndt_locality_sample.argtypes = [H, vp, C.c_size_t, C.c_size_t, C.c_uint32, C.POINTER(C.c_double), vp]
-    L.gndt_locality_sample.restype = C.c_int
-    L.gndt_last_strategy.argtypes = [H]
-    L.gndt_last_strategy.restype = C.c_int
-    L.gndt_device_info.argtypes = [C.c_int32, C.c_char_p, C.POINTER(C.c_int32), C.POINTER(u64)]
-    for name in ("gndt_create", "gndt_set_origin", "gndt_build", "gndt_build_device", "gndt_update", "gndt_update_device",
-                 "gndt_remove", "gndt_remove_device",
-                 "gndt_reset", "gndt_accumulate_device", "gndt_finalize_device", "gndt_sync", "gndt_export_device",
-                 "gndt_export", "gndt_stats_export_device", "gndt_stats_merge_device", "gndt_trans_morton_xyz",
-                 "gndt_compute_cost", "gndt_cost_export_device", "gndt_cost_export", "gndt_query_device", "gndt_query",
-                 "gndt_crop_device", "gndt_crop", "gndt_crop_box_from_world", "gndt_raster_shape", "gndt_raster_device", "gndt_raster", "gndt_clear_rays_device", "gndt_clear_rays",
-                 "gndt_score_poses_device", "gndt_score_poses", "gndt_score_derivs_device", "gndt_score_derivs", "gndt_score_maps_device", "gndt_score_maps_derivs_device", "gndt_cast_rays_device", "gndt_cast_rays", "gndt_view_gain_device", "gndt_view_gain", "gndt_plan_routes_device", "gndt_plan_routes", "gndt_frontiers_device", "gndt_frontiers", "gndt_segment_scan_device", "gndt_segment_scan", "gndt_clearance_device", "gndt_clearance", "gndt_obstacle_field_device", "gndt_obstacle_field", "gndt_route_field_device", "gndt_route_field", "gndt_descend_routes_device", "gndt_descend_routes", "gndt_walk_paths_device", "gndt_walk_paths", "gndt_shortcut_routes_device", "gndt_shortcut_routes", "gndt_footprint_poses_device", "gndt_footprint_poses", "gndt_coarsen_device", "gndt_merge_map_device",
-                 "gndt_shard_stats_device", "gndt_finalize_stats_device",
-                 "gndt_pcd_read", "gndt_pack_points_device", "gndt_build_cloud", "gndt_get_origin",
-                 "gndt_count_morton", "gndt_morton_to_xy", "gndt_device_info", "gndt_set_profiling", "gndt_get_phase_times"):
-        getattr(L, name).restype = C.c_int
+    for name, argtypes in _prototypes().items():
+        fn = getattr(L, name)
+        if argtypes is not None:
+            fn.argtypes = argtypes
+        fn.restype = _RESTYPES.get(name, C.c_int)
     _lib = L
     return L

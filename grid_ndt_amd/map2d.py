@@ -11,42 +11,24 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import CastOut, CastParams, CastStats, Cells, ClearParams, ClearStats, CropBox, CostStats, ExchangeTimes, FrontierParams, GndtError, MergeParams, MergeStats, OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteInfo, ScoreParams, SegmentParams, ShortcutParams, Stats, WalkInfo, WalkParams
+from ._arrays import DeviceArrays, HostArrays, _stream_ptr, _stream_wait, _torch_stream_ctx   # noqa: F401 (tools read _stream_ptr here)
+from ._lib import (CastOut, CastParams, CastStats, Cells, ClearanceParams, ClearParams, ClearStats, CommSelftest, CropBox, CostStats,
+                   DescendParams, ExchangeTimes, FootprintParams, FrontierParams, GndtError, MergeParams, MergeStats, ObstacleParams,
+                   OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteFieldParams, ScoreParams, SegmentParams,
+                   ShortcutParams, Stats, ViewParams, WalkParams)
 
 DEMANDS = {"slope": 0, "true": 1}
 FLAG_HAS_STATS, FLAG_SLOPE, FLAG_DOWN = 1, 2, 4
+_ROBOT_DEFAULTS = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)     # RobotSphere(0.25), robot.h:38-46
 
 
-_HIP_STREAM_LEGACY = 1      # hipStreamLegacy ((hipStream_t)1): the null stream by its explicit name
+_ROUTE_HOST_AS = {"start_row": np.int32}       # gndt_route_info on the host: start_row with GNDT_NO_ROW as -1
+_FOOT_HOST_AS = {"flags": np.int32}            # gndt_footprint_info on the host: the flags as the signed words the device hands out
 
 
-def _stream_ptr(stream):
-    """libgndt takes NULL as "the handle's own (non-blocking) stream".  torch's default stream IS the null stream
-    (cuda_stream == 0), and work the caller enqueues there — filling the input buffer, say — is not ordered with a
-    non-blocking stream: the null stream is therefore passed by its explicit name, hipStreamLegacy."""
-    if stream is None:
-        try:
-            import torch
-            if torch.cuda.is_available():
-                return C.c_void_p(torch.cuda.current_stream().cuda_stream or _HIP_STREAM_LEGACY)
-        except ImportError:
-            pass
-        return C.c_void_p(0)
-    if hasattr(stream, "cuda_stream"):
-        return C.c_void_p(stream.cuda_stream or _HIP_STREAM_LEGACY)
-    return C.c_void_p(int(stream))
-
-
-def _torch_stream_ctx(stream):
-    """torch's current stream := `stream` while tensors that the call's kernels read or write are made, so that the caching allocator
-    ties them to the stream the kernels run on.  A raw hipStream_t is wrapped (torch.cuda.ExternalStream); None: torch's current one."""
-    import contextlib
-    if stream is None:
-        return contextlib.nullcontext()
-    import torch
-    if not hasattr(stream, "cuda_stream"):
-        stream = torch.cuda.ExternalStream(int(stream))
-    return torch.cuda.stream(stream)
+def _enum(table, value):
+    """a mode by its name in `table`, or by its number"""
+    return table[value] if isinstance(value, str) else int(value)
 
 
 class _DevArray:
@@ -70,6 +52,7 @@ class TwoDmap:
         self.cloudFirst = None
         self._h = None
         self._demand = None
+        self._fns, self._torch_device = {}, None
 
     # ---- setters / getters with the reference's names (map2D.h:487-502) ----
     def getGridLen(self):
@@ -128,7 +111,7 @@ class TwoDmap:
             raise GndtError(rc, msg.decode() if msg else "")
 
     def _ensure(self, demand, need_origin=True):
-        d = DEMANDS[demand] if isinstance(demand, str) else int(demand)
+        d = _enum(DEMANDS, demand)
         if self._h is not None and self._demand == d:
             return
         self._destroy()
@@ -145,6 +128,39 @@ class TwoDmap:
         if self.cloudFirst is not None:
             o = (C.c_float * 3)(*self.cloudFirst)
             self._check(self._L.gndt_set_origin(self._h, o))
+
+    def _handle(self):
+        """the consumers' preamble: a map that was never built still has a handle to ask (with the demand it was last given)"""
+        if self._h is None:
+            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+
+    def _call(self, be, name, *args):
+        """gndt_<name>_device with the backend's stream behind the arguments, or gndt_<name> (the pair is looked up once a map)"""
+        fns = self._fns.get(name)
+        if fns is None:
+            fns = self._fns[name] = (getattr(self._L, "gndt_" + name), getattr(self._L, "gndt_" + name + "_device"))
+        rc = fns[1](self._h, *args, _stream_ptr(be.stream)) if be.on_dev else fns[0](self._h, *args)
+        if rc:
+            self._check(rc)
+
+    def _cuda(self):
+        """the handle's device as torch names it"""
+        if self._torch_device is None:
+            import torch
+            self._torch_device = torch.device("cuda", self.device)
+        return self._torch_device
+
+    @staticmethod
+    def _robot(robot):
+        """-> (byref(gndt_robot) or None for the library's defaults, the dict with the defaults filled in)"""
+        d = dict(_ROBOT_DEFAULTS)
+        if robot is None:
+            return None, d
+        d.update(robot)
+        return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"])), d
+
+    def _robot_ref(self, robot):
+        return None if robot is None else self._robot(robot)[0]
 
     @staticmethod
     def _as_input(points):
@@ -240,17 +256,9 @@ class TwoDmap:
 
     def stats_export(self, stream=None):
         """Device-resident sufficient statistics as torch tensors (views of libgndt memory)."""
-        import torch
         st = Stats()
         self._check(self._L.gndt_stats_export_device(self._h, C.byref(st), _stream_ptr(stream)))
-        n = int(st.num_nodes)
-        dev = f"cuda:{self.device}"
-        if n == 0:
-            return {"key": torch.zeros(0, dtype=torch.int64, device=dev), "sums": torch.zeros(0, 9, dtype=torch.float64, device=dev),
-                    "count": torch.zeros(0, dtype=torch.int32, device=dev), "first_idx": torch.zeros(0, dtype=torch.int32, device=dev)}
-        mk = lambda p, shape, ts: torch.as_tensor(_DevArray(p, shape, ts, self), device=dev)
-        return {"key": mk(st.key, (n,), "<i8"), "sums": mk(st.sums, (n, 9), "<f8"),
-                "count": mk(st.count, (n,), "<i4"), "first_idx": mk(st.first_idx, (n,), "<i4")}
+        return self._stats_tensors(st)
 
     def _stats_tensors(self, st):
         import torch
@@ -405,7 +413,6 @@ class TwoDmap:
 
     def comm_selftest(self, comm, stream=None, demand="slope"):
         """gndt_comm_selftest: one verified round of every collective the sharded builds use (all ranks call it together)."""
-        from ._lib import CommSelftest
         self._ensure(demand, need_origin=False)
         rep = CommSelftest()
         self._check(self._L.gndt_comm_selftest(self._h, comm.handle, C.byref(rep), _stream_ptr(stream)))
@@ -564,12 +571,7 @@ class TwoDmap:
         reachable_height, max_rough, max_angle_deg (defaults: RobotSphere(0.25), robot.h:38-46).
         Returns the statistics dict; h / state per result row come from cost_export()."""
         g = (C.c_float * 3)(*[float(v) for v in goal])
-        rb = None
-        if robot is not None:
-            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
-        self._check(self._L.gndt_compute_cost(self._h, g, rb, _stream_ptr(stream)))
+        self._check(self._L.gndt_compute_cost(self._h, g, self._robot_ref(robot), _stream_ptr(stream)))
         st = CostStats()
         self._check(self._L.gndt_cost_export(self._h, None, None, C.byref(st)))
         return self._cost_stats(st)
@@ -592,8 +594,7 @@ class TwoDmap:
 
     # ---- route planning (gndt_plan_routes*: AstarPlanar::findRoute, GlobalPlan.h:49-166, for a batch of starts) ----
     ROUTE_STATUS = {0: "found", 1: "no_start", 2: "no_route", 3: "limit", 4: "no_goal"}
-    ROUTE_INFO_DTYPE = np.dtype([("status", np.int32), ("length", np.uint32), ("start_row", np.uint32), ("expansions", np.uint32),
-                                 ("queue_peak", np.uint32), ("cost", np.float32), ("h_start", np.float32), ("reserved", np.uint32)])
+    ROUTE_INFO_DTYPE = _lib.ROUTE_INFO
 
     def plan_routes(self, starts, start_mode="node", route_cap=None, max_expansions=0, stream=None, host=False, scratch_bytes=0):
         """The reference planner's routes from `starts` ([K,3] or [K,4] float32) to the goal of the last computeCost, one device call
@@ -603,13 +604,15 @@ class TwoDmap:
         info: dict of [K] arrays status (ROUTE_STATUS), length, start_row (int32, -1: none), expansions, queue_peak, cost, h_start.
         torch CUDA starts are answered on the device (torch tensors, enqueued on `stream`, default torch's current stream, not awaited);
         host=True or a host array goes through gndt_plan_routes (numpy)."""
+        # (one of the three small calls a planner makes thousands of times a second — query and score_poses are the others: their two
+        # branches stay written out, the single body over a backend costs them a microsecond in twenty; DESIGN 4.5b)
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         ptr, K, stride, on_dev, keep = self._as_input(starts)
         if route_cap is None:
             route_cap = max(min(int(self.sync()[2]), 1024), 1)
         route_cap = int(route_cap)
-        prm = PlanParams(self.QUERY_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), int(max_expansions), int(scratch_bytes))
+        prm = PlanParams(_enum(self.QUERY_MODES, start_mode), int(max_expansions), int(scratch_bytes))
         if on_dev and host:
             ptr, K, stride, on_dev, keep = self._as_input(keep.detach().cpu().numpy())
         if on_dev:
@@ -620,17 +623,13 @@ class TwoDmap:
             self._check(self._L.gndt_plan_routes_device(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
                                                         C.c_void_p(rows.data_ptr() if K and route_cap else 0), route_cap,
                                                         C.c_void_p(raw.data_ptr() if K else 0), _stream_ptr(stream)))
-            info = {"status": raw[:, 0], "length": raw[:, 1], "start_row": raw[:, 2], "expansions": raw[:, 3], "queue_peak": raw[:, 4],
-                    "cost": raw[:, 5].view(torch.float32), "h_start": raw[:, 6].view(torch.float32)}
-            return rows, info
+            return rows, _lib.record_views(raw, _lib.ROUTE_INFO)
         rows = np.empty((K, route_cap), np.int32)
-        raw = np.zeros(K, self.ROUTE_INFO_DTYPE)
+        raw = np.zeros(K, _lib.ROUTE_INFO)
         self._check(self._L.gndt_plan_routes(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
                                              C.c_void_p(rows.ctypes.data if K and route_cap else 0), route_cap,
                                              C.c_void_p(raw.ctypes.data if K else 0)))
-        info = {k: raw[k] for k in ("status", "length", "expansions", "queue_peak", "cost", "h_start")}
-        info["start_row"] = raw["start_row"].view(np.int32)
-        return rows, info
+        return rows, HostArrays.fields(raw, _lib.ROUTE_INFO, _ROUTE_HOST_AS)
 
     def findRoute(self, start):
         """AstarPlanar::findRoute(start -> the goal of the last computeCost): the route as a list of rows of export(), start slope
@@ -653,9 +652,10 @@ class TwoDmap:
         whose mean z is nearest the point's z.  A torch CUDA tensor is answered on the device (torch int32 rows, enqueued on `stream`,
         default torch's current stream); a host array through gndt_query (numpy).  cost=True also returns the cost map's h (float32,
         FLT_MAX where there is no row) and state (int32) of every row: (rows, h, state)."""
+        # (a hot small call: its two branches stay written out, see plan_routes)
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        m = self.QUERY_MODES[mode] if isinstance(mode, str) else int(mode)
+            self._handle()
+        m = _enum(self.QUERY_MODES, mode)
         ptr, n, stride, on_dev, keep = self._as_input(points)
         if on_dev:
             import torch
@@ -689,10 +689,9 @@ class TwoDmap:
         """The same for an inclusive box of signed column indices (sx_min, sx_max, sy_min, sy_max); mode "keep_inside" / "drop_inside"
         (or GNDT_CROP_*).  Enqueued on `stream` (default torch's current stream); the counts are read by the next sync / export."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        m = self.CROP_MODES[mode] if isinstance(mode, str) else int(mode)
+            self._handle()
         b = CropBox(*[int(v) for v in box])
-        self._check(self._L.gndt_crop_device(self._h, C.byref(b), m, _stream_ptr(stream)))
+        self._check(self._L.gndt_crop_device(self._h, C.byref(b), _enum(self.CROP_MODES, mode), _stream_ptr(stream)))
 
     # ---- raster export (gndt_raster*: one pixel per column of a box, the reference's showBottom / showSlopeList, map2D.h:980-1284) ----
     RASTER_MODES = {"lowest": 0, "highest": 1, "nearest_z": 2}
@@ -707,8 +706,8 @@ class TwoDmap:
         "state" (int32, 0 there) of the cost map.  Torch tensors on the handle's device enqueued on `stream` (default torch's current
         stream), or numpy arrays through gndt_raster with host=True.  Also returns x0, y0 (the world centre of pixel (0, 0)) and res."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        m = self.RASTER_MODES[mode] if isinstance(mode, str) else int(mode)
+            self._handle()
+        m = _enum(self.RASTER_MODES, mode)
         if z_ref is None:
             z_ref = float("nan") if m == self.RASTER_MODES["nearest_z"] else 0.0
         layers = tuple(layers)
@@ -717,22 +716,10 @@ class TwoDmap:
                 raise ValueError(f"unknown raster layer {name!r} (one of {', '.join(self.RASTER_LAYERS)})")
         b = CropBox(*[int(v) for v in box])
         w, ht = raster_shape(box)
-        out = {}
-        if host:
-            for name in layers:
-                out[name] = np.empty((ht, w), self.RASTER_LAYERS[name])
-            ptr = lambda name: C.c_void_p(out[name].ctypes.data if name in out else 0)
-        else:
-            import torch
-            tdt = {np.int32: torch.int32, np.float32: torch.float32}
-            for name in layers:
-                out[name] = torch.empty((ht, w), dtype=tdt[self.RASTER_LAYERS[name]], device=f"cuda:{self.device}")
-            ptr = lambda name: C.c_void_p(out[name].data_ptr() if name in out else 0)
-        L = RasterLayers(*[ptr(name) for name in ("row", "z", "rough", "nodes", "h", "state")])
-        if host:
-            self._check(self._L.gndt_raster(self._h, C.byref(b), m, float(z_ref), C.byref(L)))
-        else:
-            self._check(self._L.gndt_raster_device(self._h, C.byref(b), m, float(z_ref), C.byref(L), _stream_ptr(stream)))
+        be = HostArrays if host else DeviceArrays(self._cuda(), stream)
+        out = {name: be.empty((ht, w), self.RASTER_LAYERS[name]) for name in layers}
+        L = RasterLayers(*[be.ptr(out.get(name)) for name in ("row", "z", "rough", "nodes", "h", "state")])
+        self._call(be, "raster", C.byref(b), m, float(z_ref), C.byref(L))
         sx0 = _first_nonzero(b.sx_min)
         sy0 = _first_nonzero(b.sy_min)
         out.update(x0=_column_centre(self.cloudFirst[0], self.gridLen, sx0), y0=_column_centre(self.cloudFirst[1], self.gridLen, sy0),
@@ -742,9 +729,7 @@ class TwoDmap:
     # ---- frontier extraction (gndt_frontiers*: the slopes where the known map ends, clustered on the device) ----
     FRONTIER_CANDIDATES = {"reached": 0, "slopes": 1}
     FRONTIER_OPEN_RULES = {"column": 0, "level": 1}
-    FRONTIER_DTYPE = np.dtype([("label", np.int32), ("size", np.int32), ("best_row", np.int32), ("best_h", np.float32),
-                               ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
-                               ("sum_px", np.int64), ("sum_py", np.int64), ("sum_pz", np.int64), ("open_sides", np.int32), ("reserved", np.int32)])
+    FRONTIER_DTYPE = _lib.FRONTIER
 
     def frontiers(self, candidates="reached", open_rule="column", level_reach=1, min_open=1, link_dz=1, min_size=1, box=None, labels=False,
                   max_clusters=None, stream=None, host=False):
@@ -760,10 +745,11 @@ class TwoDmap:
         tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited: the arrays then have
         max_clusters entries, filled from the front, with size 0 behind the counts[0] the call found.  Or numpy arrays through
         gndt_frontiers with host=True, cut to min(counts[0], max_clusters) entries."""
+        # (left with its two branches written out: the single body over a backend cost its device twin 0.9 us in 61, DESIGN 4.5b;
+        # the records are decoded through the record table like everywhere else)
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        prm = FrontierParams(self.FRONTIER_CANDIDATES[candidates] if isinstance(candidates, str) else int(candidates),
-                             self.FRONTIER_OPEN_RULES[open_rule] if isinstance(open_rule, str) else int(open_rule),
+            self._handle()
+        prm = FrontierParams(_enum(self.FRONTIER_CANDIDATES, candidates), _enum(self.FRONTIER_OPEN_RULES, open_rule),
                              int(level_reach), int(min_open), int(link_dz), int(min_size))
         b = C.byref(CropBox(*[int(v) for v in box])) if box is not None else None
         n = int(self.sync()[0]) if labels else 0
@@ -776,10 +762,10 @@ class TwoDmap:
             if max_clusters is None:
                 call(None, 0)
                 max_clusters = int(counts[0])
-            recs = np.zeros(int(max_clusters), self.FRONTIER_DTYPE)
+            recs = np.zeros(int(max_clusters), _lib.FRONTIER)
             call(recs, len(recs))
             recs = recs[:min(int(counts[0]), len(recs))]
-            out = {k: recs[k] for k in self.FRONTIER_DTYPE.names if k != "reserved"}
+            out = HostArrays.fields(recs, _lib.FRONTIER)
         else:
             import torch
             dev = f"cuda:{self.device}"
@@ -794,12 +780,9 @@ class TwoDmap:
                 with _torch_stream_ctx(stream):         # (read on the stream the count was enqueued on: the copy waits for it)
                     max_clusters = int(counts[0].item())
             with _torch_stream_ctx(stream):
-                recs = torch.zeros((int(max_clusters), 16), dtype=torch.int32, device=dev)
+                recs = torch.zeros((int(max_clusters), _lib.FRONTIER.itemsize // 4), dtype=torch.int32, device=dev)
             call(recs, recs.shape[0])
-            wide = recs.view(torch.int64)
-            out = {"label": recs[:, 0], "size": recs[:, 1], "best_row": recs[:, 2], "best_h": recs[:, 3].view(torch.float32),
-                   "sx_min": recs[:, 4], "sx_max": recs[:, 5], "sy_min": recs[:, 6], "sy_max": recs[:, 7],
-                   "sum_px": wide[:, 4], "sum_py": wide[:, 5], "sum_pz": wide[:, 6], "open_sides": recs[:, 14]}
+            out = _lib.record_views(recs, _lib.FRONTIER)
         out["counts"] = counts
         if labels:
             out["labels"] = label
@@ -850,40 +833,21 @@ class TwoDmap:
         the order left, right, forward, back; 0xFF for a row without a slope) — each only when asked for — and `counts` ([4]: sources,
         slopes with finite hops, the largest finite hops, 0).  Torch tensors on the handle's device, enqueued on `stream` (default
         torch's current stream) and not awaited; or numpy arrays through gndt_clearance with host=True."""
-        from ._lib import ClearanceParams
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if isinstance(sources, str):
             sources = (sources,)
         mask = int(sources) if not hasattr(sources, "__iter__") else sum({self.CLEARANCE_SOURCES[s] for s in sources})
         prm = ClearanceParams(mask, int(max_hops))
-        rb = None
-        if robot is not None:
-            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        rb = self._robot_ref(robot)
         want = {"hops": (hops, np.int32), "nearest": (nearest, np.int32), "sides": (sides, np.uint8)}
         n = int(self.sync()[0])
         room = max(n, 1)           # (an empty map still names its outputs: a NULL one means "not asked for")
-        out = {}
-        if host:
-            for k, (on, dt) in want.items():
-                if on:
-                    out[k] = np.empty(room, dt)
-            out["counts"] = np.zeros(4, np.int32)
-            ptr = lambda k: C.c_void_p(out[k].ctypes.data if k in out else 0)
-            self._check(self._L.gndt_clearance(self._h, rb, C.byref(prm), ptr("hops"), ptr("nearest"), ptr("sides"), ptr("counts")))
-        else:
-            import torch
-            dev = f"cuda:{self.device}"
-            with _torch_stream_ctx(stream):
-                for k, (on, dt) in want.items():
-                    if on:
-                        out[k] = torch.empty(room, dtype=torch.int32 if dt is np.int32 else torch.uint8, device=dev)
-                out["counts"] = torch.zeros(4, dtype=torch.int32, device=dev)
-            ptr = lambda k: C.c_void_p(out[k].data_ptr() if k in out else 0)
-            self._check(self._L.gndt_clearance_device(self._h, rb, C.byref(prm), ptr("hops"), ptr("nearest"), ptr("sides"), ptr("counts"),
-                                                      _stream_ptr(stream)))
+        be = HostArrays if host else DeviceArrays(self._cuda(), stream)
+        with be.ctx():
+            out = {k: be.empty(room, dt) for k, (on, dt) in want.items() if on}
+            out["counts"] = be.zeros(4, np.int32)
+        self._call(be, "clearance", rb, C.byref(prm), *[be.ptr(out.get(k)) for k in ("hops", "nearest", "sides", "counts")])
         for k in want:
             if k in out:
                 out[k] = out[k][:n]
@@ -925,14 +889,9 @@ class TwoDmap:
         slopes with finite obstacle hops, the largest of those, boxes, boxes covering a slope, slopes in reach, dropped boxes, 0).
         Torch tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited, for torch boxes
         or a segment_scan() dict; numpy arrays through gndt_obstacle_field for numpy boxes or host=True."""
-        from ._lib import ObstacleParams
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-        rb = None
-        if robot is not None:
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+            self._handle()
+        rb, d = self._robot(robot)
         if levels_above is None:
             levels_above = int(np.ceil(2.0 * float(d["radius"]) / self.zLen))
         prm = ObstacleParams(int(inflate), int(max_hops), int(levels_above), int(levels_below), int(max_columns))
@@ -942,45 +901,30 @@ class TwoDmap:
         room = max(n, 1)
         if base is not None and int(base.shape[0]) != n:
             raise ValueError(f"base has {int(base.shape[0])} entries, the map {n} rows: a clearance field of another map")
-        to_np = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
         count_dev = None
         if isinstance(boxes, dict):                        # segment_scan()'s answer
             if isinstance(boxes["label"], np.ndarray) or host:
+                to_np = lambda v: v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)
                 six = np.stack([to_np(boxes[k]) for k in ("sx_min", "sx_max", "sy_min", "sy_max", "sz_min", "sz_max")], 1)
                 boxes = six[:min(int(to_np(boxes["counts"])[0]), len(six))]
             else:                                          # on the device: the records where they lie, cut by counts[0] there
                 boxes, count_dev = boxes["sx_min"], boxes["counts"]
         on_dev = hasattr(boxes, "is_cuda") and boxes.is_cuda and not host
+        be = DeviceArrays(boxes.device, stream) if on_dev else HostArrays
         if count_dev is not None:
             keep, nb, stride = boxes, int(boxes.shape[0]), 4 * int(boxes.stride(0)) if boxes.shape[0] else 72
-        elif on_dev:
-            import torch
-            keep = boxes.to(torch.int32).contiguous().reshape(-1, 6)
-            nb, stride = int(keep.shape[0]), 24
         else:
-            keep = np.ascontiguousarray(to_np(boxes), dtype=np.int32).reshape(-1, 6)
+            keep = be.here(boxes, np.int32).reshape(-1, 6)
             nb, stride = int(keep.shape[0]), 24
-        out = {}
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                out["hops"] = torch.empty(room, dtype=torch.int32, device=keep.device)
-                if obstacle:
-                    out["obstacle"] = torch.empty(room, dtype=torch.int32, device=keep.device)
-                out["counts"] = torch.zeros(8, dtype=torch.int32, device=keep.device)
-                bs = None if base is None else torch.as_tensor(base.view(np.int32) if isinstance(base, np.ndarray) else base, device=keep.device).contiguous()
-            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            self._check(self._L.gndt_obstacle_field_device(self._h, rb, p(keep), nb, stride, p(count_dev), C.byref(prm), p(bs), p(out["hops"]),
-                                                           p(out.get("obstacle")), p(out["counts"]), _stream_ptr(stream)))
-        else:
-            out["hops"] = np.empty(room, np.int32)
+        with be.ctx():
+            out = {"hops": be.empty(room, np.int32)}
             if obstacle:
-                out["obstacle"] = np.empty(room, np.int32)
-            out["counts"] = np.zeros(8, np.int32)
-            bs = None if base is None else np.ascontiguousarray(to_np(base)).view(np.uint32)
-            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_obstacle_field(self._h, rb, p(keep), nb, stride, C.byref(prm), p(bs), p(out["hops"]), p(out.get("obstacle")),
-                                                    p(out["counts"])))
+                out["obstacle"] = be.empty(room, np.int32)
+            out["counts"] = be.zeros(8, np.int32)
+            bs = be.here(base, np.int32)
+        # (only the device twin can read the box count where a device scan left it)
+        self._call(be, "obstacle_field", rb, be.ptr(keep), nb, stride, *([be.ptr(count_dev)] if be.on_dev else []), C.byref(prm), be.ptr(bs),
+                   be.ptr(out["hops"]), be.ptr(out.get("obstacle")), be.ptr(out["counts"]))
         for k in ("hops", "obstacle"):
             if k in out:
                 out[k] = out[k][:n]
@@ -1008,9 +952,7 @@ class TwoDmap:
     WALK_STATUS = {0: "done", 1: "no_start", 2: "blocked", 3: "left_map", 4: "overhead", 5: "too_close", 6: "limit"}
     WALK_START_MODES = {"nearest_slope": 1, "node": 2}
     WALK_NO_SIDE = -1          # GNDT_WALK_NO_SIDE as the int32 stop_side comes back in
-    WALK_INFO_DTYPE = np.dtype([("status", np.int32), ("stop_side", np.int32), ("steps", np.int32), ("waypoints", np.int32),
-                                ("start_row", np.int32), ("end_row", np.int32), ("length", np.float32), ("climb", np.float32),
-                                ("rough_max", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 2)])
+    WALK_INFO_DTYPE = _lib.WALK_INFO
 
     def walk_paths(self, paths, robot=None, start_mode="nearest_slope", overhead=False, hops=None, min_hops=0, max_steps=0, rows=0,
                    stream=None, host=False):
@@ -1025,7 +967,7 @@ class TwoDmap:
         `rows` [K, rows] (int32, -1 behind a walk's end) when asked.  torch tensors on the paths' device, enqueued on `stream` (default
         torch's current stream) and not awaited; host=True or a numpy array goes through gndt_walk_paths (numpy)."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         on_dev = hasattr(paths, "is_cuda") and paths.is_cuda and not host
         if hasattr(paths, "detach") and not on_dev:
             paths = paths.detach().cpu().numpy()
@@ -1034,56 +976,26 @@ class TwoDmap:
         K, T, stride = int(paths.shape[0]), int(paths.shape[1]), 4 * int(paths.shape[2])
         if isinstance(hops, dict):
             hops = hops["hops"]
-        prm = WalkParams(self.WALK_START_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), 1 if overhead else 0,
-                         int(min_hops), int(max_steps))
-        rb = None
-        if robot is not None:
-            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        prm = WalkParams(_enum(self.WALK_START_MODES, start_mode), 1 if overhead else 0, int(min_hops), int(max_steps))
+        rb = self._robot_ref(robot)
         row_cap = int(rows)
         n = int(self.sync()[0])
         if hops is not None and int(hops.shape[0]) != n:
             raise ValueError(f"hops has {int(hops.shape[0])} entries, the map {n} rows: a clearance field of another map")
-        names = ("status", "stop_side", "steps", "waypoints", "start_row", "end_row", "length", "climb", "rough_max", "hops_min")
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                p = paths.contiguous().float()
-                if isinstance(hops, np.ndarray):
-                    hops = np.ascontiguousarray(hops).view(np.int32)
-                hp = None if hops is None else torch.as_tensor(hops, device=p.device).contiguous()
-                if hp is not None and hp.dtype != torch.int32:
-                    hp = hp.to(torch.int32)
-                raw = torch.zeros((max(K, 1), 12), dtype=torch.int32, device=p.device)
-                out_rows = torch.empty((K, row_cap), dtype=torch.int32, device=p.device) if row_cap else None
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            self._check(self._L.gndt_walk_paths_device(self._h, ptr(p), K, T, stride, rb, C.byref(prm), ptr(hp),
-                                                       C.c_void_p(out_rows.data_ptr()) if row_cap else None, row_cap,
-                                                       C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
-            raw = raw[:K]
-            out = {k: (raw[:, i].view(torch.float32) if k in ("length", "climb", "rough_max") else raw[:, i]) for i, k in enumerate(names)}
-        else:
-            p = np.ascontiguousarray(paths, np.float32)
-            hp = None if hops is None else np.ascontiguousarray(hops.cpu().numpy() if hasattr(hops, "cpu") else hops).view(np.uint32)
-            raw = np.zeros(max(K, 1), self.WALK_INFO_DTYPE)
-            out_rows = np.empty((K, row_cap), np.int32) if row_cap else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_walk_paths(self._h, ptr(p), K, T, stride, rb, C.byref(prm), ptr(hp),
-                                                C.c_void_p(out_rows.ctypes.data) if row_cap else None, row_cap, C.c_void_p(raw.ctypes.data)))
-            out = {k: raw[k][:K] for k in names}
+        be = DeviceArrays(paths.device, stream) if on_dev else HostArrays
+        with be.ctx():
+            p = be.here(paths, np.float32)
+            hp = be.here(hops, np.int32)
+            raw = be.records(max(K, 1), _lib.WALK_INFO)
+            out_rows = be.empty((K, row_cap), np.int32) if row_cap else None
+        self._call(be, "walk_paths", be.ptr(p), K, T, stride, rb, C.byref(prm), be.ptr(hp), be.addr(out_rows) if row_cap else None, row_cap,
+                   be.addr(raw))
+        out = be.fields(raw[:K], _lib.WALK_INFO)
         if row_cap:
             out["rows"] = out_rows
         return out
 
     # ---- route field (gndt_route_field* / gndt_descend_routes*: cost-to-go to a set of goals that keeps clear of obstacles) ----
-    def _robot_ref(self, robot):
-        if robot is None:
-            return None
-        d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-        d.update(robot)
-        return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
-
     def route_field(self, goals, goal_costs=None, robot=None, hops=None, min_hops=0, soft_hops=0, soft_weight=0.0, overhead=False, max_cost=0.0,
                     max_rounds=0, next=True, stream=None, host=False):
         """For every slope the least cost to reach any of `goals` along the steps a robot can take, and the slope to step to next
@@ -1098,9 +1010,8 @@ class TwoDmap:
         converged, sweeps that changed something, 0, 0) and `converged` (counts[4], a view: reading it waits for the stream).  Torch
         tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited; or numpy arrays through
         gndt_route_field with host=True."""
-        from ._lib import RouteFieldParams
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if isinstance(hops, dict):
             hops = hops["hops"]
         n = int(self.sync()[0])
@@ -1121,30 +1032,14 @@ class TwoDmap:
         G = int(goals.shape[0])
         if goal_costs is not None and int(goal_costs.shape[0]) != G:
             raise ValueError("goal_costs must have one entry per goal")
-        if host:
-            as_np = lambda a, dt: None if a is None else np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).astype(dt, copy=False)
-            g = as_np(goals, np.int64).astype(np.uint32)
-            gc, hp = as_np(goal_costs, np.float32), as_np(hops, np.int64)
-            hp = None if hp is None else hp.astype(np.uint32)
-            out = {"cost": np.empty(room, np.float32), "counts": np.zeros(8, np.int32)}
+        be = HostArrays if host else DeviceArrays(self._cuda(), stream)
+        with be.ctx():
+            g, gc, hp = be.here(goals, np.int32), be.here(goal_costs, np.float32), be.here(hops, np.int32)
+            out = {"cost": be.empty(room, np.float32), "counts": be.zeros(8, np.int32)}
             if next:
-                out["next"] = np.empty(room, np.int32)
-            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_route_field(self._h, rb, C.byref(prm), ptr(g), G, ptr(gc), ptr(hp), ptr(out["cost"]), ptr(out.get("next")),
-                                                 ptr(out["counts"])))
-        else:
-            import torch
-            dev = f"cuda:{self.device}"
-            with _torch_stream_ctx(stream):
-                to_dev = lambda a, dt: None if a is None else torch.as_tensor(np.ascontiguousarray(a).view(np.int32) if isinstance(a, np.ndarray) and
-                                                                           a.dtype == np.uint32 else a, device=dev).to(dt).contiguous()
-                g, gc, hp = to_dev(goals, torch.int32), to_dev(goal_costs, torch.float32), to_dev(hops, torch.int32)
-                out = {"cost": torch.empty(room, dtype=torch.float32, device=dev), "counts": torch.zeros(8, dtype=torch.int32, device=dev)}
-                if next:
-                    out["next"] = torch.empty(room, dtype=torch.int32, device=dev)
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            self._check(self._L.gndt_route_field_device(self._h, rb, C.byref(prm), ptr(g), G, ptr(gc), ptr(hp), ptr(out["cost"]), ptr(out.get("next")),
-                                                        ptr(out["counts"]), _stream_ptr(stream)))
+                out["next"] = be.empty(room, np.int32)
+        self._call(be, "route_field", rb, C.byref(prm), be.ptr(g), G, be.ptr(gc), be.ptr(hp), be.ptr(out["cost"]), be.ptr(out.get("next")),
+                   be.ptr(out["counts"]))
         for k in ("cost", "next"):
             if k in out:
                 out[k] = out[k][:n]
@@ -1158,9 +1053,8 @@ class TwoDmap:
         (ROUTE_STATUS), length, start_row, expansions (the steps followed), queue_peak (0), cost and h_start (the field's cost at the
         start).  route_cap None: the map's slope count or 1024, whichever is less.  torch CUDA starts are answered on the device
         (enqueued on `stream`, not awaited); host=True or a host array goes through gndt_descend_routes (numpy)."""
-        from ._lib import DescendParams
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if "next" not in field:
             raise ValueError("descend_routes needs a field with `next` (route_field(next=True))")
         ptr, K, stride, on_dev, keep = self._as_input(starts)
@@ -1171,45 +1065,23 @@ class TwoDmap:
         cost, nxt = field["cost"], field["next"]
         if int(cost.shape[0]) != n or int(nxt.shape[0]) != n:
             raise ValueError(f"the field has {int(cost.shape[0])} entries, the map {n} rows: a field of another map")
-        prm = DescendParams(self.WALK_START_MODES[start_mode] if isinstance(start_mode, str) else int(start_mode), int(max_steps))
+        prm = DescendParams(_enum(self.WALK_START_MODES, start_mode), int(max_steps))
         if on_dev and host:
             ptr, K, stride, on_dev, keep = self._as_input(keep.detach().cpu().numpy())
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                c = torch.as_tensor(cost, device=keep.device).to(torch.float32).contiguous()
-                x = torch.as_tensor(nxt, device=keep.device).to(torch.int32).contiguous()
-                rows = torch.empty((K, route_cap), dtype=torch.int32, device=keep.device)
-                raw = torch.empty((max(K, 1), 8), dtype=torch.int32, device=keep.device)[:K]
-                if n == 0:         # (an empty map still names its field)
-                    c, x = torch.zeros(1, dtype=torch.float32, device=keep.device), torch.zeros(1, dtype=torch.int32, device=keep.device)
-            self._check(self._L.gndt_descend_routes_device(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
-                                                           C.c_void_p(c.data_ptr()), C.c_void_p(x.data_ptr()),
-                                                           C.c_void_p(rows.data_ptr() if K and route_cap else 0), route_cap if K else 0,
-                                                           C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
-            info = {"status": raw[:, 0], "length": raw[:, 1], "start_row": raw[:, 2], "expansions": raw[:, 3], "queue_peak": raw[:, 4],
-                    "cost": raw[:, 5].view(torch.float32), "h_start": raw[:, 6].view(torch.float32)}
-            return rows, info
-        as_np = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).astype(dt, copy=False)
-        c, x = as_np(cost, np.float32), as_np(nxt, np.int32)
-        if n == 0:                 # (an empty map still names its field)
-            c, x = np.zeros(1, np.float32), np.zeros(1, np.int32)
-        rows = np.empty((K, route_cap), np.int32)
-        raw = np.zeros(max(K, 1), self.ROUTE_INFO_DTYPE)
-        self._check(self._L.gndt_descend_routes(self._h, C.c_void_p(ptr if K else 0), K, stride, C.byref(prm),
-                                                C.c_void_p(c.ctypes.data), C.c_void_p(x.ctypes.data),
-                                                C.c_void_p(rows.ctypes.data if K and route_cap else 0), route_cap if K else 0,
-                                                C.c_void_p(raw.ctypes.data)))
-        raw = raw[:K]
-        info = {k: raw[k] for k in ("status", "length", "expansions", "queue_peak", "cost", "h_start")}
-        info["start_row"] = raw["start_row"].view(np.int32)
-        return rows, info
+        be = DeviceArrays(keep.device, stream) if on_dev else HostArrays
+        with be.ctx():
+            c, x = be.here(cost, np.float32), be.here(nxt, np.int32)
+            rows = be.empty((K, route_cap), np.int32)
+            raw = be.records(max(K, 1), _lib.ROUTE_INFO, zeroed=False)[:K]
+            if n == 0:             # (an empty map still names its field)
+                c, x = be.zeros(1, np.float32), be.zeros(1, np.int32)
+        self._call(be, "descend_routes", C.c_void_p(ptr if K else 0), K, stride, C.byref(prm), be.addr(c), be.addr(x), be.ptr(rows),
+                   route_cap if K else 0, be.addr(raw))
+        return rows, be.fields(raw, _lib.ROUTE_INFO, _ROUTE_HOST_AS)
 
     # ---- route shortcutting (gndt_shortcut_routes*: slope-to-slope routes string-pulled into any-angle waypoints) ----
     SHORTCUT_STATUS = {0: "ok", 1: "empty", 2: "bad_route", 3: "limit"}
-    SHORTCUT_INFO_DTYPE = np.dtype([("status", np.int32), ("length_in", np.int32), ("waypoints", np.int32), ("path_slopes", np.int32),
-                                    ("links_tested", np.int32), ("fallback_links", np.int32), ("cost_in", np.float32),
-                                    ("cost_out", np.float32), ("hops_min", np.int32), ("reserved", np.int32, 3)])
+    SHORTCUT_INFO_DTYPE = _lib.SHORTCUT_INFO
 
     def shortcut_routes(self, routes, lengths=None, robot=None, window=64, overhead=False, hops=None, min_hops=0, waypoint_cap=None, path_cap=0,
                         max_links=0, stream=None, host=False):
@@ -1224,7 +1096,7 @@ class TwoDmap:
         path_cap `path_rows` [K, path_cap] (int32, -1 behind the end).  torch tensors on the routes' device, enqueued on `stream`
         (default torch's current stream) and not awaited; host=True or numpy arrays go through gndt_shortcut_routes (numpy)."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if isinstance(routes, (tuple, list)) and len(routes) == 2 and isinstance(routes[1], dict):
             routes, lengths = routes[0], routes[1]["length"]
         if lengths is None:
@@ -1238,57 +1110,31 @@ class TwoDmap:
         if isinstance(hops, dict):
             hops = hops["hops"]
         prm = ShortcutParams(int(window), 1 if overhead else 0, int(min_hops), int(max_links))
-        rb = None
-        if robot is not None:
-            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        rb = self._robot_ref(robot)
         n = int(self.sync()[0])
         if hops is not None and int(hops.shape[0]) != n:
             raise ValueError(f"hops has {int(hops.shape[0])} entries, the map {n} rows: a clearance field of another map")
-        names = ("status", "length_in", "waypoints", "path_slopes", "links_tested", "fallback_links", "cost_in", "cost_out", "hops_min")
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                r = routes.contiguous()
-                if r.dtype != torch.int32:
-                    r = r.to(torch.int32)
-                ln = torch.as_tensor(lengths, device=r.device)
-                if ln.dtype != torch.int32 or (K > 1 and ln.stride(0) < 1):
-                    ln = ln.to(torch.int32).contiguous()
+        be = DeviceArrays(routes.device, stream) if on_dev else HostArrays
+        with be.ctx():
+            r = be.here(routes, np.int32)
+            # the lengths are read where they lie (plan_routes' info is a column of its records): 4-byte integers at any whole stride
+            if be.on_dev:
+                ln = be.xp.as_tensor(lengths, device=r.device)
+                if ln.dtype != be.xp.int32 or (K > 1 and ln.stride(0) < 1):
+                    ln = be.here(ln, np.int32)
                 stride = 4 * int(ln.stride(0)) if K > 1 else 4
-                if isinstance(hops, np.ndarray):
-                    hops = np.ascontiguousarray(hops).view(np.int32)
-                hp = None if hops is None else torch.as_tensor(hops, device=r.device).contiguous()
-                if hp is not None and hp.dtype != torch.int32:
-                    hp = hp.to(torch.int32)
-                raw = torch.zeros((max(K, 1), 12), dtype=torch.int32, device=r.device)
-                wp = torch.empty((K, wp_cap), dtype=torch.int32, device=r.device)
-                out_path = torch.empty((K, path_cap), dtype=torch.int32, device=r.device) if path_cap else None
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            self._check(self._L.gndt_shortcut_routes_device(self._h, ptr(r), K, route_cap, ptr(ln), stride, rb, C.byref(prm), ptr(hp),
-                                                            C.c_void_p(wp.data_ptr() if wp.numel() else raw.data_ptr()), wp_cap,
-                                                            C.c_void_p(out_path.data_ptr()) if path_cap else None, path_cap,
-                                                            C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
-            raw = raw[:K]
-            out = {k: (raw[:, i].view(torch.float32) if k in ("cost_in", "cost_out") else raw[:, i]) for i, k in enumerate(names)}
-        else:
-            to_np = lambda a: a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-            r = np.ascontiguousarray(to_np(routes))
-            r = r.view(np.int32) if r.dtype in (np.int32, np.uint32) else r.astype(np.int32)
-            ln = to_np(lengths)
-            if ln.dtype.itemsize != 4 or ln.dtype.kind not in "iu" or (K > 1 and (ln.strides[0] < 4 or ln.strides[0] % 4)):
-                ln = np.ascontiguousarray(ln, np.int32)
-            stride = int(ln.strides[0]) if K > 1 else 4
-            hp = None if hops is None else np.ascontiguousarray(to_np(hops)).view(np.uint32)
-            raw = np.zeros(max(K, 1), self.SHORTCUT_INFO_DTYPE)
-            wp = np.empty((K, wp_cap), np.int32)
-            out_path = np.empty((K, path_cap), np.int32) if path_cap else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_shortcut_routes(self._h, ptr(r), K, route_cap, ptr(ln), stride, rb, C.byref(prm), ptr(hp),
-                                                     C.c_void_p(wp.ctypes.data if wp.size else raw.ctypes.data), wp_cap,
-                                                     C.c_void_p(out_path.ctypes.data) if path_cap else None, path_cap, C.c_void_p(raw.ctypes.data)))
-            out = {k: raw[k][:K] for k in names}
+            else:
+                ln = lengths.detach().cpu().numpy() if hasattr(lengths, "detach") else np.asarray(lengths)
+                if ln.dtype.itemsize != 4 or ln.dtype.kind not in "iu" or (K > 1 and (ln.strides[0] < 4 or ln.strides[0] % 4)):
+                    ln = np.ascontiguousarray(ln, np.int32)
+                stride = int(ln.strides[0]) if K > 1 else 4
+            hp = be.here(hops, np.int32)
+            raw = be.records(max(K, 1), _lib.SHORTCUT_INFO)
+            wp = be.empty((K, wp_cap), np.int32)
+            out_path = be.empty((K, path_cap), np.int32) if path_cap else None
+        self._call(be, "shortcut_routes", be.ptr(r), K, route_cap, be.ptr(ln), stride, rb, C.byref(prm), be.ptr(hp),
+                   be.addr(wp if K and wp_cap else raw), wp_cap, be.addr(out_path) if path_cap else None, path_cap, be.addr(raw))
+        out = be.fields(raw[:K], _lib.SHORTCUT_INFO)
         out["waypoint_rows"] = wp
         if path_cap:
             out["path_rows"] = out_path
@@ -1332,10 +1178,7 @@ class TwoDmap:
     FOOT_STATUS = {0: "ok", 1: "bad_pose", 2: "no_ground", 3: "sparse"}
     FOOT_FLAGS = {"tilt": 1, "step": 2, "cover": 4, "low": 8}
     FOOT_WEIGHTS = {"cell": 0, "count": 1}
-    FOOT_INFO_DTYPE = np.dtype([("status", np.int32), ("flags", np.uint32), ("centre_row", np.int32), ("cells", np.uint16),
-                                ("support", np.uint16), ("gaps", np.uint16), ("unknown", np.uint16), ("z", np.float32),
-                                ("normal", np.float32, 3), ("along", np.float32), ("across", np.float32), ("rms", np.float32),
-                                ("step_max", np.float32), ("bump_max", np.float32), ("headroom", np.float32), ("reserved", np.uint32)])
+    FOOT_INFO_DTYPE = _lib.FOOTPRINT_INFO
 
     def footprints(self, poses, half_length, half_width, robot=None, max_dz=0.0, height=0.0, min_cells=0, min_cover=0.0, weight="cell",
                    rows=0, stream=None, host=False):
@@ -1352,58 +1195,31 @@ class TwoDmap:
         last) when asked.  torch tensors on the poses' device, enqueued on `stream` (default torch's current stream) and not
         awaited; host=True or a numpy array goes through gndt_footprint_poses (numpy)."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         on_dev = hasattr(poses, "is_cuda") and poses.is_cuda and not host
         if hasattr(poses, "detach") and not on_dev:
             poses = poses.detach().cpu().numpy()
         if len(poses.shape) != 2 or poses.shape[1] not in (4, 5):
             raise ValueError("poses must be [K, 5] (x, y, z, hx, hy) or [K, 4] (x, y, z, yaw)")
         K = int(poses.shape[0])
-        prm = _lib.FootprintParams(float(half_length), float(half_width), float(max_dz), float(height), int(min_cells), float(min_cover),
-                                   self.FOOT_WEIGHTS[weight] if isinstance(weight, str) else int(weight))
-        rb = None
-        if robot is not None:
-            d = dict(radius=0.25, reachable_height=0.15, max_rough=100.0, max_angle_deg=30.0)
-            d.update(robot)
-            rb = C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+        prm = FootprintParams(float(half_length), float(half_width), float(max_dz), float(height), int(min_cells), float(min_cover),
+                              _enum(self.FOOT_WEIGHTS, weight))
+        rb = self._robot_ref(robot)
         row_cap = int(rows)
-        ints = {"status": 0, "flags": 1, "centre_row": 2}
-        floats = {"z": 5, "along": 9, "across": 10, "rms": 11, "step_max": 12, "bump_max": 13, "headroom": 14}
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                p = poses.float()
-                if p.shape[1] == 4:
-                    p = torch.cat([p[:, :3], torch.cos(p[:, 3:4]), torch.sin(p[:, 3:4])], 1)
-                p = p.contiguous()
-                raw = torch.zeros((max(K, 1), 16), dtype=torch.int32, device=p.device)
-                out_rows = torch.empty((K, row_cap), dtype=torch.int32, device=p.device) if row_cap else None
-            # (K = 0: an empty tensor's pointer is NULL, and rows NULL goes with a cap of 0)
-            self._check(self._L.gndt_footprint_poses_device(self._h, C.c_void_p(p.data_ptr() if K else 0), K, 20, rb, C.byref(prm),
-                                                            C.c_void_p(out_rows.data_ptr()) if row_cap and K else None, row_cap if K else 0,
-                                                            C.c_void_p(raw.data_ptr()), _stream_ptr(stream)))
-            with _torch_stream_ctx(stream):
-                raw = raw[:K]
-                out = {k: raw[:, i] for k, i in ints.items()}
-                out.update({k: raw[:, i].view(torch.float32) for k, i in floats.items()})
-                out["cells"], out["support"] = raw[:, 3] & 0xFFFF, (raw[:, 3] >> 16) & 0xFFFF
-                out["gaps"], out["unknown"] = raw[:, 4] & 0xFFFF, (raw[:, 4] >> 16) & 0xFFFF
-                out["normal"] = raw[:, 6:9].view(torch.float32)
-                out["pitch"], out["roll"] = torch.atan(out["along"]), torch.atan(out["across"])
-                out["ok"] = (out["status"] == 0) & (out["flags"] == 0)
-        else:
-            p = np.asarray(poses, np.float32)
+        be = DeviceArrays(poses.device, stream) if on_dev else HostArrays
+        xp = be.xp
+        with be.ctx():
+            p = be.here(poses, np.float32)
             if p.shape[1] == 4:
-                p = np.concatenate([p[:, :3], np.cos(p[:, 3:4]), np.sin(p[:, 3:4])], 1)
-            p = np.ascontiguousarray(p, np.float32)
-            raw = np.zeros(max(K, 1), self.FOOT_INFO_DTYPE)
-            out_rows = np.empty((K, row_cap), np.int32) if row_cap else None
-            self._check(self._L.gndt_footprint_poses(self._h, C.c_void_p(p.ctypes.data if K else 0), K, 20, rb, C.byref(prm),
-                                                     C.c_void_p(out_rows.ctypes.data) if row_cap and K else None, row_cap if K else 0,
-                                                     C.c_void_p(raw.ctypes.data)))
-            out = {k: raw[k][:K] for k in self.FOOT_INFO_DTYPE.names if k != "reserved"}
-            out["flags"] = out["flags"].view(np.int32)
-            out["pitch"], out["roll"] = np.arctan(out["along"]), np.arctan(out["across"])
+                p = xp.concatenate([p[:, :3], xp.cos(p[:, 3:4]), xp.sin(p[:, 3:4])], 1)
+            raw = be.records(max(K, 1), _lib.FOOTPRINT_INFO)
+            out_rows = be.empty((K, row_cap), np.int32) if row_cap else None
+        # (K = 0: no poses is a NULL pointer, and rows NULL goes with a cap of 0)
+        self._call(be, "footprint_poses", be.ptr(p), K, 20, rb, C.byref(prm), be.addr(out_rows) if row_cap and K else None,
+                   row_cap if K else 0, be.addr(raw))
+        with be.ctx():
+            out = be.fields(raw[:K], _lib.FOOTPRINT_INFO, host_as=_FOOT_HOST_AS)
+            out["pitch"], out["roll"] = xp.arctan(out["along"]), xp.arctan(out["across"])
             out["ok"] = (out["status"] == 0) & (out["flags"] == 0)
         if row_cap:
             out["rows"] = out_rows
@@ -1440,25 +1256,14 @@ class TwoDmap:
         words of the map as it was before the call (bits 0-30 the pass count, bit 31 CLEAR_PROTECTED): a torch int32 tensor on the device
         for device points, a numpy uint32 array otherwise: (stats, passes).  The stats are awaited, so the call always waits."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         o = (C.c_float * 3)(*[float(v) for v in origin[:3]])
         prm = ClearParams(float(max_range), float(end_margin), int(min_passes), 1 if count_only else 0)
         st = ClearStats()
         ptr, n, stride, on_dev, keep = self._as_input(points)
-        rows = None
-        if on_dev:
-            if passes:
-                import torch
-                nodes = self.sync()[0]
-                rows = torch.zeros(nodes, dtype=torch.int32, device=keep.device)
-            self._check(self._L.gndt_clear_rays_device(self._h, o, C.c_void_p(ptr if n else 0), n, stride, C.byref(prm),
-                                                       C.c_void_p(rows.data_ptr() if rows is not None and rows.numel() else 0),
-                                                       C.byref(st), _stream_ptr(stream)))
-        else:
-            if passes:
-                rows = np.zeros(self.sync()[0], np.uint32)
-            self._check(self._L.gndt_clear_rays(self._h, o, C.c_void_p(ptr if n else 0), n, stride, C.byref(prm),
-                                                C.c_void_p(rows.ctypes.data if rows is not None and rows.size else 0), C.byref(st)))
+        be = DeviceArrays(keep.device, stream) if on_dev else HostArrays
+        rows = be.zeros(self.sync()[0], np.uint32) if passes else None
+        self._call(be, "clear_rays", o, C.c_void_p(ptr if n else 0), n, stride, C.byref(prm), be.ptr(rows), C.byref(st))
         out = {"rays": int(st.rays), "skipped": int(st.skipped), "protected_rows": int(st.protected_rows), "cleared": int(st.cleared)}
         return (out, rows) if passes else out
 
@@ -1476,47 +1281,26 @@ class TwoDmap:
         tensors for torch CUDA ends (enqueued on `stream`, default torch's current stream, not awaited), numpy arrays through
         gndt_cast_rays otherwise.  stats=True waits and returns (that dict, {rays, skipped, hits})."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        prm = CastParams(self.CAST_MODES[mode] if isinstance(mode, str) else int(mode), int(min_count), float(max_range), float(min_range),
+            self._handle()
+        prm = CastParams(_enum(self.CAST_MODES, mode), int(min_count), float(max_range), float(min_range),
                          float(cov_rel), float(cov_floor), float(max_d2), 0)
         eptr, n, estride, on_dev, keep = self._as_input(ends)
         st = CastStats()
-        if on_dev:
-            import torch
-            # (the origins' upload and the outputs belong to the stream the kernel runs on)
-            with _torch_stream_ctx(stream):
-                if not isinstance(origins, torch.Tensor):
-                    origins = torch.from_numpy(np.ascontiguousarray(origins, dtype=np.float32))
-                o = origins.to(device=keep.device, dtype=torch.float32).contiguous()
-                # (one element at least: the call wants an output pointer whatever n is)
-                buf = {k: torch.empty(max(n, 1), dtype=dt, device=keep.device)
-                       for k, dt in (("row", torch.int32), ("range", torch.float32), ("d2", torch.float32))}
-            optr, oshape = o.data_ptr(), tuple(o.shape)
-            co = CastOut(*[C.c_void_p(buf[k].data_ptr()) for k in ("row", "range", "d2")])
-        else:
-            try:
-                import torch
-                if isinstance(origins, torch.Tensor):
-                    origins = origins.detach().cpu().numpy()
-            except ImportError:
-                pass
-            o = np.ascontiguousarray(origins, dtype=np.float32)
-            buf = {k: np.empty(max(n, 1), dt) for k, dt in (("row", np.int32), ("range", np.float32), ("d2", np.float32))}
-            optr, oshape = o.ctypes.data, o.shape
-            co = CastOut(*[C.c_void_p(buf[k].ctypes.data) for k in ("row", "range", "d2")])
+        be = DeviceArrays(keep.device, stream) if on_dev else HostArrays
+        with be.ctx():      # (the origins' upload and the outputs belong to the stream the kernel runs on)
+            o = be.here(origins, np.float32)
+            # (one element at least: the call wants an output pointer whatever n is)
+            buf = {k: be.empty(max(n, 1), dt) for k, dt in (("row", np.int32), ("range", np.float32), ("d2", np.float32))}
+        co = CastOut(*[be.addr(buf[k]) for k in ("row", "range", "d2")])
+        oshape = tuple(o.shape)
         if len(oshape) == 1 and oshape[0] in (3, 4):
             ostride = 0
         elif len(oshape) == 2 and oshape[0] == n and oshape[1] in (3, 4):
             ostride = 4 * oshape[1]
         else:
             raise ValueError("origins must be (3,) or (n, 3|4) with one row per end point")
-        stp = C.byref(st) if stats else None
-        if on_dev:
-            self._check(self._L.gndt_cast_rays_device(self._h, C.c_void_p(optr if n else 0), ostride, C.c_void_p(eptr if n else 0), n, estride,
-                                                      C.byref(prm), C.byref(co), stp, _stream_ptr(stream)))
-        else:
-            self._check(self._L.gndt_cast_rays(self._h, C.c_void_p(optr if n else 0), ostride, C.c_void_p(eptr if n else 0), n, estride,
-                                               C.byref(prm), C.byref(co), stp))
+        self._call(be, "cast_rays", be.addr(o) if n else None, ostride, C.c_void_p(eptr if n else 0), n, estride, C.byref(prm), C.byref(co),
+                   C.byref(st) if stats else None)
         out = {k: v[:n] for k, v in buf.items()}
         if stats:
             return out, {"rays": int(st.rays), "skipped": int(st.skipped), "hits": int(st.hits)}
@@ -1539,8 +1323,7 @@ class TwoDmap:
         return self.cast_rays(np.asarray(T[:, 3], np.float32), ends, **kw)
 
     # ---- view gain (gndt_view_gain*: the unknown columns a sensor would see from each of K poses) ----
-    VIEW_INFO_DTYPE = np.dtype([("rays", np.uint32), ("skipped", np.uint32), ("hits", np.uint32), ("unknown", np.uint32), ("known", np.uint32),
-                                ("status", np.uint32), ("steps", np.uint64), ("sum_ux", np.int64), ("sum_uy", np.int64)])
+    VIEW_INFO_DTYPE = _lib.VIEW_INFO
 
     def view_gain(self, poses, directions, max_range, min_count=0, min_range=0.0, per_ray=False, stream=None, host=False):
         """How much a sensor would learn at each of K `poses` ([K, 12], [K, 3, 4], [K, 4, 4] or one matrix, [R | t], map <- sensor): the
@@ -1554,59 +1337,38 @@ class TwoDmap:
         ranges).  Torch tensors on the handle's device, enqueued on `stream` (default torch's current stream) and not awaited; numpy
         arrays through gndt_view_gain with host=True."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
-        prm = _lib.ViewParams(float(max_range), float(min_range), int(min_count))
-        fields = self.VIEW_INFO_DTYPE.names
+            self._handle()
+        prm = ViewParams(float(max_range), float(min_range), int(min_count))
         def flat(p):
             """numpy poses -> float64 [K, 12]: also the flat [K, 12] frontier_views returns, and one pose as [12]"""
             p = p.detach().cpu().numpy() if hasattr(p, "detach") else np.asarray(p, np.float64)
             if p.ndim in (1, 2) and p.shape[-1] == 12:
                 return np.ascontiguousarray(p, np.float64).reshape(-1, 12)
             return self._as_poses(p)
-        if host:
-            T = flat(poses)
-            d = directions.detach().cpu().numpy() if hasattr(directions, "detach") else directions
-            d = np.ascontiguousarray(d, np.float32)
-            if d.ndim != 2 or d.shape[1] not in (3, 4):
+        be = HostArrays if host else DeviceArrays(self._cuda(), stream)
+        with be.ctx():
+            if be.on_dev and getattr(poses, "is_cuda", False):          # (poses on the device are shaped there)
+                T = poses.to(be.xp.float64)
+                if T.dim() == 1:
+                    T = T[None]
+                elif T.dim() == 2 and T.shape[1] != 12:
+                    T = T[None]
+                if T.dim() == 3:
+                    if T.shape[1] not in (3, 4) or T.shape[2] != 4:
+                        raise ValueError("poses must be [K, 12], [K, 3, 4], [K, 4, 4] or one such matrix")
+                    T = T[:, :3, :].reshape(-1, 12)
+                T = T.contiguous()
+            else:
+                T = be.here(flat(poses), np.float64)
+            d = be.here(directions, np.float32)
+            if len(d.shape) != 2 or d.shape[1] not in (3, 4):
                 raise ValueError("directions must be [N, 3] or [N, 4]")
-            K, n = T.shape[0], d.shape[0]
-            raw = np.zeros(K, self.VIEW_INFO_DTYPE)
-            row = np.full((K, n), -1, np.int32) if per_ray else None
-            rng = np.full((K, n), np.nan, np.float32) if per_ray else None
-            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_view_gain(self._h, p(T), K, p(d), n, 4 * d.shape[1], C.byref(prm), p(raw), p(row), p(rng)))
-            out = {k: raw[k] for k in fields}
-        else:
-            import torch
-            dev = f"cuda:{self.device}"
-            with _torch_stream_ctx(stream):
-                if isinstance(poses, torch.Tensor) and poses.is_cuda:
-                    T = poses.to(torch.float64)
-                    if T.dim() == 1:
-                        T = T[None]
-                    elif T.dim() == 2 and T.shape[1] != 12:
-                        T = T[None]
-                    if T.dim() == 3:
-                        if T.shape[1] not in (3, 4) or T.shape[2] != 4:
-                            raise ValueError("poses must be [K, 12], [K, 3, 4], [K, 4, 4] or one such matrix")
-                        T = T[:, :3, :].reshape(-1, 12)
-                    T = T.contiguous()
-                else:
-                    T = torch.from_numpy(flat(poses)).to(dev)
-                d = directions if isinstance(directions, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(directions, np.float32))
-                d = d.to(device=dev, dtype=torch.float32).contiguous()
-                if d.dim() != 2 or d.shape[1] not in (3, 4):
-                    raise ValueError("directions must be [N, 3] or [N, 4]")
-                K, n = int(T.shape[0]), int(d.shape[0])
-                raw = torch.zeros((K, 12), dtype=torch.int32, device=dev)
-                row = torch.full((K, n), -1, dtype=torch.int32, device=dev) if per_ray else None
-                rng = torch.full((K, n), float("nan"), dtype=torch.float32, device=dev) if per_ray else None
-            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            self._check(self._L.gndt_view_gain_device(self._h, p(T), K, p(d), n, 4 * int(d.shape[1]), C.byref(prm), p(raw), p(row), p(rng),
-                                                      _stream_ptr(stream)))
-            wide = raw.view(torch.int64)             # (views: nothing is enqueued behind the caller's stream)
-            out = {k: raw[:, i] for i, k in enumerate(fields[:6])}
-            out.update(steps=wide[:, 3], sum_ux=wide[:, 4], sum_uy=wide[:, 5])
+            K, n = int(T.shape[0]), int(d.shape[0])
+            raw = be.records(K, _lib.VIEW_INFO)
+            row = be.full((K, n), -1, np.int32) if per_ray else None
+            rng = be.full((K, n), float("nan"), np.float32) if per_ray else None
+        self._call(be, "view_gain", be.ptr(T), K, be.ptr(d), n, 4 * int(d.shape[1]), C.byref(prm), be.ptr(raw), be.ptr(row), be.ptr(rng))
+        out = be.fields(raw, _lib.VIEW_INFO)    # (views: nothing is enqueued behind the caller's stream)
         if per_ray:
             out.update(row=row, range=rng)
         return out
@@ -1663,18 +1425,17 @@ class TwoDmap:
         d2 of every point at pose k, inf where it met no node) and row (int32, that node's row, -1).  A torch CUDA tensor is scored on
         the device (torch tensors, enqueued on `stream`, default torch's current stream, not awaited); a host array through
         gndt_score_poses (numpy)."""
+        # (a hot small call: its two branches stay written out, see plan_routes)
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         T = self._as_poses(poses)
         K = T.shape[0]
         ptr, n, stride, on_dev, keep = self._as_input(points)
         want = per_point is not None
         prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), int(per_point) if want else 0)
         if on_dev:
-            import contextlib
             import torch
-            # (the poses' upload and the outputs belong to the stream the kernels run on)
-            with torch.cuda.stream(stream) if hasattr(stream, "cuda_stream") else contextlib.nullcontext():
+            with _torch_stream_ctx(stream):     # (the poses' upload and the outputs belong to the stream the kernels run on)
                 Td = torch.from_numpy(T).to(keep.device)
                 rec = torch.empty((K, 4), dtype=torch.int64, device=keep.device)
                 d2 = torch.empty(n, dtype=torch.float32, device=keep.device) if want else None
@@ -1682,16 +1443,14 @@ class TwoDmap:
             p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
             self._check(self._L.gndt_score_poses_device(self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), K, C.byref(prm), p(rec),
                                                         p(d2), p(row), _stream_ptr(stream)))
-            fl = rec.view(torch.float64)       # (a view: nothing is enqueued behind the caller's stream)
-            out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+            out = _lib.record_views(rec, _lib.POSE_SCORE)       # (views: nothing is enqueued behind the caller's stream)
         else:
-            rec = np.zeros((K, 4), np.int64)
+            rec = np.zeros(K, _lib.POSE_SCORE)
             d2 = np.empty(n, np.float32) if want else None
             row = np.empty(n, np.int32) if want else None
             p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
             self._check(self._L.gndt_score_poses(self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), K, C.byref(prm), p(rec), p(d2), p(row)))
-            fl = rec.view(np.float64)
-            out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+            out = HostArrays.fields(rec, _lib.POSE_SCORE)
         if want:
             out.update(d2=d2, row=row)
         return out
@@ -1699,10 +1458,7 @@ class TwoDmap:
     # ---- scan segmentation (gndt_segment_scan*: the points of a scan the map does not explain, clustered) ----
     SEG_UNKEYED, SEG_EXPLAINED, SEG_OFF_SURFACE, SEG_UNMAPPED = 0, 1, 2, 3
     SEG_CLASSES = {"off_surface": 1 << 2, "unmapped": 1 << 3}
-    SEG_DTYPE = np.dtype([("label", np.uint32), ("cells", np.uint32), ("off_surface", np.uint32), ("unmapped", np.uint32),
-                          ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
-                          ("sz_min", np.int32), ("sz_max", np.int32), ("sum_x", np.int64), ("sum_y", np.int64), ("sum_z", np.int64),
-                          ("z_lo", np.float32), ("z_hi", np.float32)])
+    SEG_DTYPE = _lib.SCAN_CLUSTER
 
     def segment_scan(self, points, pose=None, neighbourhood=7, novel_d2=0.0, classes=None, min_points=1, connectivity=26,
                      min_cluster_points=1, min_cluster_cells=1, labels=False, max_clusters=None, stream=None, min_count=0, cov_rel=0.0,
@@ -1721,7 +1477,7 @@ class TwoDmap:
         `stream`, default torch's current stream, not awaited: the arrays then have max_clusters entries, filled from the front); a
         host array through gndt_segment_scan (numpy, cut to min(counts[0], max_clusters) entries)."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if classes is None:
             mask = 0
         elif isinstance(classes, int):
@@ -1734,44 +1490,27 @@ class TwoDmap:
                             int(connectivity), int(min_cluster_points), int(min_cluster_cells))
         T = self._as_poses(pose)[0] if pose is not None else None
         ptr, n, stride, on_dev, keep = self._as_input(points)
-        if on_dev:
-            import torch
-            with _torch_stream_ctx(stream):
-                Td = torch.from_numpy(T).to(keep.device) if T is not None else None
-                counts = torch.zeros(4, dtype=torch.int32, device=keep.device)
-                cls = torch.empty(n, dtype=torch.uint8, device=keep.device) if labels else None
-                lab = torch.empty(n, dtype=torch.int32, device=keep.device) if labels else None
-            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            call = lambda recs, cap, c, l: self._check(self._L.gndt_segment_scan_device(
-                self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), C.byref(prm), p(c), p(l), p(recs) if cap else C.c_void_p(0), cap,
-                p(counts), _stream_ptr(stream)))
-            if max_clusters is None:
-                call(None, 0, None, None)
-                with _torch_stream_ctx(stream):         # (read on the stream the count was enqueued on: the copy waits for it)
-                    max_clusters = int(counts[0].item())
-            with _torch_stream_ctx(stream):
-                recs = torch.zeros((int(max_clusters), 18), dtype=torch.int32, device=keep.device)
-            call(recs, recs.shape[0], cls, lab)
-            wide = recs.view(torch.int64) if recs.shape[0] else recs.new_zeros((0, 9), dtype=torch.int64)
-            out = {"label": recs[:, 0], "cells": recs[:, 1], "off_surface": recs[:, 2], "unmapped": recs[:, 3],
-                   "sx_min": recs[:, 4], "sx_max": recs[:, 5], "sy_min": recs[:, 6], "sy_max": recs[:, 7], "sz_min": recs[:, 8],
-                   "sz_max": recs[:, 9], "sum_x": wide[:, 5], "sum_y": wide[:, 6], "sum_z": wide[:, 7],
-                   "z_lo": recs[:, 16].view(torch.float32), "z_hi": recs[:, 17].view(torch.float32)}
-        else:
-            counts = np.zeros(4, np.uint32)
-            cls = np.empty(n, np.uint8) if labels else None
-            lab = np.empty(n, np.int32) if labels else None
-            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            call = lambda recs, cap, c, l: self._check(self._L.gndt_segment_scan(
-                self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), C.byref(prm), p(c), p(l), p(recs) if cap else C.c_void_p(0), cap,
-                p(counts)))
-            if max_clusters is None:
-                call(None, 0, None, None)
-                max_clusters = int(counts[0])
-            recs = np.zeros(int(max_clusters), self.SEG_DTYPE)
-            call(recs, len(recs), cls, lab)
+        be = DeviceArrays(keep.device, stream) if on_dev else HostArrays
+        with be.ctx():
+            Td = be.here(T, np.float64)
+            counts = be.zeros(4, np.uint32)
+            cls = be.empty(n, np.uint8) if labels else None
+            lab = be.empty(n, np.int32) if labels else None
+
+        def call(recs):     # (the count-only first call asks for no labels)
+            fill = recs is not None
+            self._call(be, "segment_scan", C.c_void_p(ptr if n else 0), n, stride, be.ptr(Td), C.byref(prm), be.ptr(cls if fill else None),
+                       be.ptr(lab if fill else None), be.ptr(recs), len(recs) if fill else 0, be.ptr(counts))
+        if max_clusters is None:
+            call(None)
+            with be.ctx():                      # (read on the stream the count was enqueued on: the copy waits for it)
+                max_clusters = int(counts[0].item())
+        with be.ctx():
+            recs = be.records(int(max_clusters), _lib.SCAN_CLUSTER)
+        call(recs)
+        if not be.on_dev:                       # (the host list is cut to the clusters found, the device list is not awaited)
             recs = recs[:min(int(counts[0]), len(recs))]
-            out = {k: recs[k] for k in self.SEG_DTYPE.names}
+        out = be.fields(recs, _lib.SCAN_CLUSTER)
         out["counts"] = counts
         if labels:
             out.update(point_class=cls, point_label=lab)
@@ -1823,33 +1562,24 @@ class TwoDmap:
         [K, 6, 6], symmetric, filled from the record's 21 values).  A torch CUDA tensor is scored on the device (torch tensors,
         enqueued on `stream`, default torch's current stream, not awaited); a host array through gndt_score_derivs (numpy)."""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         T = self._as_poses(poses)
         K = T.shape[0]
         ptr, n, stride, on_dev, keep = self._as_input(points)
         prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), 0)
-        if on_dev:
-            import contextlib
-            import torch
-            if stream is None:
-                ctx = contextlib.nullcontext()
-            else:
-                ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
-            with ctx:       # (the poses' upload, the outputs and the Hessian's gather belong to the stream the kernels run on)
-                Td = torch.from_numpy(T).to(keep.device)
-                rec = torch.empty((K, 31), dtype=torch.int64, device=keep.device)
-                p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-                self._check(self._L.gndt_score_derivs_device(self._h, C.c_void_p(ptr if n else 0), n, stride, p(Td), K, C.byref(prm), p(rec),
-                                                             _stream_ptr(stream)))
-                fl = rec.view(torch.float64)
-                H = fl[:, 10:31][:, torch.from_numpy(self._h_index()).to(keep.device)].reshape(K, 6, 6)
-        else:
-            rec = np.zeros((K, 31), np.int64)
-            p = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-            self._check(self._L.gndt_score_derivs(self._h, C.c_void_p(ptr if n else 0), n, stride, p(T), K, C.byref(prm), p(rec)))
-            fl = rec.view(np.float64)
-            H = fl[:, 10:31][:, self._h_index()].reshape(K, 6, 6)
-        return {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3], "g": fl[:, 4:10], "H": H}
+        be = DeviceArrays(keep.device, stream) if on_dev else HostArrays
+        with be.ctx():      # (the poses' upload, the outputs and the Hessian's gather belong to the stream the kernels run on)
+            Td = be.here(T, np.float64)
+            rec = be.records(K, _lib.POSE_DERIVS, zeroed=False)
+            self._call(be, "score_derivs", C.c_void_p(ptr if n else 0), n, stride, be.ptr(Td), K, C.byref(prm), be.ptr(rec))
+            return self._with_hessian(be, be.fields(rec, _lib.POSE_DERIVS))
+
+    def _with_hessian(self, be, out):
+        """gndt_pose_derivs' fields with H, the record's 21 upper-triangle values, gathered into the symmetric [K, 6, 6] (on the
+        device the gather is a kernel: call it under be.ctx())"""
+        tri = out["H"]
+        out["H"] = tri[:, be.here(self._h_index(), np.int64)].reshape(tri.shape[0], 6, 6)
+        return out
 
     def register(self, points, T0, neighbourhood=7, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, step_t=None, step_r=0.05,
                  tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None, pyramid=None):
@@ -1865,23 +1595,12 @@ class TwoDmap:
         from . import registration
         kw = dict(neighbourhood=neighbourhood, min_count=min_count, cov_rel=cov_rel, cov_floor=cov_floor, max_d2=max_d2, stream=stream)
 
-        def wait():
-            if hasattr(stream, "synchronize"):
-                stream.synchronize()
-            elif stream is not None:
-                import torch
-                torch.cuda.ExternalStream(int(stream)).synchronize()
-
-        def host(out, names):
-            wait()
-            return {k: (out[k].cpu().numpy() if hasattr(out[k], "cpu") else np.asarray(out[k])) for k in names}
-
         def callables(m):
             def evaluate(T):
-                return host(m.score_derivs(points, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
+                return _to_host(stream, m.score_derivs(points, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
 
             def score(T):
-                return host(m.score_poses(points, T, **kw), ("score",))["score"]
+                return _to_host(stream, m.score_poses(points, T, **kw), ("score",))["score"]
 
             return evaluate, score
 
@@ -1906,7 +1625,7 @@ class TwoDmap:
             raise GndtError(1, "coarsen: this map has no finished build")
         fxy = int(factor_xy)
         fz = fxy if factor_z is None else int(factor_z)
-        d = self._demand if demand is None else (DEMANDS[demand] if isinstance(demand, str) else int(demand))
+        d = self._demand if demand is None else _enum(DEMANDS, demand)
         if into is None:
             # (the handle's lengths are fp32: the multiplied fp32 values, which a power of two keeps exact)
             into = TwoDmap(float(np.float32(self.gridLen) * np.float32(fxy)), float(np.float32(self.zLen) * np.float32(fz)),
@@ -1942,7 +1661,7 @@ class TwoDmap:
         if other._h is None:
             raise GndtError(1, "merge_from: the other map has no finished build")
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         T = None if pose is None else self._as_poses(pose)
         if T is not None and T.shape[0] != 1:
             raise ValueError("merge_from takes one pose")
@@ -1954,36 +1673,30 @@ class TwoDmap:
         return {k: int(getattr(st, k)) for k, _ in MergeStats._fields_}
 
     # ---- map-to-map scoring (gndt_score_maps*: the other map's nodes scored as Gaussians against this map) ----
-    def _maps_call(self, other, poses, prm, stream, width, per_node):
-        """the two entry points' common part: -> (records [K, width] int64 device tensor, d2, row)"""
-        import contextlib
-        import torch
+    def _maps_call(self, other, poses, prm, stream, dtype, per_node):
+        """the two entry points' common part: -> (the backend, records of `dtype` on the device, d2, row)"""
         if self._h is None:
-            self._ensure(self._demand if self._demand is not None else "slope", need_origin=False)
+            self._handle()
         if other._h is None:
             raise GndtError(1, "score_map: the other map has no finished build")
         T = self._as_poses(poses)
         K = T.shape[0]
-        dev = torch.device("cuda", self.device)
-        if stream is None:
-            ctx = contextlib.nullcontext()
-        else:
-            ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
-        with ctx:           # (the poses' upload and the outputs belong to the stream the kernels run on)
-            Td = torch.from_numpy(T).to(dev)
-            rec = torch.empty((K, width), dtype=torch.int64, device=dev)
+        be = DeviceArrays(self._cuda(), stream)
+        with be.ctx():      # (the poses' upload and the outputs belong to the stream the kernels run on)
+            Td = be.here(T, np.float64)
+            rec = be.records(K, dtype, zeroed=False)
             d2 = row = None
             if per_node:
                 n = other.sync()[0]
-                d2 = torch.empty(n, dtype=torch.float32, device=dev)
-                row = torch.empty(n, dtype=torch.int32, device=dev)
-            p = lambda t: C.c_void_p(t.data_ptr() if t is not None and t.numel() else 0)
-            if width == 4:
-                rc = self._L.gndt_score_maps_device(self._h, other._h, p(Td), K, C.byref(prm), p(rec), p(d2), p(row), _stream_ptr(stream))
+                d2 = be.empty(n, np.float32)
+                row = be.empty(n, np.int32)
+            if dtype is _lib.POSE_SCORE:
+                rc = self._L.gndt_score_maps_device(self._h, other._h, be.ptr(Td), K, C.byref(prm), be.ptr(rec), be.ptr(d2), be.ptr(row),
+                                                    _stream_ptr(stream))
             else:
-                rc = self._L.gndt_score_maps_derivs_device(self._h, other._h, p(Td), K, C.byref(prm), p(rec), _stream_ptr(stream))
+                rc = self._L.gndt_score_maps_derivs_device(self._h, other._h, be.ptr(Td), K, C.byref(prm), be.ptr(rec), _stream_ptr(stream))
             self._check(rc)
-        return rec, d2, row
+        return be, rec, d2, row
 
     def score_map(self, other, poses, neighbourhood=1, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, per_node=None, stream=None):
         """How well the map `other` fits this map at each of the K `poses` (this map <- other): every node of `other` that has
@@ -1995,10 +1708,8 @@ class TwoDmap:
         current stream), not awaited."""
         want = per_node is not None
         prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), int(per_node) if want else 0)
-        rec, d2, row = self._maps_call(other, poses, prm, stream, 4, want)
-        import torch
-        fl = rec.view(torch.float64)
-        out = {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3]}
+        be, rec, d2, row = self._maps_call(other, poses, prm, stream, _lib.POSE_SCORE, want)
+        out = be.fields(rec, _lib.POSE_SCORE)
         if want:
             out.update(d2=d2, row=row)
         return out
@@ -2007,18 +1718,10 @@ class TwoDmap:
         """score_map's score with its gradient and Hessian with respect to a left pose perturbation xi = (v, w), which moves the means
         and rotates the covariances of `other`'s nodes (include/gndt.h "map-to-map scoring").  Returns score_derivs' dict of device
         tensors: score, d2_sum (the bits score_map gives), matched, terms, g [K, 6] and H [K, 6, 6]."""
-        import contextlib
-        import torch
         prm = ScoreParams(int(neighbourhood), int(min_count), float(cov_rel), float(cov_floor), float(max_d2), 0)
-        rec, _, _ = self._maps_call(other, poses, prm, stream, 31, False)
-        if stream is None:
-            ctx = contextlib.nullcontext()
-        else:
-            ctx = torch.cuda.stream(stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream)))
-        with ctx:           # (the Hessian's gather runs behind the kernels)
-            fl = rec.view(torch.float64)
-            H = fl[:, 10:31][:, torch.from_numpy(self._h_index()).to(rec.device)].reshape(rec.shape[0], 6, 6)
-        return {"score": fl[:, 0], "d2_sum": fl[:, 1], "matched": rec[:, 2], "terms": rec[:, 3], "g": fl[:, 4:10], "H": H}
+        be, rec, _, _ = self._maps_call(other, poses, prm, stream, _lib.POSE_DERIVS, False)
+        with be.ctx():      # (the Hessian's gather runs behind the kernels)
+            return self._with_hessian(be, be.fields(rec, _lib.POSE_DERIVS))
 
     def register_map(self, other, T0, neighbourhood=7, min_count=0, cov_rel=0.0, cov_floor=0.0, max_d2=0.0, step_t=None, step_r=0.05,
                      tol_t=1e-4, tol_r=1e-5, max_iterations=30, stream=None, pyramid=None, other_pyramid=None):
@@ -2030,20 +1733,12 @@ class TwoDmap:
         from . import registration
         kw = dict(neighbourhood=neighbourhood, min_count=min_count, cov_rel=cov_rel, cov_floor=cov_floor, max_d2=max_d2, stream=stream)
 
-        def host(out, names):
-            if hasattr(stream, "synchronize"):
-                stream.synchronize()
-            elif stream is not None:
-                import torch
-                torch.cuda.ExternalStream(int(stream)).synchronize()
-            return {k: out[k].cpu().numpy() for k in names}
-
         def callables(m, o):
             def evaluate(T):
-                return host(m.score_map_derivs(o, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
+                return _to_host(stream, m.score_map_derivs(o, T, **kw), ("score", "d2_sum", "matched", "terms", "g", "H"))
 
             def score(T):
-                return host(m.score_map(o, T, **kw), ("score",))["score"]
+                return _to_host(stream, m.score_map(o, T, **kw), ("score",))["score"]
 
             return evaluate, score
 
@@ -2116,6 +1811,12 @@ class TwoDmap:
                                 ("rough", (n,), "<f4"), ("normal", (n, 3), "<f4"), ("flags", (n,), "<i4")):
             out[name] = mk(getattr(c, name), shape, ts)
         return out
+
+
+def _to_host(stream, out, names):
+    """register's and register_map's reads: wait for `stream`, then the named entries of `out` as numpy arrays"""
+    _stream_wait(stream)
+    return {k: (out[k].cpu().numpy() if hasattr(out[k], "cpu") else np.asarray(out[k])) for k in names}
 
 
 def count_morton(a, b):
