@@ -7,6 +7,7 @@ The map is a 16 x 16-column plane around the origin (so column indices of both s
 difference from the host twin.  tests/test_binding_calls_host.py checks what the host twins hand to the C library."""
 import numpy as np
 import pytest
+from tests.gpu_kit import dev as _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -74,11 +75,6 @@ def _cloud():
     Z = np.where(X < 1.0, 0.05, 0.30)                                   # one level up from x = 1 on
     keep = ~((X > -2.0) & (X < -1.0) & (Y > 0.5) & (Y < 1.5))           # the hole
     return np.stack([X, Y, Z], 1)[keep].astype(np.float32)
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _new_map():

@@ -6,20 +6,9 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
-
-
-def _handle(P, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(cloud[1:])).cuda()
 
 
 def _ref(cloud, P):
@@ -31,9 +20,9 @@ def test_dense_box_takes_blocked_buckets_and_gives_the_oracles_map(demand):
     P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08, demand=demand)
     cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
     ref = _ref(cloud, P)
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:])
     names = []
     for k in range(3):
         m.create2DMap(demand, t)
@@ -45,7 +34,7 @@ def test_dense_box_takes_blocked_buckets_and_gives_the_oracles_map(demand):
     # another cloud of the same scene (other noise: a few points beyond the first cloud's extent — the box has a block of margin)
     other = scenes.uniform_box(2_500_001, seed=0x5EED0777, half_xy=50.0)
     other[0] = cloud[0]
-    m.create2DMap(demand, _dev(other))
+    m.create2DMap(demand, dev(other[1:]))
     out = m.export()
     assert m.STRATEGY_NAMES[m.last_strategy()] == "partition_blocked" and m.retry_count() == 0
     rep = parity.compare(out, _ref(other, P), demand)
@@ -55,22 +44,22 @@ def test_dense_box_takes_blocked_buckets_and_gives_the_oracles_map(demand):
 def test_cloud_that_leaves_the_box_is_rebuilt_with_hashed_buckets():
     P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
     cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:])
     for _ in range(2):
         m.create2DMap("slope", t)
         m.sync()
     assert m.last_strategy() == 7
     wide = cloud.copy()
     wide[1:, :2] *= np.float32(1.5)                       # same size, 1.5 x the extent: most points outside the box
-    m.create2DMap("slope", _dev(wide))
+    m.create2DMap("slope", dev(wide[1:]))
     out = m.export()
     assert m.last_strategy() != 7 and m.retry_count() >= 1
     rep = parity.compare(out, _ref(wide, P))
     assert rep["ok"], rep["fail"]
     before = m.retry_count()
-    m.create2DMap("slope", _dev(wide))                    # the handle has forgotten the box: hashed from the start, no re-run
+    m.create2DMap("slope", dev(wide[1:]))                    # the handle has forgotten the box: hashed from the start, no re-run
     out = m.export()
     assert m.last_strategy() == 2 and m.retry_count() == before
     assert parity.compare(out, _ref(wide, P))["ok"]
@@ -89,9 +78,9 @@ def test_tall_or_uneven_maps_keep_hashed_buckets():
     sparse = scenes.uniform_box(1_300_001, half_xy=100.0)  # 8 points per column
     cases.append(("sparse", sparse, dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)))
     for name, cloud, P in cases:
-        m = _handle(P)
+        m = handle(P)
         m.setCloudFirst(cloud[0])
-        t = _dev(cloud)
+        t = dev(cloud[1:])
         for _ in range(3):
             m.create2DMap("slope", t)
             m.sync()

@@ -7,6 +7,7 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
@@ -14,25 +15,13 @@ P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
 BLOCKED = 7      # GNDT_STRATEGY_PARTITION_BLOCKED
 
 
-def _handle():
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"])
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(cloud[1:])).cuda()
-
-
 def _blocked_builds(cloud, builds=3):
     """Builds of `cloud` on a fresh handle: the first teaches the handle the box, the later ones must take blocked buckets and give
     the oracle's map."""
     ref = parity.ref_from_cloud(cloud, P, mode=2)
-    m = _handle()
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:])
     for k in range(builds):
         m.create2DMap("slope", t)
         out = m.export()
@@ -74,7 +63,7 @@ def test_out_of_block_record_in_a_late_chunk_reruns_hashed():
     m = _blocked_builds(cloud, builds=2)
     late = cloud.copy()
     late[-1] = np.array([1.1, 1.1, 6.2], np.float32)      # the last point, 12 levels up: beyond its block's levels
-    m.create2DMap("slope", _dev(late))
+    m.create2DMap("slope", dev(late[1:]))
     out = m.export()
     assert m.last_strategy() != BLOCKED and m.retry_count() >= 1
     rep = parity.compare(out, parity.ref_from_cloud(late, P, mode=2))

@@ -20,16 +20,14 @@ What can go wrong and where it is looked for:
   * the production combination: a 1.1 M-point box that takes 8 x 8 x 8 blocks with no debug option set."""
 import contextlib
 import functools
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import blocked_scenes as bs
 from tests import parity
+from tests import poison_tier
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
@@ -53,18 +51,6 @@ def two_kernel_tail(column_dest=1):
             T.set_debug_option(T.DEBUG_COLUMN_DEST, 1)
 
 
-def _handle(P, strategy=bs.TWO_LEVEL, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, min_points=P["min_points"], **kw)      # a fresh handle
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.array(cloud[1:])).cuda()      # (a copy: the shared clouds are read-only)
-
-
 def _is_the_oracles_map(m, ref, P, what):
     out = m.export()
     rep = parity.compare(out, ref, P["demand"], min_points=P["min_points"])
@@ -79,9 +65,9 @@ def _blocked(m, retries, what):
 def _decided_then_blocked(cloud, ref, P, want, what, builds=2):
     """A fresh handle: the first build hashed, its map decides the layout `want`; every later build blocked and not re-run; every map
     the oracle's.  -> the handle, the last export."""
-    m = _handle(P)
+    m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     out = retries = None
     for k in range(builds):
         m.create2DMap(P["demand"], t)
@@ -107,7 +93,7 @@ def test_every_block_shape_through_the_column_pass(name, demand):
         m, _ = _decided_then_blocked(cloud, ref, P, bs.SMALL_SCENES[name]["layout"], name, builds=3)
         other = bs.small_cloud(name, bs.SEED + 1)
         retries = m.retry_count()
-        m.create2DMap(demand, _dev(other))
+        m.create2DMap(demand, dev(other[1:], copy=True))
         _is_the_oracles_map(m, parity.ref_from_cloud(other, P, mode=2), P, (name, "other cloud"))
         _blocked(m, retries, (name, "other cloud"))
 
@@ -243,7 +229,7 @@ def test_a_table_that_holds_another_clouds_columns(demand):
         m, _ = _decided_then_blocked(a, ref_a, P, bs.SMALL_SCENES[name]["layout"], "A")
         retries = m.retry_count()
         for cloud, ref, what in ((b, ref_b, "B"), (a, ref_a, "A again")):
-            m.create2DMap(demand, _dev(cloud))
+            m.create2DMap(demand, dev(cloud[1:], copy=True))
             _is_the_oracles_map(m, ref, P, what)
             _blocked(m, retries, what)
 
@@ -262,11 +248,11 @@ def test_the_build_after_a_cloud_that_left_the_box():
     with two_kernel_tail():
         m, _ = _decided_then_blocked(a, ref_a, P, lay, "A")
         before = m.retry_count()
-        m.create2DMap("slope", _dev(out))
+        m.create2DMap("slope", dev(out[1:], copy=True))
         _is_the_oracles_map(m, ref_out, P, "the cloud that leaves the box")
         assert m.last_strategy() == bs.HASHED and m.retry_count() > before and m.block_layout()["state"] == -1
         for k in range(2):
-            m.create2DMap("slope", _dev(a))
+            m.create2DMap("slope", dev(a[1:], copy=True))
             _is_the_oracles_map(m, ref_a, P, ("A after the miss", k))
 
 
@@ -281,15 +267,15 @@ def test_the_build_after_the_staging_rows_ran_out():
     ref_a, ref_b = parity.ref_from_cloud(a, P, mode=2), parity.ref_from_cloud(b, P, mode=2)
     assert int(ref_a["num_nodes"]) == bs.SMALL_FOLDED_NODES
     with two_kernel_tail():
-        m = _handle(P, max_nodes_hint=bs.SMALL_FOLDED_NODES)
+        m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"], max_nodes_hint=bs.SMALL_FOLDED_NODES)
         m.setCloudFirst(a[0])
-        ta = _dev(a)
+        ta = dev(a[1:], copy=True)
         for k in range(2):
             m.create2DMap("slope", ta)
             _is_the_oracles_map(m, ref_a, P, ("folded cloud, build", k))
         assert m.last_strategy() == bs.BLOCKED and m.block_layout() == bs.SMALL_SCENES[name]["layout"]
         before = m.retry_count()
-        m.create2DMap("slope", _dev(b))
+        m.create2DMap("slope", dev(b[1:], copy=True))
         _is_the_oracles_map(m, ref_b, P, "unfolded cloud")
         assert m.retry_count() > before and m.last_strategy() == bs.BLOCKED
         after = m.retry_count()
@@ -325,24 +311,25 @@ POISON_IDS = [HERE + "test_every_block_shape_through_the_column_pass[flat_1-slop
               HERE + "test_the_build_after_a_cloud_that_left_the_box",
               HERE + "test_the_build_after_the_staging_rows_ran_out",
               HERE + "test_the_column_pass_and_the_node_pass_agree[flat_1]"]
-POISON_LIMIT_S = 60
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# measured_s: the whole child (interpreter start to exit) on the MI355X under the regular library; limit_s: three times that, rounded
+# up to 10 s (poison_malloc adds a fill and a device synchronisation to every allocation).
+GROUP = dict(measured_s=4.88, limit_s=20, ids=POISON_IDS)
 
 
-@pytest.mark.parametrize("byte", [0xA5, 0x7F], ids=["0xA5", "0x7F"])
+def test_every_node_id_of_the_poison_group_is_collected():
+    poison_tier.ids_collected(GROUP["ids"])
+
+
+def test_the_poison_limit_is_three_times_the_measured_time():
+    poison_tier.limit_follows_rule(GROUP["measured_s"], GROUP["limit_s"])
+
+
+@poison_tier.refused_under_variant
+@pytest.mark.parametrize("byte", poison_tier.BYTES, ids=poison_tier.BYTE_IDS)
 def test_under_poison(byte):
     """POISON_IDS in one child process on the -DGNDT_POISON variant (tests/poisoned_child.py, as tests/test_gpu_poisoned.py runs its
     groups): a column record or an ord_* word that nobody wrote reads as the fill byte there, not as a fresh process's zero."""
-    from grid_ndt_amd import _lib
-    _lib.build_native(variant="poison")          # (built by __graft_entry__.build(): nothing compiles here)
-    env = dict(os.environ, GNDT_LIB_VARIANT="poison")
-    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + POISON_IDS
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=POISON_LIMIT_S)
-    print(r.stdout[-6000:])
-    lines = [line for line in r.stdout.splitlines() if line.startswith('{"poisoned_child"')]
-    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-3000:])
-    rep = json.loads(lines[0])
-    assert rep["exit"] == 0 and rep["byte"] == byte and rep["device_bytes"] > 0 and rep["lib"] == _lib.lib_path("poison"), rep
+    poison_tier.run_group("the column table", GROUP["ids"], GROUP["limit_s"], byte)
 
 
 # ---- production -------------------------------------------------------------------------------------------------------------------------
@@ -355,9 +342,9 @@ def test_a_production_size_box_with_no_option_set():
     ref = parity.ref_from_cloud(cloud, P, mode=2)
     want = bs.plan(ref, bs.POINTS)
     assert (1 << want["shx"], 1 << want["shy"], 1 << want["shz"]) == (8, 8, 8)
-    m = _handle(P, strategy=0)
+    m = handle(P, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     for k in range(3):
         m.create2DMap("slope", t)
         _is_the_oracles_map(m, ref, P, (name, "build", k))

@@ -13,6 +13,7 @@ import pytest
 
 from tests import blocked_scenes as bs
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 SCENE = "levels_4_at_interval"
 BLOCKED = 7             # GNDT_STRATEGY_PARTITION_BLOCKED
@@ -120,26 +121,14 @@ def test_fixture_cloud_keeps_the_scenes_block_and_the_oracle_alone_passes(kind):
 
 
 # ---- GPU tier ----
-def _handle(P):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], min_points=P["min_points"])
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.array(cloud[1:])).cuda()
-
-
 def _blocked_builds(kind, demand):
     """Three builds on a fresh handle: the layout after the first is the rule's on the oracle's map, builds 2 and 3 are blocked, not
     re-run, and the oracle's map.  -> the handle."""
     P = bs.params(SCENE, demand)
     cloud, ref = _cloud(kind), _ref(kind, demand)
-    m = _handle(P)
+    m = handle(P, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     for k in range(3):
         m.create2DMap(demand, t)
         if k == 0:
@@ -179,12 +168,12 @@ def test_record_outside_its_block_and_record_beyond_the_key_range():
     P = bs.params(SCENE)
     m = _blocked_builds("borders", "slope")
     cloud = _cloud("borders")
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     # |nz| = 2.5 M > 2^21 - 1: found by the bucket kernel; the handle keeps its box
     bad = cloud.copy()
     bad[-1, 2] = np.float32(2.0e5)
     with pytest.raises(g.GndtError) as e:
-        m.create2DMap("slope", _dev(bad))
+        m.create2DMap("slope", dev(bad[1:], copy=True))
         m.sync()
     assert e.value.code == ERR_KEY_RANGE, str(e.value)
     m.create2DMap("slope", t)
@@ -196,7 +185,7 @@ def test_record_outside_its_block_and_record_beyond_the_key_range():
     out_of_box = cloud.copy()
     out_of_box[-1] = np.float32([1.1, 1.1, 0.2])
     before = m.retry_count()
-    m.create2DMap("slope", _dev(out_of_box))
+    m.create2DMap("slope", dev(out_of_box[1:], copy=True))
     out = m.export()
     assert m.last_strategy() != BLOCKED and m.retry_count() > before, (m.STRATEGY_NAMES[m.last_strategy()], m.retry_count())
     rep = parity.compare(out, parity.ref_from_cloud(out_of_box, P, mode=2), "slope")

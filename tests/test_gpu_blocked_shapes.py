@@ -10,23 +10,12 @@ import pytest
 
 from tests import blocked_scenes as bs
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
 BLOCKED = 7             # GNDT_STRATEGY_PARTITION_BLOCKED
 ERR_KEY_RANGE = 4
-
-
-def _handle(P):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], min_points=P["min_points"])      # a fresh handle, no hint
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.array(cloud[1:])).cuda()      # (a copy: the shared clouds are read-only)
 
 
 def _is_the_oracles_map(m, ref, P, what):
@@ -43,9 +32,9 @@ def _shape_and_parity(name, demand, min_points=3):
     ref = parity.ref_from_cloud(cloud, P, mode=2)
     want = bs.plan(ref, bs.POINTS)
     assert (1 << want["shx"], 1 << want["shy"], 1 << want["shz"]) == bs.SCENES[name]["block"], want      # (the fixture: also CPU tier)
-    m = _handle(P)
+    m = handle(P, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     for k in range(3):
         m.create2DMap(demand, t)
         _is_the_oracles_map(m, ref, P, (name, "build", k))
@@ -56,7 +45,7 @@ def _shape_and_parity(name, demand, min_points=3):
         else:
             assert m.last_strategy() == BLOCKED and m.retry_count() == 0, (k, m.STRATEGY_NAMES[m.last_strategy()], m.retry_count())
     other = bs.cloud(name, bs.SEED + 1)
-    m.create2DMap(demand, _dev(other))
+    m.create2DMap(demand, dev(other[1:], copy=True))
     _is_the_oracles_map(m, parity.ref_from_cloud(other, P, mode=2), P, (name, "other cloud"))
     assert m.last_strategy() == BLOCKED and m.retry_count() == 0, (m.STRATEGY_NAMES[m.last_strategy()], m.retry_count())
     assert m.block_layout() == want
@@ -84,9 +73,9 @@ def test_key_range_errors_inside_a_blocked_build():
     P = bs.params(name)
     cloud = bs.cloud(name)
     ref = parity.ref_from_cloud(cloud, P, mode=2)
-    m = _handle(P)
+    m = handle(P, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     for _ in range(2):
         m.create2DMap("slope", t)
         m.sync()
@@ -95,7 +84,7 @@ def test_key_range_errors_inside_a_blocked_build():
         bad = cloud.copy()
         bad[-1, axis] = np.float32(value)
         with pytest.raises(g.GndtError) as e:
-            m.create2DMap("slope", _dev(bad))
+            m.create2DMap("slope", dev(bad[1:], copy=True))
             m.sync()
         assert e.value.code == ERR_KEY_RANGE, str(e.value)
         during = m.STRATEGY_NAMES[m.last_strategy()]
@@ -114,15 +103,15 @@ def test_staging_rows_run_out_inside_a_blocked_build():
     a = bs.folded(b)
     ref_a = parity.ref_from_cloud(a, P, mode=2)
     assert int(ref_a["num_nodes"]) == bs.FOLDED_NODES
-    m = _handle(P)
+    m = handle(P, min_points=P["min_points"])
     m.setCloudFirst(a[0])
-    ta = _dev(a)
+    ta = dev(a[1:], copy=True)
     for k in range(2):
         m.create2DMap("slope", ta)
         _is_the_oracles_map(m, ref_a, P, ("folded cloud, build", k))
     assert m.last_strategy() == BLOCKED
     before = m.retry_count()
-    m.create2DMap("slope", _dev(b))
+    m.create2DMap("slope", dev(b[1:], copy=True))
     _is_the_oracles_map(m, parity.ref_from_cloud(b, P, mode=2), P, "unfolded cloud")
     print(f"[blocked shapes] staging rows: re-runs {before} -> {m.retry_count()}, the build ended as {m.STRATEGY_NAMES[m.last_strategy()]}")
     assert m.retry_count() > before

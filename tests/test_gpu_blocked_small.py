@@ -23,22 +23,11 @@ import pytest
 
 from tests import blocked_scenes as bs
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
 EXACT_FIELDS = ("sx", "sy", "sz", "count", "first_idx", "flags")
-
-
-def _handle(P):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=bs.TWO_LEVEL, min_points=P["min_points"])      # a fresh handle, no hint
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.array(cloud[1:])).cuda()      # (a copy: the shared clouds are read-only)
 
 
 def _set_origin(m, origin):
@@ -66,9 +55,9 @@ def test_with_the_default_floor_a_small_scene_is_never_blocked():
     P = bs.small_params(name)
     cloud = bs.small_cloud(name)
     ref = parity.ref_from_cloud(cloud, P, mode=2)
-    m = _handle(P)
+    m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:], copy=True)
     for k in range(3):
         m.create2DMap("slope", t)
         _is_the_oracles_map(m, ref, P, ("default floor, build", k))
@@ -97,9 +86,9 @@ def test_every_block_shape_small(name, demand):
     want = bs.plan(ref, bs.SMALL_POINTS)
     assert want == bs.SMALL_SCENES[name]["layout"]               # (the fixture: also CPU tier)
     with bs.blocked_floor():
-        m = _handle(P)
+        m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
         m.setCloudFirst(cloud[0])
-        t = _dev(cloud)
+        t = dev(cloud[1:], copy=True)
         retries = None
         for k in range(3):
             m.create2DMap(demand, t)
@@ -112,7 +101,7 @@ def test_every_block_shape_small(name, demand):
             else:
                 _blocked_and_not_rerun(m, retries, (name, k))
         other = bs.small_cloud(name, bs.SEED + 1)
-        m.create2DMap(demand, _dev(other))
+        m.create2DMap(demand, dev(other[1:], copy=True))
         _is_the_oracles_map(m, parity.ref_from_cloud(other, P, mode=2), P, (name, "other cloud"))
         _blocked_and_not_rerun(m, retries, (name, "other cloud"))
         assert m.block_layout() == want
@@ -128,9 +117,9 @@ def test_fuzzed_boxes(seed):
     want = bs.plan(ref, b["n"])
     assert want["state"] == 1
     with bs.blocked_floor():
-        m = _handle(P)
+        m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
         m.setCloudFirst(cloud[0])
-        t = _dev(cloud)
+        t = dev(cloud[1:], copy=True)
         m.create2DMap(b["demand"], t)
         _is_the_oracles_map(m, ref, P, (seed, "first build"))
         got, retries = m.block_layout(), m.retry_count()
@@ -156,13 +145,13 @@ def test_staging_rows_run_out_inside_a_small_blocked_build():
         m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=bs.TWO_LEVEL, min_points=P["min_points"], max_nodes_hint=bs.SMALL_FOLDED_NODES)
         m.setInterval(P["slope_interval"])
         m.setCloudFirst(a[0])
-        ta = _dev(a)
+        ta = dev(a[1:], copy=True)
         for k in range(2):
             m.create2DMap("slope", ta)
             _is_the_oracles_map(m, ref_a, P, ("folded cloud, build", k))
         assert m.last_strategy() == bs.BLOCKED and m.block_layout() == bs.SMALL_SCENES[name]["layout"]
         before = m.retry_count()
-        m.create2DMap("slope", _dev(b))
+        m.create2DMap("slope", dev(b[1:], copy=True))
         _is_the_oracles_map(m, parity.ref_from_cloud(b, P, mode=2), P, "unfolded cloud")
         print(f"[blocked small] staging rows: re-runs {before} -> {m.retry_count()}, the build ended as {m.STRATEGY_NAMES[m.last_strategy()]}")
         assert m.retry_count() > before and m.last_strategy() == bs.BLOCKED      # (more rows is not a "no": the re-run is blocked again)
@@ -176,7 +165,7 @@ def test_layout_lifetime_on_one_handle():
     mem = bs.LayoutMemory(floor=bs.SMALL_FLOOR)
     seen = []
     with bs.blocked_floor():
-        m = _handle(P)
+        m = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
         m.setCloudFirst(bs.small_cloud(bs.LIFETIME_SCENE)[0])
         m._ensure("slope")                                       # (the handle itself: made by the first call that needs it)
         assert m.block_layout()["state"] == 0
@@ -189,7 +178,7 @@ def test_layout_lifetime_on_one_handle():
             ref = parity.ref_from_cloud(cloud, P, mode=2)
             n = cloud.shape[0] - 1
             before, model_before = m.retry_count(), mem.retries
-            m.create2DMap("slope", _dev(cloud))
+            m.create2DMap("slope", dev(cloud[1:], copy=True))
             _is_the_oracles_map(m, ref, P, what)
             model_strategy = mem.build(ref, n)
             assert (model_strategy, mem.retries - model_before, mem.state) == (strategy, reruns, state), what      # (the script: also CPU tier)
@@ -223,9 +212,9 @@ def test_large_then_small_on_one_handle(large, small):
     ref = parity.ref_from_cloud(cloud, P, mode=2)
     want = bs.SMALL_SCENES[small]["layout"]
     with bs.blocked_floor():
-        used = _handle(P)
+        used = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
         used.setCloudFirst(big[0])
-        tb = _dev(big)
+        tb = dev(big[1:], copy=True)
         for _ in range(2):
             used.create2DMap("slope", tb)
             used.sync()
@@ -234,9 +223,9 @@ def test_large_then_small_on_one_handle(large, small):
         del tb
         _set_origin(used, cloud[0])
         assert used.block_layout()["state"] == (1 if np.array_equal(big[0], cloud[0]) else 0)
-        fresh = _handle(P)
+        fresh = handle(P, bs.TWO_LEVEL, min_points=P["min_points"])
         fresh.setCloudFirst(cloud[0])
-        t = _dev(cloud)
+        t = dev(cloud[1:], copy=True)
         outs = []
         for m in (used, fresh):
             m.create2DMap("slope", t)

@@ -15,6 +15,7 @@ from grid_ndt_amd import scenes
 from grid_ndt_amd.map2d import _stream_ptr
 from tests import cast_ref as cf
 from tests import query_ref as qr
+from tests.gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -23,11 +24,6 @@ VOXEL, NDT = cf.VOXEL, cf.NDT
 MODE_NAMES = {VOXEL: "voxel", NDT: "ndt"}
 FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
 N = 2000
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _sensor(k, lift):
@@ -55,7 +51,7 @@ def scene(name):
         m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
         m.setInterval(P["slope_interval"])
         m.setCloudFirst(cloud[0])
-        m.create2DMap("slope", _dev(cloud[1:]))
+        m.create2DMap("slope", dev(cloud[1:]))
         m.sync()
         if name == "tile":
             assert m.STRATEGY_NAMES[m.last_strategy()] == "tile"
@@ -101,20 +97,20 @@ def test_both_entry_points_equal_the_restatement_bit_for_bit(name, mode):
     assert hit.sum() > 100 and (want["status"] == cf.MISS).sum() > 100 and (want["status"] == cf.SKIPPED).sum() > 10
     ends = s["ends"]
     # shared origin (stride 0): device and host, end strides 12 and 16, the stats
-    out, st = m.cast_rays(s["sensor"], _dev(ends), mode=mn, stats=True)
+    out, st = m.cast_rays(s["sensor"], dev(ends), mode=mn, stats=True)
     cf.assert_same(host(out), want, (name, mode, "device"))
     assert st == want["stats"]
-    cf.assert_same(host(m.cast_rays(s["sensor"], _dev(pad4(ends)), mode=mn)), want, "device, stride 16")
+    cf.assert_same(host(m.cast_rays(s["sensor"], dev(pad4(ends)), mode=mn)), want, "device, stride 16")
     out, st = m.cast_rays(s["sensor"], ends, mode=mn, stats=True)
     cf.assert_same(out, want, "host")
     assert st == want["stats"]
     cf.assert_same(m.cast_rays(s["sensor"], pad4(ends), mode=mn), want, "host, stride 16")
     # batches around a wave: every lane count of the last wave's tally, with the tally and without, device and host
     for n in (1, 63, 64, 65):
-        out, st = m.cast_rays(s["sensor"], _dev(ends[:n]), mode=mn, stats=True)
+        out, st = m.cast_rays(s["sensor"], dev(ends[:n]), mode=mn, stats=True)
         cf.assert_same(host(out), sliced(want, n), n)
         assert st["rays"] + st["skipped"] == n and st["hits"] == int((want["row"][:n] != cf.NO_ROW).sum())
-        cf.assert_same(host(m.cast_rays(s["sensor"], _dev(ends[:n]), mode=mn)), sliced(want, n), (n, "no stats"))
+        cf.assert_same(host(m.cast_rays(s["sensor"], dev(ends[:n]), mode=mn)), sliced(want, n), (n, "no stats"))
         out, st_h = m.cast_rays(s["sensor"], ends[:n], mode=mn, stats=True)
         cf.assert_same(out, sliced(want, n), (n, "host"))
         assert st_h == st
@@ -122,10 +118,10 @@ def test_both_entry_points_equal_the_restatement_bit_for_bit(name, mode):
     want = ref(s, mode, per_ray=True)
     assert (want["row"] != cf.NO_ROW).sum() > 100
     for o in (s["origins"], pad4(s["origins"])):
-        cf.assert_same(host(m.cast_rays(_dev(o), _dev(ends), mode=mn)), want, ("device origins", o.shape))
+        cf.assert_same(host(m.cast_rays(dev(o), dev(ends), mode=mn)), want, ("device origins", o.shape))
         cf.assert_same(m.cast_rays(o, ends, mode=mn), want, ("host origins", o.shape))
     for n in (1, 63, 64, 65):
-        cf.assert_same(host(m.cast_rays(_dev(s["origins"][:n]), _dev(ends[:n]), mode=mn)), sliced(want, n), (n, "device origins"))
+        cf.assert_same(host(m.cast_rays(dev(s["origins"][:n]), dev(ends[:n]), mode=mn)), sliced(want, n), (n, "device origins"))
         cf.assert_same(m.cast_rays(s["origins"][:n], ends[:n], mode=mn), sliced(want, n), (n, "host origins"))
 
 
@@ -141,7 +137,7 @@ def test_parameters_equal_the_restatement(mode):
     for kw in cases:
         want = ref(s, mode, **kw)
         assert not np.array_equal(want["row"], base["row"]), kw              # the parameter matters on these rays
-        cf.assert_same(host(s["m"].cast_rays(s["sensor"], _dev(s["ends"]), mode=MODE_NAMES[mode], **kw)), want, kw)
+        cf.assert_same(host(s["m"].cast_rays(s["sensor"], dev(s["ends"]), mode=MODE_NAMES[mode], **kw)), want, kw)
 
 
 @pytest.mark.parametrize("mode", [VOXEL, NDT])
@@ -152,7 +148,7 @@ def test_lanes_that_leave_the_walk_at_different_steps(mode):
     # a wave of 64 identical rays, between two waves of different ones
     ends = np.concatenate([good[:64], np.tile(good[5], (64, 1)), good[64:128]])
     want = cf.cast(cells, s["origin"], P["grid_len"], P["z_len"], s["sensor"], ends, mode=mode)
-    cf.assert_same(host(m.cast_rays(s["sensor"], _dev(ends), mode=MODE_NAMES[mode])), want, "identical")
+    cf.assert_same(host(m.cast_rays(s["sensor"], dev(ends), mode=MODE_NAMES[mode])), want, "identical")
     assert len(set(want["row"][64:128].tolist())) == 1
     # zero-length rays inside occupied voxels alternating with rays across the whole map
     lo, hi = s["pts"].min(0), s["pts"].max(0)
@@ -167,7 +163,7 @@ def test_lanes_that_leave_the_walk_at_different_steps(mode):
     assert (steps[0::2] == 1).all() and (steps[1::2] > 100).all()
     if mode == VOXEL:                                                         # (a scan point's voxel holds a node: range 0)
         assert (want["row"][0::2] != cf.NO_ROW).all() and (want["range"][0::2] == 0).all()
-    cf.assert_same(host(m.cast_rays(_dev(origins), _dev(ends), mode=MODE_NAMES[mode])), want, "alternating")
+    cf.assert_same(host(m.cast_rays(dev(origins), dev(ends), mode=MODE_NAMES[mode])), want, "alternating")
 
 
 @pytest.mark.parametrize("name", ["atomic", "partition", "tile"])
@@ -176,7 +172,7 @@ def test_voxel_hits_against_the_clearing_walk_and_the_node_query(name):
     import torch
     s = scene(name)
     m = s["m"]
-    pts = _dev(s["pts"][:4096])
+    pts = dev(s["pts"][:4096])
     out = m.cast_rays(s["sensor"], pts, mode="voxel", min_count=1)
     row, rng = out["row"].cpu().numpy().astype(np.int64), out["range"].cpu().numpy()
     _, words = m.clear_rays(s["sensor"], pts, count_only=True, passes=True)
@@ -194,8 +190,8 @@ def test_the_map_is_untouched_and_the_bits_repeat():
     import torch
     s = scene("atomic")
     m = s["m"]
-    e = _dev(s["ends"])
-    o = _dev(s["origins"])
+    e = dev(s["ends"])
+    o = dev(s["origins"])
     for mode in ("voxel", "ndt"):
         a = host(m.cast_rays(o, e, mode=mode))
         b = host(m.cast_rays(o, e, mode=mode))
@@ -231,7 +227,7 @@ def test_cast_scan_is_cast_rays_of_the_documented_ends():
     ends = np.stack([T[i, 3] + R * ((T[i, 0] * x + T[i, 1] * y) + T[i, 2] * z) for i in range(3)], 1).astype(np.float32)
     for mode in ("voxel", "ndt"):
         got = host(m.cast_scan(T, d, R, mode=mode))
-        want = host(m.cast_rays(T[:, 3].astype(np.float32), _dev(ends), mode=mode))
+        want = host(m.cast_rays(T[:, 3].astype(np.float32), dev(ends), mode=mode))
         assert (want["row"] >= 0).sum() > 500
         for k in ("row", "range", "d2"):
             assert np.array_equal(got[k].view(np.uint32), want[k].view(np.uint32)), (mode, k)
@@ -259,7 +255,7 @@ def test_invalid_arguments_leave_the_outputs_untouched():
     bad_params = [ok(mode=2), ok(mode=-1), ok(reserved=1), ok(min_count=-1), ok(mode=1, min_count=1), ok(mode=1, min_count=2)]
     bad_params += [ok(**{k: v}) for k in ("max_range", "min_range", "cov_rel", "cov_floor", "max_d2") for v in (-1.0, nan, inf)]
     for device in (True, False):
-        mk = (lambda a, dt=np.float32: _dev(a, dt)) if device else (lambda a, dt=np.float32: np.ascontiguousarray(a, dt))
+        mk = (lambda a, dt=np.float32: dev(a, dt)) if device else (lambda a, dt=np.float32: np.ascontiguousarray(a, dt))
         o, e = mk(s["sensor"]), mk(ends)
         outs = [mk(np.full(n, -7, np.int32), np.int32), mk(np.full(n, -7.0, np.float32)), mk(np.full(n, -7.0, np.float32))]
         ptr = lambda t: t.data_ptr() if device else t.ctypes.data
@@ -288,17 +284,17 @@ def test_invalid_arguments_leave_the_outputs_untouched():
     small = scenes.terrain_cloud(20_000)
     h5.setCloudFirst(small[0])
     with pytest.raises(g.GndtError) as err:
-        h5.cast_rays(s["sensor"], _dev(ends))
+        h5.cast_rays(s["sensor"], dev(ends))
     assert err.value.code == 1                                                    # no finished build
-    h5.create2DMap("slope", _dev(small[1:]))
+    h5.create2DMap("slope", dev(small[1:]))
     for mc in (3, 4):
         with pytest.raises(g.GndtError) as err:
-            h5.cast_rays(s["sensor"], _dev(ends), mode="ndt", min_count=mc)
+            h5.cast_rays(s["sensor"], dev(ends), mode="ndt", min_count=mc)
         assert err.value.code == 1
-    h5.cast_rays(s["sensor"], _dev(ends), mode="ndt", min_count=5)
-    h5.cast_rays(s["sensor"], _dev(ends), mode="voxel", min_count=1)
+    h5.cast_rays(s["sensor"], dev(ends), mode="ndt", min_count=5)
+    h5.cast_rays(s["sensor"], dev(ends), mode="voxel", min_count=1)
     with pytest.raises(ValueError):
-        m.cast_rays(s["origins"][:5], _dev(ends))
+        m.cast_rays(s["origins"][:5], dev(ends))
 
 
 def test_capture_is_refused_and_the_empty_batch():
@@ -308,7 +304,7 @@ def test_capture_is_refused_and_the_empty_batch():
     s = scene("atomic")
     m = s["m"]
     # n == 0: GNDT_OK, stats zeroed, nothing written
-    outs = [_dev(np.full(4, -7, np.int32), np.int32), _dev(np.full(4, -7.0)), _dev(np.full(4, -7.0))]
+    outs = [dev(np.full(4, -7, np.int32), np.int32), dev(np.full(4, -7.0)), dev(np.full(4, -7.0))]
     st = CastStats(5, 5, 5)
     for device in (True, False):
         st = CastStats(5, 5, 5)
@@ -316,14 +312,14 @@ def test_capture_is_refused_and_the_empty_batch():
         assert (st.rays, st.skipped, st.hits) == (0, 0, 0)
     torch.cuda.synchronize()
     assert all(bool((t == -7).all()) for t in outs)
-    out, st = m.cast_rays(s["sensor"], _dev(np.zeros((0, 3), np.float32)), stats=True)
+    out, st = m.cast_rays(s["sensor"], dev(np.zeros((0, 3), np.float32)), stats=True)
     assert st == {"rays": 0, "skipped": 0, "hits": 0} and all(len(out[k]) == 0 for k in ("row", "range", "d2"))
     out = m.cast_rays(s["sensor"], np.zeros((0, 4), np.float32), mode="ndt")
     assert all(len(out[k]) == 0 for k in ("row", "range", "d2"))
     # a stream under capture
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
-        o, e = _dev(s["sensor"]), _dev(s["ends"][:256])
+        o, e = dev(s["sensor"]), dev(s["ends"][:256])
         stream.wait_stream(torch.cuda.default_stream())
         graph = torch.cuda.CUDAGraph()
         with pytest.raises(g.GndtError) as err:

@@ -9,6 +9,7 @@ from grid_ndt_amd import scenes
 from tests import clear_ref as cr
 from tests import parity
 from tests import query_ref as qr
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
@@ -17,18 +18,6 @@ TERRAIN = scenes.TERRAIN_PARAMS
 FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
 MASK = np.uint32(0x7FFFFFFF)
 DEBUG_CLEAR_EXTENT = 5
-
-
-def _handle(P, strategy=AUTO, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def _assert_same(got, want, fields=FIELDS):
@@ -49,7 +38,7 @@ def _sensor(k, lift=4.0):
 
 
 def _words(m, o, pts, **kw):
-    st, w = m.clear_rays(o, _dev(pts), count_only=True, passes=True, **kw)
+    st, w = m.clear_rays(o, dev(pts), count_only=True, passes=True, **kw)
     return st, w.cpu().numpy().view(np.uint32)
 
 
@@ -68,10 +57,10 @@ def _scene(name):
         P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
         cloud, strategy = scenes.uniform_box(2_500_001, half_xy=50.0), AUTO
         sensor, pts = np.array([3.1, -2.2, 0.7], np.float32), cloud[1::250]
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
 
     def make():
-        m = _handle(P, strategy)
+        m = handle(P, strategy)
         m.setCloudFirst(cloud[0])
         for _ in range(2 if name == "blocked" else 1):
             m.create2DMap("slope", t)
@@ -116,17 +105,17 @@ def _rescan(frame, seed=4):
 
 def _twins(P, origin, body):
     """two handles with the same fp64 sums (the statistics of one build merged into both), stream position = len(body)"""
-    x = _handle(P, ATOMIC)
+    x = handle(P, ATOMIC)
     x.setCloudFirst(origin)
-    x.change2DMap("slope", _dev(body))
+    x.change2DMap("slope", dev(body))
     st = {k: v.clone() for k, v in x.stats_export().items()}
     out = []
     for _ in range(2):
-        m = _handle(P, ATOMIC)
+        m = handle(P, ATOMIC)
         m.setCloudFirst(origin)
         m.reset("slope")
         m.stats_merge(st["key"], st["sums"], st["count"], st["first_idx"])
-        m.accumulate("slope", _dev(np.zeros((0, 3), np.float32)), first_idx_base=len(body))
+        m.accumulate("slope", dev(np.zeros((0, 3), np.float32)), first_idx_base=len(body))
         m.finalize()
         out.append(m)
     return out
@@ -145,14 +134,14 @@ def test_clear_equals_remove_and_the_oracle():
     words, _, _ = cr.passes(before, origin, P["grid_len"], P["z_len"], sensor, nxt)
     drop = cr.cleared_rows(words, 1)
     assert 0 < drop.sum() < before["num_nodes"]
-    st, got = a.clear_rays(sensor, _dev(nxt), passes=True)
+    st, got = a.clear_rays(sensor, dev(nxt), passes=True)
     got = got.cpu().numpy().view(np.uint32)
     assert st["cleared"] == int(drop.sum()) and st["rays"] == len(nxt)
     assert np.array_equal(got[~drop & ((words & cr.PROTECTED) == 0)], words[~drop & ((words & cr.PROTECTED) == 0)])
     sx, sy, sz, _, ok = qr.keys(body, origin, P["grid_len"], P["z_len"])
     assert ok.all()
     gone = np.isin(qr.pack(sx, sy, sz), _keys(before)[drop])
-    b.del2DMap("slope", _dev(body[gone]))
+    b.del2DMap("slope", dev(body[gone]))
     ea, eb = a.export(), b.export()
     _assert_same(ea, eb)
     assert not np.isin(_keys(ea), _keys(before)[drop]).any()
@@ -161,7 +150,7 @@ def test_clear_equals_remove_and_the_oracle():
     ref["first_idx"] = np.flatnonzero(alive)[ref["first_idx"].astype(np.int64)].astype(ref["first_idx"].dtype)
     parity.assert_parity(ea, ref)
     for m in (a, b):
-        m.change2DMap("slope", _dev(nxt))
+        m.change2DMap("slope", dev(nxt))
     ea, eb = a.export(), b.export()
     for k in ("num_nodes", "num_columns", "num_slopes"):
         assert ea[k] == eb[k]
@@ -195,24 +184,24 @@ def test_ghost_obstacle_is_cleared():
     P = TERRAIN
     origin, frames, obs, s3 = _ghost_stream()
     assert len(obs) > 1000
-    a, b = _handle(P, ATOMIC), _handle(P, ATOMIC)
+    a, b = handle(P, ATOMIC), handle(P, ATOMIC)
     for m in (a, b):
         m.setCloudFirst(origin)
     for k, f in enumerate(frames[:3]):
-        a.change2DMap("slope", _dev(np.concatenate([f, obs]) if k == 1 else f))
-        b.change2DMap("slope", _dev(f))
+        a.change2DMap("slope", dev(np.concatenate([f, obs]) if k == 1 else f))
+        b.change2DMap("slope", dev(f))
         if k == 1:     # precondition: the obstacle put nodes (and with them rows and labels) that the obstacle-free stream does not have
             ghost_keys = np.setdiff1d(_keys(a.export()), _keys(b.export()))
             assert len(ghost_keys) > 100
     for m in (a, b):
-        m.change2DMap("slope", _dev(frames[3]))
+        m.change2DMap("slope", dev(frames[3]))
     ea = a.export()
     ghost_keys = np.setdiff1d(_keys(ea), _keys(b.export()))       # (what later frames did not also put points into)
     assert len(ghost_keys) > 100
     seen = qr.node_rows(ea, frames[3], origin, P["grid_len"], P["z_len"])
     seen_keys = _keys(ea)[seen[seen >= 0]]
-    sa = a.clear_rays(s3, _dev(frames[3]))
-    sb = b.clear_rays(s3, _dev(frames[3]))
+    sa = a.clear_rays(s3, dev(frames[3]))
+    sb = b.clear_rays(s3, dev(frames[3]))
     assert sa["cleared"] == sb["cleared"] + len(ghost_keys)
     ea, eb = a.export(), b.export()
     assert not np.isin(ghost_keys, _keys(ea)).any()                # the obstacle is gone
@@ -246,9 +235,9 @@ def test_min_passes():
     origin, body, nxt = fr[0], fr[1:65_537], _rescan(fr[32_769:65_537])
     sensor = _sensor(1, 1.8)
     for mp in (1, 3):
-        m = _handle(P, ATOMIC)
+        m = handle(P, ATOMIC)
         m.setCloudFirst(origin)
-        m.change2DMap("slope", _dev(body))
+        m.change2DMap("slope", dev(body))
         before = m.export()
         _, w = _words(m, sensor, nxt)
         st, got = m.clear_rays(sensor, nxt, min_passes=mp, passes=True)      # (host entry point)
@@ -271,35 +260,35 @@ def test_errors_and_lifetime():
     origin, f0, f1 = fr[0], fr[1:32_769], fr[32_769:65_537]
     sensor = _sensor(1, 1.8)
     # PARTITION-built: clearing refused, the map unchanged; count-only works
-    p = _handle(P, PARTITION)
+    p = handle(P, PARTITION)
     p.setCloudFirst(origin)
-    p.create2DMap("slope", _dev(f0))
+    p.create2DMap("slope", dev(f0))
     before = p.export()
     with pytest.raises(g.GndtError) as e:
-        p.clear_rays(sensor, _dev(f1))
+        p.clear_rays(sensor, dev(f1))
     assert e.value.code == 1
     _assert_same(p.export(), before)
-    assert p.clear_rays(sensor, _dev(f1), count_only=True)["rays"] == len(f1)
-    m = _handle(P, ATOMIC, max_points_hint=200_000, max_nodes_hint=200_000)
+    assert p.clear_rays(sensor, dev(f1), count_only=True)["rays"] == len(f1)
+    m = handle(P, ATOMIC, max_points_hint=200_000, max_nodes_hint=200_000)
     m.setCloudFirst(origin)
-    m.change2DMap("slope", _dev(f0))
-    m.change2DMap("slope", _dev(f1))
+    m.change2DMap("slope", dev(f0))
+    m.change2DMap("slope", dev(f1))
     f1 = _rescan(f1)
     before = m.export()
     for kw in ({"min_passes": 0}, {"max_range": -1.0}, {"end_margin": float("nan")}, {"max_range": float("inf")}):
         with pytest.raises(g.GndtError) as e:
-            m.clear_rays(sensor, _dev(f1), **kw)
+            m.clear_rays(sensor, dev(f1), **kw)
         assert e.value.code == 1
     for o in ((float("nan"), 0, 0), (1e7, 0, 0)):
         with pytest.raises(g.GndtError) as e:
-            m.clear_rays(o, _dev(f1))
+            m.clear_rays(o, dev(f1))
         assert e.value.code == 1
-    st = m.clear_rays(sensor, _dev(np.zeros((0, 3), np.float32)))
+    st = m.clear_rays(sensor, dev(np.zeros((0, 3), np.float32)))
     assert st == {"rays": 0, "skipped": 0, "protected_rows": 0, "cleared": 0}
     _assert_same(m.export(), before)
     bad = f1.copy()
     bad[::7] = np.nan
-    st = m.clear_rays(sensor, _dev(bad), count_only=True)
+    st = m.clear_rays(sensor, dev(bad), count_only=True)
     assert st["skipped"] == len(bad[::7]) and st["rays"] == len(bad) - len(bad[::7])
     # cost map stale after a clear; queries answer from the new map
     cells = m.export()
@@ -307,19 +296,19 @@ def test_errors_and_lifetime():
     m.computeCost(tuple(float(v) for v in cells["mean"][slopes[len(slopes) // 2]]))
     w, _, _ = cr.passes(cells, origin, P["grid_len"], P["z_len"], sensor, f1)
     drop = cr.cleared_rows(w, 1)
-    assert m.clear_rays(sensor, _dev(f1))["cleared"] == int(drop.sum()) > 0
+    assert m.clear_rays(sensor, dev(f1))["cleared"] == int(drop.sum()) > 0
     with pytest.raises(g.GndtError) as e:
         m.cost_export()
     assert e.value.code == 1
     seen = fr[1:65_537]
     sx, sy, sz, _, _ = qr.keys(seen, origin, P["grid_len"], P["z_len"])
     gone = np.isin(qr.pack(sx, sy, sz), _keys(cells)[drop])
-    rows = m.query(_dev(seen)).cpu().numpy().astype(np.int64)
+    rows = m.query(dev(seen)).cpu().numpy().astype(np.int64)
     assert (rows[gone] == qr.NO_ROW).all() and (rows[~gone] >= 0).all()
     # capture refused; a graph recorded before a clear is reported stale
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
-        buf = _dev(f1)
+        buf = dev(f1)
         s.wait_stream(torch.cuda.default_stream())
         graph = torch.cuda.CUDAGraph()
         with g.graph_capture(graph, s):
@@ -348,9 +337,9 @@ def test_hot_voxel_counts_every_ray():
     sensor = np.array([cloud[5000, 0], cloud[5000, 1], cloud[5000, 2] + 1.3], np.float32)
     rng = np.random.default_rng(5)
     near = (sensor[None, :] + rng.uniform(-0.05, 0.05, size=(20, 3))).astype(np.float32)    # nodes at the sensor
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
-    m.change2DMap("slope", _dev(np.concatenate([cloud[1:], near])))
+    m.change2DMap("slope", dev(np.concatenate([cloud[1:], near])))
     cells = m.export()
     c = cloud[9000]
     ends = np.empty((scenes.FRAME_POINTS, 3), np.float32)

@@ -7,7 +7,6 @@ row counts at the kernels' edges — the slots and the limit of the one-workgrou
 depth, the second trip of the grid-stride loops.  No tolerance anywhere:
 the one step that is not IEEE arithmetic is the gates' acosf, and every compared scene keeps its angle decisions more than 1e-3 degrees
 from the threshold."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -16,6 +15,8 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import clearance_ref as cr
 from tests import frontier_ref as fr
+from tests.gpu_kit import Padded, PaddedCall, build, debug_option, dev, robot_arg, to_np
+from tests.gpu_kit import tails_untouched as untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -29,73 +30,24 @@ FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "norma
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
-@contextlib.contextmanager
 def one_workgroup(on):
     """gndt_debug_set_option(GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP, .) for a block; the default comes back whatever happens in it"""
-    import grid_ndt_amd as g
-    g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_CLEARANCE_ONE_WORKGROUP, 1 if on else 0)
-    try:
-        yield
-    finally:
-        g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_CLEARANCE_ONE_WORKGROUP, 1)
-
-
-def _robot(robot):
-    from grid_ndt_amd._lib import Robot
-    if robot is None:
-        return None
-    d = dict(cr.ROBOT)
-    d.update(robot)
-    return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+    return debug_option("DEBUG_CLEARANCE_ONE_WORKGROUP", 1 if on else 0, 1)
 
 
 def raw(m, mask=cr.BLOCKED, max_hops=32, robot=None, outs=("hops", "nearest", "sides"), stream=None, host=False, reserved=(0,) * 6, counts=True):
     """The C entry points, every output num_nodes + PAD entries of sentinel.  -> (rc, dict(hops, nearest, sides: the outputs asked for,
     cut to num_nodes; counts; tails: what lies behind num_nodes))"""
-    import torch
     from grid_ndt_amd._lib import ClearanceParams
     n = int(m.sync()[0])
     prm = ClearanceParams(mask, max_hops, (C.c_uint32 * 6)(*reserved))
-    dt = {"hops": np.uint32, "nearest": np.uint32, "sides": np.uint8}
-    if host:
-        buf = {k: np.full(n + PAD, SENTINEL & (0xFF if k == "sides" else 0xFFFFFFFF), dt[k]) for k in outs}
-        cnt = np.full(4, SENTINEL, np.uint32)
-        ptr = lambda a: C.c_void_p(a.ctypes.data)
-    else:
-        buf = {k: torch.from_numpy(np.full(n + PAD, SENTINEL & (0xFF if k == "sides" else 0xFFFFFFFF), dt[k]).view(np.uint8)).cuda() for k in outs}
-        cnt = torch.full((4,), SENTINEL, dtype=torch.int32, device="cuda")
-        ptr = lambda a: C.c_void_p(a.data_ptr())
-    args = [m._h, _robot(robot), C.byref(prm)] + [ptr(buf[k]) if k in buf else None for k in ("hops", "nearest", "sides")] + \
-           [ptr(cnt) if counts else None]
-    if host:
-        rc = m._L.gndt_clearance(*args)
-    else:
-        rc = m._L.gndt_clearance_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        buf = {k: t.cpu().numpy().view(dt[k]) for k, t in buf.items()}
-        cnt = cnt.cpu().numpy().view(np.uint32)
-    out = {k: a[:n] for k, a in buf.items()}
-    out.update(counts=cnt, tails={k: a[n:] for k, a in buf.items()})
+    buf = {k: Padded(n, np.uint8, back=PAD, fill=SENTINEL & 0xFF) if k == "sides" else Padded(n, back=PAD, fill=SENTINEL) for k in outs}
+    cnt = Padded(4, fill=SENTINEL)
+    rc = PaddedCall(host, stream)(m._L.gndt_clearance, m._L.gndt_clearance_device, m._h, robot_arg(robot, cr.ROBOT), C.byref(prm),
+                                  *[buf.get(k) for k in ("hops", "nearest", "sides")], cnt if counts else None)
+    out = {k: p.body for k, p in buf.items()}
+    out.update(counts=cnt.a, tails={k: p.tail for k, p in buf.items()})
     return rc, out
-
-
-def untouched(got):
-    return all((t == (SENTINEL & (0xFF if k == "sides" else 0xFFFFFFFF))).all() for k, t in got["tails"].items())
 
 
 def check(m, f, mask=cr.BLOCKED, max_hops=32, what="", **kw):
@@ -125,7 +77,7 @@ def both_paths(m, f, mask=cr.BLOCKED, max_hops=32, what="", **kw):
 def drawn(name, make, P=fr.P, robot=None):
     """a map drawn from a cloud -> (m, restatement, export)"""
     if name not in _scenes:
-        m = _build(make(), P)
+        m = build(make(), P)
         cells = m.export()
         f = cr.Field(cells, robot)
         assert f.angle_margin_deg > MARGIN, (name, f.angle_margin_deg)
@@ -335,7 +287,7 @@ def test_repeat_calls_and_a_second_stream_give_the_same_bytes_and_change_nothing
 
 def test_after_a_crop_and_after_an_update():
     cloud = scenes.drivable_site(200_000)
-    m = _build(cloud, scenes.COST_PARAMS, ATOMIC)
+    m = build(cloud, scenes.COST_PARAMS, ATOMIC)
 
     def fresh(what):
         f = cr.Field(m.export())
@@ -349,7 +301,7 @@ def test_after_a_crop_and_after_an_update():
     m.crop_box((x0 + 5, x1 - 5, -1000, 1000), "keep_inside")
     cropped = fresh("crop")
     assert len(cropped["hops"]) < len(before["hops"])
-    m.change2DMap("slope", _dev(cloud[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
+    m.change2DMap("slope", dev(cloud[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
     fresh("update")
     # the middle of the site: a map of thousands of rows that the one-workgroup kernel still holds, many hops deep
     xm, w = (x0 + x1) // 2, (x1 - x0) // 5
@@ -364,7 +316,7 @@ def test_after_a_crop_and_after_an_update():
         rc, got = raw(m, host=host)
         assert rc == 0 and tuple(got["counts"]) == (0, 0, 0, 0) and untouched(got)
         cl = m.clearance(sides=True, host=host)
-        assert all(len(cl[k]) == 0 for k in ("hops", "nearest", "sides")) and not _np(cl["counts"]).any()
+        assert all(len(cl[k]) == 0 for k in ("hops", "nearest", "sides")) and not to_np(cl["counts"]).any()
 
 
 def test_outputs_are_optional_and_nothing_is_written_beyond_the_rows():
@@ -381,10 +333,6 @@ def test_outputs_are_optional_and_nothing_is_written_beyond_the_rows():
 
 # ---- the Python interface ----------------------------------------------------------------------------------------------------------
 
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
 def test_python_defaults_host_and_streams():
     import torch
     m, f, cells = site("bridge")
@@ -395,16 +343,16 @@ def test_python_defaults_host_and_streams():
         if "stream" in kw:
             s.synchronize()
         assert set(cl) == {"hops", "nearest", "counts"} and (isinstance(cl["hops"], np.ndarray) == bool(kw.get("host")))
-        assert np.array_equal(_np(cl["hops"]).view(np.uint32), want["hops"]) and np.array_equal(_np(cl["nearest"]).view(np.uint32), want["nearest"])
-        assert np.array_equal(_np(cl["counts"]).view(np.uint32), want["counts"])
-        assert (_np(cl["hops"])[want["hops"] == cr.BEYOND] == m.CLEARANCE_BEYOND).all()
+        assert np.array_equal(to_np(cl["hops"]).view(np.uint32), want["hops"]) and np.array_equal(to_np(cl["nearest"]).view(np.uint32), want["nearest"])
+        assert np.array_equal(to_np(cl["counts"]).view(np.uint32), want["counts"])
+        assert (to_np(cl["hops"])[want["hops"] == cr.BEYOND] == m.CLEARANCE_BEYOND).all()
     for host in (False, True):
         cl = m.clearance(robot=dict(radius=0.25), max_hops=2, sources=("blocked", "open"), hops=False, nearest=False, sides=True, host=host)
-        assert set(cl) == {"sides", "counts"} and np.array_equal(_np(cl["sides"]), f.sides)
-        assert np.array_equal(_np(cl["counts"]).view(np.uint32), f.clearance(3, 2)["counts"])
+        assert set(cl) == {"sides", "counts"} and np.array_equal(to_np(cl["sides"]), f.sides)
+        assert np.array_equal(to_np(cl["counts"]).view(np.uint32), f.clearance(3, 2)["counts"])
         cl = m.clearance(sources="open", max_hops=5, host=host)
-        assert np.array_equal(_np(cl["hops"]).view(np.uint32), f.clearance(cr.OPEN, 5)["hops"])
-        assert np.array_equal(_np(m.clearance(sources=6, host=host)["hops"]).view(np.uint32), f.clearance(6, 32)["hops"])
+        assert np.array_equal(to_np(cl["hops"]).view(np.uint32), f.clearance(cr.OPEN, 5)["hops"])
+        assert np.array_equal(to_np(m.clearance(sources=6, host=host)["hops"]).view(np.uint32), f.clearance(6, 32)["hops"])
 
 
 def test_clearance_vectors_are_the_gather_and_subtraction_on_the_export():
@@ -414,13 +362,13 @@ def test_clearance_vectors_are_the_gather_and_subtraction_on_the_export():
         cl = m.clearance(host=host)
         vec = m.clearance_vectors(cl)
         assert (hasattr(vec, "cpu") != host) and tuple(vec.shape) == (cells["num_nodes"], 3)
-        near = _np(cl["nearest"]).astype(np.int64)
+        near = to_np(cl["nearest"]).astype(np.int64)
         none = near < 0
         assert none.any() and not none.all()
         want = mean[np.where(none, 0, near)] - mean
-        got = _np(vec)
+        got = to_np(vec)
         assert np.isnan(got[none]).all() and got[~none].tobytes() == want[~none].tobytes()
-        assert (got[_np(cl["hops"]) == 0] == 0).all()          # a source's barrier is where it stands
+        assert (got[to_np(cl["hops"]) == 0] == 0).all()          # a source's barrier is where it stands
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------

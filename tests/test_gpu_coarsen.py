@@ -19,7 +19,8 @@ from tests import query_ref as qr
 from tests import raster_ref as rr
 from tests import score_derivs_ref as dr
 from tests import score_ref as sr
-from tests.test_gpu_score import ATOMIC, BOX, ERR_INVALID, PARTITION, TILE, _dev, _handle, _np, six_poses, yaw
+from tests.gpu_kit import dev, handle, to_np
+from tests.test_gpu_score import ATOMIC, BOX, ERR_INVALID, PARTITION, TILE, six_poses, yaw
 
 pytestmark = pytest.mark.gpu
 
@@ -50,15 +51,15 @@ def _oracle(name, fxy, fz):
 
 
 def _fine(cloud, P, how=ATOMIC):
-    m = _handle(P, TILE if how == TILE else ATOMIC)
+    m = handle(P, TILE if how == TILE else ATOMIC)
     m.setCloudFirst(cloud[0])
     body = cloud[1:]
     if how == "frames":
         a, b = len(body) // 3, 2 * len(body) // 3
         for part in (body[:a], body[a:b], body[b:]):
-            m.change2DMap("slope", _dev(part))
+            m.change2DMap("slope", dev(part))
     else:
-        m.create2DMap("slope", _dev(body))
+        m.create2DMap("slope", dev(body))
     return m
 
 
@@ -155,7 +156,7 @@ def test_a_source_emptied_by_a_crop_gives_an_empty_destination():
     assert c.sync() == (0, 0, 0) and c.export()["num_nodes"] == 0
     # ... and it goes on from there: a frame given to both is the coarse build of that frame at the stream's indices
     for x in (m, c):
-        x.change2DMap("slope", _dev(cloud[1:2001]))
+        x.change2DMap("slope", dev(cloud[1:2001]))
     assert c.export()["num_nodes"] > 0 and np.array_equal(np.sort(_stats(c)["count"]), np.sort(_stats(m.coarsen(2))["count"]))
 
 
@@ -184,14 +185,14 @@ def test_after_remove_crop_and_clear():
     origin, body = cloud[0], cloud[1:]
     m = _fine(cloud, P)
     n0 = m.sync()[0]
-    m.del2DMap("slope", _dev(body[5000:16000]))
+    m.del2DMap("slope", dev(body[5000:16000]))
     _check_against_restatement(m, P, origin, 2, 2)
     m.crop((-4.2, -3.1), (3.3, 5.0))
     n1 = m.sync()[0]
     assert 0 < n1 < n0
     _check_against_restatement(m, P, origin, 4, 2)
     sensor = origin + np.float32([0.2, 0.1, 0.05])
-    st = m.clear_rays(sensor, _dev(body[::50]))
+    st = m.clear_rays(sensor, dev(body[::50]))
     assert st["cleared"] > 0 and 0 < m.sync()[0] < n1
     _check_against_restatement(m, P, origin, 2, 1)
     _check_against_restatement(m, P, origin, 8, 8)
@@ -203,14 +204,14 @@ def test_coarse_map_follows_the_stream():
     cloud, P = _scene("campus_frame")
     body = cloud[1:]
     a, b = len(body) // 3, 2 * len(body) // 3
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
-    m.change2DMap("slope", _dev(body[:a]))
-    m.change2DMap("slope", _dev(body[a:b]))
+    m.change2DMap("slope", dev(body[:a]))
+    m.change2DMap("slope", dev(body[a:b]))
     c = m.coarsen(2, 2)
     assert c.cloudFirst == m.cloudFirst
     for x in (m, c):
-        x.change2DMap("slope", _dev(body[b:]))
+        x.change2DMap("slope", dev(body[b:]))
     parity.assert_parity(c.export(), _oracle("campus_frame", 2, 2))
     parity.assert_parity(m.export(), parity.ref_from_cloud(cloud, P))
 
@@ -226,7 +227,7 @@ def test_the_source_is_untouched():
     goal = tuple(float(v) for v in before["mean"][slopes[len(slopes) // 2]])
     m.computeCost(goal, robot={"radius": 0.25})
     cost = m.cost_export()
-    pts = _dev(cloud[1:][::7])
+    pts = dev(cloud[1:][::7])
     rows = m.query(pts).cpu().numpy()
     c = m.coarsen(2)
     c2 = m.coarsen(4, 2, into=None)
@@ -246,9 +247,9 @@ def test_a_destination_that_held_a_map_is_replaced():
     cloud, P = _scene("uniform_box")
     Pc = _coarse_params(P, 2, 2)
     other = scenes.terrain_cloud(30_000)
-    dst = _handle(Pc, ATOMIC)
+    dst = handle(Pc, ATOMIC)
     dst.setCloudFirst(other[0])
-    dst.create2DMap("slope", _dev(other[1:]))
+    dst.create2DMap("slope", dev(other[1:]))
     held = dst.export()
     goal = tuple(float(v) for v in held["mean"][np.flatnonzero(held["flags"] & 2)[0]])
     dst.computeCost(goal, robot={"radius": 0.25})
@@ -260,7 +261,7 @@ def test_a_destination_that_held_a_map_is_replaced():
     with pytest.raises(g.GndtError):
         dst.cost_export()                                            # the old map's cost map is gone with it
     pts = np.ascontiguousarray(cloud[1:][::9])
-    got = dst.query(_dev(pts)).cpu().numpy().astype(np.int64)
+    got = dst.query(dev(pts)).cpu().numpy().astype(np.int64)
     want = qr.node_rows(cells, pts, cloud[0], Pc["grid_len"], Pc["z_len"])
     assert np.array_equal(got, want) and (want >= 0).all()
     box = (int(cells["sx"].min()), int(cells["sx"].max()), int(cells["sy"].min()), int(cells["sy"].max()))
@@ -268,10 +269,10 @@ def test_a_destination_that_held_a_map_is_replaced():
         r = dst.raster(box, mode, layers=("row", "z", "rough", "nodes"))
         w = rr.raster(cells, box, mode, 0.0)
         for k in ("row", "z", "rough", "nodes"):
-            assert rr.same(_np({"x": r[k]})["x"], w[k]), (mode, k)
+            assert rr.same(to_np({"x": r[k]})["x"], w[k]), (mode, k)
     poses = six_poses(Pc)
     for nbh in (1, 7):
-        sc = _np(dst.score_poses(_dev(pts), poses, neighbourhood=nbh))
+        sc = to_np(dst.score_poses(dev(pts), poses, neighbourhood=nbh))
         ws = sr.score(cells, cloud[0], Pc["grid_len"], Pc["z_len"], pts, poses, nbh)
         assert ws["terms"][0] > 100
         sr.assert_pose_sums(sc, ws, what=("coarsened", nbh))
@@ -285,9 +286,9 @@ def test_refusals_leave_the_destination_as_it_was():
     cloud, P = _scene("uniform_box")
     Pc = _coarse_params(P, 2, 2)
     m = _fine(cloud, P)
-    dst = _handle(Pc, ATOMIC)
+    dst = handle(Pc, ATOMIC)
     dst.setCloudFirst(cloud[0])
-    dst.create2DMap("slope", _dev(cloud[1:20001]))
+    dst.create2DMap("slope", dev(cloud[1:20001]))
     before = dst.export()
     L = m._L
     null = C.c_void_p(0)
@@ -308,16 +309,16 @@ def test_refusals_leave_the_destination_as_it_was():
     with pytest.raises(g.GndtError) as e:
         m.coarsen(4, 2, into=dst)
     assert e.value.code == ERR_INVALID and "grid_len" in str(e.value)
-    empty = _handle(P, ATOMIC)                                                       # no finished build
+    empty = handle(P, ATOMIC)                                                       # no finished build
     empty.setCloudFirst(cloud[0])
     empty.reset("slope")
     refused(L.gndt_coarsen_device(empty._h, dst._h, 2, 2, null))
     with pytest.raises(g.GndtError) as e:
-        _handle(P, ATOMIC).coarsen(2)
+        handle(P, ATOMIC).coarsen(2)
     assert e.value.code == ERR_INVALID
-    part = _handle(P, PARTITION)                                                     # a map that is not in the node table
+    part = handle(P, PARTITION)                                                     # a map that is not in the node table
     part.setCloudFirst(cloud[0])
-    part.create2DMap("slope", _dev(cloud[1:]))
+    part.create2DMap("slope", dev(cloud[1:]))
     refused(L.gndt_coarsen_device(part._h, dst._h, 2, 2, null))
     assert "node table" in L.gndt_last_error(dst._h).decode()
     if torch.cuda.device_count() > 1:                                                # handles on different devices
@@ -352,7 +353,7 @@ def test_register_with_a_pyramid_recovers_a_start_beyond_the_fine_basin():
     from tests.test_score_derivs_host import starts
     cloud, P = scenes.drivable_site(100_000), scenes.COST_PARAMS
     m = _fine(cloud, P)
-    t = _dev(cloud[1:][::5])
+    t = dev(cloud[1:][::5])
     g_, z_ = P["grid_len"], P["z_len"]
     C_start = yaw(5.0, (2.0 * g_, 1.5 * g_, -0.5 * z_))
     fine = m.register(t, C_start)

@@ -9,27 +9,12 @@ import numpy as np
 import pytest
 
 from grid_ndt_amd import scenes
+from tests.gpu_kit import dev, handle, to_np
 
 pytestmark = pytest.mark.gpu
 
 ATOMIC, PARTITION = 1, 2
 ERR_KEY_RANGE = 4
-
-
-def _handle(P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def _np(a):
-    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
 
 
 def _setup(cells):
@@ -59,14 +44,14 @@ def _reach(m, paths, walk_first=False):
     out = {}
 
     def bare():
-        out.update({"wk0_" + k: _np(v) for k, v in m.walk_paths(_dev(paths), rows=4).items()})
+        out.update({"wk0_" + k: to_np(v) for k, v in m.walk_paths(dev(paths), rows=4).items()})
 
     if walk_first:
         bare()
     cl = m.clearance(sources=("blocked", "open"))
-    out.update({"cl_" + k: _np(v) for k, v in cl.items()})
+    out.update({"cl_" + k: to_np(v) for k, v in cl.items()})
     out.update({"clh_" + k: v for k, v in m.clearance(sides=True, host=True).items()})
-    out.update({"wk_" + k: _np(v) for k, v in m.walk_paths(_dev(paths), hops=cl["hops"], rows=4).items()})
+    out.update({"wk_" + k: to_np(v) for k, v in m.walk_paths(dev(paths), hops=cl["hops"], rows=4).items()})
     out.update({"wkh_" + k: v for k, v in m.walk_paths(paths, hops=out["cl_hops"], rows=4, host=True).items()})
     if not walk_first:
         bare()
@@ -75,14 +60,14 @@ def _reach(m, paths, walk_first=False):
 
 def _consume(m, pts, box, sensor, ends, paths, walk_first=False):
     out = _reach(m, paths, walk_first)
-    out["node"] = _np(m.query(_dev(pts)))
+    out["node"] = to_np(m.query(dev(pts)))
     out["nearest"] = m.query(pts, mode="nearest_slope")                       # (host entry point)
     r = m.raster(box, "lowest", layers=("row", "z", "nodes"))
-    out.update({"r_" + k: _np(r[k]) for k in ("row", "z", "nodes")})
+    out.update({"r_" + k: to_np(r[k]) for k in ("row", "z", "nodes")})
     out["r_high"] = m.raster(box, "highest", layers=("row",), host=True)["row"]
-    st, w = m.clear_rays(sensor, _dev(ends), count_only=True, passes=True)
+    st, w = m.clear_rays(sensor, dev(ends), count_only=True, passes=True)
     out["clear"] = st
-    out["passes"] = _np(w)
+    out["passes"] = to_np(w)
     st_h, w_h = m.clear_rays(sensor, ends, count_only=True, passes=True)
     out["clear_h"] = st_h
     out["passes_h"] = w_h
@@ -104,8 +89,8 @@ def _both_orders(m, pts, goal, box, sensor, ends, paths, flood_first, walk_first
         c = _consume(m, pts, box, sensor, ends, paths, walk_first)
         f = _flood(m, goal)
     c.update(f)
-    rows, h, state = m.query(_dev(pts), cost=True)                             # the gather reads index and cost map together
-    c.update(g_rows=_np(rows), g_h=_np(h), g_state=_np(state))
+    rows, h, state = m.query(dev(pts), cost=True)                             # the gather reads index and cost map together
+    c.update(g_rows=to_np(rows), g_h=to_np(h), g_state=to_np(state))
     c["r_cost"] = m.raster(box, "nearest_z", goal[2], layers=("row", "h", "state"), host=True)
     return c
 
@@ -151,9 +136,9 @@ def test_flood_and_consumers_in_either_order_answer_the_same(name):
     res = []
     # the flood first; the consumers first, where the clearance field is what builds the index; the same with a walk in front of it
     for flood_first, walk_first in ((True, False), (False, False), (False, True)):
-        m = _handle(P, strategy)
+        m = handle(P, strategy)
         m.setCloudFirst(cloud[0])
-        m.create2DMap("slope", _dev(cloud[1:]))
+        m.create2DMap("slope", dev(cloud[1:]))
         cells = m.export()
         goal, box, sensor, ends = _setup(cells)
         c = _both_orders(m, pts, goal, box, sensor, ends, _paths(cells, P["grid_len"]), flood_first, walk_first)
@@ -172,17 +157,17 @@ def test_either_order_on_an_updated_map_after_update_crop_and_clear():
     pts = np.ascontiguousarray(body[::7])
     handles = []
     for _ in range(2):
-        m = _handle(P, ATOMIC)
+        m = handle(P, ATOMIC)
         m.setCloudFirst(cloud[0])
-        m.change2DMap("slope", _dev(body[:half]))
+        m.change2DMap("slope", dev(body[:half]))
         handles.append(m)
     cells = handles[0].export()
     goal, box, sensor, ends = _setup(cells)
     paths = _paths(cells, P["grid_len"], around=(goal, 25.0))           # (inside the crop below)
     crop = g.crop_box_from_world(cloud[0], P["grid_len"], (goal[0] - 30.0, goal[1] - 30.0), (goal[0] + 30.0, goal[1] + 30.0))
-    steps = [("update", lambda m: m.change2DMap("slope", _dev(body[half:]))),
+    steps = [("update", lambda m: m.change2DMap("slope", dev(body[half:]))),
              ("crop", lambda m: m.crop_box(crop, "keep_inside")),
-             ("clear", lambda m: m.clear_rays(sensor, _dev(ends)))]
+             ("clear", lambda m: m.clear_rays(sensor, dev(ends)))]
     nodes = []
     for step, change in [("built", None)] + steps:
         if change is not None:
@@ -207,9 +192,9 @@ def _far_column_map():
     near = np.column_stack([rng.uniform(-3, 3, 4000), rng.uniform(-3, 3, 4000), rng.uniform(0, 0.02, 4000)]).astype(np.float32)
     far = np.float32([[3300.02, 0.03, 0.0]] * 4)
     cloud = np.vstack([np.zeros((1, 3), np.float32), near, far])
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     cells = m.export()
     assert np.abs(cells["sx"]).max() > 32767 and np.abs(cells["sx"]).max() <= 65535
     return m, cloud, cells
@@ -227,14 +212,14 @@ def test_flood_reports_column_range_whoever_built_the_index():
     m, cloud, cells = _far_column_map()                 # on its own
     assert flood_code(m) == ERR_KEY_RANGE
     m, cloud, cells = _far_column_map()                 # after a query has built the index
-    pts = _dev(cloud[1:])
-    before = _np(m.query(pts))
+    pts = dev(cloud[1:])
+    before = to_np(m.query(pts))
     assert (before >= 0).all()
     assert flood_code(m) == ERR_KEY_RANGE
-    assert np.array_equal(_np(m.query(pts)), before)
+    assert np.array_equal(to_np(m.query(pts)), before)
     assert flood_code(m) == ERR_KEY_RANGE               # twice in a row
     assert flood_code(m) == ERR_KEY_RANGE
-    assert np.array_equal(_np(m.query(pts)), before)
+    assert np.array_equal(to_np(m.query(pts)), before)
     # after the clearance field has built the index, and after a walk has: the column is in the map for both, the flood's range is not theirs
     rng = np.random.default_rng(0x5EED0C03)
     paths = np.zeros((48, 5, 3), np.float32)
@@ -250,10 +235,10 @@ def test_flood_reports_column_range_whoever_built_the_index():
         def reach():
             out = {}
             if first == "walk":
-                out.update({"wk_" + k: _np(v) for k, v in m.walk_paths(_dev(paths), rows=4).items()})
-            out.update({"cl_" + k: _np(v) for k, v in m.clearance(sources=("blocked", "open"), sides=True).items()})
+                out.update({"wk_" + k: to_np(v) for k, v in m.walk_paths(dev(paths), rows=4).items()})
+            out.update({"cl_" + k: to_np(v) for k, v in m.clearance(sources=("blocked", "open"), sides=True).items()})
             if first != "walk":
-                out.update({"wk_" + k: _np(v) for k, v in m.walk_paths(_dev(paths), rows=4).items()})
+                out.update({"wk_" + k: to_np(v) for k, v in m.walk_paths(dev(paths), rows=4).items()})
             out.update({"clh_" + k: v for k, v in m.clearance(sides=True, host=True).items()})
             out.update({"wkh_" + k: v for k, v in m.walk_paths(paths, rows=4, host=True).items()})
             return out
@@ -280,10 +265,10 @@ def test_consumer_codes_on_a_map_built_with_points_beyond_the_key_range():
     L = _lib.lib()
 
     def make(strategy):
-        m = _handle(P, strategy)
+        m = handle(P, strategy)
         m.setCloudFirst((0, 0, 0))
         with pytest.raises(g.GndtError) as e:
-            m.create2DMap("slope", _dev(cloud))
+            m.create2DMap("slope", dev(cloud))
             m.sync()
         assert e.value.code == ERR_KEY_RANGE
         return m
@@ -307,7 +292,7 @@ def test_consumer_codes_on_a_map_built_with_points_beyond_the_key_range():
             rows = np.empty(len(pts), np.int32)
             return L.gndt_query(m._h, C.c_void_p(pts.ctypes.data), len(pts), 12, 0, C.c_void_p(rows.ctypes.data), None, None)
         import torch
-        t = _dev(pts)
+        t = dev(pts)
         rows = torch.empty(len(pts), dtype=torch.int32, device="cuda")
         rc = L.gndt_query_device(m._h, C.c_void_p(t.data_ptr()), len(pts), 12, 0, C.c_void_p(rows.data_ptr()), None, None, None)
         torch.cuda.synchronize()
@@ -319,7 +304,7 @@ def test_consumer_codes_on_a_map_built_with_points_beyond_the_key_range():
         st = _lib.ClearStats()
         if host:
             return L.gndt_clear_rays(m._h, o, C.c_void_p(pts.ctypes.data), len(pts), 12, C.byref(prm), None, C.byref(st))
-        t = _dev(pts)
+        t = dev(pts)
         rc = L.gndt_clear_rays_device(m._h, o, C.c_void_p(t.data_ptr()), len(pts), 12, C.byref(prm), None, C.byref(st), None)
         return rc
 
@@ -348,7 +333,7 @@ def test_consumer_codes_on_a_map_built_with_points_beyond_the_key_range():
             info = np.zeros(4 * 12, np.uint32)
             return L.gndt_walk_paths(m._h, C.c_void_p(paths.ctypes.data), 4, 2, 12, None, C.byref(prm), None, None, 0, C.c_void_p(info.ctypes.data))
         import torch
-        t = _dev(paths)
+        t = dev(paths)
         info = torch.zeros(4 * 12, dtype=torch.int32, device="cuda")
         rc = L.gndt_walk_paths_device(m._h, C.c_void_p(t.data_ptr()), 4, 2, 12, None, C.byref(prm), None, None, 0, C.c_void_p(info.data_ptr()), None)
         torch.cuda.synchronize()

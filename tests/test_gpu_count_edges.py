@@ -38,6 +38,7 @@ from tests.test_gpu_crop import FIELDS, _assert_same, _filtered
 from tests.test_gpu_frontiers import cfg as frontier_cfg
 from tests.test_gpu_frontiers import raw as frontier_raw
 from tests.test_gpu_frontiers import untouched
+from tests.gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -48,11 +49,6 @@ GL, ZL = P["grid_len"], P["z_len"]
 DEBUG_CLEAR_EXTENT = 5
 GOAL, ROBOT = (5.25, 3.25, fr.Z_FLOOR), {"radius": 0.25}
 _cache = {}
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _np(x):
@@ -80,7 +76,7 @@ def cached(key, make):
 def small():
     """the small map, built once and only read: dict(m, cells, cost) with the cost flood of GOAL on it"""
     def make():
-        m = _build(_dev(es.small_cloud()[1:]))
+        m = _build(dev(es.small_cloud()[1:]))
         cells = m.export()
         assert cells["num_nodes"] == 41 * 25 and ((cells["flags"] & 2) != 0).all()
         assert m.computeCost(GOAL, robot=ROBOT)["rc"] == 0
@@ -120,8 +116,8 @@ def test_cast_batch_edges(n, mode, per_ray):
         assert (want["row"][CAP:] != cf.NO_ROW).any()
     if n >= CAP + 65:
         assert {cf.HIT, cf.MISS, cf.SKIPPED} <= set(ref["status"][es.tail_items(n)].tolist())
-    o = _dev(es.cyclic(origins, n)) if per_ray else sensor
-    e = _dev(es.cyclic(ends, n))
+    o = dev(es.cyclic(origins, n)) if per_ray else sensor
+    e = dev(es.cyclic(ends, n))
     out, st = m.cast_rays(o, e, mode={cf.VOXEL: "voxel", cf.NDT: "ndt"}[mode], stats=True)
     cf.assert_same(_np(out), want, (n, mode, per_ray, "stats"))
     assert st == st_want
@@ -136,7 +132,7 @@ def test_clear_count_only_batch_edges(n):
     if n > CAP:                                                     # the second trip's own rays pass rows and protect rows
         tail, _, _ = cr.passes(s["cells"], ORIGIN, GL, ZL, sensor, pts[es.tail_items(n)])
         assert ((tail & cr.PROTECTED) != 0).any() and ((tail & ~cr.PROTECTED) > 0).any()
-    st, got = s["m"].clear_rays(sensor, _dev(es.cyclic(pts, n)), count_only=True, passes=True)
+    st, got = s["m"].clear_rays(sensor, dev(es.cyclic(pts, n)), count_only=True, passes=True)
     got = got.cpu().numpy().view(np.uint32)
     assert np.array_equal(got, want), (n, np.flatnonzero(got != want)[:8])
     assert (st["rays"], st["skipped"], st["cleared"]) == (rays, skipped, 0)
@@ -148,12 +144,12 @@ def test_clear_at_524289_rays_drops_the_rows_of_the_summed_words():
     afterwards is the export before it without them (one node a column: the columns and slopes left are the rows left)"""
     n, min_passes = CAP + 1, 3
     sensor, pts = es.clear_base()
-    m = _build(_dev(es.small_cloud()[1:]), ATOMIC)
+    m = _build(dev(es.small_cloud()[1:]), ATOMIC)
     before = m.export()
     words, rays, skipped = es.clear_words(before, sensor, pts, n)
     drop = cr.cleared_rows(words, min_passes)
     assert 0 < drop.sum() < len(drop) and (((words & cr.PROTECTED) != 0) & ((words & ~cr.PROTECTED) >= min_passes)).any()
-    st, _ = m.clear_rays(sensor, _dev(es.cyclic(pts, n)), min_passes=min_passes, passes=True)
+    st, _ = m.clear_rays(sensor, dev(es.cyclic(pts, n)), min_passes=min_passes, passes=True)
     assert (st["rays"], st["skipped"], st["cleared"]) == (rays, skipped, int(drop.sum()))
     want = {k: before[k][~drop] for k in FIELDS}
     want.update(num_nodes=int((~drop).sum()), num_columns=int((~drop).sum()), num_slopes=int((~drop).sum()))
@@ -176,7 +172,7 @@ def test_query_batch_edges(n, ilp, what):
     assert (want[-65:] >= 0).any() and (want[-65:] == qr.NO_ROW).any()      # the last wave's items: with a row and without
     if n > ilp * CAP:
         assert (want[ilp * CAP:] >= 0).any()
-    t = _dev(es.cyclic(base, n))
+    t = dev(es.cyclic(base, n))
     g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_QUERY_ILP, ilp)
     try:
         if what == "nearest_slope":
@@ -248,7 +244,7 @@ def test_scan_scoring_tile_and_reduce_edges(n, nbh):
     last = ref["poses_out"][2]
     if n % es.EDGES["kScoreTile"] == 1:                             # the one point of the last tile has a term
         assert last["row"][(n - 1) % BASE] != sr.NO_ROW and ref["poses_out"][0]["row"][(n - 1) % BASE] != sr.NO_ROW
-    got = _np(m.score_poses(_dev(es.cyclic(es.scan_base(), n)), es.scan_poses(), neighbourhood=nbh, per_point=2))
+    got = _np(m.score_poses(dev(es.cyclic(es.scan_base(), n)), es.scan_poses(), neighbourhood=nbh, per_point=2))
     sr.assert_pose_sums(got, want, what=(n, nbh))
     sr.assert_per_point(got["d2"], got["row"], take(last, n, ("row", "d2")), what=(n, nbh))
 
@@ -271,7 +267,7 @@ def test_score_derivs_tile_and_reduce_edges(n, nbh):
     assert (want["terms"] > 0).all() and (np.abs(want["H"]).max((1, 2)) > 0).all()
     if n % es.EDGES["kScoreTile"] == 1:
         assert _score_ref(nbh)["poses_out"][0]["row"][(n - 1) % BASE] != sr.NO_ROW
-    got = _np(m.score_derivs(_dev(es.cyclic(es.scan_base(), n)), es.scan_poses(), neighbourhood=nbh))
+    got = _np(m.score_derivs(dev(es.cyclic(es.scan_base(), n)), es.scan_poses(), neighbourhood=nbh))
     dr.assert_derivs(got, want, what=(n, nbh))
     assert np.array_equal(got["H"], got["H"].transpose(0, 2, 1))
 
@@ -283,7 +279,7 @@ def lattice(n):
     def make():
         pts, (ix, iy) = es.edge_lattice(n)
         assert len(ix) == n and len(pts) == 1 + 9 * n
-        return dict(dev=_dev(pts[1:]), ix=ix, iy=iy)
+        return dict(dev=dev(pts[1:]), ix=ix, iy=iy)
     return cached(("lattice", n), make)
 
 
@@ -322,7 +318,7 @@ def test_crop_row_count_edges(n, strategy, box):
     got = m.export()
     _assert_same(got, want)
     centres = es.cell_centres(mine["sx"], mine["sy"])
-    rows = m.query(_dev(centres), "nearest_slope").cpu().numpy().astype(np.int64)
+    rows = m.query(dev(centres), "nearest_slope").cpu().numpy().astype(np.int64)
     expect = np.where(kept, np.cumsum(kept) - 1, qr.NO_ROW)
     assert np.array_equal(rows, expect), np.flatnonzero(rows != expect)[:8]
 
@@ -368,7 +364,7 @@ def _plain(W, H):
     """the W x H floor without holes, built ATOMIC (the map lives in the node table): dict(m, cloud, cells)"""
     def make():
         cloud = es.lattice_points(W, H)
-        m = _build(_dev(cloud[1:]), ATOMIC)
+        m = _build(dev(cloud[1:]), ATOMIC)
         cells = m.export()
         assert cells["num_nodes"] == W * H
         return dict(m=m, cloud=cloud, cells=cells)
@@ -419,7 +415,7 @@ def test_clear_by_rows_past_one_trip_of_rows():
     import grid_ndt_amd as g
     W, H = PLAIN["725x724"]
     cloud = es.lattice_points(W, H)
-    m = _build(_dev(cloud[1:]), ATOMIC)
+    m = _build(dev(cloud[1:]), ATOMIC)
     before = m.export()
     rng = np.random.default_rng(59)
     sensor = np.float32([(W - 1) * GL + 0.25, 200 * GL + 0.2, 0.2])
@@ -431,12 +427,12 @@ def test_clear_by_rows_past_one_trip_of_rows():
     try:
         for ext in (1, 0):
             g.TwoDmap.set_debug_option(DEBUG_CLEAR_EXTENT, ext)
-            st, got = m.clear_rays(sensor, _dev(ends), count_only=True, passes=True)
+            st, got = m.clear_rays(sensor, dev(ends), count_only=True, passes=True)
             got = got.cpu().numpy().view(np.uint32)
             assert np.array_equal(got, words), (ext, np.flatnonzero(got != words)[:8])
             assert (st["rays"], st["skipped"], st["cleared"]) == (rays, skipped, 0)
         g.TwoDmap.set_debug_option(DEBUG_CLEAR_EXTENT, 1)
-        st, _ = m.clear_rays(sensor, _dev(ends), min_passes=2, passes=True)
+        st, _ = m.clear_rays(sensor, dev(ends), min_passes=2, passes=True)
     finally:
         g.TwoDmap.set_debug_option(DEBUG_CLEAR_EXTENT, 0)
     assert st["cleared"] == int(drop.sum())

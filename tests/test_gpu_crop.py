@@ -8,24 +8,13 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import parity
 from tests import query_ref as qr
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
 ATOMIC, PARTITION, EXACT, TWO_LEVEL, TILE, AUTO = 1, 2, 3, 4, 5, 0
 TERRAIN = scenes.TERRAIN_PARAMS
 FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
-
-
-def _handle(P, strategy=AUTO, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def _inside(cells, box):
@@ -69,20 +58,20 @@ def _path(name):
     if name in ("atomic", "partition", "exact", "two_level"):
         cloud = scenes.terrain_cloud(300_000)
         strategy = {"atomic": ATOMIC, "partition": PARTITION, "exact": EXACT, "two_level": TWO_LEVEL}[name]
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(TERRAIN, strategy)
+            m = handle(TERRAIN, strategy)
             m.setCloudFirst(cloud[0])
             m.create2DMap("slope", t)
             return m
         return make
     if name == "tile":
         cloud, P = scenes.depth_frame(), scenes.DEPTH_PARAMS
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(P, TILE)
+            m = handle(P, TILE)
             m.setCloudFirst(cloud[0])
             m.create2DMap("slope", t)
             assert m.STRATEGY_NAMES[m.last_strategy()] == "tile"
@@ -91,10 +80,10 @@ def _path(name):
     if name == "blocked":
         P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
         cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(P)
+            m = handle(P)
             m.setCloudFirst(cloud[0])
             for _ in range(2):
                 m.create2DMap("slope", t)
@@ -106,14 +95,14 @@ def _path(name):
     cuts = [1, 90_000, 170_000, cloud.shape[0]]
 
     def make():
-        m = _handle(TERRAIN, ATOMIC)
+        m = handle(TERRAIN, ATOMIC)
         m.setCloudFirst(cloud[0])
         if name == "deferred":
             m.set_deferred_emit(True)
         for a, b in zip(cuts[:-1], cuts[1:]):
-            m.change2DMap("slope", _dev(cloud[a:b]))
+            m.change2DMap("slope", dev(cloud[a:b]))
         if name == "removed":
-            m.del2DMap("slope", _dev(cloud[170_000:]))
+            m.del2DMap("slope", dev(cloud[170_000:]))
         return m
     return make
 
@@ -156,25 +145,25 @@ def test_crop_equals_remove_of_the_dropped_columns_points():
         assert 0 < dropped.sum() < len(body)
         # twins with the same fp64 sums (fp64 atomics add in any order: two builds may differ in the last bits): the statistics of one
         # build merged into two tables, the stream position raised to the body's length
-        x = _handle(P, ATOMIC)
+        x = handle(P, ATOMIC)
         x.setCloudFirst(origin)
-        x.change2DMap("slope", _dev(body))
+        x.change2DMap("slope", dev(body))
         st = {k: v.clone() for k, v in x.stats_export().items()}
-        a, b = _handle(P, ATOMIC), _handle(P, ATOMIC)
+        a, b = handle(P, ATOMIC), handle(P, ATOMIC)
         for m in (a, b):
             m.setCloudFirst(origin)
             m.reset("slope")
             m.stats_merge(st["key"], st["sums"], st["count"], st["first_idx"])
-            m.accumulate("slope", _dev(np.zeros((0, 3), np.float32)), first_idx_base=len(body))
+            m.accumulate("slope", dev(np.zeros((0, 3), np.float32)), first_idx_base=len(body))
             m.finalize()
         _assert_same(a.export(), b.export())
         a.crop_box(box, mode)
-        b.del2DMap("slope", _dev(body[dropped]))
+        b.del2DMap("slope", dev(body[dropped]))
         ea, eb = a.export(), b.export()
         _assert_same(ea, eb)
         assert 0 < ea["num_nodes"] < x.export()["num_nodes"]
         for m in (a, b):
-            m.change2DMap("slope", _dev(nxt))
+            m.change2DMap("slope", dev(nxt))
         ea, eb = a.export(), b.export()
         for k in ("num_nodes", "num_columns", "num_slopes"):
             assert ea[k] == eb[k]
@@ -199,11 +188,11 @@ def test_rolling_window_over_a_lidar_stream():
     sx, sy, _, _, ok = qr.keys(pts, origin, P["grid_len"], P["z_len"])
     assert ok.all()
     alive = np.ones(len(pts), bool)
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(origin)
     nodes_after_crop = []
     for f in range(n_frames):
-        m.change2DMap("slope", _dev(pts[f * ppf:(f + 1) * ppf]))
+        m.change2DMap("slope", dev(pts[f * ppf:(f + 1) * ppf]))
         if (f + 1) % k == 0:
             px, py = scenes._pose_xy(np.int64(f), 200.0, 14.0)
             box = m.crop((px - r, py - r), (px + r, py + r), keep="inside")
@@ -228,9 +217,9 @@ def test_consumers_after_a_crop():
     from oracle import oracle
     import grid_ndt_amd as g
     cloud, P = scenes.campus_frame(200_000), scenes.CAMPUS_PARAMS
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
-    m.create2DMap(P["demand"], _dev(cloud[1:]))
+    m.create2DMap(P["demand"], dev(cloud[1:]))
     cells = m.export()
     slopes = np.flatnonzero(cells["flags"] & 2)
     goal = tuple(float(v) for v in cells["mean"][slopes[len(slopes) // 2]])
@@ -252,7 +241,7 @@ def test_consumers_after_a_crop():
     sx, sy, _, _, _ = qr.keys(pts, cloud[0], P["grid_len"], P["z_len"])
     inb = (sx >= box[0]) & (sx <= box[1]) & (sy >= box[2]) & (sy <= box[3])
     assert 0 < inb.sum() < len(pts)
-    rows = m.query(_dev(pts)).cpu().numpy().astype(np.int64)
+    rows = m.query(dev(pts)).cpu().numpy().astype(np.int64)
     assert (rows[~inb] == qr.NO_ROW).all()
     assert (rows[inb] == qr.node_rows(cells, pts[inb], cloud[0], P["grid_len"], P["z_len"])).all() and (rows[inb] >= 0).all()
     assert (np.bincount(rows[inb], minlength=cells["num_nodes"]) == cells["count"]).all()
@@ -266,9 +255,9 @@ def test_lifetime_capture_stale_graph_and_inverted_box():
     P = TERRAIN
     frames = scenes.terrain_frames(3, points_per_frame=32_768)
     origin, f0, f1 = frames[0], frames[1:32_769], frames[32_769:65_537]
-    m = _handle(P, ATOMIC, max_points_hint=200_000, max_nodes_hint=200_000)
+    m = handle(P, ATOMIC, max_points_hint=200_000, max_nodes_hint=200_000)
     m.setCloudFirst(origin)
-    m.change2DMap("slope", _dev(f0))
+    m.change2DMap("slope", dev(f0))
     before = m.export()
     box = (int(before["sx"].min()), int(before["sx"].max()) // 2 or 1, int(before["sy"].min()), int(before["sy"].max()))
     # inverted boxes: refused, nothing changes
@@ -282,7 +271,7 @@ def test_lifetime_capture_stale_graph_and_inverted_box():
     _assert_same(m.export(), before)
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
-        buf = _dev(f1)
+        buf = dev(f1)
         s.wait_stream(torch.cuda.default_stream())
         graph = torch.cuda.CUDAGraph()
         with g.graph_capture(graph, s):

@@ -9,22 +9,11 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import parity
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
 P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08, demand="slope")
-
-
-def _handle(strategy=2, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(cloud):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(cloud[1:])).cuda()
 
 
 def _check(m, cloud, what):
@@ -35,7 +24,7 @@ def _check(m, cloud, what):
 
 def test_builds_of_changing_size_on_one_handle():
     """one-level, exact and two-level partitions, growing and shrinking clouds, the same cloud again: both sets of cursors are taken in turn"""
-    m = _handle()
+    m = handle(P, 2)
     first = scenes.uniform_box(300_001, half_xy=20.0)
     m.setCloudFirst(first[0])
     # (half_xy 20: a few hundred buckets — the one-level partition; 60: more buckets than one level writes — counting partition below
@@ -46,7 +35,7 @@ def test_builds_of_changing_size_on_one_handle():
     for k, (n, half) in enumerate(cases):
         cloud = scenes.uniform_box(n, seed=0x1000 + k, half_xy=half)
         cloud[0] = first[0]
-        m.create2DMap("slope", _dev(cloud))
+        m.create2DMap("slope", dev(cloud[1:]))
         _check(m, cloud, (k, n, half))
         used.append(m.last_strategy())
     assert used.count(6) >= 6 and (2 in used or 7 in used), used
@@ -63,7 +52,7 @@ def test_campus_frames_in_a_row():
     for k in range(10):
         c = frames[k % 5].copy()
         c[0] = frames[0][0]
-        m.create2DMap("slope", _dev(c))
+        m.create2DMap("slope", dev(c[1:]))
         out = m.export()
         rep = parity.compare(out, parity.ref_from_cloud(c, CP, mode=2), "slope")
         assert rep["ok"], (k, m.last_strategy(), rep["fail"])
@@ -72,13 +61,13 @@ def test_campus_frames_in_a_row():
 
 def test_points_outside_the_key_range_are_counted_once_per_build():
     import grid_ndt_amd as g
-    m = _handle()
+    m = handle(P, 2)
     cloud = scenes.uniform_box(500_001, half_xy=25.0)
     m.setCloudFirst(cloud[0])
-    good = _dev(cloud)
+    good = dev(cloud[1:])
     bad = cloud.copy()
     bad[[7, 70_000, 499_999]] = np.float32([0.5 * 70000, 1.0, 1.0])     # |nx| > 65535 (Stopwatch.h:102-110)
-    bad_t = _dev(bad)
+    bad_t = dev(bad[1:])
     for k in range(2):
         m.create2DMap("slope", good)
         _check(m, cloud, ("good", k))
@@ -99,10 +88,10 @@ def test_other_strategies_between_partition_builds():
     frame = scenes.uniform_box(50_001, seed=0x77, half_xy=22.0)[1:]
     import grid_ndt_amd as g
     import torch
-    maps = {s: _handle(strategy=s) for s in (2, 1, 5)}
+    maps = {s: handle(P, s) for s in (2, 1, 5)}
     for m in maps.values():
         m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:])
     whole = np.concatenate([cloud, frame], 0)
     for rnd in range(3):
         for s, m in maps.items():
@@ -124,7 +113,7 @@ def test_other_strategies_between_partition_builds():
     used = set()
     for rnd in range(3):
         for c in (depth, sparse, sparse):
-            auto.create2DMap("slope", _dev(c))
+            auto.create2DMap("slope", dev(c[1:]))
             out = auto.export()
             used.add(auto.last_strategy())
             rep = parity.compare(out, parity.ref_from_cloud(c, DP, mode=2), DP.get("demand", "slope"))
@@ -136,10 +125,10 @@ def test_recorded_build_switches_the_folding_off_for_good():
     """a handle that ever recorded a hipGraph keeps k_part_clear in front of every build: a replay works on the set it was recorded with"""
     import torch
     import grid_ndt_amd as g
-    m = _handle(max_nodes_hint=400_000, max_points_hint=700_000)
+    m = handle(P, 2, max_nodes_hint=400_000, max_points_hint=700_000)
     cloud = scenes.uniform_box(600_001, half_xy=28.0)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud)
+    t = dev(cloud[1:])
     for _ in range(3):
         m.create2DMap("slope", t)
         m.sync()
@@ -151,7 +140,7 @@ def test_recorded_build_switches_the_folding_off_for_good():
     with g.graph_capture(graph):
         m.create2DMap("slope", buf)
     for k in range(3):
-        buf.copy_(_dev(other) if k % 2 else t)
+        buf.copy_(dev(other[1:]) if k % 2 else t)
         graph.replay()
         torch.cuda.synchronize()
         _check(m, other if k % 2 else cloud, ("replay", k))

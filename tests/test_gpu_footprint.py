@@ -6,20 +6,16 @@ over-allocated with a sentinel tail that must stay untouched.  Box sizes n = 1, 
 `support`; a mixed batch against its poses alone, permuted, and run twice; the handle's lives; every refused argument; and a poisoned
 tier of this file's own.  No tolerance anywhere."""
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import footprint_cases as fc
 from tests import footprint_ref as fr
+from tests import poison_tier
+from tests.gpu_kit import Padded, PaddedCall, build, dev, robot_arg, to_np
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_INVALID = 1
 ATOMIC = 1
 SENTINEL = 0xDEADBEEF
@@ -30,61 +26,18 @@ P = fc.PLANE_P
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
-def _robot(robot):
-    from grid_ndt_amd._lib import Robot
-    if robot is None:
-        return None
-    d = dict(fr.ROBOT)
-    d.update(robot)
-    return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
-
-
 def raw(m, poses, hl, hw, robot=None, max_dz=0.0, height=0.0, min_cells=0, min_cover=0.0, weight=0, row_cap=0, stride=20, stream=None, host=False,
         reserved=(0,) * 5):
     """The C entry points; info K + PAD records and K * row_cap + PAD row words of sentinel -> (rc, info [K], rows, untouched: the
     tails still hold the sentinel)"""
-    import torch
     from grid_ndt_amd._lib import FootprintParams
     K = len(poses)
     prm = FootprintParams(hl, hw, max_dz, height, min_cells, min_cover, weight, (C.c_uint32 * 5)(*reserved))
-    buf = fc.strided(poses, stride)
-    info = np.full((K + PAD) * 16, SENTINEL, np.uint32)
-    rows = np.full(K * row_cap + PAD, SENTINEL, np.uint32)
-    if host:
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-        rc = m._L.gndt_footprint_poses(m._h, ptr(buf) if K else None, K, stride, _robot(robot), C.byref(prm), ptr(rows) if row_cap else None, row_cap,
-                                       ptr(info))
-    else:
-        to = lambda a: torch.from_numpy(a.view(np.int32)).cuda()
-        d_buf, d_info, d_rows = to(buf.view(np.uint32)), to(info), to(rows)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream())
-        rc = m._L.gndt_footprint_poses_device(m._h, ptr(d_buf) if K else None, K, stride, _robot(robot), C.byref(prm), ptr(d_rows) if row_cap else None,
-                                              row_cap, ptr(d_info), C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        info, rows = (t.cpu().numpy().view(np.uint32) for t in (d_info, d_rows))
-    untouched = bool((info[K * 16:] == SENTINEL).all() and (rows[K * row_cap:] == SENTINEL).all())
-    return rc, info[:K * 16].view(fr.INFO_DTYPE), rows[:K * row_cap].reshape(K, row_cap), untouched
+    info, rows = Padded(K, words=16, back=PAD, fill=SENTINEL), Padded(K * row_cap, back=PAD, fill=SENTINEL)
+    rc = PaddedCall(host, stream, wait_for_current=True)(m._L.gndt_footprint_poses, m._L.gndt_footprint_poses_device, m._h,
+                                                         fc.strided(poses, stride) if K else None, K, stride, robot_arg(robot, fr.ROBOT), C.byref(prm),
+                                                         rows if row_cap else None, row_cap, info)
+    return rc, info.body.view(fr.INFO_DTYPE), rows.body.reshape(K, row_cap), info.untouched() and rows.untouched()
 
 
 def check(m, t, poses, hl, hw, what="", entries=(False, True), stream=None, row_cap=8, **kw):
@@ -103,7 +56,7 @@ def drawn(name, make=None, P=P):
     """a map built from a cloud -> (m, the rows of its export for the shim, the cloud)"""
     if name not in _scenes:
         cloud = make()
-        m = _build(cloud, P)
+        m = build(cloud, P)
         _scenes[name] = (m, fc.map_rows(m.export(), cloud[0, :3], P), cloud)
     return _scenes[name]
 
@@ -199,16 +152,16 @@ def test_the_python_wrapper_yaw_poses_and_paths():
     poses = _poses(t, 7)
     want, wrows = fc.run(t, poses, 1.2, 0.6, row_cap=5, height=1.0)
     for host in (False, True):
-        got = m.footprints(poses if host else _dev(poses), 1.2, 0.6, height=1.0, rows=5, host=host)
+        got = m.footprints(poses if host else dev(poses), 1.2, 0.6, height=1.0, rows=5, host=host)
         for k in ("status", "flags", "centre_row", "cells", "support", "gaps", "unknown"):
-            assert np.array_equal(_np(got[k]).astype(np.int64) & 0xFFFFFFFF, want[k].astype(np.int64)), (host, k)
+            assert np.array_equal(to_np(got[k]).astype(np.int64) & 0xFFFFFFFF, want[k].astype(np.int64)), (host, k)
         for k in ("z", "normal", "along", "across", "rms", "step_max", "bump_max", "headroom"):
-            assert np.array_equal(_np(got[k]).view(np.uint32), want[k].view(np.uint32)), (host, k)
-        assert np.array_equal(_np(got["rows"]).view(np.uint32), wrows)
+            assert np.array_equal(to_np(got[k]).view(np.uint32), want[k].view(np.uint32)), (host, k)
+        assert np.array_equal(to_np(got["rows"]).view(np.uint32), wrows)
         # (the arctangent is the wrapper's, numpy's on the host and torch's on the device: theirs differ in the last place of fp32)
-        assert np.abs(_np(got["pitch"]) - np.arctan(want["along"])).max() <= (0 if host else 1e-6)
-        assert np.abs(_np(got["roll"]) - np.arctan(want["across"])).max() <= (0 if host else 1e-6)
-        assert np.array_equal(_np(got["ok"]), (want["status"] == 0) & (want["flags"] == 0))
+        assert np.abs(to_np(got["pitch"]) - np.arctan(want["along"])).max() <= (0 if host else 1e-6)
+        assert np.abs(to_np(got["roll"]) - np.arctan(want["across"])).max() <= (0 if host else 1e-6)
+        assert np.array_equal(to_np(got["ok"]), (want["status"] == 0) & (want["flags"] == 0))
     yaw = np.arctan2(poses[:, 4].astype(np.float64), poses[:, 3].astype(np.float64)).astype(np.float32)
     by_yaw = m.footprints(np.concatenate([poses[:, :3], yaw[:, None]], 1), 1.2, 0.6)
     assert np.array_equal(by_yaw["cells"], want["cells"]) and np.abs(by_yaw["along"] - want["along"]).max() < 1e-5
@@ -217,11 +170,11 @@ def test_the_python_wrapper_yaw_poses_and_paths():
     paths = np.zeros((2, 4, 3), np.float32)
     paths[0, :, 0], paths[0, :, 1] = [-2.0, -1.0, 0.2, 1.5], [0.3, 0.5, 0.4, 0.1]
     paths[1, :, 0], paths[1, :, 1] = [1.0, 1.2, np.nan, 0.0], [-2.0, -1.0, 0.0, 0.0]
-    along = m.footprints_along(_dev(paths), 0.6, 0.4)
+    along = m.footprints_along(dev(paths), 0.6, 0.4)
     flat, _ = fc.run(t, rollouts.headings(paths).reshape(8, 5), 0.6, 0.4)
-    assert tuple(along["status"].shape) == (2, 4) and np.array_equal(_np(along["status"]).ravel(), flat["status"])
-    assert np.array_equal(_np(along["z"]).view(np.uint32).ravel(), flat["z"].view(np.uint32))
-    assert _np(along["status"])[1].tolist() == [0, 0, 1, 1] and _np(along["stands"]).tolist() == [True, True]
+    assert tuple(along["status"].shape) == (2, 4) and np.array_equal(to_np(along["status"]).ravel(), flat["status"])
+    assert np.array_equal(to_np(along["z"]).view(np.uint32).ravel(), flat["z"].view(np.uint32))
+    assert to_np(along["status"])[1].tolist() == [0, 0, 1, 1] and to_np(along["stands"]).tolist() == [True, True]
     assert m.footprints_along(paths, 0.6, 0.4, host=True)["stands"].tolist() == [True, True]
     for rows in (0, 3):                                      # no poses, with and without rows asked for, through both entry points
         for empty in (torch.zeros((0, 5), device="cuda"), np.zeros((0, 5), np.float32)):
@@ -235,7 +188,7 @@ def test_the_python_wrapper_yaw_poses_and_paths():
 def test_first_builder_of_the_column_index_a_large_host_call_then_a_small_one():
     import torch
     cloud = fc.kerb_cloud(0.2)
-    m = _build(cloud, P)                                     # a handle no consumer has touched: this call makes the column index
+    m = build(cloud, P)                                     # a handle no consumer has touched: this call makes the column index
     t = fc.map_rows(m.export(), cloud[0, :3], P)
     poses = fc.headed([[0.1, 0.7, 0.1], [-0.2, -1.3, 0.3], [2.3, 2.1, 0.2]], [0.0, 2.0, -1.0])          # two across the kerb, one beside it
     want = check(m, t, poses, 1.2, 0.6, "first call", entries=(False,))
@@ -255,7 +208,7 @@ def test_after_an_update_a_crop_a_clear_and_a_flood():
     from grid_ndt_amd import scenes
     cloud = scenes.bridge_ground()
     BP = scenes.BRIDGE_PARAMS
-    m = _build(cloud, BP, ATOMIC)                            # (updates need the additive strategy)
+    m = build(cloud, BP, ATOMIC)                            # (updates need the additive strategy)
     rng = np.random.default_rng(12)
     ok = 0
 
@@ -271,13 +224,13 @@ def test_after_an_update_a_crop_a_clear_and_a_flood():
 
     before = fresh("before")
     x0, x1 = int(before.sx.min()), int(before.sx.max())
-    m.change2DMap("slope", _dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
+    m.change2DMap("slope", dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
     fresh("update")
     m.crop_box((x0 + (x1 - x0) // 4, x1 - (x1 - x0) // 4, -100000, 100000), "keep_inside")
     cropped = fresh("crop")
     assert cropped.n < before.n and ok > 40
     ends = cropped.mean[(cropped.flags & 2) != 0][::7].astype(np.float32) + np.float32([0, 0, -0.4])
-    m.clear_rays((8.0, 3.0, 6.0), _dev(ends))
+    m.clear_rays((8.0, 3.0, 6.0), dev(ends))
     cleared = fresh("clear")
     assert cleared.n < cropped.n
     # a flood in between: the call only reads, h and state are what they were
@@ -317,7 +270,7 @@ def test_refused_arguments():
             assert raw(m, poses, 1.2, 0.6, stride=stride, host=host)[0] == 0
     prm = FootprintParams(1.2, 0.6)
     buf = torch.zeros(256, dtype=torch.int32, device="cuda")
-    d_poses = _dev(fc.strided(poses, 32))
+    d_poses = dev(fc.strided(poses, 32))
     p = lambda x, off=0: C.c_void_p(x.data_ptr() + off)
     call = m._L.gndt_footprint_poses_device
     X, B = p(d_poses), C.byref(prm)
@@ -347,10 +300,10 @@ def test_refused_arguments():
     e = g.TwoDmap(0.5, 0.25)
     e.setCloudFirst((0.0, 0.0, 0.0))
     with pytest.raises(g.GndtError) as err:
-        e.footprints(_dev(poses), 1.2, 0.6)
+        e.footprints(dev(poses), 1.2, 0.6)
     assert err.value.code == ERR_INVALID
     with pytest.raises(ValueError):
-        m.footprints(_dev(poses[:, :3]), 1.2, 0.6)                                       # neither a vector nor a yaw
+        m.footprints(dev(poses[:, :3]), 1.2, 0.6)                                       # neither a vector nor a yaw
     # a capturing stream: refused, and the capture goes on
     st = torch.cuda.Stream()
     graph = torch.cuda.CUDAGraph()
@@ -374,34 +327,19 @@ POISON_IDS = ["test_every_box_size_both_weights_and_a_band[1]", "test_every_box_
               "test_every_box_size_both_weights_and_a_band[15]", "test_wavefront_and_workgroup_edges_of_K[5]",
               "test_row_caps_around_support", "test_a_mixed_batch_alone_permuted_and_twice",
               "test_first_builder_of_the_column_index_a_large_host_call_then_a_small_one", "test_after_an_update_a_crop_a_clear_and_a_flood"]
-POISON_MEASURED_S = 4.47
-POISON_LIMIT_S = 20
-_stopped = []        # why the tier stopped: a child ended abnormally
+HERE = "tests/test_gpu_footprint.py::"
+GROUP = dict(measured_s=4.47, limit_s=20, ids=[HERE + i for i in POISON_IDS])
 
 
-@pytest.mark.skipif(bool(os.environ.get("GNDT_LIB_VARIANT")), reason="this process runs on a variant of the library itself: no children of its own")
-@pytest.mark.parametrize("byte", [0xA5, 0x7F], ids=["0xA5", "0x7F"])
+def test_every_node_id_of_the_poison_group_is_collected():
+    poison_tier.ids_collected(GROUP["ids"])
+
+
+def test_the_poison_limit_is_three_times_the_measured_time():
+    poison_tier.limit_follows_rule(GROUP["measured_s"], GROUP["limit_s"])
+
+
+@poison_tier.refused_under_variant
+@pytest.mark.parametrize("byte", poison_tier.BYTES, ids=poison_tier.BYTE_IDS)
 def test_footprints_under_poison(byte):
-    from grid_ndt_amd import _lib
-    from tests.test_gpu_poisoned import _abnormal, _env
-    if _stopped:
-        pytest.fail(f"not started: {_stopped[0]}", pytrace=False)
-    _lib.build_native(variant="poison")          # (the build has made it: nothing compiles inside the child's limit)
-    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + ["tests/test_gpu_footprint.py::" + i for i in POISON_IDS]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, env=_env("poison"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=POISON_LIMIT_S)
-        returncode, output = r.returncode, r.stdout
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout or ""
-        returncode, output = None, out.decode(errors="replace") if isinstance(out, bytes) else out
-    print(output[-6000:])
-    why = _abnormal(returncode, output)
-    if why:
-        _stopped.append(f"the child under {byte:#x} {why}")
-        pytest.fail(_stopped[0] + "\n" + output[-3000:], pytrace=False)
-    lines = [line for line in output.splitlines() if line.startswith('{"poisoned_child"')]
-    assert returncode == 0 and len(lines) == 1, (returncode, output[-3000:])
-    rep = json.loads(lines[0])
-    assert rep["exit"] == 0 and rep["byte"] == byte
-    assert rep["device_bytes"] > 0 and rep["host_bytes"] > 0, rep
-    assert rep["lib"] == _lib.lib_path("poison")
+    poison_tier.run_group("the footprints", GROUP["ids"], GROUP["limit_s"], byte)

@@ -12,6 +12,7 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import frontier_ref as fr
 from tests import plan_ref as pr
+from tests.gpu_kit import Padded, PaddedCall, build, dev, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +24,6 @@ FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "norma
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
 def cfg(candidates=fr.SLOPES, open_rule=fr.OPEN_COLUMN, level_reach=1, min_open=1, link_dz=1):
     return dict(candidates=candidates, open_rule=open_rule, level_reach=level_reach, min_open=min_open, link_dz=link_dz)
 
@@ -45,39 +31,20 @@ def cfg(candidates=fr.SLOPES, open_rule=fr.OPEN_COLUMN, level_reach=1, min_open=
 def raw(m, c, box=None, min_size=1, cap=None, labels=True, stream=None, host=False, reserved=(0, 0), counts=True, clusters=True):
     """The C entry points.  cap None: as many records as the map has rows.  -> (rc, dict(label, clusters [min(counts[0], cap)],
     counts, buf: the whole record buffer with PAD sentinel records on either side))"""
-    import torch
     from grid_ndt_amd._lib import CropBox, FrontierParams
     n = int(m.sync()[0])
     cap = n if cap is None else cap
     prm = FrontierParams(c["candidates"], c["open_rule"], c["level_reach"], c["min_open"], c["link_dz"], min_size, (C.c_uint32 * 2)(*reserved))
-    b = None if box is None else C.byref(CropBox(*box))
-    if host:
-        buf = np.full((cap + 2 * PAD) * 16, SENTINEL, np.uint32)
-        lab = np.full(max(n, 1), SENTINEL, np.uint32)
-        cnt = np.full(4, SENTINEL, np.uint32)
-        ptr = lambda a, off=0: C.c_void_p(a.ctypes.data + off)
-    else:
-        buf = torch.full(((cap + 2 * PAD) * 16,), SENTINEL, dtype=torch.int32, device="cuda")
-        lab = torch.full((max(n, 1),), SENTINEL, dtype=torch.int32, device="cuda")
-        cnt = torch.full((4,), SENTINEL, dtype=torch.int32, device="cuda")
-        ptr = lambda a, off=0: C.c_void_p(a.data_ptr() + off)
-    args = [m._h, b, C.byref(prm), ptr(lab) if labels else None, ptr(buf, PAD * 64) if cap and clusters else None, cap,
-            ptr(cnt) if counts else None]
-    if host:
-        rc = m._L.gndt_frontiers(*args)
-    else:
-        rc = m._L.gndt_frontiers_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        buf, lab, cnt = (t.cpu().numpy().view(np.uint32) for t in (buf, lab, cnt))
-    recs = buf.view(fr.RECORD)
-    k = min(int(cnt[0]), cap) if rc == 0 else 0
-    return rc, dict(label=lab[:n], clusters=recs[PAD:PAD + k], counts=cnt, buf=buf)
+    buf, lab, cnt = Padded(cap, words=16, front=PAD, back=PAD, fill=SENTINEL), Padded(max(n, 1), fill=SENTINEL), Padded(4, fill=SENTINEL)
+    rc = PaddedCall(host, stream)(m._L.gndt_frontiers, m._L.gndt_frontiers_device, m._h, None if box is None else C.byref(CropBox(*box)),
+                                  C.byref(prm), lab if labels else None, buf if cap and clusters else None, cap, cnt if counts else None)
+    k = min(int(cnt.a[0]), cap) if rc == 0 else 0
+    return rc, dict(label=lab.a[:n], clusters=buf.a.view(fr.RECORD)[PAD:PAD + k], counts=cnt.a, buf=buf.a)
 
 
 def untouched(buf, written):
     """the sentinel records before the list and everything behind its `written` records"""
-    w = buf.reshape(-1, 16)
-    return (w[:PAD] == SENTINEL).all() and (w[PAD + written:] == SENTINEL).all()
+    return Padded.over(buf, words=16, front=PAD, fill=SENTINEL).untouched(written)
 
 
 def check(m, ref_map, c, cost=None, box=None, min_size=1, what="", **kw):
@@ -100,7 +67,7 @@ def drawn(name, cells, seed=None):
     """a map drawn from a cell list -> (m, ref_map, export)"""
     key = (name, seed)
     if key not in _scenes:
-        m = _build(fr.cells_cloud(cells, seed), fr.P)
+        m = build(fr.cells_cloud(cells, seed), fr.P)
         cells_out = m.export()
         _scenes[key] = (m, fr.Map(cells_out), cells_out)
     return _scenes[key]
@@ -115,7 +82,7 @@ def flooded(name):
             cloud, P, goal, robot = scenes.drivable_site(), scenes.COST_PARAMS, scenes.DRIVABLE_GOAL, dict(radius=0.25)
         else:
             cloud, P, goal, robot = scenes.bridge_ground(), scenes.BRIDGE_PARAMS, pr.BRIDGE_GOALS["deck"], None
-        m = _build(cloud, P)
+        m = build(cloud, P)
         assert m.computeCost(goal, robot)["rc"] == 0
         cells = m.export()
         _scenes[name] = (m, fr.Map(cells), cells, m.cost_export())
@@ -283,7 +250,7 @@ def test_repeat_calls_and_a_second_stream_give_the_same_bytes_and_change_nothing
 def test_after_a_crop_and_after_an_update():
     import grid_ndt_amd as g
     site = scenes.drivable_site(200_000)
-    m = _build(site, scenes.COST_PARAMS, ATOMIC)
+    m = build(site, scenes.COST_PARAMS, ATOMIC)
     assert m.computeCost(scenes.DRIVABLE_GOAL)["rc"] == 0
     check(m, fr.Map(m.export()), cfg(fr.REACHED), m.cost_export(), what="before")
 
@@ -305,7 +272,7 @@ def test_after_a_crop_and_after_an_update():
     x0, x1 = int(m.export()["sx"].min()), int(m.export()["sx"].max())
     m.crop_box((x0 + 5, x1 - 5, -1000, 1000), "keep_inside")
     stale_then_flooded("crop")
-    m.change2DMap("slope", _dev(site[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
+    m.change2DMap("slope", dev(site[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
     stale_then_flooded("update")
     # everything cropped away: four zero counts, nothing else written
     m.crop_box((x1 + 50, x1 + 60, 1, 2), "keep_inside")
@@ -317,10 +284,6 @@ def test_after_a_crop_and_after_an_update():
 
 # ---- the Python interface and the round trip into the planner ---------------------------------------------------------------------
 
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
 @pytest.mark.parametrize("name", ["floor", "site"])
 def test_best_rows_are_starts_the_planner_finds_routes_from(name):
     m, ref_map, cells, cost = flooded(name)
@@ -328,18 +291,18 @@ def test_best_rows_are_starts_the_planner_finds_routes_from(name):
         f = m.frontiers(labels=True, host=host)                          # reached, column: the defaults
         ref = ref_map.frontiers(fr.REACHED, h_bits=cost["h"].view(np.uint32), state=cost["state"])
         K = len(ref["clusters"])
-        assert K >= 1 and tuple(_np(f["counts"]).tolist()) == (K, ref["rows"], K, 0)
+        assert K >= 1 and tuple(to_np(f["counts"]).tolist()) == (K, ref["rows"], K, 0)
         for k in fr.RECORD.names[:-1]:
-            assert _np(f[k]).tobytes() == ref["clusters"][k].tobytes(), (k, host)
-        assert np.array_equal(_np(f["labels"]).view(np.uint32), ref["label"])
+            assert to_np(f[k]).tobytes() == ref["clusters"][k].tobytes(), (k, host)
+        assert np.array_equal(to_np(f["labels"]).view(np.uint32), ref["label"])
         pts = m.frontier_points(f, "best")
         assert pts.shape == (K, 3) and (hasattr(pts, "cpu") != host)
         rows, info = m.plan_routes(pts, start_mode="nearest_slope", route_cap=8, host=host)
-        assert (_np(info["status"]) == 0).all(), _np(info["status"])      # GNDT_ROUTE_FOUND
-        assert np.array_equal(_np(info["start_row"]), _np(f["best_row"]))
-        assert np.array_equal(_np(info["h_start"]).view(np.uint32), _np(f["best_h"]).view(np.uint32))
+        assert (to_np(info["status"]) == 0).all(), to_np(info["status"])      # GNDT_ROUTE_FOUND
+        assert np.array_equal(to_np(info["start_row"]), to_np(f["best_row"]))
+        assert np.array_equal(to_np(info["h_start"]).view(np.uint32), to_np(f["best_h"]).view(np.uint32))
         # the centroid: origin + (sum / size + 0.5) * cell, from the records
-        cen = _np(m.frontier_points(f, "centroid"))
+        cen = to_np(m.frontier_points(f, "centroid"))
         o, rec = np.asarray(m.cloudFirst, np.float64), ref["clusters"]
         want = np.stack([o[0] + (rec["sum_px"] / rec["size"] + 0.5) * m.gridLen, o[1] + (rec["sum_py"] / rec["size"] + 0.5) * m.gridLen,
                          o[2] + (rec["sum_pz"] / rec["size"] + 0.5) * m.zLen], 1).astype(np.float32)
@@ -354,16 +317,16 @@ def test_python_list_capacity_and_options():
     box = None
     for host in (False, True):
         f = m.frontiers("slopes", "level", level_reach=3, min_open=2, link_dz=2, min_size=2, box=box, host=host)
-        assert "labels" not in f and np.array_equal(_np(f["counts"]).view(np.uint32), counts)
-        assert _np(f["label"]).view(np.uint32).tolist() == recs["label"].tolist() and _np(f["size"]).tolist() == recs["size"].tolist()
+        assert "labels" not in f and np.array_equal(to_np(f["counts"]).view(np.uint32), counts)
+        assert to_np(f["label"]).view(np.uint32).tolist() == recs["label"].tolist() and to_np(f["size"]).tolist() == recs["size"].tolist()
         f = m.frontiers("slopes", "level", level_reach=3, min_open=2, link_dz=2, min_size=2, max_clusters=2, host=host)
-        assert _np(f["label"]).view(np.uint32).tolist() == recs["label"][:2].tolist() and int(_np(f["counts"])[0]) == len(recs)
+        assert to_np(f["label"]).view(np.uint32).tolist() == recs["label"][:2].tolist() and int(to_np(f["counts"])[0]) == len(recs)
         f = m.frontiers("slopes", "level", level_reach=3, min_open=2, link_dz=2, min_size=2, max_clusters=len(recs) + 2, host=host)
         # room to spare: the host list is cut to what was found; the device list keeps its capacity, size 0 behind the clusters,
         # and such an entry is no point
-        assert _np(f["size"]).tolist() == recs["size"].tolist() + ([] if host else [0, 0])
+        assert to_np(f["size"]).tolist() == recs["size"].tolist() + ([] if host else [0, 0])
         for which in ("best", "centroid"):
-            pts = _np(m.frontier_points(f, which))
+            pts = to_np(m.frontier_points(f, which))
             assert pts.shape == (len(recs) + (0 if host else 2), 3)
             assert np.isfinite(pts[:len(recs)]).all() and np.isnan(pts[len(recs):]).all()
 
@@ -379,10 +342,10 @@ def test_python_call_on_another_stream_sizes_its_list_on_that_stream():
         s = torch.cuda.Stream()
         f = m.frontiers("reached", "level", level_reach=1, labels=True, stream=s)
         s.synchronize()
-        assert np.array_equal(_np(f["counts"]).view(np.uint32), counts)
+        assert np.array_equal(to_np(f["counts"]).view(np.uint32), counts)
         for k in fr.RECORD.names[:-1]:
-            assert _np(f[k]).tobytes() == recs[k].tobytes(), k
-        assert np.array_equal(_np(f["labels"]).view(np.uint32), ref["label"])
+            assert to_np(f[k]).tobytes() == recs[k].tobytes(), k
+        assert np.array_equal(to_np(f["labels"]).view(np.uint32), ref["label"])
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------
@@ -420,7 +383,7 @@ def test_refused_arguments():
     assert m._L.gndt_frontiers_device(None, None, C.byref(prm), None, None, 0, p(cnt), None) == ERR_INVALID
     assert m._L.gndt_frontiers(None, None, C.byref(prm), None, None, 0, None) == ERR_INVALID
     # REACHED without a cost map, and no finished build
-    e = _build(fr.cells_cloud([(0, 0), (1, 0)]), fr.P)
+    e = build(fr.cells_cloud([(0, 0), (1, 0)]), fr.P)
     assert raw(e, cfg(fr.REACHED))[0] == ERR_INVALID and raw(e, cfg(fr.SLOPES))[0] == 0
     e = g.TwoDmap(0.5, 0.25)
     e.setCloudFirst((0.0, 0.0, 0.0))

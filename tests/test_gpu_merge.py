@@ -16,7 +16,8 @@ from tests import merge_ref as mr
 from tests import parity
 from tests import query_ref as qr
 from tests.test_gpu_coarsen import _cells_cloud, _coarse_params, _fine, _same_bits, _scene, _stats
-from tests.test_gpu_score import ATOMIC, BOX, ERR_INVALID, PARTITION, TILE, _dev, _handle
+from tests.gpu_kit import dev, handle
+from tests.test_gpu_score import ATOMIC, BOX, ERR_INVALID, PARTITION, TILE
 from tests.test_merge_host import lattice_pose, moved_cloud, rigid
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +34,7 @@ def _oracle(tag, cloud, P):
 
 
 def _empty(P, origin):
-    d = _handle(P, ATOMIC)
+    d = handle(P, ATOMIC)
     d.setCloudFirst(origin)
     return d
 
@@ -122,14 +123,14 @@ def test_merge_into_a_populated_map_continues_the_stream():
     body = cloud[1:]
     a, b = len(body) // 3, 2 * len(body) // 3
     dst = _empty(P, cloud[0])
-    dst.create2DMap("slope", _dev(body[:a]))
+    dst.create2DMap("slope", dev(body[:a]))
     src = _empty(P, cloud[0])
-    src.create2DMap("slope", _dev(body[a:b]))
+    src.create2DMap("slope", dev(body[a:b]))
     n0 = dst.sync()[0]
     st = dst.merge_from(src)
     assert st["merged_points"] == b - a and st["new_nodes"] == dst.sync()[0] - n0
     parity.assert_parity(dst.export(), _oracle(("campus", b), cloud[:1 + b], P))
-    dst.change2DMap("slope", _dev(body[b:]))
+    dst.change2DMap("slope", dev(body[b:]))
     parity.assert_parity(dst.export(), _oracle(("campus_frame", 1), cloud, P))
 
 
@@ -164,7 +165,7 @@ def test_a_general_pose_against_the_restatement():
     Pd = dict(P, grid_len=0.3, z_len=0.2)
     o2 = cloud[0, :3] + np.float32([0.37, -0.21, 0.05])
     dst = _empty(Pd, o2)
-    dst.create2DMap("slope", _dev(cloud[1:10001]))
+    dst.create2DMap("slope", dev(cloud[1:10001]))
     pose = rigid(17.0, 4.0, (0.731, -0.419, 0.057))
     st = _check_against_restatement(dst, src, pose, (cloud[0, :3], P["grid_len"], P["z_len"]), (o2, Pd["grid_len"], Pd["z_len"]), base=10000)
     assert st["merged_nodes"] == src.sync()[0] and st["new_nodes"] > 0
@@ -234,12 +235,12 @@ def test_empty_sources_and_nodes_that_do_not_travel():
     d = _empty(P, cloud[0])
     st = d.merge_from(m)
     assert st == {k: 0 for k in st} and d.sync() == (0, 0, 0)
-    d.change2DMap("slope", _dev(body[:500]))
+    d.change2DMap("slope", dev(body[:500]))
     assert int(d.export()["first_idx"].min()) == len(body)
     # a translation of 10^6 m: every node is skipped, the map is the same bits, the stream position has advanced
     src = _fine(cloud, P)
     dst = _empty(P, cloud[0])
-    dst.create2DMap("slope", _dev(body[:20000]))
+    dst.create2DMap("slope", dev(body[:20000]))
     before = dst.export()
     far = np.concatenate([np.eye(3), [[1e6], [0.0], [0.0]]], 1)
     st = dst.merge_from(src, pose=far)
@@ -247,7 +248,7 @@ def test_empty_sources_and_nodes_that_do_not_travel():
     assert st == {"source_nodes": n, "merged_nodes": 0, "merged_points": 0, "below_min_count": 0, "skipped": n, "new_nodes": 0}
     _same_bits(dst.export(), before)
     lone = cloud[:1, :3] + np.float32([[41.3, 37.7, 9.1]])                     # a cell nothing has touched
-    dst.change2DMap("slope", _dev(lone))
+    dst.change2DMap("slope", dev(lone))
     after = dst.export()
     new = np.flatnonzero(after["first_idx"] == 20000 + len(body))
     assert after["num_nodes"] == before["num_nodes"] + 1 and new.size == 1 and after["count"][new].tolist() == [1]
@@ -260,7 +261,7 @@ def test_a_small_destination_table_grows():
     cloud, P = _scene("campus_frame")
     body = cloud[1:]
     dst = _empty(P, cloud[0])
-    dst.create2DMap("slope", _dev(body[:800]))
+    dst.create2DMap("slope", dev(body[:800]))
     early = dst.export()
     assert early["num_nodes"] <= 1024
     src = _fine(cloud, P)
@@ -285,7 +286,7 @@ def test_the_source_is_untouched():
     goal = tuple(float(v) for v in before["mean"][slopes[len(slopes) // 2]])
     m.computeCost(goal, robot={"radius": 0.25})
     cost = m.cost_export()
-    pts = _dev(cloud[1:][::7])
+    pts = dev(cloud[1:][::7])
     rows = m.query(pts).cpu().numpy()
     d = _empty(dict(P, grid_len=0.4, z_len=0.2), cloud[0])
     assert d.merge_from(m, pose=rigid(3.0, 1.0, (0.2, 0.1, 0.0)))["merged_nodes"] == counts[0]
@@ -307,7 +308,7 @@ def test_refusals_leave_the_destination_as_it_was():
     cloud, P = _scene("uniform_box")
     src = _fine(cloud, P)
     dst = _empty(P, cloud[0])
-    dst.create2DMap("slope", _dev(cloud[1:20001]))
+    dst.create2DMap("slope", dev(cloud[1:20001]))
     before = dst.export()
     L = src._L
     null = C.c_void_p(0)
@@ -339,12 +340,12 @@ def test_refusals_leave_the_destination_as_it_was():
     empty = _empty(P, cloud[0])                                                     # no finished build in the source
     empty.reset("slope")
     refused(call(dst._h, empty._h))
-    part = _handle(P, PARTITION)                                                    # a source that is not in the node table
+    part = handle(P, PARTITION)                                                    # a source that is not in the node table
     part.setCloudFirst(cloud[0])
-    part.create2DMap("slope", _dev(cloud[1:]))
+    part.create2DMap("slope", dev(cloud[1:]))
     refused(call(dst._h, part._h))
     assert "node table" in L.gndt_last_error(dst._h).decode()
-    bare = _handle(P, ATOMIC)                                                       # a destination without an origin
+    bare = handle(P, ATOMIC)                                                       # a destination without an origin
     bare._ensure("slope", need_origin=False)
     assert call(bare._h, src._h) == ERR_INVALID and "origin" in L.gndt_last_error(bare._h).decode()
     held = part.export()                                                            # a destination that holds a PARTITION-built map
@@ -352,7 +353,7 @@ def test_refusals_leave_the_destination_as_it_was():
     _same_bits(part.export(), held)
     full = _empty(P, cloud[0])                                                      # the two streams together exceed 2^32 - 2 points
     full.reset("slope")
-    full.accumulate("slope", _dev(cloud[1:101]), first_idx_base=0xFFFFFFFE - 100 - (len(cloud) - 1) + 1)
+    full.accumulate("slope", dev(cloud[1:101]), first_idx_base=0xFFFFFFFE - 100 - (len(cloud) - 1) + 1)
     held = _sorted_stats(_stats(full))
     assert call(full._h, src._h) == ERR_INVALID and "2^32" in L.gndt_last_error(full._h).decode()
     now = _sorted_stats(_stats(full))
@@ -387,9 +388,9 @@ def test_stitch_registers_then_merges():
     from tests.test_score_derivs_host import starts
     cloud, P = scenes.drivable_site(100_000), scenes.COST_PARAMS
     other = _empty(P, cloud[0])
-    other.create2DMap("slope", _dev(cloud[1:][::2]))
+    other.create2DMap("slope", dev(cloud[1:][::2]))
     cells = other.export()
-    scan = _dev(cells["mean"][(cells["flags"] & 1) != 0])
+    scan = dev(cells["mean"][(cells["flags"] & 1) != 0])
     T0 = starts(P)["B"]
     a, b = _fine(cloud, P), _fine(cloud, P)
     ref = a.register(scan, T0)
@@ -410,14 +411,14 @@ def test_an_update_graph_recorded_before_a_merge_is_reported_stale():
     P = scenes.TERRAIN_PARAMS
     frames = scenes.terrain_frames(3, points_per_frame=32_768)
     origin, f0, f1 = frames[0], frames[1:32_769], frames[32_769:65_537]
-    dst = _handle(P, ATOMIC, max_points_hint=400_000, max_nodes_hint=400_000)
+    dst = handle(P, ATOMIC, max_points_hint=400_000, max_nodes_hint=400_000)
     dst.setCloudFirst(origin)
-    dst.change2DMap("slope", _dev(f0))
+    dst.change2DMap("slope", dev(f0))
     src = _empty(P, origin)
-    src.create2DMap("slope", _dev(f1[:8000]))
+    src.create2DMap("slope", dev(f1[:8000]))
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
-        buf = _dev(f1)
+        buf = dev(f1)
         s.wait_stream(torch.cuda.default_stream())
         graph = torch.cuda.CUDAGraph()
         with g.graph_capture(graph, s):

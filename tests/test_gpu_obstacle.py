@@ -14,6 +14,8 @@ import pytest
 from tests import clearance_ref as cr
 from tests import frontier_ref as fr
 from tests import obstacle_ref as ob
+from tests.gpu_kit import Padded, PaddedCall, at, build, dev, robot_arg
+from tests.gpu_kit import tails_untouched as untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -29,17 +31,11 @@ def _tgc():
     return tgc
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
 def raw(m, boxes, inflate=0, max_hops=8, levels_above=0, levels_below=0, max_columns=0, base=None, in_place=False, n_boxes_dev=None,
         stride=24, robot=None, outs=("hops", "obstacle"), stream=None, host=False, reserved=(0, 0), counts=True, n_boxes=None, params=True,
         misalign=0):
     """The C entry points, every output num_nodes + PAD entries of sentinel.  -> (rc, dict(hops, obstacle: the outputs asked for, cut to
     num_nodes; counts; tails: what lies behind num_nodes))"""
-    import torch
     from grid_ndt_amd._lib import ObstacleParams
     n = int(m.sync()[0])
     prm = ObstacleParams(inflate, max_hops, levels_above, levels_below, max_columns, (C.c_uint32 * 2)(*reserved))
@@ -49,45 +45,26 @@ def raw(m, boxes, inflate=0, max_hops=8, levels_above=0, levels_below=0, max_col
     off = (recs.shape[1] - 6) // 2                        # the six words somewhere inside a wider record
     if boxes is not None:
         recs[:len(boxes), off:off + 6] = boxes
-    buf = {k: np.full(n + PAD, SENTINEL, np.uint32) for k in outs}
-    bs = None if base is None else np.concatenate([np.ascontiguousarray(base).view(np.uint32), np.full(PAD, SENTINEL, np.uint32)])
-    if in_place:
-        buf["hops"][:] = bs
-    cnt = np.full(8, SENTINEL, np.uint32)
-    if host:
-        keep = (recs, bs)
-        ptr = lambda a, o=0: None if a is None else C.c_void_p(a.ctypes.data + o)
-        args = [m._h, tgc_robot(robot), None if boxes is None else ptr(recs, 4 * off + misalign), nb, stride, C.byref(prm) if params else None,
-                ptr(buf["hops"]) if in_place else ptr(bs)] + [ptr(buf.get(k)) for k in ("hops", "obstacle")] + [ptr(cnt) if counts else None]
-        rc = m._L.gndt_obstacle_field(*args)
-    else:
-        to = lambda a: None if a is None else torch.from_numpy(a.view(np.int32)).cuda()
-        d_recs, d_bs, d_cnt = to(recs), to(bs), to(cnt)
-        d_nb = None if n_boxes_dev is None else to(np.array([n_boxes_dev], np.uint32))
-        d_buf = {k: to(a) for k, a in buf.items()}
-        ptr = lambda t, o=0: None if t is None else C.c_void_p(t.data_ptr() + o)
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream())
-        args = [m._h, tgc_robot(robot), None if boxes is None else ptr(d_recs, 4 * off + misalign), nb, stride, ptr(d_nb),
-                C.byref(prm) if params else None, ptr(d_buf["hops"]) if in_place else ptr(d_bs)] + \
-               [ptr(d_buf.get(k)) for k in ("hops", "obstacle")] + [ptr(d_cnt) if counts else None]
-        rc = m._L.gndt_obstacle_field_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        buf = {k: t.cpu().numpy().view(np.uint32) for k, t in d_buf.items()}
-        cnt = d_cnt.cpu().numpy().view(np.uint32)
-        if bs is not None:
-            assert d_bs.cpu().numpy().view(np.uint32).tobytes() == bs.tobytes()          # the base is read, never written
-    out = {k: a[:n] for k, a in buf.items()}
-    out.update(counts=cnt, tails={k: a[n:] for k, a in buf.items()})
+    buf = {k: Padded(n, back=PAD, fill=SENTINEL) for k in outs}
+    bs = None
+    if base is not None:
+        base = np.ascontiguousarray(base).view(np.uint32)
+        bs = Padded(len(base), back=PAD, fill=SENTINEL)
+        bs.body[:] = base
+        if in_place:
+            buf["hops"].a[:] = bs.a
+    cnt = Padded(8, fill=SENTINEL)
+    # (the host entry point has no count on the device)
+    nbd = [] if host else [None if n_boxes_dev is None else np.array([n_boxes_dev], np.uint32)]
+    rc = PaddedCall(host, stream, wait_for_current=True)(
+        m._L.gndt_obstacle_field, m._L.gndt_obstacle_field_device, m._h, robot_arg(robot, cr.ROBOT),
+        None if boxes is None else at(recs, 4 * off + misalign), nb, stride, *nbd, C.byref(prm) if params else None,
+        buf["hops"] if in_place else bs, buf.get("hops"), buf.get("obstacle"), cnt if counts else None)
+    if bs is not None:
+        assert bs.body.tobytes() == base.tobytes() and bs.untouched()          # the base is read, never written
+    out = {k: p.body for k, p in buf.items()}
+    out.update(counts=cnt.a, tails={k: p.tail for k, p in buf.items()})
     return rc, out
-
-
-def tgc_robot(robot):
-    return _tgc()._robot(robot)
-
-
-def untouched(got):
-    return all((t == SENTINEL).all() for t in got["tails"].values())
 
 
 REF_KEYS = ("inflate", "max_hops", "levels_above", "levels_below", "max_columns", "base", "n_boxes_dev")
@@ -303,7 +280,7 @@ def test_refused_arguments():
     # a device pointer that is not aligned to 4 bytes: each of the five in turn
     import torch
     from grid_ndt_amd._lib import ObstacleParams
-    d_box, buf = _dev(box, np.int32), torch.zeros(300, dtype=torch.int32, device="cuda")
+    d_box, buf = dev(box, np.int32), torch.zeros(300, dtype=torch.int32, device="cuda")
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     good = dict(n_boxes_dev=p(buf, 1184), base=p(buf, 0), hops=p(buf, 0), obstacle=p(buf, 4 * 260 - 4 * 256 + 0), counts=p(buf, 1152))
     prm2 = ObstacleParams(0, 2, 0, 0, 0)
@@ -337,7 +314,7 @@ def test_refused_arguments():
     s = torch.cuda.Stream()
     graph = torch.cuda.CUDAGraph()
     outs = [torch.zeros(256, dtype=torch.int32, device="cuda") for _ in range(2)] + [torch.zeros(8, dtype=torch.int32, device="cuda")]
-    d_box = _dev(box, np.int32)
+    d_box = dev(box, np.int32)
     torch.cuda.synchronize()
     with g.graph_capture(graph, stream=s):
         rc = m._L.gndt_obstacle_field_device(m._h, None, C.c_void_p(d_box.data_ptr()), 1, 24, None, C.byref(prm), None, C.c_void_p(outs[0].data_ptr()),
@@ -355,7 +332,7 @@ def test_repeat_calls_streams_and_a_small_call_after_a_large_one():
     """the marks are stamped, not cleared: the same call again, a call on another stream, and a small call behind one that had every row
     of the map in its worklist all find the earlier calls' stamps, slots and cover words in place"""
     import torch
-    m = _tgc()._build(cr.lattice(14641, fr.P), fr.P)
+    m = build(cr.lattice(14641, fr.P), fr.P)
     cells = m.export()
     f = cr.Field(cells)
     assert cells["num_nodes"] == 14641
@@ -375,7 +352,7 @@ def test_repeat_calls_streams_and_a_small_call_after_a_large_one():
 
 def test_first_builder_of_the_index_and_after_an_update_a_crop_and_a_clear():
     cloud = fr.cells_cloud([(ix, iy) for ix in range(-12, 12) for iy in range(-10, 10)])
-    m = _tgc()._build(cloud, fr.P, ATOMIC)
+    m = build(cloud, fr.P, ATOMIC)
     boxes = [[-2, 2, -1, 1, 1, 1], [9, 9, 9, 9, 1, 1]]
 
     def fresh(what):
@@ -387,12 +364,12 @@ def test_first_builder_of_the_index_and_after_an_update_a_crop_and_a_clear():
 
     n0, before = fresh("first call: the column index is this call's")
     more = fr.cells_cloud([(ix, iy) for ix in range(12, 15) for iy in range(-10, 10)])[1:]
-    m.change2DMap("slope", _dev(more[:, :3]))
+    m.change2DMap("slope", dev(more[:, :3]))
     n1, _ = fresh("update")
     m.crop_box((-9, 1000, -1000, 1000), "keep_inside")
     n2, _ = fresh("crop")
     ends = np.float32([[ix * fr.GL + 0.25, 2 * fr.GL + 0.25, -3.0] for ix in range(4, 8)])
-    st = m.clear_rays((3.0, 1.25, 4.0), _dev(ends))
+    st = m.clear_rays((3.0, 1.25, 4.0), dev(ends))
     n3, after = fresh("clear")
     assert n1 == n0 + 60 and n2 < n1 and st["cleared"] > 0 and n3 == n2 - st["cleared"]
     assert after["counts"][0] > 0
@@ -425,7 +402,7 @@ def test_segment_then_field_then_walk_and_shortcut_on_one_stream():
     paths = np.concatenate([_tgc_path((0.76, 0.3), (0.76, 5.7)), _tgc_path((2.76, 0.3), (2.76, 5.7))])       # along columns 2 and 6
     stream = torch.cuda.Stream()
     stream.wait_stream(torch.cuda.current_stream())
-    d_frame, d_paths = _dev(frame), _dev(paths)
+    d_frame, d_paths = dev(frame), dev(paths)
     stream.wait_stream(torch.cuda.current_stream())
     seg = m.segment_scan(d_frame, max_clusters=8, stream=stream)
     field1 = m.obstacle_field(seg, max_hops=8, levels_above=2, obstacle=True, stream=stream)
@@ -459,7 +436,7 @@ def test_segment_then_field_then_walk_and_shortcut_on_one_stream():
     without = tgs.check(m, s, rows, lengths, "no field", caps=False)
     with_field = tgs.check(m, s, rows, lengths, "with the field", caps=False, hops=want["hops"], min_hops=2)
     # ... and the same from the field as it lies on the device
-    d_rows, d_len = _dev(rows.view(np.int32), np.int32), _dev(lengths, np.int32)
+    d_rows, d_len = dev(rows.view(np.int32), np.int32), dev(lengths, np.int32)
     stream.wait_stream(torch.cuda.current_stream())
     got = m.shortcut_routes(d_rows, lengths=d_len, hops=field1, min_hops=2, stream=stream)
     stream.synchronize()

@@ -7,13 +7,11 @@ a pass reads before anything wrote it is 0 in a fresh process and the byte here 
 in the future".  The group holds the reuse and the edge cases because they are the ones that read the per-row marks of earlier calls.
 The children run one at a time, each under the time limit below; a child that is killed at its limit, ends by a signal, with status 134
 or 139, or reports an illegal memory access stops the tier: the case after it fails at once with "not started" and touches no GPU."""
-import json
-import subprocess
-import sys
-
 import pytest
 
-from tests.test_gpu_poisoned import BYTES, ROOT, _abnormal, _env
+from tests import poison_tier
+
+poison_tier.refuse_under_variant()
 
 OBS = "tests/test_gpu_obstacle.py::"
 # measured_s: the whole child (interpreter start to exit) on the MI355X under the regular library; limit_s: three times that, rounded
@@ -36,40 +34,12 @@ GROUP = dict(measured_s=4.68, limit_s=20, ids=[
 
 
 def test_every_node_id_is_collected_and_the_limit_is_three_times_the_measured_time():
-    ids = GROUP["ids"]
-    assert len(ids) == len(set(ids)) == 13
-    r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + ids, cwd=ROOT, env=_env(),
-                       capture_output=True, text=True, timeout=300)
-    found = {line.strip() for line in r.stdout.splitlines() if "::" in line}
-    assert r.returncode == 0 and found == set(ids), (sorted(set(ids) - found), r.stdout[-2000:], r.stderr[-2000:])
-    assert GROUP["measured_s"] > 0 and GROUP["limit_s"] == -(-3 * GROUP["measured_s"] // 10) * 10
-
-
-_stopped = []        # why the tier stopped: a child ended abnormally
+    assert len(GROUP["ids"]) == 13
+    poison_tier.ids_collected(GROUP["ids"])
+    poison_tier.limit_follows_rule(GROUP["measured_s"], GROUP["limit_s"])
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("byte", BYTES, ids=["0xA5", "0x7F"])
+@pytest.mark.parametrize("byte", poison_tier.BYTES, ids=poison_tier.BYTE_IDS)
 def test_obstacle_field_under_poison(byte):
-    from grid_ndt_amd import _lib
-    if _stopped:
-        pytest.fail(f"not started: {_stopped[0]}", pytrace=False)
-    _lib.build_native(variant="poison")          # (__graft_entry__.build() has built it: nothing compiles inside the child's limit)
-    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + GROUP["ids"]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, env=_env("poison"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=GROUP["limit_s"])
-        returncode, output = r.returncode, r.stdout
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout or ""
-        returncode, output = None, out.decode(errors="replace") if isinstance(out, bytes) else out
-    print(output[-6000:])
-    why = _abnormal(returncode, output)
-    if why:
-        _stopped.append(f"the child under {byte:#x} {why}")
-        pytest.fail(_stopped[0] + "\n" + output[-3000:], pytrace=False)
-    lines = [line for line in output.splitlines() if line.startswith('{"poisoned_child"')]
-    assert returncode == 0 and len(lines) == 1, (returncode, output[-3000:])
-    rep = json.loads(lines[0])
-    assert rep["exit"] == 0 and rep["byte"] == byte
-    assert rep["device_bytes"] > 0 and rep["host_bytes"] > 0, rep
-    assert rep["lib"] == _lib.lib_path("poison")
+    poison_tier.run_group("the obstacle field", GROUP["ids"], GROUP["limit_s"], byte)

@@ -14,27 +14,13 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import plan_ref as pr
+from tests.gpu_kit import build, dev
 
 pytestmark = pytest.mark.gpu
 
 CAP = 256          # route_cap of the comparisons: above every route of these scenes (the longest is 174 slopes)
 FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
 _scenes = {}
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _build(cloud, P):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"])
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
 
 
 def _flooded(m, cloud, P, goal, robot):
@@ -53,14 +39,14 @@ def scene(name):
         return _scenes[name]
     if name == "floor":
         cloud, P = pr.floor_cloud(), pr.FLOOR_P
-        m = _build(cloud, P)
+        m = build(cloud, P)
         pm = _flooded(m, cloud, P, pr.FLOOR_GOAL, pr.FLOOR_ROBOT)
         pts = pm.start_points(pm.slopes)
         s = dict(m=m, pm=pm, pts=pts, kinds=None, oracle=np.arange(0, len(pts), 25))
     elif name.startswith("site_"):
         demand, radius = pr.SITE_RUNS[name[5:]]
         cloud, P = scenes.drivable_site(), dict(scenes.COST_PARAMS, demand=demand)
-        m = _build(cloud, P)
+        m = build(cloud, P)
         pm = _flooded(m, cloud, P, scenes.DRIVABLE_GOAL, dict(radius=radius))
         bare = pr.find_bare_point(pm, cloud, lambda p: m.query(p, "node"))
         pts, kinds = pr.site_starts(pm, bare_point=bare)
@@ -78,7 +64,7 @@ def bridge(which):
     """One map, two goals: the flood is run again whenever the other goal is asked for (the tables of the first flood are kept)."""
     if "m" not in _bridge:
         _bridge["cloud"] = scenes.bridge_ground()
-        _bridge["m"] = _build(_bridge["cloud"], scenes.BRIDGE_PARAMS)
+        _bridge["m"] = build(_bridge["cloud"], scenes.BRIDGE_PARAMS)
         _bridge["now"] = None
     m = _bridge["m"]
     if _bridge["now"] != which:
@@ -119,7 +105,7 @@ def same(got, want, what):
 def check_scene(s, name):
     m, pm, pts = s["m"], s["pm"], s["pts"]
     want = shim_answers(s)
-    got = host(*m.plan_routes(_dev(pts), route_cap=CAP))
+    got = host(*m.plan_routes(dev(pts), route_cap=CAP))
     same(got, want, (name, "device"))
     rows, info = got
     assert info["length"].max() <= CAP
@@ -162,7 +148,7 @@ def test_host_entry_point_and_find_route():
     m, pm, pts = s["m"], s["pm"], s["pts"]
     want = shim_answers(s)
     same(host(*m.plan_routes(pts, route_cap=CAP)), want, "gndt_plan_routes")
-    same(host(*m.plan_routes(_dev(pts), route_cap=CAP, host=True)), want, "host=True")
+    same(host(*m.plan_routes(dev(pts), route_cap=CAP, host=True)), want, "host=True")
     k = int(np.flatnonzero(s["kinds"] == "trav")[3])
     assert m.findRoute(pts[k]) == pm.oracle_route(pts[k]) and len(pm.oracle_route(pts[k])) > 1
     assert m.findRoute(pts[np.flatnonzero(s["kinds"] == "unreached")[0]]) is None
@@ -177,15 +163,15 @@ def test_chunked_launches_give_the_same_bytes():
     assert len(pts) == 64
     # a query's state: 16 bytes a row and 8 a queue entry beyond the LDS tier (include/gndt.h); room for 25 to 29 queries: 3 launches
     one = 16 * pm.n + 8 * pr.shim().planshim_queue_entries(len(pm.slopes))
-    got = host(*m.plan_routes(_dev(pts), route_cap=CAP, scratch_bytes=25 * one))
+    got = host(*m.plan_routes(dev(pts), route_cap=CAP, scratch_bytes=25 * one))
     same(got, (want[0][::25], want[1][::25]), "three launches")
-    got = host(*m.plan_routes(_dev(pts), route_cap=CAP, scratch_bytes=one))
+    got = host(*m.plan_routes(dev(pts), route_cap=CAP, scratch_bytes=one))
     same(got, (want[0][::25], want[1][::25]), "one query a launch")
     import grid_ndt_amd as g
     with pytest.raises(g.GndtError) as e:
-        m.plan_routes(_dev(pts), route_cap=CAP, scratch_bytes=4096)
+        m.plan_routes(dev(pts), route_cap=CAP, scratch_bytes=4096)
     assert e.value.code == 5       # GNDT_ERR_CAPACITY: one query does not fit
-    same(host(*m.plan_routes(_dev(pts), route_cap=CAP)), (want[0][::25], want[1][::25]), "after the refusal")
+    same(host(*m.plan_routes(dev(pts), route_cap=CAP)), (want[0][::25], want[1][::25]), "after the refusal")
 
 
 def test_capped_lds_tier_spills_and_gives_the_same_bytes():
@@ -195,7 +181,7 @@ def test_capped_lds_tier_spills_and_gives_the_same_bytes():
     assert want[1]["queue_peak"].max() > 64
     m.set_debug_option(m.DEBUG_PLAN_LDS_ENTRIES, 64)
     try:
-        got = host(*m.plan_routes(_dev(s["pts"]), route_cap=CAP))
+        got = host(*m.plan_routes(dev(s["pts"]), route_cap=CAP))
     finally:
         m.set_debug_option(m.DEBUG_PLAN_LDS_ENTRIES, 1024)
     same(got, want, "64 entries in LDS")
@@ -213,13 +199,13 @@ def test_truncation_and_the_guard():
     lengths = winfo["length"][::25]
     cap = int(np.sort(lengths)[len(lengths) // 2])                 # half of the routes are longer than this
     assert (lengths > cap).any() and (lengths <= cap).any()
-    rows, info = host(*m.plan_routes(_dev(pts), route_cap=cap))
+    rows, info = host(*m.plan_routes(dev(pts), route_cap=cap))
     same((rows, info), s["pm"].shim_routes(pts, route_cap=cap)[:2], "truncated")
     assert np.array_equal(info["length"], lengths) and np.array_equal(rows, wrows[::25, :cap])
-    rows0, info0 = host(*m.plan_routes(_dev(pts), route_cap=0))
+    rows0, info0 = host(*m.plan_routes(dev(pts), route_cap=0))
     assert rows0.shape == (64, 0) and pr.info_bytes(info0) == pr.info_bytes(winfo[::25])
     few = int(np.median(winfo["expansions"][::25]))
-    got = host(*m.plan_routes(_dev(pts), route_cap=CAP, max_expansions=few))
+    got = host(*m.plan_routes(dev(pts), route_cap=CAP, max_expansions=few))
     want = s["pm"].shim_routes(pts, route_cap=CAP, max_expansions=few)
     same(got, want, "guard")
     assert (got[1]["status"] == pr.LIMIT).any() and (got[1]["status"] == pr.FOUND).any()
@@ -229,22 +215,22 @@ def test_edge_inputs():
     s = scene("site_r025")
     m, pm, pts = s["m"], s["pm"], s["pts"]
     want = shim_answers(s)
-    rows, info = m.plan_routes(_dev(np.zeros((0, 3), np.float32)), route_cap=CAP)
+    rows, info = m.plan_routes(dev(np.zeros((0, 3), np.float32)), route_cap=CAP)
     assert tuple(rows.shape) == (0, CAP) and len(info["status"]) == 0
     rows, info = m.plan_routes(np.zeros((0, 3), np.float32), route_cap=CAP)
     assert rows.shape == (0, CAP)
     pad = np.concatenate([pts, np.full((len(pts), 1), 7.0, np.float32)], 1)
-    same(host(*m.plan_routes(_dev(pad), route_cap=CAP)), want, "stride 16")
+    same(host(*m.plan_routes(dev(pad), route_cap=CAP)), want, "stride 16")
     same(host(*m.plan_routes(pad, route_cap=CAP)), want, "stride 16, host")
     # nearest_slope: the start is gndt_query's answer for the point, whatever its z
     lifted = pts.copy()
     lifted[:, 2] += np.float32(0.4)
-    q = m.query(_dev(lifted), "nearest_slope").cpu().numpy()
-    got = host(*m.plan_routes(_dev(lifted), start_mode="nearest_slope", route_cap=CAP))
+    q = m.query(dev(lifted), "nearest_slope").cpu().numpy()
+    got = host(*m.plan_routes(dev(lifted), start_mode="nearest_slope", route_cap=CAP))
     assert np.array_equal(got[1]["start_row"].view(np.int32), q) and (q >= 0).sum() > 40
     same(got, pm.shim_routes(lifted, mode=pr.NEAREST_SLOPE, route_cap=CAP)[:2], "nearest_slope")
-    node = host(*m.plan_routes(_dev(lifted), route_cap=CAP))
-    qn = m.query(_dev(lifted), "node").cpu().numpy()
+    node = host(*m.plan_routes(dev(lifted), route_cap=CAP))
+    qn = m.query(dev(lifted), "node").cpu().numpy()
     start = np.where((qn >= 0) & ((pm.flags[np.maximum(qn, 0)] & 2) != 0), qn, -1)
     assert np.array_equal(node[1]["start_row"].view(np.int32), start)
 
@@ -252,7 +238,7 @@ def test_edge_inputs():
 def test_repeat_calls_and_streams_give_identical_bytes():
     import torch
     s = scene("site_r06")
-    m, pts = s["m"], _dev(s["pts"])
+    m, pts = s["m"], dev(s["pts"])
     first = host(*m.plan_routes(pts, route_cap=CAP))
     same(host(*m.plan_routes(pts, route_cap=CAP)), first, "second call")
     torch.cuda.synchronize()
@@ -270,7 +256,7 @@ def test_the_call_modifies_nothing():
     s = scene("site_true")
     m = s["m"]
     cells0, cost0 = m.export(), m.cost_export()
-    m.plan_routes(_dev(s["pts"]), route_cap=CAP)
+    m.plan_routes(dev(s["pts"]), route_cap=CAP)
     m.plan_routes(s["pts"], route_cap=8)
     cells1, cost1 = m.export(), m.cost_export()
     for k in FIELDS:
@@ -282,10 +268,10 @@ def test_the_call_modifies_nothing():
 
 def test_no_goal_gives_every_query_no_goal():
     cloud, P = pr.floor_cloud(8), pr.FLOOR_P
-    m = _build(cloud, P)
+    m = build(cloud, P)
     assert m.computeCost((100.0, 100.0, 0.06), pr.FLOOR_ROBOT)["rc"] != 0
     pts = np.float32([[1.25, 1.25, 0.06], [np.nan, 0, 0], [2.25, 1.25, 0.06]])
-    for starts in (_dev(pts), pts):
+    for starts in (dev(pts), pts):
         rows, info = host(*m.plan_routes(starts, route_cap=5))
         assert (info["status"] == pr.NO_GOAL).all() and (info["length"] == 0).all() and (rows == pr.NO_ROW).all()
         assert (info["start_row"] == pr.NO_ROW).all() and (info["cost"] == pr.FLT_MAX).all() and (info["h_start"] == pr.FLT_MAX).all()
@@ -300,8 +286,8 @@ def test_refusals():
     import grid_ndt_amd as g
     from grid_ndt_amd import _lib
     cloud, P = pr.floor_cloud(8), pr.FLOOR_P
-    m = _build(cloud, P)
-    pts = _dev(np.float32([[1.25, 1.25, 0.06], [2.25, 1.25, 0.06]]))
+    m = build(cloud, P)
+    pts = dev(np.float32([[1.25, 1.25, 0.06], [2.25, 1.25, 0.06]]))
 
     def refused(call, code=1):
         with pytest.raises(g.GndtError) as e:
@@ -331,7 +317,7 @@ def test_refusals():
     # a capturing stream
     stream = torch.cuda.Stream()
     with torch.cuda.stream(stream):
-        p2 = _dev(np.float32([[1.25, 1.25, 0.06], [2.25, 1.25, 0.06]]))
+        p2 = dev(np.float32([[1.25, 1.25, 0.06], [2.25, 1.25, 0.06]]))
         stream.wait_stream(torch.cuda.default_stream())
         graph = torch.cuda.CUDAGraph()
         with pytest.raises(g.GndtError) as err:
@@ -343,7 +329,7 @@ def test_refusals():
         assert (host(*m.plan_routes(p2, route_cap=8, stream=stream))[1]["status"] == pr.FOUND).all()
         stream.synchronize()
     # a cost map made stale by an update
-    m.change2DMap("slope", _dev(cloud[1:40, :3] + np.float32([0.0, 0.0, 1.0])))
+    m.change2DMap("slope", dev(cloud[1:40, :3] + np.float32([0.0, 0.0, 1.0])))
     m.sync()
     refused(lambda: m.plan_routes(pts, route_cap=8))
     assert m.computeCost((1.25, 1.25, 0.06), pr.FLOOR_ROBOT)["rc"] == 0

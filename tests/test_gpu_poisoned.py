@@ -33,19 +33,18 @@ communicator and RCCL stay out: poison_malloc synchronises the whole device on e
 
 hipGraph capture and replay are not in the groups: capture refuses allocation, and tools/fuzz_graph.py owns that ground."""
 import ctypes as C
-import json
 import os
 import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import poison_tier
+from tests.poison_tier import ROOT
+from tests.poison_tier import env as _env
 
-if os.environ.get("GNDT_LIB_VARIANT"):
-    pytest.skip("this process runs on a variant of the library itself (a child of this module): no children of its own", allow_module_level=True)
+poison_tier.refuse_under_variant()
 
-BYTES = (0xA5, 0x7F)
 REUSE = "tests/test_gpu_scratch_reuse.py::"
 CLEARANCE = "tests/test_gpu_clearance.py::"
 WALK = "tests/test_gpu_walk.py::"
@@ -176,14 +175,6 @@ GROUPS = {
 }
 
 
-def _env(variant=None):
-    env = dict(os.environ)
-    env.pop("GNDT_LIB_VARIANT", None)
-    if variant:
-        env["GNDT_LIB_VARIANT"] = variant
-    return env
-
-
 # ---- CPU tier --------------------------------------------------------------------------------------------------------------------------
 
 def test_variant_cross_compiles_for_gfx950_and_exports_every_declared_symbol(native_lib):
@@ -254,62 +245,18 @@ def test_the_variant_is_chosen_by_the_environment_in_python_only():
 
 
 def test_every_node_id_of_the_groups_is_collected():
-    ids = [i for grp in GROUPS.values() for i in grp["ids"]]
-    assert len(ids) == len(set(ids))
-    r = subprocess.run([sys.executable, "-m", "pytest", "--collect-only", "-q", "-p", "no:cacheprovider"] + ids, cwd=ROOT, env=_env(),
-                       capture_output=True, text=True, timeout=300)
-    found = {line.strip() for line in r.stdout.splitlines() if "::" in line}
-    missing = [i for i in ids if i not in found]
-    assert r.returncode == 0 and not missing, (missing, r.stdout[-2000:], r.stderr[-2000:])
-    assert len(found) == len(ids), sorted(found - set(ids))
+    poison_tier.ids_collected([i for grp in GROUPS.values() for i in grp["ids"]])
 
 
 def test_the_limits_are_three_times_the_measured_times():
-    for name, grp in GROUPS.items():
-        assert grp["measured_s"] > 0 and grp["limit_s"] == -(-3 * grp["measured_s"] // 10) * 10, name
+    for grp in GROUPS.values():
+        poison_tier.limit_follows_rule(grp["measured_s"], grp["limit_s"])
 
 
 # ---- GPU tier --------------------------------------------------------------------------------------------------------------------------
 
-_stopped = []        # why the tier stopped: a child ended abnormally
-
-
-def _abnormal(returncode, output):
-    if returncode is None:
-        return "killed at its time limit"
-    if returncode < 0:
-        return f"ended by signal {-returncode}"
-    if returncode in (134, 139):
-        return f"ended with status {returncode}"
-    if "illegal memory access" in output:
-        return "reported an illegal memory access"
-    return None
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize("byte", BYTES, ids=["0xA5", "0x7F"])
+@pytest.mark.parametrize("byte", poison_tier.BYTES, ids=poison_tier.BYTE_IDS)
 @pytest.mark.parametrize("group", list(GROUPS))
 def test_group_under_poison(group, byte):
-    from grid_ndt_amd import _lib
-    if _stopped:
-        pytest.fail(f"not started: {_stopped[0]}", pytrace=False)
-    grp = GROUPS[group]
-    _lib.build_native(variant="poison")          # (__graft_entry__.build() has built it: nothing compiles inside the child's limit)
-    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + grp["ids"]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, env=_env("poison"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=grp["limit_s"])
-        returncode, output = r.returncode, r.stdout
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout or ""
-        returncode, output = None, out.decode(errors="replace") if isinstance(out, bytes) else out
-    print(output[-6000:])
-    why = _abnormal(returncode, output)
-    if why:
-        _stopped.append(f"the child of {group} under {byte:#x} {why}")
-        pytest.fail(_stopped[0] + "\n" + output[-3000:], pytrace=False)
-    lines = [line for line in output.splitlines() if line.startswith('{"poisoned_child"')]
-    assert returncode == 0 and len(lines) == 1, (returncode, output[-3000:])
-    rep = json.loads(lines[0])
-    assert rep["exit"] == 0 and rep["byte"] == byte
-    assert rep["device_bytes"] > 0 and rep["host_bytes"] > 0, rep
-    assert rep["lib"] == _lib.lib_path("poison")
+    poison_tier.run_group(group, GROUPS[group]["ids"], GROUPS[group]["limit_s"], byte)

@@ -7,24 +7,13 @@ import pytest
 
 from grid_ndt_amd import scenes
 from tests import query_ref as qr
+from tests.gpu_kit import dev, handle
 
 pytestmark = pytest.mark.gpu
 
 ATOMIC, PARTITION, EXACT, TWO_LEVEL, TILE, AUTO = 1, 2, 3, 4, 5, 0
 TERRAIN = scenes.TERRAIN_PARAMS
 FACE = dict(grid_len=0.5, z_len=0.25, slope_interval=0.08, demand="slope")
-
-
-def _handle(P, strategy=AUTO, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def _scene(name):
@@ -53,9 +42,9 @@ def _assert_rows_are_the_builds(m, pts, rows, origin, P, first=True):
 @pytest.mark.parametrize("name", ["bridge_ground", "campus", "terrain", "face_lattice"])
 def test_node_query_of_every_built_point_is_its_node(name, strategy):
     cloud, P = _scene(name)
-    m = _handle(P, strategy)
+    m = handle(P, strategy)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     rows = m.query(t)
     _assert_rows_are_the_builds(m, cloud[1:], rows, cloud[0], P)
@@ -70,9 +59,9 @@ def test_node_query_after_blocked_buckets():
     the query, keying with the IEEE divide, names the same nodes"""
     P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
     cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     for _ in range(2):
         m.create2DMap("slope", t)
         m.sync()
@@ -83,18 +72,18 @@ def test_node_query_after_blocked_buckets():
 @pytest.mark.parametrize("deferred", [False, True])
 def test_node_query_after_updates_and_removal(deferred):
     cloud, P = scenes.terrain_cloud(240_000), TERRAIN
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
     if deferred:
         m.set_deferred_emit(True)
     cuts = [1, 90_000, 170_000, cloud.shape[0]]
     for a, b in zip(cuts[:-1], cuts[1:]):
-        m.change2DMap("slope", _dev(cloud[a:b]))
-        got = m.query(_dev(cloud[1:b]))
+        m.change2DMap("slope", dev(cloud[a:b]))
+        got = m.query(dev(cloud[1:b]))
         _assert_rows_are_the_builds(m, cloud[1:b], got, cloud[0], P, first=False)
     # the last batch leaves again: the rest still finds its nodes, and nothing names a row beyond the map
-    m.del2DMap("slope", _dev(cloud[170_000:]))
-    _assert_rows_are_the_builds(m, cloud[1:170_000], m.query(_dev(cloud[1:170_000])), cloud[0], P, first=False)
+    m.del2DMap("slope", dev(cloud[170_000:]))
+    _assert_rows_are_the_builds(m, cloud[1:170_000], m.query(dev(cloud[1:170_000])), cloud[0], P, first=False)
 
 
 def test_index_follows_the_map_from_build_to_build():
@@ -104,28 +93,28 @@ def test_index_follows_the_map_from_build_to_build():
     b[1:, :2] += np.float32(3.7)                     # another map, same origin
     b[0] = a[0]
     for strategy in (AUTO, ATOMIC):
-        m = _handle(P, strategy)
+        m = handle(P, strategy)
         m.setCloudFirst(a[0])
-        m.create2DMap("slope", _dev(a[1:]))
-        _assert_rows_are_the_builds(m, a[1:], m.query(_dev(a[1:])), a[0], P)
-        m.create2DMap("slope", _dev(b[1:]))
-        _assert_rows_are_the_builds(m, b[1:], m.query(_dev(b[1:])), a[0], P)
+        m.create2DMap("slope", dev(a[1:]))
+        _assert_rows_are_the_builds(m, a[1:], m.query(dev(a[1:])), a[0], P)
+        m.create2DMap("slope", dev(b[1:]))
+        _assert_rows_are_the_builds(m, b[1:], m.query(dev(b[1:])), a[0], P)
     # ... and an update in place of B
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(a[0])
-    m.change2DMap("slope", _dev(a[1:]))
-    _assert_rows_are_the_builds(m, a[1:], m.query(_dev(a[1:])), a[0], P, first=False)
-    m.change2DMap("slope", _dev(b[1:]))
+    m.change2DMap("slope", dev(a[1:]))
+    _assert_rows_are_the_builds(m, a[1:], m.query(dev(a[1:])), a[0], P, first=False)
+    m.change2DMap("slope", dev(b[1:]))
     both = np.concatenate([a[1:], b[1:]])
-    _assert_rows_are_the_builds(m, both, m.query(_dev(both)), a[0], P, first=False)
+    _assert_rows_are_the_builds(m, both, m.query(dev(both)), a[0], P, first=False)
 
 
 @pytest.mark.parametrize("name", ["bridge_ground", "terrain", "face_lattice"])
 def test_nearest_slope_matches_a_brute_force_over_the_rows(name):
     cloud, P = _scene(name)
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     cells = m.export()
     body = cloud[1:]
     lo, hi = body.min(0), body.max(0)
@@ -134,7 +123,7 @@ def test_nearest_slope_matches_a_brute_force_over_the_rows(name):
     pts[:1000, 2] = rng.uniform(-1e4, 1e4, size=1000).astype(np.float32)            # z far from every slope
     pts = np.concatenate([pts, body[:50_000], qr.odd_points(cloud[0], P["grid_len"], P["z_len"], (float(lo.min()), float(hi.max())))])
     want = qr.nearest_slope_rows(cells, pts, cloud[0], P["grid_len"], P["z_len"])
-    got = m.query(_dev(pts), "nearest_slope").cpu().numpy()
+    got = m.query(dev(pts), "nearest_slope").cpu().numpy()
     assert (got == want).all(), np.flatnonzero(got != want)[:10]
     assert (want >= 0).mean() > 0.1 and (want == qr.NO_ROW).any()
     assert (m.query(pts, "nearest_slope") == want).all()
@@ -143,9 +132,9 @@ def test_nearest_slope_matches_a_brute_force_over_the_rows(name):
 def test_cost_gather_is_cost_export_at_the_rows():
     import grid_ndt_amd as g
     cloud, P = scenes.bridge_ground(), scenes.BRIDGE_PARAMS
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     with pytest.raises(g.GndtError) as e:           # no cost map yet
         m.query(t, cost=True)
@@ -157,7 +146,7 @@ def test_cost_gather_is_cost_export_at_the_rows():
     pts = np.concatenate([cloud[1:], rng.uniform(lo - 2, hi + 2, size=(50_000, 3)).astype(np.float32),
                           np.float32([[np.nan, 0, 0], [1e9, 1e9, 0]])])
     for mode in ("node", "nearest_slope"):
-        rows, h, st = (x.cpu().numpy() for x in m.query(_dev(pts), mode, cost=True))
+        rows, h, st = (x.cpu().numpy() for x in m.query(dev(pts), mode, cost=True))
         hit = rows >= 0
         assert hit.any() and (~hit).any()
         assert (h[hit].view(np.uint32) == ce["h"][rows[hit]].view(np.uint32)).all()
@@ -176,12 +165,12 @@ def test_edge_cases():
     import torch
     import grid_ndt_amd as g
     cloud, P = scenes.campus_frame(100_000), scenes.CAMPUS_PARAMS
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
     with pytest.raises(g.GndtError) as e:            # no build yet
-        m.query(_dev(cloud[1:10]))
+        m.query(dev(cloud[1:10]))
     assert e.value.code == 1
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     assert m.query(t[:0]).shape == (0,) and m.query(cloud[1:1]).shape == (0,)      # n = 0
     t4 = torch.cat([t, torch.full((t.shape[0], 1), 5.0, device=t.device)], 1).contiguous()
@@ -193,7 +182,7 @@ def test_edge_cases():
             m.query(t, bad)
         assert e.value.code == 1
     # an empty map: every answer is "no row"
-    e0 = _handle(P)
+    e0 = handle(P)
     e0.setCloudFirst(cloud[0])
     e0.create2DMap("slope", np.zeros((0, 3), np.float32))
     assert e0.sync()[0] == 0
@@ -207,9 +196,9 @@ def test_full_size_s2_query_of_its_ten_million_points(hint):
     """The bench workload (10 M uniform points, 0.5 m cells), built with and without max_nodes_hint, then all its points queried"""
     cloud = scenes.uniform_box(10_000_001)
     P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
-    m = _handle(P, max_nodes_hint=hint)
+    m = handle(P, max_nodes_hint=hint)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     n = m.sync()[0]
     rows = m.query(t).cpu().numpy().astype(np.int64)

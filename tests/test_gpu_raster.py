@@ -11,6 +11,7 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import query_ref as qr
 from tests import raster_ref as rr
+from tests.gpu_kit import dev, handle, stream_arg, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +19,6 @@ ATOMIC, PARTITION, EXACT, TWO_LEVEL, TILE, AUTO = 1, 2, 3, 4, 5, 0
 TERRAIN = scenes.TERRAIN_PARAMS
 MAP_LAYERS = ("row", "z", "rough", "nodes")
 ERR_INVALID = 1
-
-
-def _handle(P, strategy=AUTO, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
 
 
 def _box_of(cells):
@@ -52,7 +37,7 @@ def _assert_raster(m, cells, box, layers=MAP_LAYERS, host=False):
             got = m.raster(box, mode, z_ref, layers=layers, host=host)
             want = rr.raster(cells, box, mode, 0.0 if z_ref is None else z_ref)
             for k in layers:
-                assert rr.same(_np(got[k]), want[k]), (box, mode, z_ref, k)
+                assert rr.same(to_np(got[k]), want[k]), (box, mode, z_ref, k)
 
 
 def _path(name):
@@ -62,10 +47,10 @@ def _path(name):
         P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08) if name == "partition_one_level" else TERRAIN
         cloud = scenes.uniform_box(300_001, half_xy=20.0) if name == "partition_one_level" else scenes.terrain_cloud(300_000)
         strategy = {"atomic": ATOMIC, "partition_one_level": PARTITION, "exact": EXACT, "two_level": TWO_LEVEL, "auto": AUTO}[name]
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(P, strategy)
+            m = handle(P, strategy)
             m.setCloudFirst(cloud[0])
             m.create2DMap("slope", t)
             m.sync()
@@ -75,10 +60,10 @@ def _path(name):
         return make
     if name == "tile":
         cloud, P = scenes.depth_frame(), scenes.DEPTH_PARAMS
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(P, TILE)
+            m = handle(P, TILE)
             m.setCloudFirst(cloud[0])
             m.create2DMap("slope", t)
             assert m.STRATEGY_NAMES[m.last_strategy()] == "tile"
@@ -87,10 +72,10 @@ def _path(name):
     if name == "blocked":
         P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
         cloud = scenes.uniform_box(2_500_001, half_xy=50.0)
-        t = _dev(cloud[1:])
+        t = dev(cloud[1:])
 
         def make():
-            m = _handle(P)
+            m = handle(P)
             m.setCloudFirst(cloud[0])
             for _ in range(2):
                 m.create2DMap("slope", t)
@@ -102,14 +87,14 @@ def _path(name):
     cuts = [1, 90_000, 170_000, cloud.shape[0]]
 
     def make():
-        m = _handle(TERRAIN, ATOMIC)
+        m = handle(TERRAIN, ATOMIC)
         m.setCloudFirst(cloud[0])
         if name == "deferred":
             m.set_deferred_emit(True)
         for a, b in zip(cuts[:-1], cuts[1:]):
-            m.change2DMap("slope", _dev(cloud[a:b]))
+            m.change2DMap("slope", dev(cloud[a:b]))
         if name == "removed":
-            m.del2DMap("slope", _dev(cloud[170_000:]))
+            m.del2DMap("slope", dev(cloud[170_000:]))
         if name == "cropped":
             c = m.export()
             x0, x1, y0, y1 = _box_of(c)
@@ -132,9 +117,9 @@ def test_raster_is_the_restatement_on_every_path(name):
 
 def _bridge():
     cloud = scenes.bridge_ground()
-    m = _handle(scenes.BRIDGE_PARAMS)
+    m = handle(scenes.BRIDGE_PARAMS)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     return m, cloud
 
 
@@ -149,16 +134,16 @@ def test_bridge_lowest_and_highest_differ_on_exactly_the_multi_slope_columns():
     count = np.zeros((ys.size, xs.size), np.int64)
     np.add.at(count, (np.searchsorted(ys, cells["sy"][slope]), np.searchsorted(xs, cells["sx"][slope])), 1)
     multi = count > 1
-    assert int((_np(lo["nodes"]) > 0).sum()) == 9600 and multi.sum() == 5076
-    assert ((_np(lo["row"]) != _np(hi["row"])) == multi).all()
+    assert int((to_np(lo["nodes"]) > 0).sum()) == 9600 and multi.sum() == 5076
+    assert ((to_np(lo["row"]) != to_np(hi["row"])) == multi).all()
     near = m.raster(box, "nearest_z", 3.0, layers=MAP_LAYERS)          # the deck's height (scenes.bridge_ground)
-    deck = multi & (np.abs(_np(hi["z"]) - np.float32(3.0)) < np.float32(0.05))
-    assert deck.sum() > 1000 and (np.abs(_np(near["z"])[deck] - np.float32(3.0)) < np.float32(0.05)).all()
+    deck = multi & (np.abs(to_np(hi["z"]) - np.float32(3.0)) < np.float32(0.05))
+    assert deck.sum() > 1000 and (np.abs(to_np(near["z"])[deck] - np.float32(3.0)) < np.float32(0.05)).all()
     for mode in ("lowest", "highest", "nearest_z"):
         want = rr.raster(cells, box, mode, 3.0)
         got = {"lowest": lo, "highest": hi, "nearest_z": near}[mode]
         for k in MAP_LAYERS:
-            assert rr.same(_np(got[k]), want[k]), (mode, k)
+            assert rr.same(to_np(got[k]), want[k]), (mode, k)
 
 
 def test_nearest_z_is_the_nearest_slope_query_at_the_pixel_centres():
@@ -179,16 +164,16 @@ def test_nearest_z_is_the_nearest_slope_query_at_the_pixel_centres():
         assert ok.all() and (sx.reshape(H, W) == rr.axis(box[0], box[1])[None, :]).all()
         assert (sy.reshape(H, W) == rr.axis(box[2], box[3])[:, None]).all()
         q = m.query(torch.from_numpy(pts).cuda(), "nearest_slope")
-        assert (_np(q).reshape(H, W) == _np(r["row"])).all()
+        assert (to_np(q).reshape(H, W) == to_np(r["row"])).all()
 
 
 def test_cost_layers_are_the_cost_map_at_the_rows_and_refused_after_an_update():
     import grid_ndt_amd as g
     CP = scenes.COST_PARAMS
     site = scenes.drivable_site(200_000)
-    m = _handle(CP, ATOMIC)
+    m = handle(CP, ATOMIC)
     m.setCloudFirst(site[0])
-    m.create2DMap("slope", _dev(site[1:]))
+    m.create2DMap("slope", dev(site[1:]))
     m.computeCost(scenes.DRIVABLE_GOAL)
     cells = m.export()
     cost = m.cost_export()
@@ -196,14 +181,14 @@ def test_cost_layers_are_the_cost_map_at_the_rows_and_refused_after_an_update():
     for mode in ("lowest", "highest", "nearest_z"):
         for host in (False, True):
             got = m.raster(box, mode, 0.3, layers=("row", "h", "state"), host=host)
-            row = _np(got["row"]).astype(np.int64)
+            row = to_np(got["row"]).astype(np.int64)
             hit = row >= 0
             assert hit.any() and (~hit).any()
-            h, st = _np(got["h"]), _np(got["state"])
+            h, st = to_np(got["h"]), to_np(got["state"])
             assert np.array_equal(h[hit].view(np.uint32), cost["h"][row[hit]].view(np.uint32))
             assert (st[hit] == cost["state"][row[hit]]).all()
             assert (h[~hit] == rr.FLT_MAX).all() and (st[~hit] == 0).all()
-    m.change2DMap("slope", _dev(site[1:1000]))
+    m.change2DMap("slope", dev(site[1:1000]))
     for layers in (("row", "h"), ("state",)):
         with pytest.raises(g.GndtError) as e:
             m.raster(box, "lowest", layers=layers)
@@ -219,7 +204,7 @@ def test_host_variant_equals_device_variant():
         d = m.raster(box, mode, z, layers=MAP_LAYERS)
         h = m.raster(box, mode, z, layers=MAP_LAYERS, host=True)
         for k in MAP_LAYERS:
-            assert isinstance(h[k], np.ndarray) and rr.same(h[k], _np(d[k])), (mode, k)
+            assert isinstance(h[k], np.ndarray) and rr.same(h[k], to_np(d[k])), (mode, k)
         assert (h["x0"], h["y0"], h["res"]) == (d["x0"], d["y0"], d["res"])
     # a smaller raster after a larger one reuses the scratch; a larger one grows it
     small = (box[0], box[0] + 3, box[2], box[2] + 2)
@@ -234,17 +219,17 @@ def test_edge_boxes():
     big = (x0 - 13, x1 + 9, y0 - 5, y1 + 11)
     _assert_raster(m, cells, big)
     r = m.raster(big, "lowest", layers=("row", "nodes"))
-    row, nodes = _np(r["row"]), _np(r["nodes"])
+    row, nodes = to_np(r["row"]), to_np(r["nodes"])
     assert (row[:5] == -1).all() and (nodes[:5] == 0).all() and (row[:, -9:] == -1).all()
     # outside the map: every pixel empty, no error
     out = m.raster((x1 + 100, x1 + 140, y0, y0 + 10), "highest", layers=MAP_LAYERS)
-    assert (_np(out["row"]) == -1).all() and (_np(out["nodes"]) == 0).all() and np.isnan(_np(out["z"])).all()
+    assert (to_np(out["row"]) == -1).all() and (to_np(out["nodes"]) == 0).all() and np.isnan(to_np(out["z"])).all()
     # one pixel
     sl = np.flatnonzero(cells["flags"] & 2)
     r0 = int(sl[len(sl) // 7])
     one = (int(cells["sx"][r0]),) * 2 + (int(cells["sy"][r0]),) * 2
     p = m.raster(one, "nearest_z", float(cells["mean"][r0, 2]), layers=MAP_LAYERS)
-    assert _np(p["row"]).shape == (1, 1) and int(_np(p["row"])[0, 0]) == r0
+    assert to_np(p["row"]).shape == (1, 1) and int(to_np(p["row"])[0, 0]) == r0
     _assert_raster(m, cells, one)
     # touching 0: (0, 3) is the columns 1..3
     _assert_raster(m, cells, (0, 3, -2, 0))
@@ -266,7 +251,7 @@ def _raw(m, box, mode=0, z_ref=0.0, layers=None, stream=None, host=False):
     b = None if box is None else C.byref(CropBox(*box))
     if host:
         return m._L.gndt_raster(m._h, b, mode, z_ref, C.byref(L))
-    s = C.c_void_p(0 if stream is None else (stream.cuda_stream or 1))
+    s = stream_arg(stream)
     rc = m._L.gndt_raster_device(m._h, b, mode, z_ref, C.byref(L), s)
     torch.cuda.synchronize()
     return rc
@@ -296,7 +281,7 @@ def test_refused_arguments():
     assert m._L.gndt_raster_device(None, None, 0, 0.0, None, None) == ERR_INVALID
     assert m._L.gndt_raster(None, None, 0, 0.0, None) == ERR_INVALID
     # no finished build
-    e = _handle(TERRAIN)
+    e = handle(TERRAIN)
     e.setCloudFirst((0.0, 0.0, 0.0))
     with pytest.raises(g.GndtError) as err:
         e.raster((1, 2, 1, 2))
@@ -322,9 +307,9 @@ def test_refused_arguments():
 def test_raster_right_after_a_build_sees_that_build():
     """no sync between the build and the raster: the raster finishes the build first (and its index follows every new build)"""
     cloud = scenes.terrain_cloud(300_000)
-    t1, t2 = _dev(cloud[1:150_000]), _dev(cloud[1:])
+    t1, t2 = dev(cloud[1:150_000]), dev(cloud[1:])
     for strategy in (PARTITION, ATOMIC):
-        m = _handle(TERRAIN, strategy)
+        m = handle(TERRAIN, strategy)
         m.setCloudFirst(cloud[0])
         m.create2DMap("slope", t1)
         m.sync()
@@ -335,7 +320,7 @@ def test_raster_right_after_a_build_sees_that_build():
             cells = m.export()
             want = rr.raster(cells, box, "highest")
             for k in MAP_LAYERS:
-                assert rr.same(_np(got[k]), want[k]), (strategy, k)
+                assert rr.same(to_np(got[k]), want[k]), (strategy, k)
 
 
 def test_s2_full_box():
@@ -343,9 +328,9 @@ def test_s2_full_box():
     lattice), every mode, every map layer"""
     cloud = scenes.uniform_box(10_000_001)
     P = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08)
-    m = _handle(P, max_nodes_hint=1 << 20)
+    m = handle(P, max_nodes_hint=1 << 20)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     cells = m.export()
     box = _box_of(cells)
     W, H = len(rr.axis(box[0], box[1])), len(rr.axis(box[2], box[3]))

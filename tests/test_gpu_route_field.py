@@ -6,7 +6,6 @@ two storeys, the site with the frontiers' goals and against the planner, lattice
 descent at the wavefront's and the grid's edges of K and under its guards, routes straight into shortcut_routes, repeat calls, streams,
 crop and update, scratch reuse, the Python interface and every refused argument.  No tolerance anywhere but in the comparison with the
 planner, whose bound is the rounding of two sums of the same terms in opposite orders."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -17,6 +16,8 @@ from tests import clearance_ref as cr
 from tests import frontier_ref as fr
 from tests import obstacle_ref as ob
 from tests import route_field_ref as rr
+from tests.gpu_kit import Padded, PaddedCall, build, debug_option, dev, robot_arg, to_np
+from tests.gpu_kit import tails_untouched as untouched
 
 pytestmark = pytest.mark.gpu
 
@@ -31,64 +32,28 @@ def _tgc():
     return tgc
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
-@contextlib.contextmanager
 def one_workgroup(on):
     """gndt_debug_set_option(GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP, .) for a block; the default comes back whatever happens in it"""
-    import grid_ndt_amd as g
-    g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_ROUTE_FIELD_ONE_WORKGROUP, 1 if on else 0)
-    try:
-        yield
-    finally:
-        g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_ROUTE_FIELD_ONE_WORKGROUP, 1)
+    return debug_option("DEBUG_ROUTE_FIELD_ONE_WORKGROUP", 1 if on else 0, 1)
 
 
 def raw(m, goals, goal_costs=None, hops=None, robot=None, outs=("cost", "next"), stream=None, host=False, reserved=(0, 0), counts=True, G=None,
         checks=0, min_hops=0, soft_hops=0, soft_weight=0.0, max_cost=0.0, max_rounds=0):
     """The C entry points, every output num_nodes + PAD entries of sentinel -> (rc, dict(cost, next: the outputs asked for, cut to
     num_nodes; counts; tails: what lies behind num_nodes))"""
-    import torch
     from grid_ndt_amd._lib import RouteFieldParams
     n = int(m.sync()[0])
     prm = RouteFieldParams(checks, min_hops, soft_hops, soft_weight, max_cost, max_rounds, (C.c_uint32 * 2)(*reserved))
     g = np.ascontiguousarray(np.asarray(goals).astype(np.int64) & 0xFFFFFFFF, np.uint32)
     gc = None if goal_costs is None else np.ascontiguousarray(goal_costs, np.float32)
     hp = None if hops is None else np.ascontiguousarray(hops, np.uint32)
-    G = len(g) if G is None else G
-    buf = {k: np.full(n + PAD, SENTINEL, np.uint32) for k in outs}
-    cnt = np.full(8, SENTINEL, np.uint32)
-    if host:
-        ins = [g, gc, hp]
-        ptr = lambda a: C.c_void_p(a.ctypes.data if a is not None and a.size else 0)
-    else:
-        ins = [None if a is None else torch.from_numpy(a.view(np.int32)).cuda() for a in (g, gc, hp)]
-        buf = {k: torch.from_numpy(a.view(np.int32)).cuda() for k, a in buf.items()}
-        cnt = torch.from_numpy(cnt.view(np.int32)).cuda()
-        ptr = lambda a: C.c_void_p(a.data_ptr() if a is not None and a.numel() else 0)
-    args = [m._h, _tgc()._robot(robot), C.byref(prm), ptr(ins[0]), G, ptr(ins[1]), ptr(ins[2])] + \
-           [ptr(buf[k]) if k in buf else None for k in ("cost", "next")] + [ptr(cnt) if counts else None]
-    if host:
-        rc = m._L.gndt_route_field(*args)
-    else:
-        rc = m._L.gndt_route_field_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        buf = {k: t.cpu().numpy().view(np.uint32) for k, t in buf.items()}
-        cnt = cnt.cpu().numpy().view(np.uint32)
-    out = {k: a[:n] for k, a in buf.items()}
-    out.update(counts=cnt, tails={k: a[n:] for k, a in buf.items()})
+    buf = {k: Padded(n, back=PAD, fill=SENTINEL) for k in outs}
+    cnt = Padded(8, fill=SENTINEL)
+    rc = PaddedCall(host, stream)(m._L.gndt_route_field, m._L.gndt_route_field_device, m._h, robot_arg(robot, cr.ROBOT), C.byref(prm), g,
+                                  len(g) if G is None else G, gc, hp, buf.get("cost"), buf.get("next"), cnt if counts else None)
+    out = {k: p.body for k, p in buf.items()}
+    out.update(counts=cnt.a, tails={k: p.tail for k, p in buf.items()})
     return rc, out
-
-
-def untouched(got):
-    return all((t == SENTINEL).all() for t in got["tails"].values())
 
 
 def check(m, r, goals, goal_costs=None, what="", **kw):
@@ -123,31 +88,17 @@ def row_at(cells, sx, sy, top=False):
 
 def raw_descend(m, starts, cost, nxt, route_cap, max_steps=0, start_mode=0, stream=None, host=False, reserved=(0,) * 6, stride=12):
     """the C entry points with sentinel behind rows and info -> (rc, rows [K, cap], info [K, 8] uint32, untouched)"""
-    import torch
     from grid_ndt_amd._lib import DescendParams
     prm = DescendParams(start_mode, max_steps, (C.c_uint32 * 6)(*reserved))
     s = np.ascontiguousarray(starts, np.float32)
     if stride == 16:
         s = np.ascontiguousarray(np.concatenate([s[:, :3], np.full((len(s), 1), 7.0, np.float32)], 1))
     K = len(s)
-    rows = np.full(K * route_cap + PAD, SENTINEL, np.uint32)
-    info = np.full((K + 1) * 8, SENTINEL, np.uint32)
-    c, x = np.ascontiguousarray(cost, np.float32), np.ascontiguousarray(nxt, np.uint32)
-    if host:
-        ptr = lambda a: C.c_void_p(a.ctypes.data)
-        arrs = [s, c, x, rows, info]
-    else:
-        arrs = [torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda() for a in (s, c, x, rows, info)]
-        ptr = lambda a: C.c_void_p(a.data_ptr())
-    args = [m._h, ptr(arrs[0]), K, stride, C.byref(prm), ptr(arrs[1]), ptr(arrs[2]), ptr(arrs[3]) if route_cap else None, route_cap, ptr(arrs[4])]
-    if host:
-        rc = m._L.gndt_descend_routes(*args)
-    else:
-        rc = m._L.gndt_descend_routes_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        rows, info = (a.cpu().numpy().view(np.uint32) for a in arrs[3:])
-    ok = (rows[K * route_cap:] == SENTINEL).all() and (info[8 * K:] == SENTINEL).all()
-    return rc, rows[:K * route_cap].reshape(K, route_cap), info[:8 * K].reshape(K, 8), ok
+    rows, info = Padded(K * route_cap, back=PAD, fill=SENTINEL), Padded(K, words=8, back=1, fill=SENTINEL)
+    rc = PaddedCall(host, stream)(m._L.gndt_descend_routes, m._L.gndt_descend_routes_device, m._h, s, K, stride, C.byref(prm),
+                                  np.ascontiguousarray(cost, np.float32), np.ascontiguousarray(nxt, np.uint32), rows if route_cap else None, route_cap,
+                                  info)
+    return rc, rows.body.reshape(K, route_cap), info.body.reshape(K, 8), rows.untouched() and info.untouched()
 
 
 def check_descend(m, cells, r, start_rows, route_cap, max_steps=0, cost=None, nxt=None, what="", **kw):
@@ -177,7 +128,7 @@ def corridor():
 def box_hops(m, f, cells, box):
     """obstacle_field's hops for one box, asserted against tests/obstacle_ref.py first"""
     got = m.obstacle_field(np.int32([box]), max_hops=8, levels_above=0)
-    hops = _np(got["hops"]).view(np.uint32)
+    hops = to_np(got["hops"]).view(np.uint32)
     assert np.array_equal(hops, ob.field(f, cells, [box], max_hops=8)["hops"])
     return hops
 
@@ -254,7 +205,7 @@ def test_site_the_frontiers_goals_and_the_planner_on_the_same_map():
     assert rr.LDS_ROWS >= n > 16000                            # the one-workgroup kernel holds the site
     assert m.computeCost(scenes.DRIVABLE_GOAL)["rc"] == 0
     fro = m.frontiers()
-    goals = _np(fro["best_row"]).astype(np.int64)
+    goals = to_np(fro["best_row"]).astype(np.int64)
     assert len(goals) >= 3
     gc = np.linspace(0.0, 2.0, len(goals)).astype(np.float32)
     r = rr.Route(f, cells, goals, gc)
@@ -265,7 +216,7 @@ def test_site_the_frontiers_goals_and_the_planner_on_the_same_map():
     both_paths(m, rh, goals, gc, hops=hops, min_hops=1, soft_hops=3, soft_weight=0.5, checks=OVERHEAD, what="frontiers, hops")
     assert int(rh.counts[2]) < int(r.counts[2])
     # one goal, the flood's: every planned route along the field's edges costs at least what the field says, up to two sums' rounding
-    goal = int(_np(m.query(np.float32([scenes.DRIVABLE_GOAL]), "node"))[0])
+    goal = int(to_np(m.query(np.float32([scenes.DRIVABLE_GOAL]), "node"))[0])
     one = rr.Route(f, cells, [goal])
     got = both_paths(m, one, [goal], what="one goal")
     rng = np.random.default_rng(5)
@@ -379,15 +330,15 @@ def test_routes_go_straight_into_shortcut_routes():
     hops = box_hops(m, f, cells, [1, 6, 6, 6, 1, 1])
     starts = np.array([row_at(cells, sx, sy) for sx in range(1, 8) for sy in (12, 9, 7)])
     for host in (False, True):
-        fld = m.route_field(np.int32([goal]) if host else _dev([goal], np.int32), hops=hops, min_hops=1, host=host)
+        fld = m.route_field(np.int32([goal]) if host else dev([goal], np.int32), hops=hops, min_hops=1, host=host)
         pts = cells["mean"][starts]
-        rows, info = m.descend_routes(pts if host else _dev(pts), fld, route_cap=40, host=host)
+        rows, info = m.descend_routes(pts if host else dev(pts), fld, route_cap=40, host=host)
         got = m.shortcut_routes((rows, info), hops=hops, min_hops=1, host=host)
         torch.cuda.synchronize()
-        assert (_np(info["status"]) == rr.FOUND).all() and (_np(got["status"]) == 0).all()         # SHORTCUT_STATUS ok: never bad_route
-        way = _np(got["waypoint_rows"])
+        assert (to_np(info["status"]) == rr.FOUND).all() and (to_np(got["status"]) == 0).all()         # SHORTCUT_STATUS ok: never bad_route
+        way = to_np(got["waypoint_rows"])
         for k in range(len(starts)):
-            w = way[k][:int(_np(got["waypoints"])[k])]
+            w = way[k][:int(to_np(got["waypoints"])[k])]
             assert len(w) >= 2 and w[0] == starts[k] and w[-1] == goal and (hops[w] >= 1).all()
         xyz = m.route_waypoints(rows)
         assert tuple(xyz.shape) == (len(starts), 40, 3)
@@ -430,7 +381,7 @@ def test_repeat_calls_a_side_stream_and_a_larger_call_first():
 def test_first_builder_of_the_index_after_a_crop_and_after_an_update():
     cloud = scenes.drivable_site(200_000)
     for on in (True, False):
-        m = _tgc()._build(cloud, scenes.COST_PARAMS, 1)
+        m = build(cloud, scenes.COST_PARAMS, 1)
 
         def fresh(what):
             cells = m.export()
@@ -448,7 +399,7 @@ def test_first_builder_of_the_index_after_a_crop_and_after_an_update():
         x0, x1 = int(cells["sx"].min()), int(cells["sx"].max())
         m.crop_box((x0 + 5, x1 - 5, -1000, 1000), "keep_inside")
         assert fresh("crop")["num_nodes"] < cells["num_nodes"]
-        m.change2DMap("slope", _dev(cloud[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
+        m.change2DMap("slope", dev(cloud[1:1000, :3] + np.float32([0.0, 0.0, 0.02])))
         fresh("update")
         # everything cropped away: zero counts but "converged", nothing else written
         m.crop_box((x1 + 50, x1 + 60, 1, 2), "keep_inside")
@@ -456,10 +407,10 @@ def test_first_builder_of_the_index_after_a_crop_and_after_an_update():
         for host in (False, True):
             rc, got = raw(m, [0, 1], host=host)
             assert rc == 0 and tuple(got["counts"]) == (0, 0, 0, 0, 1, 0, 0, 0) and untouched(got)
-            fld = m.route_field(np.int32([0]) if host else _dev([0], np.int32), host=host)
+            fld = m.route_field(np.int32([0]) if host else dev([0], np.int32), host=host)
             assert len(fld["cost"]) == 0 and len(fld["next"]) == 0 and int(fld["converged"]) == 1
-            rows, info = m.descend_routes(np.zeros((2, 3), np.float32) if host else _dev(np.zeros((2, 3))), fld, route_cap=4, host=host)
-            assert (_np(info["status"]) == rr.NO_START).all() and (_np(rows) == -1).all()
+            rows, info = m.descend_routes(np.zeros((2, 3), np.float32) if host else dev(np.zeros((2, 3))), fld, route_cap=4, host=host)
+            assert (to_np(info["status"]) == rr.NO_START).all() and (to_np(rows) == -1).all()
 
 
 def test_outputs_are_optional_no_goals_and_out_of_sweeps():
@@ -513,7 +464,7 @@ def test_refused_arguments():
     # device pointers: alignment, NULL fields, rows without a cap
     from grid_ndt_amd._lib import DescendParams, RouteFieldParams
     prm, dp = RouteFieldParams(), DescendParams()
-    g = _dev(goal, np.int32)
+    g = dev(goal, np.int32)
     cost, nxt, cnt = (torch.zeros(n + 4, dtype=torch.int32, device="cuda") for _ in range(3))
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     L = m._L
@@ -524,7 +475,7 @@ def test_refused_arguments():
         assert L.gndt_route_field_device(m._h, None, C.byref(prm), *args, None) == ERR_INVALID
     assert L.gndt_route_field_device(m._h, None, None, p(g), 1, None, None, p(cost), p(nxt), p(cnt), None) == ERR_INVALID
     assert L.gndt_route_field_device(None, None, C.byref(prm), p(g), 1, None, None, p(cost), p(nxt), p(cnt), None) == ERR_INVALID
-    s = _dev(cells["mean"][:2])
+    s = dev(cells["mean"][:2])
     rows, info = torch.zeros(16, dtype=torch.int32, device="cuda"), torch.zeros(32, dtype=torch.int32, device="cuda")
     ok = (p(s), 2, 12, C.byref(dp), p(cost), p(nxt), p(rows), 4, p(info))
     assert L.gndt_descend_routes_device(m._h, *ok, None) == 0
@@ -559,28 +510,28 @@ def test_python_interface_rows_points_numpy_torch_and_streams():
     s = torch.cuda.Stream()
     kw = dict(hops=dict(hops=hops), min_hops=1, soft_hops=2, soft_weight=0.5, overhead=True, max_cost=20.0)
     pts = cells["mean"][[goal, 10]]
-    for goals, extra in ((np.int32([goal, 10]), dict(host=True)), (_dev([goal, 10], np.int32), dict()), (pts, dict(host=True)),
-                         (_dev(pts), dict(stream=s)), (_dev(pts), dict(max_rounds=4096))):
-        gc = np.float32([0.0, 1.0]) if extra.get("host") else _dev([0.0, 1.0])
+    for goals, extra in ((np.int32([goal, 10]), dict(host=True)), (dev([goal, 10], np.int32), dict()), (pts, dict(host=True)),
+                         (dev(pts), dict(stream=s)), (dev(pts), dict(max_rounds=4096))):
+        gc = np.float32([0.0, 1.0]) if extra.get("host") else dev([0.0, 1.0])
         fld = m.route_field(goals, gc, **kw, **extra)
         if "stream" in extra:
             s.synchronize()
         torch.cuda.synchronize()
         assert set(fld) == {"cost", "next", "counts", "converged"} and isinstance(fld["cost"], np.ndarray) == bool(extra.get("host"))
-        assert np.array_equal(rr.bits(_np(fld["cost"])), rr.bits(r.cost)) and np.array_equal(_np(fld["next"]).view(np.uint32), r.next)
-        assert np.array_equal(_np(fld["counts"]).view(np.uint32)[:5], r.counts) and int(fld["converged"]) == 1
-        assert (_np(fld["next"])[r.next == rr.NO_ROW] == m.NO_ROW).all()
+        assert np.array_equal(rr.bits(to_np(fld["cost"])), rr.bits(r.cost)) and np.array_equal(to_np(fld["next"]).view(np.uint32), r.next)
+        assert np.array_equal(to_np(fld["counts"]).view(np.uint32)[:5], r.counts) and int(fld["converged"]) == 1
+        assert (to_np(fld["next"])[r.next == rr.NO_ROW] == m.NO_ROW).all()
     assert set(m.route_field(np.int32([goal]), next=False, host=True)) == {"cost", "counts", "converged"}
     starts = cells["mean"][[0, 40, 100, 155]]
     for host in (False, True):
-        rows, info = m.descend_routes(starts if host else _dev(starts), fld, host=host)
+        rows, info = m.descend_routes(starts if host else dev(starts), fld, host=host)
         torch.cuda.synchronize()
         assert tuple(rows.shape) == (4, 156) and isinstance(rows, np.ndarray) == host
         for k, q in enumerate((0, 40, 100, 155)):
             st, ln, wr, ex, c, hs = rr.descend(r.cost, r.next, q, 156)
-            got = {key: _np(v)[k] for key, v in info.items()}
+            got = {key: to_np(v)[k] for key, v in info.items()}
             assert (got["status"], got["length"], got["start_row"], got["expansions"], got["queue_peak"]) == (st, ln, q, ex, 0)
-            assert rr.bits(got["cost"]) == rr.bits(c) and np.array_equal(_np(rows)[k].view(np.uint32), wr)
+            assert rr.bits(got["cost"]) == rr.bits(c) and np.array_equal(to_np(rows)[k].view(np.uint32), wr)
     with pytest.raises(ValueError):
         m.route_field(np.int32([goal]), hops=hops[:10], host=True)
     with pytest.raises(ValueError):

@@ -16,6 +16,7 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import query_ref as qr
 from tests import score_ref as sr
+from tests.gpu_kit import dev, handle, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -24,22 +25,6 @@ ERR_INVALID = 1
 TERRAIN = scenes.TERRAIN_PARAMS
 FACE = dict(grid_len=0.5, z_len=0.25, slope_interval=0.08, demand="slope")
 BOX = dict(grid_len=0.5, z_len=0.5, slope_interval=0.08, demand="slope")
-
-
-def _handle(P, strategy=AUTO, **kw):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy, **kw)
-    m.setInterval(P["slope_interval"])
-    return m
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-
-
-def _np(out):
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in out.items()}
 
 
 def _scene(name):
@@ -52,9 +37,9 @@ def _scene(name):
 
 def _built(name, strategy=AUTO):
     cloud, P = _scene(name)
-    m = _handle(P, strategy)
+    m = handle(P, strategy)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     return cloud, P, m
 
 
@@ -76,7 +61,7 @@ def _ref(m, cloud, P, scan, poses, nbh, per_point=None, **kw):
 
 def _bits(out):
     """the four sums of a result as integers"""
-    o = _np(out)
+    o = to_np(out)
     return (o["score"].astype(np.float64).view(np.uint64).tolist(), o["d2_sum"].astype(np.float64).view(np.uint64).tolist(),
             o["matched"].tolist(), o["terms"].tolist())
 
@@ -88,13 +73,13 @@ def _bits(out):
 def test_scores_equal_the_restatement(name, strategy):
     cloud, P, m = _built(name, strategy)
     scan = np.ascontiguousarray(cloud[1:][::5])
-    t = _dev(scan)
+    t = dev(scan)
     poses = six_poses(P)
     for nbh in (1, 7):
         want = _ref(m, cloud, P, scan, poses, nbh)
         assert want["terms"][0] > 100 and (want["terms"][:4] > 0).all()
         for k in (0, 3):
-            got = _np(m.score_poses(t, poses, neighbourhood=nbh, per_point=k))
+            got = to_np(m.score_poses(t, poses, neighbourhood=nbh, per_point=k))
             sr.assert_pose_sums(got, want, what=(name, strategy, nbh))
             sr.assert_per_point(got["d2"], got["row"], want["poses_out"][k], what=(name, strategy, nbh, k))
             # off the map, and the pose with a NaN: all four sums exactly 0
@@ -112,7 +97,7 @@ def test_identity_is_the_peak_and_matches_the_scan(name):
     scan = np.ascontiguousarray(cloud[1:][::7][:20000])
     g, z = P["grid_len"], P["z_len"]
     poses = [yaw(0)] + [yaw(0, (f * g, 0, 0)) for f in (0.1, 0.3, 0.5, 1.0)] + [yaw(0, (0, 0, f * z)) for f in (0.1, 0.3, 0.5, 1.0)] + [yaw(2.0)]
-    got = _np(m.score_poses(_dev(scan), np.stack(poses)))
+    got = to_np(m.score_poses(dev(scan), np.stack(poses)))
     print(name, "score", got["score"].tolist(), "matched / n", got["matched"][0] / len(scan))
     assert (got["score"][0] > got["score"][1:]).all(), got["score"]
     if name != "campus":                                          # (campus: mostly single-point nodes, 0.11 by the definition)
@@ -126,16 +111,16 @@ def test_results_are_the_same_bits_every_way():
     import torch
     cloud, P, m = _built("terrain")
     scan = np.ascontiguousarray(cloud[1:][::3])
-    t3, t4 = _dev(scan[:, :3]), _dev(scenes.with_stride4(scan[:, :3]))
+    t3, t4 = dev(scan[:, :3]), dev(scenes.with_stride4(scan[:, :3]))
     poses = six_poses(P)
     for nbh in (1, 7):
         first = m.score_poses(t3, poses, neighbourhood=nbh, per_point=3)
-        b0, d0, r0 = _bits(first), _np(first)["d2"].view(np.uint32), _np(first)["row"]
+        b0, d0, r0 = _bits(first), to_np(first)["d2"].view(np.uint32), to_np(first)["row"]
         assert b0[3][0] > 1000
         for _ in range(4):                                         # five calls in all
             again = m.score_poses(t3, poses, neighbourhood=nbh, per_point=3)
             assert _bits(again) == b0
-            assert np.array_equal(_np(again)["d2"].view(np.uint32), d0) and np.array_equal(_np(again)["row"], r0)
+            assert np.array_equal(to_np(again)["d2"].view(np.uint32), d0) and np.array_equal(to_np(again)["row"], r0)
         # a batch of 6 = six single-pose calls
         for k in range(6):
             one = _bits(m.score_poses(t3, poses[k], neighbourhood=nbh))
@@ -150,7 +135,7 @@ def test_results_are_the_same_bits_every_way():
         assert _bits(other) == b0
         # pose T on cloud P = the identity on fl32(T P)
         moved = sr.transform(poses[3], scan)
-        assert [v[0] for v in _bits(m.score_poses(_dev(moved), yaw(0), neighbourhood=nbh))] == [v[3] for v in b0]
+        assert [v[0] for v in _bits(m.score_poses(dev(moved), yaw(0), neighbourhood=nbh))] == [v[3] for v in b0]
 
 
 def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
@@ -158,9 +143,9 @@ def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
     poses), so the batch goes in two groups — pose k's record and the per-point outputs of a pose of the second group are what a
     single-pose call gives"""
     cloud = scenes.uniform_box(3_000_001)
-    m = _handle(BOX, max_nodes_hint=1 << 20)
+    m = handle(BOX, max_nodes_hint=1 << 20)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     rng = np.random.default_rng(9)
     poses = np.stack([yaw(float(a), (float(x), float(y), 0.0)) for a, x, y in zip(rng.uniform(-1, 1, 240), rng.uniform(-.2, .2, 240), rng.uniform(-.2, .2, 240))])
@@ -170,7 +155,7 @@ def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
     for k in (0, 1, 237, 238, 239):
         one = m.score_poses(t, poses[k], per_point=0)
         assert [v[0] for v in _bits(one)] == [v[k] for v in bb], k
-    assert np.array_equal(_np(one)["d2"].view(np.uint32), _np(batch)["d2"].view(np.uint32)) and np.array_equal(_np(one)["row"], _np(batch)["row"])
+    assert np.array_equal(to_np(one)["d2"].view(np.uint32), to_np(batch)["d2"].view(np.uint32)) and np.array_equal(to_np(one)["row"], to_np(batch)["row"])
 
 
 # ---- 5. the score follows the map ----
@@ -181,24 +166,24 @@ def test_score_follows_the_map():
     body = cloud[1:]
     half = len(body) // 2
     scan = np.ascontiguousarray(body[::7])
-    t = _dev(scan)
+    t = dev(scan)
     poses = six_poses(P)[:4]
-    m = _handle(P, ATOMIC)
+    m = handle(P, ATOMIC)
     m.setCloudFirst(cloud[0])
-    m.change2DMap("slope", _dev(body[:half]))
+    m.change2DMap("slope", dev(body[:half]))
 
     def check(step):
         for nbh in (1, 7):
-            got = _np(m.score_poses(t, poses, neighbourhood=nbh, per_point=0))
+            got = to_np(m.score_poses(t, poses, neighbourhood=nbh, per_point=0))
             want = _ref(m, cloud, P, scan, poses, nbh, per_point=0)
             sr.assert_pose_sums(got, want, what=(step, nbh))
             sr.assert_per_point(got["d2"], got["row"], want, what=(step, nbh))
         return int(got["terms"][0])
 
     terms = [check("built")]
-    m.change2DMap("slope", _dev(body[half:]))
+    m.change2DMap("slope", dev(body[half:]))
     terms.append(check("update"))
-    m.del2DMap("slope", _dev(body[:half // 2]))
+    m.del2DMap("slope", dev(body[:half // 2]))
     terms.append(check("remove"))
     cells = m.export()
     mid = cells["mean"][cells["num_nodes"] // 2]
@@ -206,11 +191,11 @@ def test_score_follows_the_map():
     m.crop_box(box, "keep_inside")
     terms.append(check("crop"))
     ends = np.ascontiguousarray(cells["mean"][:: max(1, cells["num_nodes"] // 4000)], np.float32)
-    st = m.clear_rays((float(mid[0]), float(mid[1]), float(mid[2]) + 2.0), _dev(ends))
+    st = m.clear_rays((float(mid[0]), float(mid[1]), float(mid[2]) + 2.0), dev(ends))
     assert st["cleared"] > 0
     terms.append(check("clear"))
     m.set_deferred_emit(True)
-    m.change2DMap("slope", _dev(body[:half // 2]))
+    m.change2DMap("slope", dev(body[:half // 2]))
     terms.append(check("deferred"))
     assert terms[1] > terms[0] > 0 and terms[3] < terms[2] and terms[5] > terms[4] > 0, terms
 
@@ -222,10 +207,10 @@ def test_score_and_flood_do_not_depend_on_who_built_the_index():
     goal = (9.5, 3.0, 1.0)
     res = []
     for score_first in (True, False):
-        m = _handle(P)
+        m = handle(P)
         m.setCloudFirst(cloud[0])
-        m.create2DMap("slope", _dev(cloud[1:]))
-        t = _dev(scan)
+        m.create2DMap("slope", dev(cloud[1:]))
+        t = dev(scan)
         before = _bits(m.score_poses(t, poses, neighbourhood=7)) if score_first else None
         st = m.computeCost(goal, robot={"radius": 0.25})
         c = m.cost_export()
@@ -256,7 +241,7 @@ def _raw(m, pts, poses, K, prm, out=True, d2=False, row=False, host=False, strid
     rec = torch.zeros((max(K, 1), 4), dtype=torch.int64, device="cuda")
     a = torch.zeros(max(n, 1), dtype=torch.float32, device="cuda")
     b = torch.zeros(max(n, 1), dtype=torch.int32, device="cuda")
-    tp = _dev(pts) if pts is not None else None
+    tp = dev(pts) if pts is not None else None
     tq = torch.from_numpy(poses).cuda() if poses is not None else None
     ptr = lambda x: C.c_void_p(x.data_ptr())
     rc = m._L.gndt_score_poses_device(m._h, ptr(tp) if tp is not None else None, n, stride, ptr(tq) if tq is not None else None, K,
@@ -273,15 +258,15 @@ def test_host_entry_point_empty_inputs_and_errors():
     scan = np.ascontiguousarray(cloud[1:][::4])
     poses = six_poses(P)
     for nbh in (1, 7):
-        dev = m.score_poses(_dev(scan), poses, neighbourhood=nbh, per_point=3, max_d2=9.0)
+        on_dev = m.score_poses(dev(scan), poses, neighbourhood=nbh, per_point=3, max_d2=9.0)
         host = m.score_poses(scan, poses, neighbourhood=nbh, per_point=3, max_d2=9.0)
-        assert _bits(dev) == _bits(host) and _bits(host)[3][0] > 1000
-        assert np.array_equal(_np(dev)["d2"].view(np.uint32), host["d2"].view(np.uint32)) and np.array_equal(_np(dev)["row"], host["row"])
+        assert _bits(on_dev) == _bits(host) and _bits(host)[3][0] > 1000
+        assert np.array_equal(to_np(on_dev)["d2"].view(np.uint32), host["d2"].view(np.uint32)) and np.array_equal(to_np(on_dev)["row"], host["row"])
     # n == 0 with K > 0: K zeroed records; K == 0: nothing
-    for pts in (_dev(np.zeros((0, 3), np.float32)), np.zeros((0, 3), np.float32)):
-        out = _np(m.score_poses(pts, poses))
+    for pts in (dev(np.zeros((0, 3), np.float32)), np.zeros((0, 3), np.float32)):
+        out = to_np(m.score_poses(pts, poses))
         assert len(out["score"]) == 6 and not out["score"].any() and not out["d2_sum"].any() and not out["matched"].any() and not out["terms"].any()
-        out = _np(m.score_poses(pts, poses, per_point=1))
+        out = to_np(m.score_poses(pts, poses, per_point=1))
         assert out["d2"].shape == (0,) and out["row"].shape == (0,)
     T = np.ascontiguousarray(poses.reshape(6, 12))
     ok = (1, 0, 0.0, 0.0, 0.0, 0)
@@ -317,27 +302,27 @@ def test_host_entry_point_empty_inputs_and_errors():
     assert m._L.gndt_score_poses(None, None, 0, 12, None, 0, None, None, None, None) == ERR_INVALID
     # min_count below the handle's min_points
     cloud5, P5 = _scene("uniform_box")
-    m5 = _handle(P5, ATOMIC, min_points=5)
+    m5 = handle(P5, ATOMIC, min_points=5)
     m5.setCloudFirst(cloud5[0])
-    m5.create2DMap("slope", _dev(cloud5[1:]))
+    m5.create2DMap("slope", dev(cloud5[1:]))
     s5 = np.ascontiguousarray(cloud5[1::3])
     assert _raw(m5, s5, T, 6, (1, 4, 0.0, 0.0, 0.0, 0)) == ERR_INVALID
     assert _raw(m5, s5, T, 6, (1, 5, 0.0, 0.0, 0.0, 0)) == 0
-    got = _np(m5.score_poses(_dev(s5), poses, neighbourhood=7))
+    got = to_np(m5.score_poses(dev(s5), poses, neighbourhood=7))
     sr.assert_pose_sums(got, sr.score(m5.export(), cloud5[0], P5["grid_len"], P5["z_len"], s5, poses, 7, min_points=5))
     # no finished build
-    e = _handle(TERRAIN)
+    e = handle(TERRAIN)
     e.setCloudFirst((0.0, 0.0, 0.0))
     with pytest.raises(g.GndtError) as err:
-        e.score_poses(_dev(scan), poses)
+        e.score_poses(dev(scan), poses)
     assert err.value.code == ERR_INVALID
     # a capturing stream: refused, and the capture goes on
     from grid_ndt_amd._lib import ScoreParams
-    want = _bits(m.score_poses(_dev(scan), poses))
+    want = _bits(m.score_poses(dev(scan), poses))
     s = torch.cuda.Stream()
     graph = torch.cuda.CUDAGraph()
     x = torch.zeros(16, device="cuda")
-    tp, tq = _dev(scan), torch.from_numpy(T).cuda()
+    tp, tq = dev(scan), torch.from_numpy(T).cuda()
     rec = torch.zeros((6, 4), dtype=torch.int64, device="cuda")
     prm = ScoreParams(*ok)
     torch.cuda.synchronize()
@@ -349,7 +334,7 @@ def test_host_entry_point_empty_inputs_and_errors():
     graph.replay()
     torch.cuda.synchronize()
     assert float(x[0]) == 1.0
-    assert _bits(m.score_poses(_dev(scan), poses)) == want
+    assert _bits(m.score_poses(dev(scan), poses)) == want
 
 
 # ---- 7. the map is untouched ----
@@ -361,7 +346,7 @@ def test_the_map_is_untouched(strategy):
     counts = m.sync()
     scan = np.ascontiguousarray(cloud[1:][::3])
     for nbh in (1, 7):
-        m.score_poses(_dev(scan), six_poses(P), neighbourhood=nbh, per_point=2)
+        m.score_poses(dev(scan), six_poses(P), neighbourhood=nbh, per_point=2)
         m.score_poses(scan, six_poses(P), neighbourhood=nbh, per_point=2)
     after = m.export()
     assert m.sync() == counts

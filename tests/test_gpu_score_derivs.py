@@ -19,7 +19,8 @@ import pytest
 from grid_ndt_amd import scenes
 from tests import score_derivs_ref as dr
 from tests import score_ref as sr
-from tests.test_gpu_score import ATOMIC, AUTO, BOX, ERR_INVALID, PARTITION, TERRAIN, TILE, _built, _dev, _handle, _np, six_poses, yaw
+from tests.gpu_kit import dev, handle, to_np
+from tests.test_gpu_score import ATOMIC, AUTO, BOX, ERR_INVALID, PARTITION, TERRAIN, TILE, _built, six_poses, yaw
 from tests.test_gpu_score import _bits as _score_bits
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def _ref(m, cloud, P, scan, poses, nbh, **kw):
 
 def _bits(out):
     """all 31 fields of a result as integers (H by its 21 upper-triangle values)"""
-    o = _np(out)
+    o = to_np(out)
     f = lambda a: np.ascontiguousarray(a, np.float64).view(np.uint64).tolist()
     H = np.stack([o["H"][:, a, b] for a, b in dr.TRI], 1)
     assert np.array_equal(o["H"], np.transpose(o["H"], (0, 2, 1)))
@@ -49,12 +50,12 @@ def _pose(bits, k):
 def test_derivs_equal_the_restatement(name, strategy):
     cloud, P, m = _built(name, strategy)
     scan = np.ascontiguousarray(cloud[1:][::5])
-    t = _dev(scan)
+    t = dev(scan)
     poses = six_poses(P)
     for nbh in (1, 7):
         want = _ref(m, cloud, P, scan, poses, nbh)
         assert want["terms"][0] > 100 and (want["terms"][:4] > 0).all()
-        got = _np(m.score_derivs(t, poses, neighbourhood=nbh))
+        got = to_np(m.score_derivs(t, poses, neighbourhood=nbh))
         dr.assert_derivs(got, want, what=(name, strategy, nbh))
         assert got["g"].shape == (6, 6) and got["H"].shape == (6, 6, 6) and np.array_equal(got["H"], got["H"].transpose(0, 2, 1))
         assert (np.abs(got["H"][:4]).max((1, 2)) > 0).all()
@@ -72,7 +73,7 @@ def test_results_are_the_same_bits_every_way():
     import torch
     cloud, P, m = _built("terrain")
     scan = np.ascontiguousarray(cloud[1:][::3])
-    t3, t4 = _dev(scan[:, :3]), _dev(scenes.with_stride4(scan[:, :3]))
+    t3, t4 = dev(scan[:, :3]), dev(scenes.with_stride4(scan[:, :3]))
     poses = six_poses(P)
     for nbh in (1, 7):
         plain = _score_bits(m.score_poses(t3, poses, neighbourhood=nbh))
@@ -90,16 +91,16 @@ def test_results_are_the_same_bits_every_way():
         assert _bits(other) == b0                                                            # another stream = the handle's
         assert _score_bits(m.score_poses(t3, poses, neighbourhood=nbh)) == plain             # score_poses keeps its bits afterwards
         moved = sr.transform(poses[3], scan)                                                 # pose T on cloud P = identity on fl32(T P)
-        assert _pose(_bits(m.score_derivs(_dev(moved), yaw(0), neighbourhood=nbh)), 0) == _pose(b0, 3)
+        assert _pose(_bits(m.score_derivs(dev(moved), yaw(0), neighbourhood=nbh)), 0) == _pose(b0, 3)
 
 
 def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
     """3 M points are 11 719 tiles, 2.8 MB of partial sums a pose: 30 poses exceed what one launch's scratch takes (64 MiB, 23
     poses), so the batch goes in two groups — pose k's record is what a single-pose call gives"""
     cloud = scenes.uniform_box(3_000_001)
-    m = _handle(BOX, max_nodes_hint=1 << 20)
+    m = handle(BOX, max_nodes_hint=1 << 20)
     m.setCloudFirst(cloud[0])
-    t = _dev(cloud[1:])
+    t = dev(cloud[1:])
     m.create2DMap("slope", t)
     rng = np.random.default_rng(9)
     poses = np.stack([yaw(float(a), (float(x), float(y), 0.0)) for a, x, y in zip(rng.uniform(-1, 1, 30), rng.uniform(-.2, .2, 30), rng.uniform(-.2, .2, 30))])
@@ -124,7 +125,7 @@ def _raw(m, pts, poses, K, prm, out=True, host=False, stride=12, n=None, stream=
         return m._L.gndt_score_derivs(m._h, ptr(pts) if pts is not None else None, n, stride, ptr(poses) if poses is not None else None, K,
                                       C.byref(p) if prm is not None else None, ptr(rec) if out else None)
     rec = torch.zeros((max(K, 1), 31), dtype=torch.int64, device="cuda")
-    tp = _dev(pts) if pts is not None else None
+    tp = dev(pts) if pts is not None else None
     tq = torch.from_numpy(poses).cuda() if poses is not None else None
     ptr = lambda x: C.c_void_p(x.data_ptr())
     rc = m._L.gndt_score_derivs_device(m._h, ptr(tp) if tp is not None else None, n, stride, ptr(tq) if tq is not None else None, K,
@@ -142,12 +143,12 @@ def test_host_entry_point_empty_inputs_and_errors():
     scan = np.ascontiguousarray(cloud[1:][::4])
     poses = six_poses(P)
     for nbh in (1, 7):
-        dev = m.score_derivs(_dev(scan), poses, neighbourhood=nbh, max_d2=9.0)
+        on_dev = m.score_derivs(dev(scan), poses, neighbourhood=nbh, max_d2=9.0)
         host = m.score_derivs(scan, poses, neighbourhood=nbh, max_d2=9.0)
-        assert isinstance(host["H"], np.ndarray) and _bits(dev) == _bits(host) and _bits(host)[3][0] > 1000
+        assert isinstance(host["H"], np.ndarray) and _bits(on_dev) == _bits(host) and _bits(host)[3][0] > 1000
     # n == 0 with K > 0: K zeroed records; K == 0: nothing
-    for pts in (_dev(np.zeros((0, 3), np.float32)), np.zeros((0, 3), np.float32)):
-        out = _np(m.score_derivs(pts, poses))
+    for pts in (dev(np.zeros((0, 3), np.float32)), np.zeros((0, 3), np.float32)):
+        out = to_np(m.score_derivs(pts, poses))
         assert len(out["score"]) == 6 and out["H"].shape == (6, 6, 6)
         assert not any(np.asarray(out[k]).any() for k in ("score", "d2_sum", "matched", "terms", "g", "H"))
     T = np.ascontiguousarray(poses.reshape(6, 12))
@@ -180,17 +181,17 @@ def test_host_entry_point_empty_inputs_and_errors():
     assert m._L.gndt_score_derivs_device(None, None, 0, 12, None, 0, None, None, None) == ERR_INVALID
     assert m._L.gndt_score_derivs(None, None, 0, 12, None, 0, None, None) == ERR_INVALID
     # no finished build
-    e = _handle(TERRAIN)
+    e = handle(TERRAIN)
     e.setCloudFirst((0.0, 0.0, 0.0))
     with pytest.raises(g.GndtError) as err:
-        e.score_derivs(_dev(scan), poses)
+        e.score_derivs(dev(scan), poses)
     assert err.value.code == ERR_INVALID
     # a capturing stream: refused, and the capture goes on
-    want = _bits(m.score_derivs(_dev(scan), poses))
+    want = _bits(m.score_derivs(dev(scan), poses))
     s = torch.cuda.Stream()
     graph = torch.cuda.CUDAGraph()
     x = torch.zeros(16, device="cuda")
-    tp, tq = _dev(scan), torch.from_numpy(T).cuda()
+    tp, tq = dev(scan), torch.from_numpy(T).cuda()
     rec = torch.zeros((6, 31), dtype=torch.int64, device="cuda")
     prm = ScoreParams(*ok)
     torch.cuda.synchronize()
@@ -202,7 +203,7 @@ def test_host_entry_point_empty_inputs_and_errors():
     graph.replay()
     torch.cuda.synchronize()
     assert float(x[0]) == 1.0
-    assert _bits(m.score_derivs(_dev(scan), poses)) == want
+    assert _bits(m.score_derivs(dev(scan), poses)) == want
 
 
 # ---- 4. the map is untouched ----
@@ -213,11 +214,11 @@ def test_the_map_is_untouched(strategy):
     before = m.export()
     counts = m.sync()
     scan = np.ascontiguousarray(cloud[1:][::3])
-    old = _score_bits(m.score_poses(_dev(scan), six_poses(P), neighbourhood=7))
+    old = _score_bits(m.score_poses(dev(scan), six_poses(P), neighbourhood=7))
     for nbh in (1, 7):
-        m.score_derivs(_dev(scan), six_poses(P), neighbourhood=nbh)
+        m.score_derivs(dev(scan), six_poses(P), neighbourhood=nbh)
         m.score_derivs(scan, six_poses(P), neighbourhood=nbh)
-    assert _score_bits(m.score_poses(_dev(scan), six_poses(P), neighbourhood=7)) == old
+    assert _score_bits(m.score_poses(dev(scan), six_poses(P), neighbourhood=7)) == old
     after = m.export()
     assert m.sync() == counts
     assert before.keys() == after.keys()
@@ -234,11 +235,11 @@ def test_register_on_the_device_step_by_step(scene, nbh):
     import torch
     from tests.test_score_derivs_host import RECOVERY_SCENES, assert_recovered, check_steps, starts
     cloud, P = RECOVERY_SCENES[scene]()
-    m = _handle(P)
+    m = handle(P)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     scan = np.ascontiguousarray(cloud[1:][::5])
-    t = _dev(scan)
+    t = dev(scan)
     ref_eval, ref_score = dr.callables(m.export(), cloud[0], P["grid_len"], P["z_len"], scan, nbh)
     S = starts(P)
     names = sorted(S)

@@ -18,7 +18,8 @@ from grid_ndt_amd import scenes
 from tests import score_derivs_ref as dr
 from tests import score_maps_ref as mr
 from tests import score_ref as sr
-from tests.test_gpu_score import ATOMIC, AUTO, BOX, ERR_INVALID, PARTITION, TILE, _built, _dev, _handle, _np, _scene, six_poses, yaw
+from tests.gpu_kit import dev, handle, to_np
+from tests.test_gpu_score import ATOMIC, AUTO, BOX, ERR_INVALID, PARTITION, TILE, _built, _scene, six_poses, yaw
 from tests.test_gpu_score import _bits as _score_bits
 
 pytestmark = pytest.mark.gpu
@@ -26,10 +27,10 @@ pytestmark = pytest.mark.gpu
 
 def _map_of(cloud, P, strategy=AUTO, scale=1.0, **kw):
     """the map of cloud[1:] at `scale` times P's lengths, its origin cloud[0]"""
-    m = _handle(dict(P, grid_len=float(np.float32(P["grid_len"]) * np.float32(scale)), z_len=float(np.float32(P["z_len"]) * np.float32(scale))),
+    m = handle(dict(P, grid_len=float(np.float32(P["grid_len"]) * np.float32(scale)), z_len=float(np.float32(P["z_len"]) * np.float32(scale))),
                 strategy, **kw)
     m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:]))
+    m.create2DMap("slope", dev(cloud[1:]))
     return m
 
 
@@ -45,7 +46,7 @@ def _ref(dst, cloud, P, src, poses, nbh, derivs=True, **kw):
 
 def _bits(out):
     """every value of a result as integers: the four sums, then g and H where there are any"""
-    o = _np(out)
+    o = to_np(out)
     b = list(_score_bits(out))
     for k in ("g", "H"):
         if k in o:
@@ -74,11 +75,11 @@ def test_maps_equal_the_restatement(name, strategy, source):
         # (every second point of face_lattice leaves at most 2 points in a half-length cell: no source row counts, and the answer is 0)
         empty = (name, source) == ("face_lattice", "half")
         assert (len(want["source"].idx) == 0 and not want["terms"].any()) if empty else (want["terms"][0] > 100 and (want["terms"][:4] > 0).all())
-        got = _np(dst.score_map_derivs(src, poses, neighbourhood=nbh))
+        got = to_np(dst.score_map_derivs(src, poses, neighbourhood=nbh))
         mr.assert_derivs(got, want, what=(name, strategy, source, nbh))
         assert np.array_equal(got["H"], got["H"].transpose(0, 2, 1))
         for k in (0, 3):
-            plain = _np(dst.score_map(src, poses, neighbourhood=nbh, per_node=k))
+            plain = to_np(dst.score_map(src, poses, neighbourhood=nbh, per_node=k))
             mr.assert_pose_sums(plain, want, what=(name, strategy, source, nbh))
             mr.assert_per_node(plain["d2"], plain["row"], want["poses_out"][k], what=(name, strategy, source, nbh, k))
         # off the map, and the pose with a NaN: exactly 0
@@ -102,13 +103,13 @@ def test_results_are_the_same_bits_every_way():
         b0 = _bits(first)
         assert b0[3][0] > 1000
         plain = dst.score_map(src, poses, neighbourhood=nbh, per_node=3)
-        p0, d0, r0 = _bits(plain), _np(plain)["d2"].view(np.uint32), _np(plain)["row"]
+        p0, d0, r0 = _bits(plain), to_np(plain)["d2"].view(np.uint32), to_np(plain)["row"]
         assert p0 == b0[:4]                                        # the derivatives' first four fields are the score's bits
         for _ in range(2):                                         # three calls in all
             assert _bits(dst.score_map_derivs(src, poses, neighbourhood=nbh)) == b0
             again = dst.score_map(src, poses, neighbourhood=nbh, per_node=3)
             assert _bits(again) == p0
-            assert np.array_equal(_np(again)["d2"].view(np.uint32), d0) and np.array_equal(_np(again)["row"], r0)
+            assert np.array_equal(to_np(again)["d2"].view(np.uint32), d0) and np.array_equal(to_np(again)["row"], r0)
         for k in range(6):                                         # a batch of 6 = six single-pose calls
             assert _pose(_bits(dst.score_map_derivs(src, poses[k], neighbourhood=nbh)), 0) == _pose(b0, k), (nbh, k)
             assert _pose(_bits(dst.score_map(src, poses[k], neighbourhood=nbh)), 0) == _pose(p0, k), (nbh, k)
@@ -121,9 +122,9 @@ def test_results_are_the_same_bits_every_way():
     for nbh in (1, 7):
         want = _ref(dst, cloud, P, dst, poses, nbh)
         got = dst.score_map_derivs(dst, poses, neighbourhood=nbh)
-        mr.assert_derivs(_np(got), want, what=("self", nbh))
+        mr.assert_derivs(to_np(got), want, what=("self", nbh))
         assert _bits(dst.score_map(dst, poses, neighbourhood=nbh)) == _bits(got)[:4]
-    own = _np(dst.score_map(dst, yaw(0), per_node=0))
+    own = to_np(dst.score_map(dst, yaw(0), per_node=0))
     counted = ~np.isnan(own["d2"])
     assert counted.sum() > 1000 and int(own["terms"][0]) == int(own["matched"][0])
 
@@ -147,10 +148,10 @@ def test_a_source_of_one_partial_tile_and_one_with_rows_without_statistics():
             want = _ref(dst, cloud, P, src, poses, nbh)
             assert want["terms"][0] > floor
             got = dst.score_map_derivs(src, poses, neighbourhood=nbh)
-            mr.assert_derivs(_np(got), want, what=("rows", floor, nbh))
+            mr.assert_derivs(to_np(got), want, what=("rows", floor, nbh))
             plain = dst.score_map(src, poses, neighbourhood=nbh, per_node=1)
             assert _bits(plain) == _bits(got)[:4]
-            mr.assert_per_node(_np(plain)["d2"], _np(plain)["row"], want["poses_out"][1], what=("rows", floor, nbh))
+            mr.assert_per_node(to_np(plain)["d2"], to_np(plain)["row"], want["poses_out"][1], what=("rows", floor, nbh))
 
 
 def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
@@ -158,12 +159,12 @@ def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
     one launch's scratch (64 MiB) takes some 110 poses of the one and 1 100 of the other — two poses more than that go in two groups,
     and pose k's record is what a single-pose call gives"""
     cloud = scenes.uniform_box(3_000_001)
-    dst = _handle(BOX, max_nodes_hint=1 << 20)
+    dst = handle(BOX, max_nodes_hint=1 << 20)
     dst.setCloudFirst(cloud[0])
-    dst.create2DMap("slope", _dev(cloud[1:]))
-    src = _handle(BOX, max_nodes_hint=1 << 20)
+    dst.create2DMap("slope", dev(cloud[1:]))
+    src = handle(BOX, max_nodes_hint=1 << 20)
     src.setCloudFirst(cloud[0])
-    src.create2DMap("slope", _dev(cloud[1:][::2]))
+    src.create2DMap("slope", dev(cloud[1:][::2]))
     tiles = (src.sync()[0] + 255) // 256
     waves = (29 * 16 + 2 * 16) * 8
     for width, per_tile, call in ((31, 240, dst.score_map_derivs), (4, 24, dst.score_map)):
@@ -178,7 +179,7 @@ def test_a_batch_launched_in_groups_of_poses_has_the_single_calls_bits():
             assert _pose(_bits(call(src, poses[k])), 0) == _pose(bb, k), (width, k)
     batch = dst.score_map(src, poses, per_node=K - 1)              # the per-node outputs of a pose of the second group
     one = dst.score_map(src, poses[K - 1], per_node=0)
-    assert np.array_equal(_np(one)["d2"].view(np.uint32), _np(batch)["d2"].view(np.uint32)) and np.array_equal(_np(one)["row"], _np(batch)["row"])
+    assert np.array_equal(to_np(one)["d2"].view(np.uint32), to_np(batch)["d2"].view(np.uint32)) and np.array_equal(to_np(one)["row"], to_np(batch)["row"])
 
 
 # ---- 3. errors and capture ----
@@ -249,17 +250,17 @@ def test_empty_inputs_and_errors():
     for a, b in ((dst, m5), (m5, dst)):
         assert _raw(a, b, T, 6, (1, 4, 0.0, 0.0, 0.0, 0)) == ERR_INVALID
         assert _raw(a, b, T, 6, (1, 5, 0.0, 0.0, 0.0, 0)) == 0
-    got = _np(dst.score_map_derivs(m5, poses, neighbourhood=7))
+    got = to_np(dst.score_map_derivs(m5, poses, neighbourhood=7))
     mr.assert_derivs(got, _ref(dst, cloud, P, m5, poses, 7, src_min_points=5), what="min_points 5")
     # no source rows: K zeroed records
     empty = _map_of(_second(cloud), P, ATOMIC)
     empty.crop_box((30000, 30010, 30000, 30010), "keep_inside")
     assert empty.sync()[0] == 0
-    for out in (_np(dst.score_map(empty, poses, per_node=1)), _np(dst.score_map_derivs(empty, poses))):
+    for out in (to_np(dst.score_map(empty, poses, per_node=1)), to_np(dst.score_map_derivs(empty, poses))):
         assert len(out["score"]) == 6 and not any(np.asarray(out[k]).any() for k in out if k not in ("d2", "row"))
     assert out["H"].shape == (6, 6, 6)
     # no finished build in either handle
-    e = _handle(P)
+    e = handle(P)
     e.setCloudFirst((0.0, 0.0, 0.0))
     e._ensure("slope")
     for a, b in ((dst, e), (e, dst)):
@@ -303,7 +304,7 @@ def _same_export(before, after):
 def test_the_maps_are_untouched(strategy):
     cloud, P, dst = _built("terrain", strategy)
     src = _map_of(_second(cloud), P, strategy)
-    scan = _dev(cloud[1:][::3])
+    scan = dev(cloud[1:][::3])
     before = (dst.export(), src.export(), dst.sync(), src.sync(), _score_bits(dst.score_poses(scan, six_poses(P), neighbourhood=7)))
     for nbh in (1, 7):
         dst.score_map(src, six_poses(P), neighbourhood=nbh, per_node=2)
@@ -366,7 +367,7 @@ def test_stitch_d2d_registers_then_merges_and_means_is_unchanged():
     for h1, h2 in zip(r1["history"], r2["history"]):
         assert np.array_equal(np.asarray(h1["T"]).view(np.uint64), np.asarray(h2["T"]).view(np.uint64))
     cells = src.export()
-    ref = _recovery_maps("drivable_site", "moved")[2].register(_dev(cells["mean"][(cells["flags"] & 1) != 0]), T0)
+    ref = _recovery_maps("drivable_site", "moved")[2].register(dev(cells["mean"][(cells["flags"] & 1) != 0]), T0)
     assert np.array_equal(np.asarray(r1["T"]).view(np.uint64), np.asarray(ref["T"]).view(np.uint64)) and r1["iterations"] == ref["iterations"]
     with pytest.raises(ValueError):
         c.stitch(src, T0, method="points")

@@ -34,6 +34,7 @@ from tests import score_derivs_ref as dr
 from tests import score_maps_ref as mr
 from tests import score_ref as sr
 from tests import walk_ref as wr
+from tests.gpu_kit import dev as _dev
 
 pytestmark = pytest.mark.gpu
 
@@ -70,11 +71,6 @@ def _body():
 
 def _small_body():
     return np.ascontiguousarray(_body()[::8])
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
 
 
 def _np(v):

@@ -15,6 +15,7 @@ from tests import frontier_ref as fr
 from tests import query_ref as qr
 from tests import score_ref as sr
 from tests import segment_ref as gr
+from tests.gpu_kit import Padded, PaddedCall, build, dev, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -27,27 +28,11 @@ FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "norma
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
 def raw(m, pts, pose=None, stride=12, cap=None, host=False, stream=None, want_class=True, want_label=True, clusters=True, counts=True,
         reserved=(0, 0), nbh=7, min_count=0, cov_rel=0.0, cov_floor=0.0, novel_d2=0.0, classes=0, min_points=0, connectivity=0,
         min_cluster_points=0, min_cluster_cells=0):
     """The C entry points.  cap None: as many records as the scan has points.  -> (rc, dict(point_class, point_label, clusters
     [min(counts[0], cap)], counts, buf: the whole record buffer with PAD sentinel records on either side))"""
-    import torch
     from grid_ndt_amd._lib import SegmentParams
     pts = np.ascontiguousarray(np.asarray(pts, np.float32)[:, :3])
     n = len(pts)
@@ -56,39 +41,19 @@ def raw(m, pts, pose=None, stride=12, cap=None, host=False, stream=None, want_cl
     cap = n if cap is None else cap
     prm = SegmentParams(nbh, min_count, cov_rel, cov_floor, novel_d2, classes, min_points, connectivity, min_cluster_points, min_cluster_cells,
                         (C.c_uint32 * 2)(*reserved))
-    T = None if pose is None else np.ascontiguousarray(sr.as_poses(pose)[0]).reshape(12)
-    if host:
-        buf = np.full((cap + 2 * PAD) * WORDS, SENTINEL, np.uint32)
-        cls = np.full(max(n, 1), 0x5A, np.uint8)
-        lab = np.full(max(n, 1), SENTINEL, np.uint32)
-        cnt = np.full(4, SENTINEL, np.uint32)
-        xyz, Td = pts, T
-        ptr = lambda a, off=0: C.c_void_p(a.ctypes.data + off)
-    else:
-        buf = torch.full(((cap + 2 * PAD) * WORDS,), SENTINEL, dtype=torch.int32, device="cuda")
-        cls = torch.full((max(n, 1),), 0x5A, dtype=torch.uint8, device="cuda")
-        lab = torch.full((max(n, 1),), SENTINEL, dtype=torch.int32, device="cuda")
-        cnt = torch.full((4,), SENTINEL, dtype=torch.int32, device="cuda")
-        xyz, Td = _dev(pts), None if T is None else _dev(T, np.float64)
-        ptr = lambda a, off=0: C.c_void_p(a.data_ptr() + off)
-    args = [m._h, ptr(xyz) if n else None, n, stride, None if Td is None else ptr(Td), C.byref(prm), ptr(cls) if want_class else None,
-            ptr(lab) if want_label else None, ptr(buf, PAD * 4 * WORDS) if cap and clusters else None, cap, ptr(cnt) if counts else None]
-    if host:
-        rc = m._L.gndt_segment_scan(*args)
-    else:
-        rc = m._L.gndt_segment_scan_device(*args, C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        buf, lab, cnt = (t.cpu().numpy().view(np.uint32) for t in (buf, lab, cnt))
-        cls = cls.cpu().numpy()
-    recs = buf.view(gr.RECORD)
-    k = min(int(cnt[0]), cap) if rc == 0 else 0
-    return rc, dict(point_class=cls[:n], point_label=lab[:n], clusters=recs[PAD:PAD + k], counts=cnt, buf=buf)
+    T = None if pose is None else np.ascontiguousarray(sr.as_poses(pose)[0], np.float64).reshape(12)
+    buf, cnt = Padded(cap, words=WORDS, front=PAD, back=PAD, fill=SENTINEL), Padded(4, fill=SENTINEL)
+    cls, lab = Padded(max(n, 1), np.uint8, fill=0x5A), Padded(max(n, 1), fill=SENTINEL)
+    rc = PaddedCall(host, stream)(m._L.gndt_segment_scan, m._L.gndt_segment_scan_device, m._h, pts, n, stride, T, C.byref(prm),
+                                  cls if want_class else None, lab if want_label else None, buf if cap and clusters else None, cap,
+                                  cnt if counts else None)
+    k = min(int(cnt.a[0]), cap) if rc == 0 else 0
+    return rc, dict(point_class=cls.a[:n], point_label=lab.a[:n], clusters=buf.a.view(gr.RECORD)[PAD:PAD + k], counts=cnt.a, buf=buf.a)
 
 
 def untouched(buf, written):
     """the sentinel records before the list and everything behind its `written` records"""
-    w = buf.reshape(-1, WORDS)
-    return (w[:PAD] == SENTINEL).all() and (w[PAD + written:] == SENTINEL).all()
+    return Padded.over(buf, words=WORDS, front=PAD, fill=SENTINEL).untouched(written)
 
 
 REF_KEYS = ("pose", "nbh", "novel_d2", "classes", "min_points", "connectivity", "min_count", "cov_rel", "cov_floor")
@@ -124,7 +89,7 @@ def floor():
     """the one-storey floor of 16 x 16 columns across the origin, nine points a node -> (m, export, cloud)"""
     if "floor" not in _scenes:
         cloud = fr.cells_cloud(gr.floor_cells())
-        m = _build(cloud, fr.P)
+        m = build(cloud, fr.P)
         _scenes["floor"] = (m, m.export(), cloud)
     return _scenes["floor"]
 
@@ -132,7 +97,7 @@ def floor():
 def site():
     if "site" not in _scenes:
         cloud = scenes.drivable_site()
-        m = _build(cloud, scenes.COST_PARAMS)
+        m = build(cloud, scenes.COST_PARAMS)
         _scenes["site"] = (m, m.export(), cloud)
     return _scenes["site"]
 
@@ -360,7 +325,7 @@ def test_the_class_is_a_function_of_score_poses_own_d2(nbh, stride):
     for pose in (None, T):
         q = gr.moved(scan, pose)
         xyz = scan if stride == 12 else np.concatenate([scan, np.ones((len(scan), 1), np.float32)], 1)
-        sc = m.score_poses(_dev(xyz), np.eye(4)[:3] if pose is None else pose, neighbourhood=nbh, per_point=0)
+        sc = m.score_poses(dev(xyz), np.eye(4)[:3] if pose is None else pose, neighbourhood=nbh, per_point=0)
         d2 = sc["d2"].cpu().numpy()
         _, _, _, _, keyed = qr.keys(q, np.float32(m.cloudFirst), m.gridLen, m.zLen)
         cls = gr.class_of(keyed, d2)
@@ -444,12 +409,12 @@ def test_repeat_calls_streams_and_a_small_call_after_a_large_one():
 
 def test_after_an_update_and_after_a_crop():
     cloud = fr.cells_cloud(gr.floor_cells())
-    m = _build(cloud, fr.P, ATOMIC)
+    m = build(cloud, fr.P, ATOMIC)
     box = gr.cell_points(gr.box_cells((1, 2), (1, 2), (3, 3)), per=9)
     pts = np.concatenate([gr.floor_scan(cloud), box])
     got, _ = check(m, m.export(), pts, what="before")
     assert (got["point_class"][-len(box):] == gr.UNMAPPED).all()
-    m.change2DMap("slope", _dev(box))                                     # the box joins the map: its points are explained by their own nodes
+    m.change2DMap("slope", dev(box))                                     # the box joins the map: its points are explained by their own nodes
     got, _ = check(m, m.export(), pts, what="update")
     assert (got["point_class"][-len(box):] == gr.EXPLAINED).all() and got["counts"][1] == 0
     m.crop_box((1, 8, -8, 8), "keep_inside")                              # the floor's west half leaves: its points find no node
@@ -462,10 +427,6 @@ def test_after_an_update_and_after_a_crop():
     assert (got["point_class"] == gr.UNMAPPED).all()
 
 
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
 def test_python_wrappers_shapes_and_cluster_boxes():
     import torch
     m, cells, cloud = floor()
@@ -474,23 +435,23 @@ def test_python_wrappers_shapes_and_cluster_boxes():
     ref = want(m, cells, pts)
     k = len(ref["clusters"])
     assert k == 2
-    for src in (_dev(pts), pts, _dev(np.concatenate([pts, np.ones((len(pts), 1), np.float32)], 1))):
+    for src in (dev(pts), pts, dev(np.concatenate([pts, np.ones((len(pts), 1), np.float32)], 1))):
         on_dev = hasattr(src, "cpu")
         seg = m.segment_scan(src, labels=True)
         assert isinstance(seg["label"], torch.Tensor) == on_dev
         for f in gr.RECORD.names:
-            got = np.ascontiguousarray(np.ascontiguousarray(_np(seg[f])).astype(gr.RECORD[f]))
+            got = np.ascontiguousarray(np.ascontiguousarray(to_np(seg[f])).astype(gr.RECORD[f]))
             assert seg[f].shape == (k,) and got.tobytes() == np.ascontiguousarray(ref["clusters"][f]).tobytes(), f
-        assert list(_np(seg["counts"])) == [k, ref["novel_points"], ref["novel_cells"], k]
-        assert np.array_equal(_np(seg["point_class"]), ref["point_class"]) and seg["point_class"].dtype in (np.uint8, torch.uint8)
-        assert np.array_equal(_np(seg["point_label"]).view(np.uint32), ref["point_label"])
+        assert list(to_np(seg["counts"])) == [k, ref["novel_points"], ref["novel_cells"], k]
+        assert np.array_equal(to_np(seg["point_class"]), ref["point_class"]) and seg["point_class"].dtype in (np.uint8, torch.uint8)
+        assert np.array_equal(to_np(seg["point_label"]).view(np.uint32), ref["point_label"])
         wide = m.segment_scan(src, max_clusters=5)
-        assert "point_class" not in wide and wide["label"].shape == ((5,) if on_dev else (k,)) and int(_np(wide["counts"])[0]) == k
+        assert "point_class" not in wide and wide["label"].shape == ((5,) if on_dev else (k,)) and int(to_np(wide["counts"])[0]) == k
         short = m.segment_scan(src, max_clusters=1)
-        assert short["label"].shape == (1,) and int(_np(short["counts"])[0]) == k and int(_np(short["label"])[0]) == int(ref["clusters"]["label"][0])
+        assert short["label"].shape == (1,) and int(to_np(short["counts"])[0]) == k and int(to_np(short["label"])[0]) == int(ref["clusters"]["label"][0])
         boxes, cen = m.cluster_boxes(wide)
         assert boxes.shape == (wide["label"].shape[0], 2, 3) and cen.shape == (wide["label"].shape[0], 3)
-        boxes, cen = _np(boxes), _np(cen)
+        boxes, cen = to_np(boxes), to_np(cen)
         o = np.float64(fr.ORIGIN)
         want_lo = o + np.float64([2, -5, 3]) * [fr.GL, fr.GL, fr.ZL]                    # the first box: cells 2..4, -5..-4, levels 3..6
         want_hi = o + np.float64([5, -3, 7]) * [fr.GL, fr.GL, fr.ZL]
@@ -501,16 +462,16 @@ def test_python_wrappers_shapes_and_cluster_boxes():
         assert np.allclose(cen[0], first.mean(0), atol=2e-3) and (cen[:k] >= boxes[:k, 0]).all() and (cen[:k] <= boxes[:k, 1]).all()
         if on_dev:
             assert np.isnan(boxes[k:]).all() and np.isnan(cen[k:]).all() and not np.isnan(boxes[:k]).any()
-    both = m.segment_scan(_dev(pts), classes=("off_surface", "unmapped"), connectivity=6, neighbourhood=1, min_points=2, min_cluster_cells=2)
-    assert int(_np(both["counts"])[3]) >= 1
+    both = m.segment_scan(dev(pts), classes=("off_surface", "unmapped"), connectivity=6, neighbourhood=1, min_points=2, min_cluster_cells=2)
+    assert int(to_np(both["counts"])[3]) >= 1
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
-        src = _dev(pts)
+        src = dev(pts)
     seg = m.segment_scan(src, pose=np.eye(4), stream=s)
     s.synchronize()
-    assert seg["label"].shape == (k,) and list(_np(seg["cells"])) == list(ref["clusters"]["cells"])
-    empty = m.segment_scan(_dev(np.zeros((0, 3), np.float32)), labels=True)
-    assert empty["label"].shape == (0,) and list(_np(empty["counts"])) == [0, 0, 0, 0] and empty["point_class"].shape == (0,)
+    assert seg["label"].shape == (k,) and list(to_np(seg["cells"])) == list(ref["clusters"]["cells"])
+    empty = m.segment_scan(dev(np.zeros((0, 3), np.float32)), labels=True)
+    assert empty["label"].shape == (0,) and list(to_np(empty["counts"])) == [0, 0, 0, 0] and empty["point_class"].shape == (0,)
 
 
 def test_refused_arguments():
@@ -534,7 +495,7 @@ def test_refused_arguments():
     prm = SegmentParams(7)
     cnt = torch.zeros(4, dtype=torch.int32, device="cuda")
     recs = torch.zeros(64, dtype=torch.int32, device="cuda")
-    xyz = _dev(pts)
+    xyz = dev(pts)
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     call = lambda *a: m._L.gndt_segment_scan_device(*a)
     n = len(pts)

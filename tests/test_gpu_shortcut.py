@@ -8,22 +8,18 @@ plan_routes info, the handle's lifetime, every refused argument, and a poisoned 
 one step that is not IEEE arithmetic is the gates' acosf, and every map keeps its angle decisions more than 1e-3 degrees from the
 threshold.  (The link finds its steps with the gates only: there is no steps-table variant to run a second way.)"""
 import ctypes as C
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import clearance_ref as cr
 from tests import frontier_ref as fr
+from tests import poison_tier
 from tests import shortcut_ref as sr
 from tests import walk_ref as wr
+from tests.gpu_kit import Padded, PaddedCall, build, dev, robot_arg, to_np
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ERR_INVALID = 1
 ATOMIC = 1
 SENTINEL = 0x5A5A5A5A
@@ -34,39 +30,10 @@ MAX_BLOCKS = 1024            # kShortcutMaxBlocks: one trip of the grid-stride l
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
-def _robot(robot):
-    from grid_ndt_amd._lib import Robot
-    if robot is None:
-        return None
-    d = dict(cr.ROBOT)
-    d.update(robot)
-    return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
-
-
 def raw(m, routes, lengths, robot=None, window=0, overhead=False, hops=None, min_hops=0, max_links=0, waypoint_cap=None, path_cap=0, stride=4,
         stream=None, host=False, reserved=(0,) * 4, checks=None):
     """The C entry points; info K + PAD entries, both row outputs K * cap + PAD words of sentinel -> (rc, info [K], waypoint_rows,
     path_rows, untouched: the tails still hold the sentinel).  lengths lie `stride` bytes apart, sentinel between them."""
-    import torch
     from grid_ndt_amd._lib import ShortcutParams
     routes = np.ascontiguousarray(routes, np.uint32)
     K, route_cap = routes.shape
@@ -74,27 +41,13 @@ def raw(m, routes, lengths, robot=None, window=0, overhead=False, hops=None, min
     prm = ShortcutParams(window, (1 if overhead else 0) if checks is None else checks, min_hops, max_links, (C.c_uint32 * 4)(*reserved))
     ln = np.full((max(K, 1), stride // 4), SENTINEL, np.uint32)
     ln[:K, 0] = lengths
-    info = np.full((K + PAD) * 12, SENTINEL, np.uint32)
-    wp = np.full(K * wcap + PAD, SENTINEL, np.uint32)
-    path = np.full(K * path_cap + PAD, SENTINEL, np.uint32)
+    info, wp, path = (Padded(n, words=w, back=PAD, fill=SENTINEL) for n, w in ((K, 12), (K * wcap, 1), (K * path_cap, 1)))
     hp = None if hops is None else np.ascontiguousarray(hops).view(np.uint32)
-    if host:
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-        rc = m._L.gndt_shortcut_routes(m._h, ptr(routes), K, route_cap, ptr(ln), stride, _robot(robot), C.byref(prm), ptr(hp), ptr(wp), wcap,
-                                       ptr(path) if path_cap else None, path_cap, ptr(info))
-    else:
-        to = lambda a: None if a is None else torch.from_numpy(a.view(np.int32)).cuda()
-        d_routes, d_ln, d_info, d_wp, d_path, d_hp = to(routes), to(ln), to(info), to(wp), to(path), to(hp)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream())
-        rc = m._L.gndt_shortcut_routes_device(m._h, ptr(d_routes), K, route_cap, ptr(d_ln), stride, _robot(robot), C.byref(prm), ptr(d_hp),
-                                              ptr(d_wp), wcap, ptr(d_path) if path_cap else None, path_cap, ptr(d_info),
-                                              C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        info, wp, path = (t.cpu().numpy().view(np.uint32) for t in (d_info, d_wp, d_path))
-    untouched = bool((info[K * 12:] == SENTINEL).all() and (wp[K * wcap:] == SENTINEL).all() and (path[K * path_cap:] == SENTINEL).all())
-    return rc, info[:K * 12].view(sr.INFO_DTYPE), wp[:K * wcap].reshape(K, wcap), path[:K * path_cap].reshape(K, path_cap), untouched
+    rc = PaddedCall(host, stream, wait_for_current=True)(m._L.gndt_shortcut_routes, m._L.gndt_shortcut_routes_device, m._h, routes, K, route_cap, ln,
+                                                         stride, robot_arg(robot, cr.ROBOT), C.byref(prm), hp, wp, wcap,
+                                                         path if path_cap else None, path_cap, info)
+    untouched = info.untouched() and wp.untouched() and path.untouched()
+    return rc, info.body.view(sr.INFO_DTYPE), wp.body.reshape(K, wcap), path.body.reshape(K, path_cap), untouched
 
 
 def check(m, s, routes, lengths, what="", entries=(False, True), stream=None, caps=True, **kw):
@@ -130,7 +83,7 @@ def drawn(name, make, P=fr.P, robot=None):
             m, _, cells, cloud = base[0]
         else:
             cloud = make()
-            m = _build(cloud, P)
+            m = build(cloud, P)
             cells = m.export()
         s = sr.Shortcutter(cells, cloud[0, :3], P["grid_len"], P["z_len"], robot)
         assert s.w.f.angle_margin_deg > MARGIN, (name, s.w.f.angle_margin_deg)
@@ -280,9 +233,9 @@ def test_a_pillar_with_a_real_clearance_field():
     # the Python interface takes what clearance() returned, on the device and on the host
     for host in (False, True):
         field = m.clearance(host=host)
-        got = m.shortcut_routes(rows.view(np.int32) if host else _dev(rows.view(np.int32), np.int32), lengths.view(np.int32), hops=field, min_hops=2,
+        got = m.shortcut_routes(rows.view(np.int32) if host else dev(rows.view(np.int32), np.int32), lengths.view(np.int32), hops=field, min_hops=2,
                                 host=host)
-        assert _np(got["waypoints"]).tolist() == [7] and _np(got["hops_min"]).tolist() == [0]
+        assert to_np(got["waypoints"]).tolist() == [7] and to_np(got["hops_min"]).tolist() == [0]
     with pytest.raises(ValueError):
         m.shortcut_routes(rows.view(np.int32), lengths.view(np.int32), hops=hops[:-1], host=True)
 
@@ -404,39 +357,39 @@ def test_routes_straight_out_of_a_device_side_plan_and_driven_by_the_walks():
     goal = cells["mean"][row_of(cells, 6, 6)]
     assert m.computeCost(tuple(float(v) for v in goal))["rc"] == 0
     starts = cells["mean"][[row_of(cells, ix, iy) for ix, iy in ((0, 0), (1, 2), (6, 0), (3, 1), (0, 6), (6, 6), (2, 5))]]
-    prow, pinfo = m.plan_routes(_dev(starts), route_cap=24)
+    prow, pinfo = m.plan_routes(dev(starts), route_cap=24)
     assert pinfo["length"].stride(0) == 8 and (pinfo["status"] == 0).all()
     got = m.shortcut_routes((prow, pinfo), path_cap=32)
     torch.cuda.synchronize()
-    lengths = _np(pinfo["length"]).astype(np.uint32)
-    want = s.shortcut(_np(prow).view(np.uint32), lengths, path_cap=32)
-    named = {k: _np(got[k]).view(want[0][k].dtype) for k in sr.INFO_FIELDS}
+    lengths = to_np(pinfo["length"]).astype(np.uint32)
+    want = s.shortcut(to_np(prow).view(np.uint32), lengths, path_cap=32)
+    named = {k: to_np(got[k]).view(want[0][k].dtype) for k in sr.INFO_FIELDS}
     named["reserved"] = np.zeros(1, np.uint32)
-    sr.same(named, _np(got["waypoint_rows"]), _np(got["path_rows"]), *want[:3], "planned")
+    sr.same(named, to_np(got["waypoint_rows"]), to_np(got["path_rows"]), *want[:3], "planned")
     assert (want[0]["status"] == sr.OK).all() and want[0]["waypoints"][5] == 1 and (want[0]["waypoints"] < want[0]["length_in"]).sum() >= 5
     # the same through the host entry point, from numpy arrays and the host-side plan's info (uint32 fields 32 bytes apart)
     hrow, hinfo = m.plan_routes(starts, route_cap=24, host=True)
-    assert hinfo["length"].strides == (32,) and np.array_equal(hrow, _np(prow))
+    assert hinfo["length"].strides == (32,) and np.array_equal(hrow, to_np(prow))
     hgot = m.shortcut_routes((hrow, hinfo), path_cap=32)
     assert isinstance(hgot["status"], np.ndarray)
     for k in sr.INFO_FIELDS + ("waypoint_rows", "path_rows"):
-        assert np.array_equal(_np(got[k]).view(np.uint32), hgot[k].view(np.uint32)), k
+        assert np.array_equal(to_np(got[k]).view(np.uint32), hgot[k].view(np.uint32)), k
     # the waypoints as a polyline: NaN behind the end, driven by the walks to the goal over the same slopes
     pts = m.route_waypoints(got["waypoint_rows"])
     assert pts.shape == (7, 24, 3) and pts.is_cuda
-    wrows = _np(got["waypoint_rows"])
+    wrows = to_np(got["waypoint_rows"])
     ref = np.full((7, 24, 3), np.nan, np.float32)
     for k in range(7):
         for i in range(int(want[0]["waypoints"][k])):
             ref[k, i] = s.point(int(wrows[k, i]), cells["mean"][wrows[k, i]][2])
-    assert np.array_equal(_np(pts).view(np.uint32), ref.view(np.uint32)) and np.array_equal(m.route_waypoints(wrows).view(np.uint32), ref.view(np.uint32))
+    assert np.array_equal(to_np(pts).view(np.uint32), ref.view(np.uint32)) and np.array_equal(m.route_waypoints(wrows).view(np.uint32), ref.view(np.uint32))
     walk = m.walk_paths(pts, rows=32)
-    assert (_np(walk["status"]) == wr.DONE).all() and (_np(walk["end_row"]) == row_of(cells, 6, 6)).all()
-    assert np.array_equal(_np(walk["rows"]), _np(got["path_rows"])) and np.array_equal(_np(walk["waypoints"]), want[0]["waypoints"].astype(np.int32))
-    assert np.array_equal(_np(walk["length"]).view(np.uint32), want[0]["cost_out"].view(np.uint32))
+    assert (to_np(walk["status"]) == wr.DONE).all() and (to_np(walk["end_row"]) == row_of(cells, 6, 6)).all()
+    assert np.array_equal(to_np(walk["rows"]), to_np(got["path_rows"])) and np.array_equal(to_np(walk["waypoints"]), want[0]["waypoints"].astype(np.int32))
+    assert np.array_equal(to_np(walk["length"]).view(np.uint32), want[0]["cost_out"].view(np.uint32))
     # nothing to do
     for host in (False, True):
-        none = m.shortcut_routes(np.zeros((0, 4), np.int32) if host else _dev(np.zeros((0, 4)), np.int32), np.zeros(0, np.int32), host=host)
+        none = m.shortcut_routes(np.zeros((0, 4), np.int32) if host else dev(np.zeros((0, 4)), np.int32), np.zeros(0, np.int32), host=host)
         assert len(none["status"]) == 0 and tuple(none["waypoint_rows"].shape) == (0, 4)
 
 
@@ -445,7 +398,7 @@ def test_routes_straight_out_of_a_device_side_plan_and_driven_by_the_walks():
 def test_first_consumer_call_a_larger_call_before_and_a_second_stream():
     import torch
     cloud = _gap()
-    m = _build(cloud, fr.P)                                  # a handle no consumer has touched: this call makes the column index
+    m = build(cloud, fr.P)                                  # a handle no consumer has touched: this call makes the column index
     cells = m.export()
     s = sr.Shortcutter(cells, cloud[0, :3], fr.GL, fr.ZL)
     r = route(cells, *GAP_ROUTE)
@@ -457,10 +410,10 @@ def test_first_consumer_call_a_larger_call_before_and_a_second_stream():
     for i in range(3):
         again = check(m, s, rows, lengths, ("after the larger call", i), stream=st if i else None)
         assert again[0].tobytes() == want[0].tobytes() and np.array_equal(again[1], want[1])
-    got = m.shortcut_routes(_dev(rows.view(np.int32), np.int32), _dev(lengths.view(np.int32), np.int32), stream=st, window=5, waypoint_cap=4)
+    got = m.shortcut_routes(dev(rows.view(np.int32), np.int32), dev(lengths.view(np.int32), np.int32), stream=st, window=5, waypoint_cap=4)
     st.synchronize()
     ref = s.shortcut(rows, lengths, window=5, waypoint_cap=4)
-    assert np.array_equal(_np(got["waypoint_rows"]).view(np.uint32), ref[1]) and _np(got["links_tested"]).tolist() == ref[0]["links_tested"].tolist()
+    assert np.array_equal(to_np(got["waypoint_rows"]).view(np.uint32), ref[1]) and to_np(got["links_tested"]).tolist() == ref[0]["links_tested"].tolist()
 
 
 def test_after_an_update_a_crop_and_with_another_robot():
@@ -468,7 +421,7 @@ def test_after_an_update_a_crop_and_with_another_robot():
     from tests.test_shortcut_host import staircase
     cloud = scenes.bridge_ground()
     P = scenes.BRIDGE_PARAMS
-    m = _build(cloud, P, ATOMIC)                          # (updates need the additive strategy)
+    m = build(cloud, P, ATOMIC)                          # (updates need the additive strategy)
     rng = np.random.default_rng(12)
     other = dict(reachable_height=0.05, max_angle_deg=12.0)
     shorter = 0
@@ -486,7 +439,7 @@ def test_after_an_update_a_crop_and_with_another_robot():
 
     before = fresh("before")
     x0, x1 = int(before["sx"].min()), int(before["sx"].max())
-    m.change2DMap("slope", _dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
+    m.change2DMap("slope", dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
     fresh("update")
     m.crop_box((x0 + (x1 - x0) // 4, x1 - (x1 - x0) // 4, -100000, 100000), "keep_inside")
     cropped = fresh("crop")
@@ -519,7 +472,7 @@ def test_refused_arguments():
             assert raw(m, rows, lengths, stride=stride, host=host)[0] == 0
     prm = ShortcutParams()
     buf = torch.zeros(256, dtype=torch.int32, device="cuda")
-    d_rows, d_len = _dev(rows.view(np.int32), np.int32), _dev(lengths.view(np.int32), np.int32)
+    d_rows, d_len = dev(rows.view(np.int32), np.int32), dev(lengths.view(np.int32), np.int32)
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     call = m._L.gndt_shortcut_routes_device
     R, N, B = p(d_rows), p(d_len), C.byref(prm)
@@ -585,38 +538,19 @@ POISON_IDS = ["test_open_floor_a_staircase_and_a_straight_run", "test_l_corridor
               "test_wavefront_and_workgroup_edges_of_K[5]", "test_one_call_mixes_every_status",
               "test_routes_straight_out_of_a_device_side_plan_and_driven_by_the_walks",
               "test_first_consumer_call_a_larger_call_before_and_a_second_stream"]
-POISON_MEASURED_S = 4.31
-POISON_LIMIT_S = 20
-_stopped = []        # why the tier stopped: a child ended abnormally
+HERE = "tests/test_gpu_shortcut.py::"
+GROUP = dict(measured_s=4.31, limit_s=20, ids=[HERE + i for i in POISON_IDS])
+
+
+def test_every_node_id_of_the_poison_group_is_collected():
+    poison_tier.ids_collected(GROUP["ids"])
 
 
 def test_the_poison_limit_is_three_times_the_measured_time():
-    assert POISON_MEASURED_S > 0 and POISON_LIMIT_S == -(-3 * POISON_MEASURED_S // 10) * 10
+    poison_tier.limit_follows_rule(GROUP["measured_s"], GROUP["limit_s"])
 
 
-@pytest.mark.skipif(bool(os.environ.get("GNDT_LIB_VARIANT")), reason="this process runs on a variant of the library itself: no children of its own")
-@pytest.mark.parametrize("byte", [0xA5, 0x7F], ids=["0xA5", "0x7F"])
+@poison_tier.refused_under_variant
+@pytest.mark.parametrize("byte", poison_tier.BYTES, ids=poison_tier.BYTE_IDS)
 def test_hand_drawn_maps_under_poison(byte):
-    from grid_ndt_amd import _lib
-    from tests.test_gpu_poisoned import _abnormal, _env
-    if _stopped:
-        pytest.fail(f"not started: {_stopped[0]}", pytrace=False)
-    _lib.build_native(variant="poison")          # (the build has made it: nothing compiles inside the child's limit)
-    cmd = [sys.executable, "-m", "tests.poisoned_child", hex(byte)] + ["tests/test_gpu_shortcut.py::" + i for i in POISON_IDS]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, env=_env("poison"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=POISON_LIMIT_S)
-        returncode, output = r.returncode, r.stdout
-    except subprocess.TimeoutExpired as e:
-        out = e.stdout or ""
-        returncode, output = None, out.decode(errors="replace") if isinstance(out, bytes) else out
-    print(output[-6000:])
-    why = _abnormal(returncode, output)
-    if why:
-        _stopped.append(f"the child under {byte:#x} {why}")
-        pytest.fail(_stopped[0] + "\n" + output[-3000:], pytrace=False)
-    lines = [line for line in output.splitlines() if line.startswith('{"poisoned_child"')]
-    assert returncode == 0 and len(lines) == 1, (returncode, output[-3000:])
-    rep = json.loads(lines[0])
-    assert rep["exit"] == 0 and rep["byte"] == byte
-    assert rep["device_bytes"] > 0 and rep["host_bytes"] > 0, rep
-    assert rep["lib"] == _lib.lib_path("poison")
+    poison_tier.run_group("the hand-drawn shortcut maps", GROUP["ids"], GROUP["limit_s"], byte)

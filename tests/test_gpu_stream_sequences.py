@@ -24,6 +24,7 @@ import pytest
 
 from tests import parity
 from tests import stream_model as sm
+from tests.gpu_kit import dev
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +32,6 @@ P, ORIGIN = sm.P, sm.ORIGIN
 ERR_INVALID = 1
 FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "normal", "flags")
 PARTITION_FAMILY = (2, 3, 6, 7)          # TwoDmap.STRATEGY_NAMES: the builds that keep no node table
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
 
 def _same_bytes(a, b):
@@ -57,19 +53,19 @@ class GpuBackend:
         self.m[h] = m
 
     def build(self, h, cloud):
-        self.m[h].create2DMap("slope", _dev(cloud))
+        self.m[h].create2DMap("slope", dev(cloud))
 
     def update(self, h, pts):
-        self.m[h].change2DMap("slope", _dev(pts))
+        self.m[h].change2DMap("slope", dev(pts))
 
     def remove(self, h, pts):
-        self.m[h].del2DMap("slope", _dev(pts))
+        self.m[h].del2DMap("slope", dev(pts))
 
     def crop(self, h, box):
         self.m[h].crop_box(box, "keep_inside")
 
     def clear(self, h, sensor, ends, count_only):
-        st = self.m[h].clear_rays(sensor, _dev(ends), count_only=count_only)
+        st = self.m[h].clear_rays(sensor, dev(ends), count_only=count_only)
         assert st["rays"] == len(ends) and (st["cleared"] == 0) == bool(count_only), st
 
     def merge(self, h, src):
@@ -81,7 +77,7 @@ class GpuBackend:
         self.m[h].reset("slope")
 
     def accumulate(self, h, pts, base):
-        self.m[h].accumulate("slope", _dev(pts), first_idx_base=base)
+        self.m[h].accumulate("slope", dev(pts), first_idx_base=base)
 
     def finalize(self, h):
         self.m[h].finalize()
@@ -103,7 +99,7 @@ class GpuBackend:
 
     def query(self, h, model):
         q = model.query_points()
-        rows = self.m[h].query(_dev(q)).cpu().numpy().astype(np.int64)
+        rows = self.m[h].query(dev(q)).cpu().numpy().astype(np.int64)
         assert np.array_equal(rows, sm.query_rows(model.expected(), q))
         return rows, q
 
@@ -113,7 +109,7 @@ class GpuBackend:
         assert m.last_strategy() in PARTITION_FAMILY, m.last_strategy()
         before = m.export()
         with pytest.raises(g.GndtError) as e:
-            {"update": lambda: m.change2DMap("slope", _dev(pts)), "remove": lambda: m.del2DMap("slope", _dev(pts)),
+            {"update": lambda: m.change2DMap("slope", dev(pts)), "remove": lambda: m.del2DMap("slope", dev(pts)),
              "stats_export": lambda: m.stats_export()}[what]()
         assert e.value.code == ERR_INVALID, (what, e.value.code)
         _same_bytes(m.export(), before)

@@ -18,6 +18,7 @@ from grid_ndt_amd.map2d import _stream_ptr
 from tests import cast_ref as cf
 from tests import view_ref as vr
 from tests.test_view_host import HAND_DIRS, HAND_OPEN, HAND_POSE, HAND_WALL, UNIT, hand_cloud, pose, rec
+from tests.gpu_kit import build, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -26,21 +27,6 @@ FIELDS = ("sx", "sy", "sz", "count", "first_idx", "mean", "cov", "rough", "norma
 # reach = ceil(max_range / grid_len) + 1; the launch's LDS is 8 * ceil((2 reach + 1)^2 / 32) + 1024 bytes: 65 288 at reach 253 (the
 # last that fits the 65 536 a launch gets without a grant), 65 800 at 254, 163 840 at 403 (all of a CU's LDS), 164 648 at 404
 REACH_DEFAULT, REACH_MAX = 253, 403
-
-
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap("slope", _dev(cloud[1:, :3]))
-    m.sync()
-    return m
 
 
 def host(out):
@@ -127,9 +113,9 @@ def test_the_hand_case_through_both_entry_points(wall):
     """tests/test_view_host.py derives the two records by hand"""
     s = hand_map(wall)
     want = HAND_WALL if wall else HAND_OPEN
-    dev = s["m"].view_gain(HAND_POSE, HAND_DIRS, 10.0, per_ray=True)
+    on_dev = s["m"].view_gain(HAND_POSE, HAND_DIRS, 10.0, per_ray=True)
     hst = s["m"].view_gain(HAND_POSE, HAND_DIRS, 10.0, per_ray=True, host=True)
-    for out in (host(dev), hst):
+    for out in (host(on_dev), hst):
         assert rec(records(out)[0]) == want
         assert out["range"].shape == (1, 4) and (out["range"][0, 0] == 1.5 if wall else np.isinf(out["range"][0, 0]))
         assert (out["row"][0, 1:] == -1).all() and np.isinf(out["range"][0, 1:]).all()
@@ -147,11 +133,11 @@ def test_both_entry_points_equal_the_restatement(name):
     # (a pose 1.5 m over a point of the cloud can stand inside an occupied voxel: every ray then stops in the first column, known = 1)
     assert (full["known"][3:] >= 1).all() and np.median(full["known"][3:]) > 20 and (full["known"][3:] == 1).sum() < K_MAX // 2
     assert (full["unknown"][3:] > 0).sum() > K_MAX // 2 and (full["hits"][3:] > 0).all()
-    d_pose = _dev(poses, np.float64)
+    d_pose = dev(poses, np.float64)
     for N in (1, 63, 64, 65, 255, 256, 257, 1000):
         want = vr.gain(tr, dirs=np.arange(N))
         for d in (dirs[:N], pad4(dirs[:N])):
-            d_dirs = _dev(d)
+            d_dirs = dev(d)
             for K in (1, 3, 65):
                 vr.assert_same(records(m.view_gain(d_pose[:K], d_dirs, R)), want[:K], (name, "device", K, N, d.shape[1]))
             vr.assert_same(records(m.view_gain(poses[:3], d, R, host=True)), want[:3], (name, "host", N, d.shape[1]))
@@ -268,7 +254,7 @@ def test_per_ray_outputs_are_the_casts_bit_for_bit():
     K, N = 5, 257
     poses, dirs = s["poses"][:K], s["dirs"][:N]
     o32, e32 = vr.ends(poses, dirs, R)                                    # the header's fp64 expression, in numpy
-    cast = host(m.cast_rays(_dev(np.repeat(o32, N, axis=0)), _dev(e32.reshape(K * N, 3)), mode="voxel", max_range=R))
+    cast = host(m.cast_rays(dev(np.repeat(o32, N, axis=0)), dev(e32.reshape(K * N, 3)), mode="voxel", max_range=R))
     assert (cast["row"] >= 0).sum() > 100 and np.isinf(cast["range"]).sum() > 100 and np.isnan(cast["range"]).sum() > 5 * 2
     want = vr.gain(s["trace"], poses=np.arange(K), dirs=np.arange(N))
     for out in (host(m.view_gain(poses, dirs, R, per_ray=True)), m.view_gain(poses, dirs, R, per_ray=True, host=True)):
@@ -278,7 +264,7 @@ def test_per_ray_outputs_are_the_casts_bit_for_bit():
     # every combination of NULL row / range: what is given is written, the records are the same
     prm = ViewParams(R, 0.0, 0)
     for device in (True, False):
-        mk = (lambda a, dt: _dev(a, dt)) if device else (lambda a, dt: np.ascontiguousarray(a, dt))
+        mk = (lambda a, dt: dev(a, dt)) if device else (lambda a, dt: np.ascontiguousarray(a, dt))
         dp, dd = mk(poses, np.float64), mk(dirs, np.float32)
         for want_row in (False, True):
             for want_rng in (False, True):
@@ -300,7 +286,7 @@ def test_the_map_is_untouched_and_the_bytes_repeat():
     import torch
     s = scene("atomic")
     m, R = s["m"], s["R"]
-    p, d = _dev(s["poses"][:9], np.float64), _dev(s["dirs"][:257])
+    p, d = dev(s["poses"][:9], np.float64), dev(s["dirs"][:257])
     a = host(m.view_gain(p, d, R, per_ray=True))
     b = host(m.view_gain(p, d, R, per_ray=True))
     st = torch.cuda.Stream()
@@ -334,7 +320,7 @@ def test_invalid_arguments_leave_the_outputs_untouched():
     bad_params += [ok(reserved=(C.c_uint32 * 5)(*[int(i == j) for i in range(5)])) for j in range(5)]
     bad_params += [ok(max_range=(REACH_MAX + 1) * s["P"]["grid_len"])]                  # a window beyond the LDS
     for device in (True, False):
-        mk = (lambda a, dt=np.float32: _dev(a, dt)) if device else (lambda a, dt=np.float32: np.ascontiguousarray(a, dt))
+        mk = (lambda a, dt=np.float32: dev(a, dt)) if device else (lambda a, dt=np.float32: np.ascontiguousarray(a, dt))
         p, d = mk(s["poses"][:K], np.float64), mk(s["dirs"][:N])
         outs = [mk(np.full((K, 12), -7, np.int32), np.int32), mk(np.full(K * N, -7, np.int32), np.int32), mk(np.full(K * N, -7.0))]
         assert _raw(m, p, K, d, N, 12, ok(), *outs, device=device) == 0              # the arguments the bad ones differ from are good
@@ -381,8 +367,8 @@ def test_capture_is_refused_and_the_empty_batches():
     s = scene("atomic")
     m, R = s["m"], s["R"]
     # K == 0 or N == 0: GNDT_OK, nothing written
-    p, d = _dev(s["poses"][:3], np.float64), _dev(s["dirs"][:64])
-    outs = [_dev(np.full((3, 12), -7, np.int32), np.int32), _dev(np.full(192, -7, np.int32), np.int32), _dev(np.full(192, -7.0))]
+    p, d = dev(s["poses"][:3], np.float64), dev(s["dirs"][:64])
+    outs = [dev(np.full((3, 12), -7, np.int32), np.int32), dev(np.full(192, -7, np.int32), np.int32), dev(np.full(192, -7.0))]
     hp, hd = s["poses"][:3].copy(), s["dirs"][:64].copy()
     houts = [np.full((3, 12), -7, np.int32), np.full(192, -7, np.int32), np.full(192, -7.0, np.float32)]
     for K, N in ((0, 64), (3, 0), (0, 0)):

@@ -7,7 +7,6 @@ terminators, strides, row caps, the codec's edge, the step guard, a real clearan
 stream, the Python interface and every refused argument; more paths than one trip of the kernel's grid-stride loop, and the table
 choice left at its default on both sides of its threshold and at it.  No tolerance anywhere: the one step that is not IEEE arithmetic is the
 gates' acosf, and every compared scene keeps its angle decisions more than 1e-3 degrees from the threshold."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -17,6 +16,7 @@ from grid_ndt_amd import scenes
 from tests import clearance_ref as cr
 from tests import frontier_ref as fr
 from tests import walk_ref as wr
+from tests.gpu_kit import Padded, PaddedCall, build, debug_option, dev, robot_arg, to_np
 
 pytestmark = pytest.mark.gpu
 
@@ -29,69 +29,25 @@ START = {"nearest_slope": 1, "node": 2}
 _scenes = {}
 
 
-def _dev(a, dtype=np.float32):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _build(cloud, P, strategy=0):
-    import grid_ndt_amd as g
-    m = g.TwoDmap(P["grid_len"], P["z_len"], strategy=strategy)
-    m.setInterval(P["slope_interval"])
-    m.setCloudFirst(cloud[0])
-    m.create2DMap(P.get("demand", "slope"), _dev(cloud[1:, :3]))
-    m.sync()
-    return m
-
-
-@contextlib.contextmanager
 def step_table(on):
     """gndt_debug_set_option(GNDT_DEBUG_WALK_STEP_TABLE, .) for a block; the default comes back whatever happens in it"""
-    import grid_ndt_amd as g
-    g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_WALK_STEP_TABLE, 1 if on else 0)
-    try:
-        yield
-    finally:
-        g.TwoDmap.set_debug_option(g.TwoDmap.DEBUG_WALK_STEP_TABLE, 2)
-
-
-def _robot(robot):
-    from grid_ndt_amd._lib import Robot
-    if robot is None:
-        return None
-    d = dict(cr.ROBOT)
-    d.update(robot)
-    return C.byref(Robot(d["radius"], d["reachable_height"], d["max_rough"], d["max_angle_deg"]))
+    return debug_option("DEBUG_WALK_STEP_TABLE", 1 if on else 0, 2)
 
 
 def raw(m, paths, robot=None, start_mode="nearest_slope", overhead=False, hops=None, min_hops=0, max_steps=0, row_cap=0, stream=None, host=False,
         reserved=(0,) * 4, checks=None, mode=None):
     """The C entry points, info K + PAD entries and rows K * row_cap + PAD words of sentinel -> (rc, info [K], rows [K, row_cap],
     untouched: the tails still hold the sentinel)"""
-    import torch
     from grid_ndt_amd._lib import WalkParams
     paths = np.ascontiguousarray(paths, np.float32)
     K, T, sf = paths.shape
     prm = WalkParams(START[start_mode] if mode is None else mode, (1 if overhead else 0) if checks is None else checks, min_hops, max_steps,
                      (C.c_uint32 * 4)(*reserved))
-    info = np.full((K + PAD) * 12, SENTINEL, np.uint32)
-    rows = np.full(K * row_cap + PAD, SENTINEL, np.uint32)
+    info, rows = Padded(K, words=12, back=PAD, fill=SENTINEL), Padded(K * row_cap, back=PAD, fill=SENTINEL)
     hp = None if hops is None else np.ascontiguousarray(hops).view(np.uint32)
-    if host:
-        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-        rc = m._L.gndt_walk_paths(m._h, ptr(paths), K, T, 4 * sf, _robot(robot), C.byref(prm), ptr(hp), ptr(rows) if row_cap else None, row_cap, ptr(info))
-    else:
-        to = lambda a: None if a is None else torch.from_numpy(a.view(np.int32)).cuda()
-        d_paths, d_info, d_rows, d_hp = torch.from_numpy(paths).cuda(), to(info), to(rows), to(hp)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream())
-        rc = m._L.gndt_walk_paths_device(m._h, ptr(d_paths), K, T, 4 * sf, _robot(robot), C.byref(prm), ptr(d_hp), ptr(d_rows) if row_cap else None,
-                                         row_cap, ptr(d_info), C.c_void_p(0 if stream is None else (stream.cuda_stream or 1)))
-        torch.cuda.synchronize()
-        info, rows = d_info.cpu().numpy().view(np.uint32), d_rows.cpu().numpy().view(np.uint32)
-    untouched = bool((info[K * 12:] == SENTINEL).all() and (rows[K * row_cap:] == SENTINEL).all())
-    return rc, info[:K * 12].view(wr.INFO_DTYPE), rows[:K * row_cap].reshape(K, row_cap), untouched
+    rc = PaddedCall(host, stream, wait_for_current=True)(m._L.gndt_walk_paths, m._L.gndt_walk_paths_device, m._h, paths, K, T, 4 * sf,
+                                                         robot_arg(robot, cr.ROBOT), C.byref(prm), hp, rows if row_cap else None, row_cap, info)
+    return rc, info.body.view(wr.INFO_DTYPE), rows.body.reshape(K, row_cap), info.untouched() and rows.untouched()
 
 
 def check(m, w, paths, what="", entries=(False, True), stream=None, **kw):
@@ -118,7 +74,7 @@ def drawn(name, make, P=fr.P, robot=None):
             m, _, cells, cloud = base[0]
         else:
             cloud = make()
-            m = _build(cloud, P)
+            m = build(cloud, P)
             cells = m.export()
         w = wr.Walker(cells, cloud[0, :3], P["grid_len"], P["z_len"], robot)
         assert w.f.angle_margin_deg > MARGIN, (name, w.f.angle_margin_deg)
@@ -346,7 +302,7 @@ def test_the_default_table_choice_at_its_threshold_to_the_row():
     table: the walk's scratch of 41 bytes a row and 8 is the one allocation between an inline call and it."""
     import grid_ndt_amd as g
     from grid_ndt_amd import _lib
-    m = _build(cr.lattice(2048, fr.P), fr.P)
+    m = build(cr.lattice(2048, fr.P), fr.P)
     for left in (2048, 2047):
         cells = m.export()
         n = int(cells["num_nodes"])
@@ -382,8 +338,8 @@ def test_hops_and_min_hops_against_a_real_clearance_field():
     # the Python interface takes what clearance() returned, on the device and on the host
     for host in (False, True):
         field = m.clearance(host=host)
-        got = m.walk_paths(paths if host else _dev(paths), hops=field, min_hops=2, rows=3, host=host)
-        assert _np(got["status"]).tolist() == [wr.DONE, wr.TOO_CLOSE, wr.TOO_CLOSE] and _np(got["hops_min"]).tolist() == [3, 1, 0]
+        got = m.walk_paths(paths if host else dev(paths), hops=field, min_hops=2, rows=3, host=host)
+        assert to_np(got["status"]).tolist() == [wr.DONE, wr.TOO_CLOSE, wr.TOO_CLOSE] and to_np(got["hops_min"]).tolist() == [3, 1, 0]
 
 
 def test_after_an_update_a_crop_and_with_another_robot():
@@ -391,7 +347,7 @@ def test_after_an_update_a_crop_and_with_another_robot():
     from tests.test_walk_host import random_paths
     cloud = scenes.bridge_ground()
     P = scenes.BRIDGE_PARAMS
-    m = _build(cloud, P, ATOMIC)                          # (updates need the additive strategy)
+    m = build(cloud, P, ATOMIC)                          # (updates need the additive strategy)
     rng = np.random.default_rng(9)
     other = dict(reachable_height=0.05, max_angle_deg=12.0)
     seen = set()
@@ -409,7 +365,7 @@ def test_after_an_update_a_crop_and_with_another_robot():
 
     before = fresh("before")
     x0, x1 = int(before["sx"].min()), int(before["sx"].max())
-    m.change2DMap("slope", _dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
+    m.change2DMap("slope", dev(cloud[1:4000, :3] + np.float32([0.0, 0.0, 0.3])))
     fresh("update")
     m.crop_box((x0 + (x1 - x0) // 4, x1 - (x1 - x0) // 4, -100000, 100000), "keep_inside")
     cropped = fresh("crop")
@@ -424,10 +380,6 @@ def test_after_an_update_a_crop_and_with_another_robot():
                 assert rc == 0 and info["status"][0] == wr.NO_START and info["waypoints"][0] == 0 and (rows == wr.NO_ROW).all() and untouched
 
 
-def _np(t):
-    return t.cpu().numpy() if hasattr(t, "cpu") else np.asarray(t)
-
-
 def test_a_second_stream_repeat_calls_and_the_python_interface():
     import torch
     from grid_ndt_amd import rollouts
@@ -439,16 +391,16 @@ def test_a_second_stream_repeat_calls_and_the_python_interface():
     want, want_rows, _ = check(m, w, paths, "second stream", stream=s, row_cap=5, entries=(False,))
     check(m, w, paths[:, :, [0, 1, 2, 2]], "stride 16", row_cap=5)
     for kw in (dict(), dict(host=True), dict(stream=s)):
-        got = m.walk_paths(paths if kw.get("host") else _dev(paths), rows=5, **kw)
+        got = m.walk_paths(paths if kw.get("host") else dev(paths), rows=5, **kw)
         if "stream" in kw:
             s.synchronize()
         assert isinstance(got["status"], np.ndarray) == bool(kw.get("host"))
         for k in wr.INFO_FIELDS:
-            assert _np(got[k]).view(np.uint32).tobytes() == want[k].view(np.uint32).tobytes(), (k, kw)
-        assert np.array_equal(_np(got["rows"]).view(np.uint32), want_rows)
-    got = m.walk_paths(_dev(paths), start_mode="node", overhead=True, max_steps=3, robot=dict(radius=0.2))
+            assert to_np(got[k]).view(np.uint32).tobytes() == want[k].view(np.uint32).tobytes(), (k, kw)
+        assert np.array_equal(to_np(got["rows"]).view(np.uint32), want_rows)
+    got = m.walk_paths(dev(paths), start_mode="node", overhead=True, max_steps=3, robot=dict(radius=0.2))
     ref, _, _ = w.walk(paths, start_mode="node", overhead=True, max_steps=3)
-    assert np.array_equal(_np(got["status"]), ref["status"]) and "rows" not in got
+    assert np.array_equal(to_np(got["status"]), ref["status"]) and "rows" not in got
     # flood -> arcs -> walk_paths -> choose
     assert m.computeCost((2.25, 2.25, 0.125))["rc"] == 0
     h = torch.from_numpy(m.cost_export()["h"]).cuda()
@@ -460,7 +412,7 @@ def test_a_second_stream_repeat_calls_and_the_python_interface():
     assert best in done and m.cost_export()["h"][ref["end_row"][best]] == m.cost_export()["h"][ref["end_row"][done]].min()
     # nothing to do
     for host in (False, True):
-        empty = m.walk_paths(np.zeros((0, 4, 3), np.float32) if host else _dev(np.zeros((0, 4, 3))), host=host)
+        empty = m.walk_paths(np.zeros((0, 4, 3), np.float32) if host else dev(np.zeros((0, 4, 3))), host=host)
         assert len(empty["status"]) == 0
 
 
@@ -485,7 +437,7 @@ def test_refused_arguments():
             assert raw(m, p1, reserved=tuple(int(j == k) for j in range(4)), host=host)[0] == ERR_INVALID, k
     prm = WalkParams()
     buf = torch.zeros(256, dtype=torch.int32, device="cuda")
-    pts = _dev(p1)
+    pts = dev(p1)
     p = lambda t, off=0: C.c_void_p(t.data_ptr() + off)
     call = m._L.gndt_walk_paths_device
     ok = lambda *a: call(m._h, *a)
