@@ -30,8 +30,8 @@ def lib_path(variant=None):
 
 LIB_PATH = lib_path(VARIANT)   # what lib() loads in this process
 SOURCES = ["gndt_api_core.hip", "gndt_api_table.hip", "gndt_api_build.hip", "gndt_api_dist.hip", "gndt_api_cost.hip", "gndt_api_query.hip",
-           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_view.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_route_field.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
-HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_view.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_route_field.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", "gndt_scratch.hpp", os.path.join(_ROOT, "include", "gndt.h")]
+           "gndt_api_crop.hip", "gndt_api_raster.hip", "gndt_api_clear.hip", "gndt_api_score.hip", "gndt_api_score_maps.hip", "gndt_api_cast.hip", "gndt_api_view.hip", "gndt_api_coarsen.hip", "gndt_api_merge.hip", "gndt_api_plan.hip", "gndt_api_frontier.hip", "gndt_api_patch.hip", "gndt_api_segment.hip", "gndt_api_clearance.hip", "gndt_api_obstacle.hip", "gndt_api_route_field.hip", "gndt_api_walk.hip", "gndt_api_shortcut.hip", "gndt_api_footprint.hip", "gndt_api_io.hip", "gndt_codec.cpp", "gndt_io.cpp"]
+HEADERS = ["gndt_handle.hpp", "gndt_kernels.hpp", "gndt_table.hpp", "gndt_cost.hpp", "gndt_query.hpp", "gndt_ray.hpp", "gndt_score.hpp", "gndt_score_derivs.hpp", "gndt_score_maps.hpp", "gndt_cast.hpp", "gndt_view.hpp", "gndt_plan.hpp", "gndt_frontier.hpp", "gndt_patch.hpp", "gndt_segment.hpp", "gndt_clearance.hpp", "gndt_obstacle.hpp", "gndt_route_field.hpp", "gndt_walk.hpp", "gndt_shortcut.hpp", "gndt_footprint.hpp", "gndt_coarsen.hpp", "gndt_merge.hpp", "gndt_crop.hpp", "gndt_pack.hpp", "gndt_partition.hpp", "gndt_stream.hpp", "gndt_bucket3.hpp", "gndt_blocked.hpp", "gndt_tile.hpp", "gndt_exchange.hpp", "gndt_math.hpp", "gndt_scratch.hpp", os.path.join(_ROOT, "include", "gndt.h")]
 
 GNDT_OK = 0
 ERR_NAMES = {0: "OK", 1: "INVALID", 2: "NO_DEVICE", 3: "HIP", 4: "KEY_RANGE", 5: "CAPACITY", 6: "NOMEM", 7: "PEER"}
@@ -115,6 +115,12 @@ class PlanParams(C.Structure):
 class FrontierParams(C.Structure):
     _fields_ = [("candidates", C.c_int32), ("open_rule", C.c_int32), ("level_reach", C.c_uint32), ("min_open", C.c_uint32),
                 ("link_dz", C.c_uint32), ("min_size", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PatchParams(C.Structure):
+    _fields_ = [("candidates", C.c_int32), ("connectivity", C.c_uint32), ("cos_min", C.c_float), ("max_offset", C.c_float),
+                ("max_var", C.c_float), ("cos_level", C.c_float), ("sin_level", C.c_float), ("min_size", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
 
 
 class SegmentParams(C.Structure):
@@ -295,6 +301,10 @@ POSE_DERIVS = np.dtype(POSE_SCORE.descr + [("g", np.float64, 6), ("H", np.float6
 FRONTIER = np.dtype([("label", np.int32), ("size", np.int32), ("best_row", np.int32), ("best_h", np.float32),
                      ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
                      ("sum_px", np.int64), ("sum_py", np.int64), ("sum_pz", np.int64), ("open_sides", np.int32), ("reserved", np.int32)])
+PATCH = np.dtype([("label", np.int32), ("nodes", np.int32), ("points", np.int64),
+                  ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32), ("sz_min", np.int32),
+                  ("sz_max", np.int32), ("sum_px", np.int64), ("sum_py", np.int64), ("sum_pz", np.int64),
+                  ("centroid", np.float64, 3), ("normal", np.float64, 3), ("var", np.float64), ("kind", np.int32), ("reserved", np.int32)])
 SCAN_CLUSTER = np.dtype([("label", np.uint32), ("cells", np.uint32), ("off_surface", np.uint32), ("unmapped", np.uint32),
                          ("sx_min", np.int32), ("sx_max", np.int32), ("sy_min", np.int32), ("sy_max", np.int32),
                          ("sz_min", np.int32), ("sz_max", np.int32), ("sum_x", np.int64), ("sum_y", np.int64), ("sum_z", np.int64),
@@ -302,6 +312,9 @@ SCAN_CLUSTER = np.dtype([("label", np.uint32), ("cells", np.uint32), ("off_surfa
 RECORDS = {"gndt_route_info": ROUTE_INFO, "gndt_walk_info": WALK_INFO, "gndt_shortcut_info": SHORTCUT_INFO,
            "gndt_footprint_info": FOOTPRINT_INFO, "gndt_view_info": VIEW_INFO, "gndt_pose_score": POSE_SCORE,
            "gndt_pose_derivs": POSE_DERIVS, "gndt_frontier": FRONTIER, "gndt_scan_cluster": SCAN_CLUSTER}
+# gndt_patch (PATCH above) is described and decoded the same way; tests/test_patch_host.py holds it against the header, since
+# tests/test_abi_layout_host.py names the records of this table one by one
+PATCH_RECORD = {"gndt_patch": PATCH}
 
 
 @functools.lru_cache(maxsize=None)
@@ -417,6 +430,7 @@ def _prototypes():
         "gndt_view_gain": [H, vp, sz, vp, sz, sz, P(ViewParams), vp, vp, vp],
         "gndt_plan_routes": [H, vp, sz, sz, P(PlanParams), vp, u32, vp],
         "gndt_frontiers": [H, P(CropBox), P(FrontierParams), vp, vp, u32, vp],
+        "gndt_patches": [H, P(CropBox), P(PatchParams), vp, vp, u32, vp],
         "gndt_segment_scan": [H, vp, sz, sz, vp, P(SegmentParams), vp, vp, vp, u32, vp],
         "gndt_clearance": [H, P(Robot), P(ClearanceParams), vp, vp, vp, vp],
         # (the device twin also takes the box count where it lies on the device: not the host's arguments plus a stream)
@@ -473,7 +487,7 @@ def _prototypes():
     }
     # the device twins whose arguments are the host twin's with the stream behind them
     for name in ("gndt_build", "gndt_update", "gndt_remove", "gndt_query", "gndt_crop", "gndt_raster", "gndt_clear_rays", "gndt_score_poses",
-                 "gndt_score_derivs", "gndt_cast_rays", "gndt_view_gain", "gndt_plan_routes", "gndt_frontiers", "gndt_segment_scan",
+                 "gndt_score_derivs", "gndt_cast_rays", "gndt_view_gain", "gndt_plan_routes", "gndt_frontiers", "gndt_patches", "gndt_segment_scan",
                  "gndt_clearance", "gndt_route_field", "gndt_descend_routes", "gndt_walk_paths", "gndt_shortcut_routes",
                  "gndt_footprint_poses"):
         T[name + "_device"] = T[name] + [vp]

@@ -29,6 +29,7 @@ int tuning_set_option(int option, double value) {
         case GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP: t.clearance_one_workgroup = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_OBSTACLE_TALLY: t.obstacle_tally = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP: t.route_field_one_workgroup = value != 0.0; return GNDT_OK;
+        case GNDT_DEBUG_PATCH_LDS: if (!(value == 0.0 || value == 1.0)) return GNDT_ERR_INVALID; t.patch_lds = value != 0.0; return GNDT_OK;
         case GNDT_DEBUG_VIEW_THREADS:
             if (!(value >= 64.0 && value <= 1024.0) || value != (double)(int)value || ((int)value & 63)) return GNDT_ERR_INVALID;
             t.view_threads = (int)value; return GNDT_OK;
@@ -408,7 +409,7 @@ void gndt_destroy(gndt_handle* h) {
     free_cast(h);
     free_merge(h);
     free_obstacle(h);
-    for (gndt_handle::Scratch* a : {&h->plan.scratch, &h->frontier, &h->segment, &h->clearance, &h->walk, &h->route_field}) free_scratch(*a);
+    for (gndt_handle::Scratch* a : {&h->plan.scratch, &h->frontier, &h->patch, &h->segment, &h->clearance, &h->walk, &h->route_field}) free_scratch(*a);
     for (const RowArray& a : row_arrays(h->out))
         if (*a.p) (void)hipFree(*a.p);
     void* ptrs[] = {h->st_key, h->st_sums, h->st_count, h->st_first, h->stage, h->d_cnt, h->packed, h->d_nvalid, h->index.buf, h->io};

@@ -13,6 +13,7 @@
 //   gndt_api_plan.hip   route planning: A* routes to the flood's goal for a batch of starts
 //   gndt_api_frontier.hip  frontier extraction: the slopes where the map ends, clustered
 //   gndt_api_segment.hip   scan segmentation: the points of a scan the map does not explain, clustered
+//   gndt_api_patch.hip     surface patches: the map's nodes grown into planes over their normals and means
 //   gndt_api_clearance.hip  clearance field: per slope the steps to the nearest barrier, and where it is
 //   gndt_api_route_field.hip route field: per slope the least cost to a set of goals and the step to take, routes by descent
 //   gndt_api_obstacle.hip   obstacle field: per slope the steps to the nearest slope a box of the caller's list stands on
@@ -272,6 +273,9 @@ struct gndt_handle {
     // frontier extraction (gndt_frontier.hpp): per row its parent in the union-find (4 B), its root's member count, then place in the
     // list (4 B) and its open sides (1 B), and three counts per tile of rows; grown on demand
     Scratch frontier;
+    // surface patches (gndt_patch.hpp): per listed patch its ten fp64 sums (80 B), per row its parent in the union-find (4 B) and its
+    // root's member count, then place in the list (4 B), and three counts per tile of rows; grown on demand
+    Scratch patch;
     // scan segmentation (gndt_segment.hpp): the call's cell table (16 B a slot, the smallest power of two >= 2 n slots), per point its
     // cell's slot, then root (4 B), its parent in the union-find (4 B), its root's cells and points, then place (8 B) and its class
     // (1 B), and four counts per tile of points; grown on demand
@@ -442,6 +446,7 @@ struct Tuning {
     bool clearance_one_workgroup = true;   // GNDT_DEBUG_CLEARANCE_ONE_WORKGROUP   0: every round of the clearance field its own launch
     bool obstacle_tally = false;           // GNDT_DEBUG_OBSTACLE_TALLY            1: the obstacle field's marking pass keeps the tallies gndt_debug_obstacle_marks reads
     bool route_field_one_workgroup = true; // GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 0: every sweep of the route field its own launch
+    bool patch_lds = true;                 // GNDT_DEBUG_PATCH_LDS                 0: the patches' moment pass sends every wave's sums to memory itself
     int view_threads = 1024;               // GNDT_DEBUG_VIEW_THREADS              threads of a view gain workgroup at most (64 .. 1024, whole waves; same records at every value)
     int walk_step_table = 2;               // GNDT_DEBUG_WALK_STEP_TABLE          gndt_walk_paths*: 0 the steps found on the walk, 1 read from a per-call table, 2 by the map's size
     bool clear_extent = false;   // GNDT_DEBUG_CLEAR_EXTENT        the ray walk reads a column's rows only if its level extent meets the ray's

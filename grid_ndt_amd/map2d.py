@@ -14,7 +14,7 @@ from . import _lib
 from ._arrays import DeviceArrays, HostArrays, _stream_ptr, _stream_wait, _torch_stream_ctx   # noqa: F401 (tools read _stream_ptr here)
 from ._lib import (CastOut, CastParams, CastStats, Cells, ClearanceParams, ClearParams, ClearStats, CommSelftest, CropBox, CostStats,
                    DescendParams, ExchangeTimes, FootprintParams, FrontierParams, GndtError, MergeParams, MergeStats, ObstacleParams,
-                   OwnedInfo, Params, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteFieldParams, ScoreParams, SegmentParams,
+                   OwnedInfo, Params, PatchParams, Pcd, PlanParams, PointLayout, RasterLayers, Robot, RouteFieldParams, ScoreParams, SegmentParams,
                    ShortcutParams, Stats, ViewParams, WalkParams)
 
 DEMANDS = {"slope": 0, "true": 1}
@@ -529,6 +529,7 @@ class TwoDmap:
     DEBUG_PLACE_EMIT_WORDS = 12     # bitmap words up to which ordering and emit are one kernel: 0 .. 2^24 (16 384 by default; 0: always two)
     DEBUG_ROUTE_FIELD_ONE_WORKGROUP = 14   # 0: every sweep of the route field its own launch (1 by default)
     DEBUG_VIEW_THREADS = 15                # threads of a view_gain workgroup at most: a multiple of 64 in 64 .. 1024 (1024 by default)
+    DEBUG_PATCH_LDS = 16                   # 0: the patches' moment pass without its LDS stage (1 by default)
     DEBUG_OBSTACLE_TALLY = 13       # 1: the obstacle field's marking pass keeps the tallies of gndt_debug_obstacle_marks (0 by default)
 
     @staticmethod
@@ -817,6 +818,84 @@ class TwoDmap:
         pts = xp.stack(cols, 1).float() if on_dev else np.stack(cols, 1).astype(np.float32)
         pts[fr["size"] == 0] = float("nan")
         return pts
+
+    # ---- surface patches (gndt_patches*: the map's nodes grown into planes on the device) ----
+    PATCH_CANDIDATES = {"nodes": 0, "slopes": 1}
+    PATCH_CONNECTIVITY = {6: 1, 18: 2, 26: 3}
+    PATCH_HORIZONTAL, PATCH_VERTICAL, PATCH_INCLINED, PATCH_SLOPES_ONLY = 1, 2, 4, 8
+    PATCH_DTYPE = _lib.PATCH
+
+    def patch_params(self, candidates="nodes", connectivity=26, max_angle_deg=15.0, max_offset=None, max_var=None, level_deg=10.0, min_size=1):
+        """gndt_patch_params of patches()'s arguments, the thresholds as the float32 the library reads: cos_min = float32(cos(
+        max_angle_deg)), cos_level = float32(cos(level_deg)), sin_level = float32(sin(level_deg)); max_offset None = 0.5 zLen, max_var
+        None = (0.25 zLen)^2"""
+        if connectivity not in self.PATCH_CONNECTIVITY:
+            raise ValueError("connectivity must be 6, 18 or 26")
+        max_offset = 0.5 * self.zLen if max_offset is None else max_offset
+        max_var = (0.25 * self.zLen) ** 2 if max_var is None else max_var
+        cos_min = np.float32(np.cos(np.deg2rad(float(max_angle_deg))))
+        cos_level, sin_level = np.float32(np.cos(np.deg2rad(float(level_deg)))), np.float32(np.sin(np.deg2rad(float(level_deg))))
+        return PatchParams(_enum(self.PATCH_CANDIDATES, candidates), self.PATCH_CONNECTIVITY[connectivity], float(cos_min),
+                           float(np.float32(max_offset)), float(np.float32(max_var)), float(cos_level), float(sin_level), int(min_size))
+
+    def patches(self, candidates="nodes", connectivity=26, max_angle_deg=15.0, max_offset=None, max_var=None, level_deg=10.0, min_size=1,
+                box=None, labels=False, max_patches=None, stream=None, host=False):
+        """What the map is made of, as planes (include/gndt.h "surface patches" defines every word).  A candidate is a node with
+        statistics — candidates "slopes": with a slope as well — whose rough / count is at most max_var (m^2; None = (0.25 zLen)^2).
+        Adjacent candidates (connectivity 6, 18 or 26; two levels of one column are adjacent) link when their normals are within
+        max_angle_deg of each other, sign free, and each one's mean lies within max_offset (m; None = 0.5 zLen) of the other's plane;
+        the connected components are the patches: single-link growing, so a gently curved surface is ONE patch and its `var` shows it.
+        Returns a dict with one [K] array per field of gndt_patch (label, nodes, points, sx_min .. sz_max, sum_px, sum_py, sum_pz, var,
+        kind; centroid and normal are [K, 3]) for the patches of at least min_size nodes in ascending label, `counts` ([4]: those
+        patches, candidates, patches of any size, 0) and, with labels=True, `labels` (int32 per row of export(): its patch's label, -1
+        for a row that is no candidate).  kind: PATCH_HORIZONTAL (|normal_z| >= cos(level_deg)), PATCH_VERTICAL (<= sin(level_deg)) or
+        PATCH_INCLINED, and PATCH_SLOPES_ONLY.  Labels, counts and integer fields are exact; centroid, normal and var are fp64 sums added
+        with atomics, equal to rounding from run to run.  box, max_patches, stream and host are frontiers()'s box, max_clusters,
+        stream and host: device lists keep max_patches entries with nodes 0 behind the counts[0] found, host lists are cut."""
+        if self._h is None:
+            self._handle()
+        prm = self.patch_params(candidates, connectivity, max_angle_deg, max_offset, max_var, level_deg, min_size)
+        b = C.byref(CropBox(*[int(v) for v in box])) if box is not None else None
+        n = int(self.sync()[0]) if labels else 0
+        be = HostArrays if host else DeviceArrays(self._cuda(), stream)
+        with be.ctx():
+            counts = be.zeros(4, np.uint32)
+            label = be.empty(n, np.int32) if labels else None
+        call = lambda recs, cap: self._call(be, "patches", b, C.byref(prm), be.ptr(label), be.ptr(recs) if cap else C.c_void_p(0), cap, be.addr(counts))
+        if max_patches is None:
+            call(None, 0)
+            with be.ctx():                              # (read on the stream the count was enqueued on: the copy waits for it)
+                max_patches = int(counts[0])
+        with be.ctx():
+            recs = be.records(int(max_patches), _lib.PATCH)
+        call(recs, len(recs))
+        if host:
+            recs = recs[:min(int(counts[0]), len(recs))]
+        out = be.fields(recs, _lib.PATCH)
+        out["counts"] = counts
+        if labels:
+            out["labels"] = label
+        return out
+
+    def patch_planes(self, p):
+        """The planes of patches(): (centroids [K, 3], unit normals [K, 3], offsets [K] = normal . centroid) in world coordinates, fp64;
+        numpy in, numpy out; torch in, torch out.  An entry of nodes 0 (behind the patches found) gives NaN."""
+        cen, nrm = p["centroid"], p["normal"]
+        on_dev = not isinstance(cen, np.ndarray)
+        cen, nrm = (cen.clone(), nrm.clone()) if on_dev else (cen.copy(), nrm.copy())
+        none = p["nodes"] == 0
+        cen[none] = float("nan")
+        nrm[none] = float("nan")
+        return cen, nrm, (cen * nrm).sum(1)
+
+    def patch_rows(self, p, labels, which):
+        """The member rows of patch `which` (an index into the lists of p = patches(..., labels=True)) in ascending order: int64, numpy
+        or torch as `labels` is"""
+        label = int(p["label"][which])
+        if isinstance(labels, np.ndarray):
+            return np.flatnonzero(labels == label).astype(np.int64)
+        import torch
+        return torch.nonzero(labels == label).reshape(-1)
 
     # ---- clearance field (gndt_clearance*: per slope the steps to the nearest barrier, and where it is) ----
     CLEARANCE_SOURCES = {"blocked": 1, "open": 2, "overhead": 4}

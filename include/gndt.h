@@ -620,6 +620,82 @@ int gndt_frontiers_device(gndt_handle* h, const gndt_crop_box* box, const gndt_f
 int gndt_frontiers(gndt_handle* h, const gndt_crop_box* box, const gndt_frontier_params* params,
                    uint32_t* label_host, gndt_frontier* clusters_host, uint32_t cluster_cap, uint32_t* counts_host);
 
+/* ---- surface patches: map nodes grouped into planes, on the device ------------------------------------------------------------
+ * What the map is made of: this floor, that wall, this ramp, the deck above the ground.  Every node carries the normal and the
+ * thickness of a local plane; region growing over them turns 800 k rows into a few hundred records — to publish, log and compare; to
+ * say which rows are wall, floor or inclined; to hand plane pairs to a check of a registration; to name the drivable surface as one
+ * object with an extent and a tilt.  lin(s) = s > 0 ? s - 1 : s, as in the frontiers.
+ * Rounding: every fp32 operation below is ONE rounded operation in the order written, no fused multiply-add (numpy float32 gives the
+ * same bits).
+ *   candidate   a row inside `box` (NULL = the whole map; the frontiers' box rules) that has GNDT_FLAG_HAS_STATS, under
+ *               GNDT_PATCH_SLOPES also GNDT_FLAG_SLOPE (GNDT_PATCH_NODES: nothing more), and rough <= max_var * (float)count (one fp32
+ *               multiply).  rough is the STORED value — the least eigenvalue of the node's scatter, the reference's 0 -> 0.01
+ *               included: a perfectly flat node is a candidate whenever max_var * count >= 0.01.  A node that has statistics but no
+ *               slope (demand "slope": a node with another one of its column close above it) stores no normal and rough 0: under
+ *               GNDT_PATCH_NODES it is a candidate that links to nothing (c = 0) and ends as a patch of one.  Maps built with demand
+ *               "true" give every node with statistics its normal: build so where walls — stacks of nodes — are to become patches.
+ *   adjacent    rows a != b with |lin(sx_a) - lin(sx_b)|, |lin(sy_a) - lin(sy_b)| and |lin(sz_a) - lin(sz_b)| all <= 1 and at most
+ *               `connectivity` axes differing: 1, 2 or 3 for the 6-, 18- or 26-neighbourhood; 0 = 3.  Unlike the frontiers, two nodes
+ *               of one column that are one level apart ARE adjacent: a wall is a stack.
+ *   link        two adjacent candidates with normals n, means m (fp32, as stored) for which both tests pass:
+ *                 c = (nax*nbx + nay*nby) + naz*nbz                     fabsf(c) >= cos_min          (normals are sign free)
+ *                 d = m_b - m_a componentwise;  ea = fabsf((nax*dx + nay*dy) + naz*dz),  eb = fabsf((nbx*dx + nby*dy) + nbz*dz)
+ *                                                                       ea <= max_offset and eb <= max_offset
+ *               fp32 subtraction is exactly antisymmetric, so the rule is symmetric to the bit.
+ *   patch       a connected component of the links; its label is its smallest member row.  A candidate without a link is a patch of
+ *               one.  This is single-link growing: a gently curved surface chains into ONE patch — the record's var shows it.
+ * Outputs (the frontiers' conventions): patches[] holds the patches with at least min_size members in ascending label, the first
+ * patch_cap of them (nothing is written beyond those); counts[0] is how many such patches exist — it may exceed patch_cap (patch_cap 0
+ * with patches NULL only counts) — counts[1] the candidates, counts[2] the patches of any size, counts[3] 0.  label[row] (optional,
+ * num_nodes entries) is the row's patch label, GNDT_NO_ROW for a row that is no candidate; min_size does not filter it.
+ * A patch's record: label, nodes (members), points (the sum of their counts), the bounds of their signed indices on the three axes, the
+ * sums of lin(sx), lin(sy), lin(sz), and the plane of the members merged as Gaussians: with r the label row's mean as fp64,
+ * d_i = mean_i - r, N = Sum count_i, S1 = Sum count_i d_i and S2 = Sum (scatter_i + count_i d_i d_i^T) — scatter_i the node's stored cov,
+ * moved by the moment match of the map pyramids (gndt_coarsen_device) —
+ *   C = S2 - S1 S1^T / N     centroid = r + S1 / N     normal = the unit eigenvector of C's least eigenvalue (the build's fp64 solver),
+ *   its first non-zero component in the order z, y, x positive     var = max(lambda_min, 0) / N (m^2: the patch's thickness)
+ *   kind: GNDT_PATCH_HORIZONTAL |normal_z| >= cos_level, GNDT_PATCH_VERTICAL |normal_z| <= sin_level (tested in that order),
+ *         GNDT_PATCH_INCLINED neither; GNDT_PATCH_SLOPES_ONLY every member has GNDT_FLAG_SLOPE (an integer tally).
+ * What is exact: labels, counts and every integer field (kind's SLOPES_ONLY bit included), whatever order threads work in.  The fp64 sums
+ * are accumulated with atomics, so centroid, normal, var and the three orientation bits of kind are reproducible only to fp64 rounding
+ * from run to run — the standard the build's own node statistics have; no bits are promised for them.
+ * Order and lifetime are the frontiers': the call first finishes what gndt_sync finishes, builds or reuses the map's column index and
+ * enqueues its kernels on `hip_stream` (NULL = the handle's stream), not awaited; gndt_patches is synchronous.  Row numbers stay valid
+ * until the next build, update, remove, crop or reset.  The map is not modified; no cost map is read.  Work memory (8 bytes a row and 80
+ * a listed patch) belongs to the handle and grows with the map.  A map without rows gives four zero counts.  There is no CPU path.
+ * A sharded map answers from the rows this rank holds: a plane that crosses ranks is one patch per rank.
+ * GNDT_ERR_INVALID: a null handle, params or counts, unknown candidates, connectivity > 3, a threshold (cos_min, max_offset, max_var,
+ * cos_level, sin_level) that is negative or not finite, cos_min or cos_level above 1, a non-zero reserved word, a bad box (the frontiers'
+ * rules), patches NULL with patch_cap > 0 or the reverse, a device pointer not aligned as its type is, no finished build, a stream under
+ * hipGraph capture (the call is not recorded). */
+enum { GNDT_PATCH_NODES = 0, GNDT_PATCH_SLOPES = 1 };
+enum { GNDT_PATCH_HORIZONTAL = 1, GNDT_PATCH_VERTICAL = 2, GNDT_PATCH_INCLINED = 4, GNDT_PATCH_SLOPES_ONLY = 8 };
+typedef struct gndt_patch_params {
+    int32_t  candidates;     /* GNDT_PATCH_NODES / _SLOPES */
+    uint32_t connectivity;   /* axes that may differ between adjacent rows: 1, 2 or 3; 0 = 3 */
+    float    cos_min;        /* least |cosine| between linked normals, 0 .. 1 */
+    float    max_offset;     /* m: most a linked node's mean may lie off the other's plane */
+    float    max_var;        /* m^2: a candidate's rough / count at most */
+    float    cos_level;      /* |normal_z| from which a patch is HORIZONTAL, 0 .. 1 */
+    float    sin_level;      /* |normal_z| up to which a patch is VERTICAL */
+    uint32_t min_size;       /* patches with fewer members are left out of the list; 0 = 1 */
+    uint32_t reserved[4];    /* 0 */
+} gndt_patch_params;
+typedef struct gndt_patch {            /* 128 bytes */
+    uint32_t label, nodes;  uint64_t points;                 /* smallest member row; members; sum of their counts */
+    int32_t  sx_min, sx_max, sy_min, sy_max, sz_min, sz_max;
+    int64_t  sum_px, sum_py, sum_pz;                          /* sums of lin(s) over the members */
+    double   centroid[3], normal[3], var;                     /* the members merged as Gaussians */
+    uint32_t kind, reserved;
+} gndt_patch;
+/* Device memory out: label_dev [num_nodes] or NULL, patches_dev [patch_cap], counts_dev [4]. */
+int gndt_patches_device(gndt_handle* h, const gndt_crop_box* box, const gndt_patch_params* params,
+                        uint32_t* label_dev /* [num_nodes] or NULL */, gndt_patch* patches_dev, uint32_t patch_cap,
+                        uint32_t* counts_dev /* [4] */, void* hip_stream);
+/* Host memory out, through a device scratch the handle owns and grows; returns when the answers are in place. */
+int gndt_patches(gndt_handle* h, const gndt_crop_box* box, const gndt_patch_params* params,
+                 uint32_t* label_host, gndt_patch* patches_host, uint32_t patch_cap, uint32_t* counts_host);
+
 /* ---- clearance field: hops to the nearest barrier for every slope ------------------------------------------------------------
  * What a planner asks after "can the robot stand here" (the flood's CollisionCheck) and "what does it cost to reach the goal from
  * here" (h): how far is this slope from the nearest place the robot cannot go?  The answer is an inflation layer for a costmap, a
@@ -1686,7 +1762,10 @@ int gndt_debug_enable_stamps(int on);
  *   GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP value == 0: gndt_route_field* launch every sweep on its own, the one-workgroup kernel that holds a
  *                                 small map's keys in LDS is not used (tests run the field both ways)               default 1
  *   GNDT_DEBUG_VIEW_THREADS       threads of a gndt_view_gain* workgroup at most, a multiple of 64 in 64 .. 1024 (a fan of fewer rays
- *                                 takes fewer); the records do not depend on it (tests run several)                 default 1024 */
+ *                                 takes fewer); the records do not depend on it (tests run several)                 default 1024
+ *   GNDT_DEBUG_PATCH_LDS          value == 0: the moment pass of gndt_patches* sends every wavefront's sums to memory itself instead of
+ *                                 combining a workgroup's waves in LDS first (tools/measure_patches.py A/Bs the two; the same
+ *                                 integer fields, plane fields equal to fp64 rounding)                              default 1 */
 #define GNDT_DEBUG_VERBOSE 1
 #define GNDT_DEBUG_TILE_RATIO 2
 #define GNDT_DEBUG_COST_ONE_WORKGROUP 3
@@ -1702,6 +1781,7 @@ int gndt_debug_enable_stamps(int on);
 #define GNDT_DEBUG_OBSTACLE_TALLY 13
 #define GNDT_DEBUG_ROUTE_FIELD_ONE_WORKGROUP 14
 #define GNDT_DEBUG_VIEW_THREADS 15
+#define GNDT_DEBUG_PATCH_LDS 16
 int gndt_debug_set_option(int option, double value);
 /* The -DGNDT_POISON build only (a regular build returns GNDT_ERR_INVALID and writes nothing): the bytes of device memory and of pinned
  * host memory this process has filled with the poison byte so far.  Tests prove with it that a poisoned run was one. */
