@@ -24,6 +24,9 @@ EDGES = dict(
     derivs_reduce_unroll=2, derivs_reduce_stride=2048,     # k_score_derivs_reduce
     score_reduce_points=1_048_576,              # score_reduce_stride * kScoreTile: point 1 048 576 opens tile 4096
     derivs_reduce_points=524_288,               # derivs_reduce_stride * kScoreTile: point 524 288 opens tile 2048
+    patch_reduce_blocks=512,                    # grid_for(n, 256, 512): k_patch_reduce and k_patch_moments<true> (gndt_api_patch.hip)
+    patch_reduce_cap=131_072,                   # row patch_reduce_cap is the first of their second trip
+    kPatchSlots=8, kPatchWaveMin=4,             # k_patch_moments' tagged LDS slots; rows of a patch in a wave from which they are combined
 )
 assert EDGES["grid_cap"] == EDGES["grid_block"] * EDGES["grid_max_blocks"]
 assert EDGES["kCropTile"] == EDGES["kCropT"] * EDGES["kCropV"] and EDGES["scan_carry_rows"] == EDGES["kCropScanT"] * EDGES["kCropTile"]
@@ -31,6 +34,7 @@ assert EDGES["score_reduce_stride"] == EDGES["score_reduce_unroll"] * EDGES["kSc
 assert EDGES["derivs_reduce_stride"] == EDGES["derivs_reduce_unroll"] * EDGES["kScoreReduceBlock"]
 assert EDGES["score_reduce_points"] == EDGES["score_reduce_stride"] * EDGES["kScoreTile"]
 assert EDGES["derivs_reduce_points"] == EDGES["derivs_reduce_stride"] * EDGES["kScoreTile"]
+assert EDGES["patch_reduce_cap"] == EDGES["grid_block"] * EDGES["patch_reduce_blocks"]
 
 CAP = EDGES["grid_cap"]
 BASE = 4093            # prime: coprime to 64, 256 and 524 288, so a lane's item of the second trip is another one than of the first
@@ -85,7 +89,11 @@ def lattice_points(W, H, holes=(), count=None, tail=()):
     """The points frontier_ref.cells_cloud draws for lattice_cells(W, H, holes, count, tail): the origin point, then 3 x 3 points a cell
     with the same ripple, in the same order, from the same float64 expressions.  One storey, one node per column, every one a slope;
     rows follow first sight, so row r is cell r."""
-    ix, iy = lattice_cells(W, H, holes, count, tail)
+    return cells_points(*lattice_cells(W, H, holes, count, tail))
+
+
+def cells_points(ix, iy):
+    """lattice_points for any list of cells (ix, iy), in their order"""
     k = ix
     ab = np.array([0.12, 0.25, 0.38])
     x = np.broadcast_to((ix * fr.GL)[:, None, None] + ab[None, :, None], (len(k), 3, 3))
@@ -95,6 +103,43 @@ def lattice_points(W, H, holes=(), count=None, tail=()):
     pts[0] = fr.ORIGIN
     pts[1:, 0], pts[1:, 1], pts[1:, 2] = x.reshape(-1), y.reshape(-1), z.reshape(-1)
     return pts
+
+
+FLOOR_LINE = 256        # cells a line of floors_cells: a line is a workgroup's rows
+
+
+def stripes_cells(H, lines):
+    """-> (ix, iy) of the cells (2 i, j), i < lines outer, j < H inner: every second line of cells is empty, so line i is a patch of its
+    own under every connectivity — H rows, the rows i H .. i H + H - 1, labelled i H"""
+    i, j = np.divmod(np.arange(lines * H, dtype=np.int64), H)
+    return 2 * i, j
+
+
+def floors_cells(a, n):
+    """-> (ix, iy) of two floors of lines of FLOOR_LINE cells: the first `a` cells line after line, two empty lines, then n - a cells
+    line after line: two patches, the rows 0 .. a - 1 labelled 0 and the rows a .. n - 1 labelled a"""
+    assert 0 < a < n
+    k = np.arange(n, dtype=np.int64)
+    second = k >= a
+    k = np.where(second, k - a, k)
+    first_lines = -(-a // FLOOR_LINE)
+    return k // FLOOR_LINE + np.where(second, first_lines + 2, 0), k % FLOOR_LINE
+
+
+# The surface patches' scenes (tests/test_gpu_patch_edges.py on the device, tests/test_patch_fast_ref_host.py on the oracle's maps)
+PATCH_TRIP = EDGES["patch_reduce_cap"]
+STRIPES = {3: 70, 4: 70, 5: 70, 16: 20, 96: 5}                     # H -> lines: 210 to 480 rows, one and two workgroups
+FLOORS_N = 2 * PATCH_TRIP + 4096 + 65                              # three trips of the reductions, the last wave of one row
+FLOORS_A = (PATCH_TRIP + 4096 + 30, PATCH_TRIP + 4096 + 3)         # the second floor's first row: 30 / 3 rows into a wave of trip 2
+TRIP_STRIPES = (64, 2100)                                          # a wave a patch, 3 328 rows behind the first trip
+
+
+def wave_groups(patch_of_row, wave=64):
+    """the rows of one patch in one wave, for rows 0 .. n - 1 -> (wave, patch, rows) arrays, in row order"""
+    p = np.asarray(patch_of_row, np.int64)
+    w = np.arange(len(p), dtype=np.int64) // wave
+    start = np.flatnonzero(np.r_[True, (p[1:] != p[:-1]) | (w[1:] != w[:-1])])
+    return w[start], p[start], np.diff(np.r_[start, len(p)])
 
 
 def pitch_holes(W, H, px=37, py=41):

@@ -1,7 +1,8 @@
 """Surface patches restated from the exported rows (include/gndt.h "surface patches"): a dict of keys, a breadth-first search, the link
 rule in numpy float32 with one operation a line, the plane fields in float64 with the members summed in ascending row.  Shares no code
-with grid_ndt_amd/csrc/gndt_patch.hpp.  Also the hand-drawn scene and the clouds the patch tests draw their maps with.  Test
-infrastructure only."""
+with grid_ndt_amd/csrc/gndt_patch.hpp.  patches_fast restates the same once more without the dict and the search (sorted keys,
+hooking and pointer jumping, ufunc.at) for maps of a million rows; tests/test_patch_fast_ref_host.py holds the two equal to the bit.
+Also the hand-drawn scene and the clouds the patch tests draw their maps with.  Test infrastructure only."""
 from collections import deque
 
 import numpy as np
@@ -57,8 +58,8 @@ def link_terms(na, nb, ma, mb):
     return np.abs(c), ea, eb
 
 
-class Map:
-    """The exported rows with their key dict"""
+class Rows:
+    """The exported rows as arrays"""
 
     def __init__(self, cells):
         n = self.n = int(cells["num_nodes"])
@@ -70,7 +71,6 @@ class Map:
         self.normal = np.asarray(cells["normal"][:n], F32).reshape(n, 3)
         self.cov = np.asarray(cells["cov"][:n], F32).reshape(n, 6)
         self.lin = np.stack([np.where(v > 0, v - 1, v) for v in (self.sx, self.sy, self.sz)], 1)
-        self.key = {tuple(int(v) for v in self.lin[r]): r for r in range(n)}
 
     def candidates(self, R, box=None):
         ok = (self.flags & 1) != 0
@@ -81,6 +81,14 @@ class Map:
         room = F32(R["max_var"]) * self.count.astype(F32)
         assert room.dtype == F32
         return ok & (self.rough <= room)
+
+
+class Map(Rows):
+    """The exported rows with their key dict"""
+
+    def __init__(self, cells):
+        super().__init__(cells)
+        self.key = {tuple(int(v) for v in self.lin[r]): r for r in range(self.n)}
 
     def adjacent_pairs(self, cand, connectivity):
         """every adjacent pair (a, b) of candidates with a < b"""
@@ -111,7 +119,7 @@ class Map:
 
     def patches(self, R, box=None):
         """-> dict(label [n] uint32, patches: RECORD array of EVERY patch in ascending label, rows: the candidates, pairs: (A, B,
-        linked, angle, offset) of the adjacent candidate pairs, cand)"""
+        linked, angle, offset) of the adjacent candidate pairs, cand, posed: well_posed's answer for every patch)"""
         n = self.n
         conn = int(R["connectivity"]) or 3
         cand = self.candidates(R, box)
@@ -122,7 +130,7 @@ class Map:
             nbrs[a].append(b)
             nbrs[b].append(a)
         label = np.full(n, NO_ROW, np.uint32)
-        recs = []
+        recs, posed = [], []
         for r0 in np.flatnonzero(cand).tolist():            # ascending: a component is found from its smallest row
             if label[r0] != NO_ROW:
                 continue
@@ -136,10 +144,16 @@ class Map:
                         label[t] = r0
                         queue.append(t)
             recs.append(self.record(R, r0, sorted(members)))
+            posed.append(self.last_posed())
         records = np.zeros(len(recs), RECORD)
         for i, rec in enumerate(recs):
             records[i] = rec
-        return dict(label=label, patches=records, rows=int(cand.sum()), pairs=(A, B, linked, angle, offset), cand=cand)
+        return dict(label=label, patches=records, rows=int(cand.sum()), pairs=(A, B, linked, angle, offset), cand=cand, posed=posed)
+
+    def last_posed(self):
+        """of the patch record() saw last: (well posed, spread) — see well_posed"""
+        w = self.last_eigenvalues
+        return bool(w[0] > 0.0 and w[1] >= 100.0 * w[0]), self.last_spread
 
     def record(self, R, r0, members):
         rec = np.zeros((), RECORD)
@@ -195,6 +209,131 @@ def least_eigenvalue(Cm, x0):
     return float(x)
 
 
+def least_eigenvalues(C6, x0):
+    """least_eigenvalue for arrays: C6 [P, 6] = (xx, xy, xz, yy, yz, zz), x0 [P] -> [P] float64; the same long-double operations in
+    the same order, an element whose derivative vanishes stays where it is from then on"""
+    L = np.longdouble
+    a, b, c, d, e, f = (C6[:, k].astype(L) for k in range(6))
+    x = np.asarray(x0).astype(L)
+    live = np.ones(len(x), bool)
+    for _ in range(4):
+        A, D, F = a - x, d - x, f - x
+        p = A * (D * F - e * e) - b * (b * F - e * c) + c * (b * e - D * c)
+        dp = -((D * F - e * e) + (A * F - c * c) + (A * D - b * b))
+        live &= dp != 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x = np.where(live, x - p / dp, x)
+    return x.astype(np.float64)
+
+
+KEY_BITS, KEY_BIAS = 21, 1 << 20       # a linear index of +-65 536 and a level of the codec's range fit 21 bits with room for +-1
+
+
+def patches_fast(cells, R, box=None):
+    """Map.patches without the key dict and the search, for maps of a million rows: sorted 64-bit keys and searchsorted for the
+    neighbours, link_terms on the pairs, components by hooking the larger root under the smaller and pointer jumping, the fields by
+    ufunc.at in ascending row, one batched eigh.  cells: an export, or the Rows of one.  -> dict(label, patches: RECORD array of EVERY
+    patch in ascending label, rows, cand, eigenvalues [P, 3] (the least one polished), spread [P]: tr(S2) / N — what well_posed_fast
+    reads)"""
+    m = cells if isinstance(cells, Rows) else Rows(cells)
+    n = m.n
+    conn = int(R["connectivity"]) or 3
+    cand = m.candidates(R, box)
+    rows = np.flatnonzero(cand)
+    assert n == 0 or (np.abs(m.lin).max() < KEY_BIAS - 1)
+    key = ((m.lin[rows, 0] + KEY_BIAS) << (2 * KEY_BITS)) | ((m.lin[rows, 1] + KEY_BIAS) << KEY_BITS) | (m.lin[rows, 2] + KEY_BIAS)
+    order = np.argsort(key, kind="stable")
+    ks = key[order]
+    assert (ks[1:] != ks[:-1]).all(), "two rows of one key"
+    A, B = [], []
+    for dx, dy, dz in OFFSETS:
+        if (dx != 0) + (dy != 0) + (dz != 0) > conn or not len(rows):
+            continue
+        want = key + ((dx << (2 * KEY_BITS)) + (dy << KEY_BITS) + dz)
+        pos = np.minimum(np.searchsorted(ks, want), len(ks) - 1)
+        b = rows[order[pos]]
+        hit = (ks[pos] == want) & (b > rows)
+        a, b = rows[hit], b[hit]
+        c, ea, eb = link_terms(m.normal[a], m.normal[b], m.mean[a], m.mean[b])
+        linked = (c >= R["cos_min"]) & (ea <= R["max_offset"]) & (eb <= R["max_offset"])
+        A.append(a[linked])
+        B.append(b[linked])
+    A, B = (np.concatenate(v) if v else np.zeros(0, np.int64) for v in (A, B))
+    # components: parent[x] <= x throughout, flat before every hooking, so what is hooked is a root and the root is the smallest row
+    parent = np.arange(n, dtype=np.int64)
+    rounds = 0
+    while len(A):
+        pa, pb = parent[A], parent[B]
+        apart = pa != pb
+        if not apart.any():
+            break
+        A, B, pa, pb = A[apart], B[apart], pa[apart], pb[apart]
+        np.minimum.at(parent, np.maximum(pa, pb), np.minimum(pa, pb))
+        while True:
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+        rounds += 1
+    label = np.where(cand, parent, NO_ROW).astype(np.uint32)
+    roots = rows[parent[rows] == rows]
+    at = np.searchsorted(roots, parent[rows])                      # the patch of every candidate, candidates in ascending row
+    P_ = len(roots)
+    rec = np.zeros(P_, RECORD)
+    rec["label"] = roots
+    rec["nodes"] = np.bincount(at, minlength=P_)
+    i64 = lambda fill=0: np.full(P_, fill, np.int64)
+    points = i64()
+    np.add.at(points, at, m.count[rows].astype(np.int64))
+    rec["points"] = points
+    for k, v in (("sx", m.sx), ("sy", m.sy), ("sz", m.sz)):
+        lo, hi = i64(np.iinfo(np.int64).max), i64(np.iinfo(np.int64).min)
+        np.minimum.at(lo, at, v[rows])
+        np.maximum.at(hi, at, v[rows])
+        rec[k + "_min"], rec[k + "_max"] = lo, hi
+    for axis, k in enumerate(("sum_px", "sum_py", "sum_pz")):
+        tot = i64()
+        np.add.at(tot, at, m.lin[rows, axis])
+        rec[k] = tot
+    slopes = i64()
+    np.add.at(slopes, at, ((m.flags[rows] & 2) != 0).astype(np.int64))
+    # the ten sums about the label row's mean: Map.record's terms, added in ascending row
+    ref = m.mean[roots].astype(np.float64)
+    cnt = m.count[rows].astype(np.float64)
+    d = m.mean[rows].astype(np.float64) - ref[at]
+    cv = m.cov[rows].astype(np.float64)
+    N, S1, S2 = np.zeros(P_), np.zeros((P_, 3)), np.zeros((P_, 6))
+    np.add.at(N, at, cnt)
+    for j in range(3):
+        np.add.at(S1[:, j], at, cnt * d[:, j])
+    for j, (u, v) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))):
+        np.add.at(S2[:, j], at, cv[:, j] + cnt * (d[:, u] * d[:, v]))
+    C6 = np.stack([S2[:, j] - (S1[:, u] * S1[:, v]) / N for j, (u, v) in enumerate(((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2)))], 1)
+    Cm = C6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(P_, 3, 3)
+    w, v = np.linalg.eigh(Cm) if P_ else (np.zeros((0, 3)), np.zeros((0, 3, 3)))
+    v0 = v[:, :, 0]
+    nrm = v0 / np.array([np.linalg.norm(x) for x in v0]).reshape(P_, 1)      # (norm's own dot product, vector by vector: the same bits)
+    # the sign: the last non-zero component among z, y, x is positive
+    lead = np.where(nrm[:, 2] != 0.0, nrm[:, 2], np.where(nrm[:, 1] != 0.0, nrm[:, 1], nrm[:, 0]))
+    nrm = np.where((lead < 0.0)[:, None], -nrm, nrm)
+    w = w.copy()
+    w[:, 0] = least_eigenvalues(C6, w[:, 0])
+    rec["centroid"], rec["normal"], rec["var"] = ref + S1 / N[:, None], nrm, np.maximum(w[:, 0], 0.0) / N
+    az = np.abs(nrm[:, 2])
+    kind = np.where(az >= float(R["cos_level"]), HORIZONTAL, np.where(az <= float(R["sin_level"]), VERTICAL, INCLINED))
+    rec["kind"] = kind | np.where(slopes == rec["nodes"], SLOPES_ONLY, 0)
+    spread = ((S2[:, 0] + S2[:, 3]) + S2[:, 5]) / N
+    return dict(label=label, patches=rec, rows=len(rows), cand=cand, eigenvalues=w, spread=spread, rounds=rounds)
+
+
+def well_posed_fast(ref, want):
+    """well_posed for the records `want` (any of ref's patches) from what patches_fast kept -> (posed [len(want)] bool, spread)"""
+    at = np.searchsorted(ref["patches"]["label"], want["label"])
+    assert np.array_equal(ref["patches"]["label"][at], want["label"])
+    w = ref["eigenvalues"][at]
+    return (w[:, 0] > 0.0) & (w[:, 1] >= 100.0 * w[:, 0]), ref["spread"][at]
+
+
 def listed(ref, min_size=1):
     """the patches of `ref` the call lists, and its four counts"""
     keep = ref["patches"][ref["patches"]["nodes"] >= max(int(min_size), 1)]
@@ -238,8 +377,7 @@ def well_posed(m, R, ref, rec):
     compared with the restatement's only then; the patch's mean squared distance from its label row's mean, tr(S2) / N)"""
     members = np.flatnonzero(ref["label"] == rec["label"]).tolist()
     m.record(R, int(rec["label"]), members)
-    w = m.last_eigenvalues
-    return w[0] > 0.0 and w[1] >= 100.0 * w[0], m.last_spread
+    return m.last_posed()
 
 
 def planes_agree(m, R, ref, got, want, what="", spread_slack=False):
@@ -249,12 +387,16 @@ def planes_agree(m, R, ref, got, want, what="", spread_slack=False):
     C = S2 - S1 S1^T / N cancels the patch's spread about its label row, so each of the `nodes` roundings of either side's sums, up to
     2^-53 tr(S2) a term, can land on the least eigenvalue whole, and a backward-stable solver answers for a matrix a few (8) ulps of
     the LARGEST eigenvalue (<= tr(S2)) away; a patch far thinner than its spread holds no ten digits of var in fp64, whoever sums it."""
-    posed = [well_posed(m, R, ref, rec) for rec in want]
-    keep = np.array([p[0] for p in posed], bool)
+    if "eigenvalues" in ref:                 # patches_fast's answer: m may be None
+        keep, spread = well_posed_fast(ref, want)
+    else:
+        posed = [well_posed(m, R, ref, rec) for rec in want]
+        keep, spread = np.array([p[0] for p in posed], bool), np.array([p[1] for p in posed], np.float64)
     g, w = got[keep], want[keep]
-    slack = (2.0 * w["nodes"] + 8.0) * 2.0 ** -53 * np.array([p[1] for p in posed])[keep] if spread_slack else None
+    slack = (2.0 * w["nodes"] + 8.0) * 2.0 ** -53 * spread[keep] if spread_slack else None
     dc, dn, dv = plane_deviation(g, w, slack)
     print(f"patch planes {what}: {int(keep.sum())} of {len(want)} compared, centroid {dc:.3e} m, normal {dn:.3e}, var rel {dv:.3e}")
+    ref["deviation"] = (dc, dn, dv)
     assert dc <= PLANE_ABS and dn <= PLANE_ABS and dv <= VAR_REL, (what, dc, dn, dv)
     assert np.array_equal(g["kind"], w["kind"]), (what, g["kind"], w["kind"])
     return int(keep.sum())

@@ -86,6 +86,54 @@ def test_the_launches_still_cap_at_the_tables_count():
     assert "i0 += gsz * ILP" in _text("gndt_query.hpp") and "grid_for((n + ILP - 1) / ILP, 256, 2048)" in _text("gndt_api_query.hip")
 
 
+def test_the_patch_reductions_constants_and_launch_are_the_tables():
+    E = es.EDGES
+    patch = _text("gndt_patch.hpp")
+    for name in ("kPatchSlots", "kPatchWaveMin"):
+        assert _const(patch, name) == E[name], name
+    # the one launch of fewer workgroups carries both reductions; every other row pass of the call is the frontiers' launch
+    calls = _grid_for_calls(_text("gndt_api_patch.hip"))
+    few = [c for c in calls if re.fullmatch(r"n, 256, \d+", c) and not c.endswith(", 2048")]
+    assert few == ["n, %d, %d" % (E["grid_block"], E["patch_reduce_blocks"])], calls
+    assert "n, 256, 2048" in calls
+    assert E["patch_reduce_cap"] == E["grid_block"] * E["patch_reduce_blocks"] == es.PATCH_TRIP
+    assert E["kPatchSlots"] & (E["kPatchSlots"] - 1) == 0
+
+
+@pytest.mark.parametrize("H,lines", [(3, 70), (4, 70), (5, 70), (16, 20), (64, 30), (96, 5)])
+def test_premise_stripes_are_a_patch_a_line_all_well_posed(H, lines):
+    """on the oracle's map, by the restatement alone: row r is cell r, line i is the patch of the rows i H .. i H + H - 1 under every
+    connectivity, every patch well posed, horizontal and of slopes only"""
+    from tests import patch_ref as pr
+    ix, iy = es.stripes_cells(H, lines)
+    cells = parity.ref_from_cloud(es.cells_points(ix, iy), es.P)
+    n = H * lines
+    assert cells["num_nodes"] == n and np.array_equal(cells["sx"][:n], ix + 1) and np.array_equal(cells["sy"][:n], iy + 1)
+    m = pr.Map(cells)
+    for conn in (1, 3):
+        R = pr.rule(pr.NODES, conn)
+        ref = m.patches(R)
+        recs, counts = pr.listed(ref)
+        assert tuple(counts) == (lines, n, lines, 0)
+        assert np.array_equal(ref["label"], np.arange(n) // H * H) and (recs["nodes"] == H).all()
+        assert np.array_equal(recs["label"], np.arange(lines) * H) and (recs["kind"] == pr.HORIZONTAL | pr.SLOPES_ONLY).all()
+        assert all(pr.well_posed(m, R, ref, rec)[0] for rec in recs)
+
+
+def test_premise_floors_are_two_patches_labelled_0_and_a():
+    from tests import patch_ref as pr
+    for a, n in ((300, 700), (256, 257), (1, 600)):
+        ix, iy = es.floors_cells(a, n)
+        assert len(ix) == n and iy.max() < es.FLOOR_LINE and ix[a] - ix[a - 1] == 3 and iy[a] == 0
+        cells = parity.ref_from_cloud(es.cells_points(ix, iy), es.P)
+        assert cells["num_nodes"] == n and np.array_equal(cells["sx"][:n], ix + 1) and np.array_equal(cells["sy"][:n], iy + 1)
+        ref = pr.Map(cells).patches(pr.rule())
+        assert ref["patches"]["label"].tolist() == [0, a] and ref["patches"]["nodes"].tolist() == [a, n - a]
+        assert np.array_equal(ref["label"], np.where(np.arange(n) < a, 0, a))
+    w, p, k = es.wave_groups(np.arange(700) >= 300)
+    assert (w[:6].tolist(), p[:6].tolist(), k[:6].tolist()) == ([0, 1, 2, 3, 4, 4], [0, 0, 0, 0, 0, 1], [64, 64, 64, 64, 44, 20]) and k.sum() == 700
+
+
 def test_lattice_points_is_cells_cloud_bit_for_bit():
     W, H = 25, 41
     holes = [(3, 7), (3, 8), (11, 0), (24, 40), (0, 0), (12, 20)]

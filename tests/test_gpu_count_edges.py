@@ -8,7 +8,7 @@ expected outputs are ref[i % 4093]; counts, pass words and sums are sums over th
 lattices of exactly that many rows (edge_shapes.edge_lattice), built once per module and shared by the cases that only read them; a
 crop rebuilds its map from the shared device cloud.  Every case asserts that the region it exists for is populated.
 
-Measured wall time of the cases on the MI355X (pytest --durations=0; the whole module: 220 cases in 31 s).  The first case of a
+Measured wall time of the cases on the MI355X (pytest --durations=0; the whole module: 228 cases in 25 s).  The first case of a
 group also pays what the group shares, and is named where that matters:
   cast                 28 cases  <= 0.04 s each (the very first 1.7 s: the library, the small map and its cost flood)
   clear, count-only     7 cases  <= 0.03 s (the first 0.24 s);  clear at 524 289 rays  0.04 s
@@ -20,7 +20,9 @@ group also pays what the group shares, and is named where that matters:
                                  that map (a Python loop over rows), computed once and shared by the lattice's four cases
   coarsen               2 cases  1.4 s (1025 rows) and 2.3 s (725 x 724: the oracle's map of 4.7 M points at the doubled lengths)
   merge                 2 cases  0.02 s and 6.2 s (725 x 724: the oracle solves 524 900 eigenproblems; the device's share is milliseconds)
-  clear by rows         1 case   0.31 s;  map-to-map scoring  2 cases  0.14 s and 0.29 s"""
+  clear by rows         1 case   0.31 s;  map-to-map scoring  2 cases  0.14 s and 0.29 s
+  surface patches       8 cases  <= 0.02 s; the first case on each million-row lattice 0.87 s and 0.83 s: patch_ref.patches_fast's
+                                 restatement of that map, computed once and shared by the lattice's four cases (three calls each)"""
 import numpy as np
 import pytest
 
@@ -29,6 +31,7 @@ from tests import clear_ref as cr
 from tests import edge_shapes as es
 from tests import frontier_ref as fr
 from tests import parity
+from tests import patch_ref as pr
 from tests import query_ref as qr
 from tests import raster_ref as rr
 from tests import score_derivs_ref as dr
@@ -38,7 +41,8 @@ from tests.test_gpu_crop import FIELDS, _assert_same, _filtered
 from tests.test_gpu_frontiers import cfg as frontier_cfg
 from tests.test_gpu_frontiers import raw as frontier_raw
 from tests.test_gpu_frontiers import untouched
-from tests.gpu_kit import dev
+from tests.test_gpu_patches import check as patch_check
+from tests.gpu_kit import debug_option, dev
 
 pytestmark = pytest.mark.gpu
 
@@ -323,13 +327,20 @@ def test_crop_row_count_edges(n, strategy, box):
     assert np.array_equal(rows, expect), np.flatnonzero(rows != expect)[:8]
 
 
-def _frontier_map(n):
+def _lattice_map(n):
+    """edge_lattice(n) built once and only read: dict(m, cells)"""
     def make():
         m = _build(lattice(n)["dev"])
         cells = m.export()
         assert cells["num_nodes"] == n
-        ref = fr.Map(cells).frontiers(**frontier_cfg())
-        return dict(m=m, cells=cells, ref=ref)
+        return dict(m=m, cells=cells)
+    return cached(("lattice map", n), make)
+
+
+def _frontier_map(n):
+    def make():
+        L = _lattice_map(n)
+        return dict(L, ref=fr.Map(L["cells"]).frontiers(**frontier_cfg()))
     return cached(("frontier", n), make)
 
 
@@ -358,6 +369,58 @@ def test_frontier_row_count_edges(n, min_size, long_list):
     want = recs[:cap]
     assert fr.same_records(got["clusters"], want), fr.diff_records(got["clusters"], want)
     assert untouched(got["buf"], len(want))
+
+
+def _patch_map(n):
+    """the lattice's map with its rows and patch_ref.patches_fast's answer for the whole map, computed once for the lattice's cases"""
+    def make():
+        L = _lattice_map(n)
+        rows = pr.Rows(L["cells"])
+        return dict(L, rows=rows, ref=pr.patches_fast(rows, pr.rule()))
+    return cached(("patches", n), make)
+
+
+def _hole_line_box(n):
+    """a box one line of cells wide along the lattice's last line with holes, from its first cell to between its second and third
+    hole: the holes cut the floor inside it into three patches, whose rows lie in the map's last third"""
+    W, H = es.CROP_ROWS[n]
+    holes = es.pitch_holes(W, H, 37 if W > 41 else 5, 41 if H > 41 else 5)
+    ix = max(h[0] for h in holes)
+    iy = sorted(h[1] for h in holes if h[0] == ix)
+    return (ix + 1, ix + 1, 1, (iy[1] + iy[2]) // 2 + 1)
+
+
+@pytest.mark.parametrize("call", ["whole", "min_size_2", "cap_1", "box"])
+@pytest.mark.parametrize("n", [es.EDGES["scan_carry_rows"], es.EDGES["scan_carry_rows"] + 1])
+def test_patch_row_count_edges(n, call):
+    """surface patches on the million-row lattices: the floor and the last row's cell on its own are two patches, labelled 0 and
+    n - 1 — mark, link and flatten in their second trip (row 524 288 on), k_patch_rank at tile 1024 on 1 048 577 rows, the scan's
+    second chunk; the reductions in their ninth trip.  test_gpu_patches.check against patch_ref.patches_fast (thin: centroid and
+    normal asserted, var printed): both entry points with the moment pass's LDS stage, the device's without it"""
+    f = _patch_map(n)
+    whole = f["ref"]
+    tile = es.EDGES["kCropTile"]
+    assert n > CAP and n > 8 * es.PATCH_TRIP - 1 and whole["patches"]["label"].tolist() == [0, n - 1] and whole["patches"]["nodes"].tolist() == [n - 1, 1]
+    assert (whole["label"][CAP:] == 0).sum() > CAP - 2000                                  # rows of the second trip join the floor
+    if n > es.EDGES["scan_carry_rows"]:
+        assert int(whole["patches"]["label"][-1]) // tile >= es.EDGES["kCropScanT"]         # the last root: tile 1024, the scan's second chunk
+    R = pr.rule()
+    kw, ref, counts = dict(cap=5), whole, (2, n, 2, 0)
+    if call == "min_size_2":
+        kw, counts = dict(cap=5, min_size=2), (1, n, 2, 0)
+    elif call == "cap_1":
+        kw = dict(cap=1)
+    elif call == "box":
+        box = _hole_line_box(n)
+        ref = pr.patches_fast(f["rows"], R, box)
+        kw, counts = dict(cap=5, box=box), (3, ref["rows"], 3, 0)
+        assert len(ref["patches"]) == 3 and ref["rows"] > 50 and ref["patches"]["label"].min() > 2 * n // 3
+    for lds, host in ((1, False), (1, True), (0, False)):
+        with debug_option("DEBUG_PATCH_LDS", lds, 1):
+            got, _ = patch_check(f["m"], None, R, planes="thin", ref=ref, host=host, what=("patches", n, call, lds, host), **kw)
+        assert tuple(got["counts"]) == counts and len(got["patches"]) == min(counts[0], kw["cap"])
+        if call != "box":
+            assert int(got["patches"]["nodes"][0]) == n - 1 and int(got["patches"]["points"][0]) == 9 * (n - 1)
 
 
 def _plain(W, H):

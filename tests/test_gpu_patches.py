@@ -25,6 +25,10 @@ pytestmark = pytest.mark.gpu
 
 # the worst deviations of the compared patches over this tier on the MI355X (pytest -s prints every scene's): centroid, normal, var rel
 PLANES_MEASURED = dict(centroid=0.0, normal=5.0e-16, var_rel=3.2e-12)        # inside 1e-10: the footprints' bound stays
+# the same over tests/test_gpu_patch_edges.py, the patch cases of test_gpu_count_edges.py and test_gpu_scratch_reuse.py: the stripes
+# (every patch well posed and compared) 0, 3.4e-16 and 6.9e-16; the thin floors, where var is printed only, 6.4e-13 x value on the two
+# floors of 266 305 rows and 2.5e-12 on the million-row lattices
+PLANES_MEASURED_EDGES = dict(centroid=0.0, normal=3.4e-16, var_rel=6.9e-16, var_rel_thin=2.5e-12)
 ERR_INVALID = 1
 ATOMIC, PARTITION, TILE = 1, 2, 5
 WORD_FILL = 0x5A5A5A5A
@@ -57,12 +61,13 @@ def raw(m, R, box=None, min_size=1, cap=None, labels=True, stream=None, host=Fal
                     front=buf.a[:PAD * WORDS], tails=dict(label=lab.tail, patches=body[k * WORDS:], counts=cnt.tail))
 
 
-def check(m, ref_map, R, box=None, min_size=1, what="", planes=None, **kw):
+def check(m, ref_map, R, box=None, min_size=1, what="", planes=None, ref=None, **kw):
     """one call against the restatement -> (the call's answer, the restatement).  planes: "all" compares the plane fields under the
-    issue's bounds, "thin" centroid and normal only (var printed), None nothing"""
+    issue's bounds, "thin" centroid and normal only (var printed), None nothing.  ref: the restatement's answer for (R, box) where the
+    caller has it already — Map.patches' or patch_ref.patches_fast's (ref_map may then be None); it is left as it was"""
     rc, got = raw(m, R, box=box, min_size=min_size, **kw)
     assert rc == 0, (what, m._L.gndt_last_error(m._h))
-    ref = ref_map.patches(R, box)
+    ref = ref_map.patches(R, box) if ref is None else dict(ref)
     recs, counts = pr.listed(ref, min_size)
     assert np.array_equal(got["counts"], counts), (what, got["counts"], counts)
     if kw.get("labels", True):
@@ -77,6 +82,7 @@ def check(m, ref_map, R, box=None, min_size=1, what="", planes=None, **kw):
         dc, dn, dv = pr.plane_deviation(got["patches"], want)
         print(f"patch planes {what} (thin): centroid {dc:.3e} m, normal {dn:.3e}, var rel {dv:.3e} (not asserted)")
         assert dc <= pr.PLANE_ABS and dn <= pr.PLANE_ABS, (what, dc, dn)
+        ref["deviation"] = (dc, dn, dv)
     return got, ref
 
 

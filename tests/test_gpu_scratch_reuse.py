@@ -745,3 +745,37 @@ def test_clearance_then_walk_share_nothing():
     assert (second["hops"] == clr.BEYOND).any() and second["counts"][0] > first["counts"][0]
     walk(False, second["hops"], 1)
     _same_bytes(_field(tgc.check(a, fs, clr.BLOCKED, 64, what="again")), _field(first), "the first field again")
+
+
+# ---- surface patches ---------------------------------------------------------------------------------------------------------------
+# gndt_api_patch.hip carves moments | parent | size_at | tile_cnt | slack out of h->patch by n, tiles and patch_cap: after 134 400 rows
+# and a list of 2 100 patches every region of the small call (280 rows, 70 patches) lies on the large call's moments.
+
+def test_patches():
+    from tests import edge_shapes as es
+    from tests import patch_ref as pt
+    from tests.test_gpu_patches import check
+    H, lines = es.TRIP_STRIPES
+    a = _handle(LAT, fr.ORIGIN)
+    a.create2DMap("slope", _dev(es.cells_points(*es.stripes_cells(H, lines))[1:]))
+    a.sync()
+    R = pt.rule()
+    big = a.export()
+    assert big["num_nodes"] == H * lines > es.PATCH_TRIP
+    ref = pt.patches_fast(big, R)
+    for host in (False, True):
+        large, _ = check(a, None, R, ref=ref, cap=lines, host=host, planes="all", what=("large", host))
+    assert int(large["counts"][0]) == lines
+    h, k = 4, es.STRIPES[4]
+    b, cells = _shrink_to(a, es.cells_points(*es.stripes_cells(h, k))[1:], QUADRANT, LAT, fr.ORIGIN)
+    assert cells["num_nodes"] == h * k < big["num_nodes"] // 8
+    ref = pt.patches_fast(cells, R)
+    for host in (False, True):
+        for kw in (dict(), dict(cap=es.EDGES["kPatchSlots"] + 1), dict(min_size=h + 1)):
+            got, r = check(a, None, R, ref=ref, host=host, planes="all", what=("small", host, kw), **kw)
+            other, _ = check(b, None, R, ref=ref, host=host, planes="all", what=("small, fresh handle", host, kw), **kw)
+            assert got["label"].tobytes() == other["label"].tobytes() and got["counts"].tobytes() == other["counts"].tobytes()
+            for f in pt.INTEGER_FIELDS + ("kind", "reserved"):
+                assert got["patches"][f].tobytes() == other["patches"][f].tobytes(), (host, kw, f)
+            if not kw:
+                assert 0 < int(got["counts"][0]) == k < int(large["counts"][0]) and r["compared"] == k
